@@ -14,8 +14,11 @@ from rank 0 before the timed region (the path itself has no exchange step); the 
 from the received device buffer.  `--workload configs3`: BASELINE configs[3] instead -- 100 M HiSeq reads per step over
 50 x 5 Mbp genomes, the TOTAL fixed and sharded over the N ranks (strong scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline` and `parity_window`
-(windows of the last timed step recomputed by the CPU oracle after the timed region).
+Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (from the kernel events of the same steps and the
+committed PMC passes).  A plain run sets up, warms up, times the steps and prints that line; `--full` adds what takes runs or
+checks of its own: `parity_window` (windows of the last timed step recomputed by the CPU oracle after the timed region),
+`cpu_baseline`, the side legs on other models, the end-to-end FASTQ legs and, with N > 1, the strong leg.  `--dump-outputs DIR`
+writes the rows of the last timed step (a fixed, seeded sample of them) as .npy files, to compare two builds output for output.
 """
 import argparse
 import json
@@ -56,10 +59,12 @@ def algorithmic_bytes_per_pair(read_length):
     return 4 * read_length + 2 * ((read_length + 3) // 4)
 
 
-def run_leg(args, label, model, reads, n_genomes, strong, indel, steps, warmup, rank, local_rank, world, dist, force_dist):
+def run_leg(args, label, model, reads, n_genomes, strong, indel, steps, warmup, rank, local_rank, world, dist, force_dist,
+            dump_dir=None):
     """One leg of the bench on this rank: rank 0 builds model + genomes, ONE broadcast to the other ranks (only when a process
     group exists), every rank takes chunk `rank` of the reference's divider (iss/app.py:81-83, 99-106), `warmup` untimed and
-    `steps` timed steps bracketed by barriers; the ranks' (pairs, seconds) are gathered.  Returns everything the line needs."""
+    `steps` timed steps bracketed by barriers; the ranks' (pairs, seconds) are gathered.  dump_dir: the rows of the last timed
+    step go there (dump_outputs).  Returns everything the line needs."""
     import torch
 
     from insilicoseq_amd.distributed import broadcast_model_and_genomes, rank_work
@@ -158,9 +163,12 @@ def run_leg(args, label, model, reads, n_genomes, strong, indel, steps, warmup, 
         uploaded = [int(x[0].item()) for x in allr]
         bcast_s = max(float(x[1].item()) for x in allr)  # the broadcast is over when the slowest rank holds the payload
 
-    # ---- after the timed region: windows of the LAST timed step recomputed by the CPU oracle (rank 0's rows)
+    if dump_dir is not None:  # (before anything else writes the rows)
+        dump_outputs(eng, total_pairs_step, dump_dir, rank, world)
+
+    # ---- after the timed region (--full): windows of the LAST timed step recomputed by the CPU oracle (rank 0's rows)
     parity = None
-    if rank == 0 and total_pairs_step:
+    if args.full and rank == 0 and total_pairs_step:
         parity = parity_window(eng, dense, work, letters, ordinal[0] - total_pairs_step, worker_seed)
 
     # ---- what ONE GPU does on the whole job (N > 1, strong leg): rank 0 alone, the other ranks wait at the barrier behind it.
@@ -215,7 +223,7 @@ def main():
     ap.add_argument("--workload", default=None, choices=["configs2", "configs3"],
                     help="configs2: BASELINE configs[2], 10 M NovaSeq reads per step PER GPU over 5 genomes (weak scaling); "
                          "configs3: BASELINE configs[3], 100 M HiSeq reads per step IN TOTAL over 50 genomes (strong scaling).  "
-                         "Default: configs2 is the line's metric; with --gpus N > 1 the line ALSO carries the configs3 leg (`strong_leg`)")
+                         "Default: configs2 is the line's metric; with --gpus N > 1 and --full the line ALSO carries the configs3 leg (`strong_leg`)")
     ap.add_argument("--reads", type=int, default=None, help="reads per step (configs2: per GPU; configs3: in total)")
     ap.add_argument("--strong-reads", type=int, default=100_000_000, help="total reads per step of the strong leg of a default N > 1 run")
     ap.add_argument("--model", default=None)
@@ -231,6 +239,12 @@ def main():
                     "the multi-rank logic, e.g. with ISS_BENCH_SHARE_GPU=1 on a single-GPU box)")
     ap.add_argument("--cpu-sample-pairs", type=int, default=1_500_000)
     ap.add_argument("--cpu-threads", type=int, default=None, help="threads of the all-cores CPU leg (default: min(host cores, 64))")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs or checks of its own: the oracle's parity window, the CPU baselines, the side legs on "
+                         "other models, the end-to-end legs and, with N > 1, the strong leg (the --no-* switches above apply here)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the rows of the last timed step (R1 / R2 bases and phreds as float32, coordinates as float64; a fixed, "
+                         "seeded sample of windows when they exceed 48 MiB) as DIR/<name>.npy")
     args = ap.parse_args()
     both_legs = args.workload is None  # the default invocation
     strong = args.workload == "configs3"
@@ -292,12 +306,12 @@ def main():
     label = ("BASELINE configs[3]: %d reads/step in total" % args.reads) if strong else (
         "BASELINE configs[2]: %d reads/step/GPU" % args.reads)
     L = run_leg(args, label, args.model, args.reads, args.n_genomes, strong, args.indel, args.steps, args.warmup, rank, local_rank,
-                world, dist, force_dist)
-    # N > 1, default invocation: the line ALSO carries BASELINE configs[3] -- 100 M HiSeq reads per step in TOTAL over 50
+                world, dist, force_dist, dump_dir=args.dump_outputs)
+    # N > 1, default invocation with --full: the line ALSO carries BASELINE configs[3] -- 100 M HiSeq reads per step in TOTAL over 50
     # records, chunk r of the divider per rank (strong scaling); a weak curve alone says nothing about a path without a
     # data-path collective
     L3 = None
-    if both_legs and dist is not None and world > 1:
+    if args.full and both_legs and dist is not None and world > 1:
         L["eng"].close()
         L["eng"] = None
         L3 = run_leg(args, "BASELINE configs[3]: %d reads/step in total" % args.strong_reads, "hiseq", args.strong_reads, 50, True,
@@ -357,9 +371,10 @@ def main():
             "indel_scripted_reads_per_step": stats["scripted_reads"] / max(args.steps + args.warmup, 1),
             "model_broadcast_s": bcast_s, "model_broadcast_bytes": L["bcast_info"].get("payload_bytes"),
             "genomes_uploaded_per_rank": L["genomes_uploaded"],
-            "parity_window": parity,
             "library_build_id": library_build_id(),
         }
+        if args.full:
+            out["parity_window"] = parity
         out["n_ranks_seen"] = dist.get_world_size() if dist is not None else 1
         out["backend"] = (args.backend if dist is not None else None)
         if dist is not None:
@@ -369,7 +384,7 @@ def main():
             out["scaling_efficiency"] = leg["scaling_efficiency"]
             if L3 is not None:
                 out["strong_leg"] = leg_summary(L3, world)
-        if world == 1 and not args.no_other_workloads and not strong and args.model == "novaseq" and args.indel is None:
+        if args.full and world == 1 and not args.no_other_workloads and not strong and args.model == "novaseq" and args.indel is None:
             # the same work list on the other models of the parity suite (a few steps each; BASELINE's metric stays the line above)
             out["other_workloads"] = {}
             for name, model, indel in (("indel_heavy", "novaseq", (0.001, 0.003)), ("hiseq", "hiseq", None),
@@ -391,7 +406,7 @@ def main():
                 out["other_workloads"]["mt_mode"] = mt_mode_leg(local_rank, dense, genomes[0])
             except Exception as e:
                 out["other_workloads"]["mt_mode"] = {"error": repr(e)}
-        if world == 1 and not args.no_end_to_end:
+        if args.full and world == 1 and not args.no_end_to_end:
             eng.close()  # (the legs below bring their own engines: the rows of the timed region go back to the allocator first)
             eng = None
             e2e_records = [Record(letters[id(r)], id=r.id) for r in records]
@@ -400,7 +415,7 @@ def main():
             out["end_to_end"] = end_to_end(dense, e2e_records, abundance, args.e2e_pairs)
             out["end_to_end_gzip"] = end_to_end(dense, e2e_records, abundance, args.e2e_pairs, compress=True)
             out["end_to_end_4_workers"] = end_to_end(dense, e2e_records, abundance, args.e2e_pairs, workers=4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu_work = [(letters[id(r)], n) for r, n in work]
             out["cpu_baseline"] = cpu_baseline(dense, cpu_work, args.cpu_sample_pairs)
             try:  # the same oracle on all host cores (threads: the C call releases the GIL), ~5 s
@@ -437,7 +452,8 @@ def headline(out):
     h["roofline"] = {k: _sig(v, 6) for k, v in out["roofline"].items() if k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
                                                                                   "traffic_fresh", "avg_launch_ms", "launches")}
     h["kernel_ms_per_step"] = {k: _sig(v, 4) for k, v in out["kernel_ms_per_step"].items() if k != "note"}
-    h["parity_window"] = str(out.get("parity_window"))[:60]
+    if "parity_window" in out:
+        h["parity_window"] = str(out["parity_window"])[:60]
     if "cpu_baseline" in out:
         h["cpu_baseline"] = {k: _sig(v) for k, v in out["cpu_baseline"].items() if k != "note"}
         h["cpu_baseline"]["sample"] = str(h["cpu_baseline"].get("sample", "")).replace(" of the same work list (proportional per genome)", "")
@@ -497,6 +513,34 @@ def parity_window(eng, dense, work, letters, step_first_ordinal, worker_seed, n=
             checked += cnt
             i += cnt
     return "ok (%d pairs of the last timed step, item boundaries included, bit-identical to the CPU oracle)" % checked
+
+
+def dump_outputs(eng, total_pairs, out_dir, rank=0, world=1, budget_bytes=48 << 20, window=256):
+    """The rows the last timed step left on the device -- what a caller of iss_generate_batch receives: R1 / R2 bases and phreds
+    (float32 [pairs, read_length]) and each pair's coordinates (float64 [pairs, 4]) -- as out_dir/<name>.npy, with pair_index
+    (float64: the pair's place in the step).  More than budget_bytes: windows of `window` consecutive pairs at places drawn with
+    a fixed seed, so two runs with the same arguments dump the same pairs.  N > 1: every rank its own files (<name>_rank<r>),
+    the budget shared."""
+    RL = eng.read_length
+    per_pair = 4 * RL * 4 + 4 * 8 + 8
+    slots = -(-total_pairs // window)
+    n_win = min(slots, max(1, budget_bytes // max(world, 1) // (per_pair * window)))
+    picked = np.sort(np.random.RandomState(SEED).choice(slots, n_win, replace=False)) if slots else []
+    keys = ("r1_base", "r1_qual", "r2_base", "r2_qual")
+    parts = {k: [] for k in keys + ("coords", "pair_index")}
+    for slot in picked:
+        s0 = int(slot) * window
+        m = min(window, total_pairs - s0)
+        rows = eng.download(s0, m)
+        for k in keys:
+            parts[k].append(rows[k].astype(np.float32))
+        parts["coords"].append(eng.coords(s0, m).astype(np.float64))
+        parts["pair_index"].append(np.arange(s0, s0 + m, dtype=np.float64))
+    empty = {"coords": np.zeros((0, 4)), "pair_index": np.zeros(0)}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in parts.items():
+        a = np.concatenate(v) if v else empty.get(k, np.zeros((0, RL), dtype=np.float32))
+        np.save(os.path.join(out_dir, k + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
 
 
 def side_workload(device, model, indel, genomes, records, abundance, reads, steps=6, warmup=2):

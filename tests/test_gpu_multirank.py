@@ -11,6 +11,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+# A shared GPU machine lets at most this many processes have the GPU open at once; a dry run on one GPU opens it in every
+# rank, in this test's process and in the launcher (world 8 on one GPU: 10 processes)
+MAX_GPU_PROCESSES = 6
+
 
 def _free_port():
     s = socket.socket()
@@ -99,21 +103,31 @@ def test_two_ranks_through_the_device(tmp_path):
 def test_bench_multirank_dry_run(world):
     """bench.py's own N > 1 code -- torch.distributed.run rendezvous on 127.0.0.1, the process group, the one broadcast of
     tables + packed genomes, chunk r of the reference's divider per rank (iss/app.py:81-83), the barrier-bracketed timed
-    region, the all_gather of every rank's (pairs, seconds), elapsed = max over ranks -- as a dry run on ONE GPU (gloo;
-    ISS_BENCH_SHARE_GPU=1).  The driver's 8-GPU run differs in the backend name ("nccl" = RCCL) and the device per rank; world 8
-    is that run's shape: eight chunks of both legs, a rank uploading only the records its chunk names."""
+    region, the all_gather of every rank's (pairs, seconds), elapsed = max over ranks -- with gloo, one rank per GPU where there
+    are `world` GPUs, else as a dry run with every rank on GPU 0 (ISS_BENCH_SHARE_GPU=1) where its processes fit
+    MAX_GPU_PROCESSES (worlds 2 and 3).  The driver's 8-GPU run differs in the backend name ("nccl" = RCCL); world 8 is that
+    run's shape: eight chunks of both legs, a rank uploading only the records its chunk names -- on one GPU its ten processes
+    exceed MAX_GPU_PROCESSES, so it runs where there are eight GPUs."""
     import json
     import subprocess
     import sys
 
+    import torch
+
+    n_gpus = torch.cuda.device_count()
+    if n_gpus < world and world + 2 > MAX_GPU_PROCESSES:  # (the ranks, this process and the launcher on one GPU)
+        pytest.skip("needs %d GPUs, found %d (%d ranks on one GPU: %d processes with it open, more than the %d a shared "
+                    "machine allows)" % (world, n_gpus, world, world + 2, MAX_GPU_PROCESSES))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     reads, strong_reads = 300000, 1_200_000
-    env = dict(os.environ, ISS_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    if n_gpus < world:
+        env["ISS_BENCH_SHARE_GPU"] = "1"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world),
                           "--backend", "gloo", "--reads", str(reads), "--strong-reads", str(strong_reads), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-end-to-end", "--no-other-workloads"], cwd=root, env=env, capture_output=True,
-                         text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-other-workloads"], cwd=root, env=env,
+                         capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]  # rank 0 prints ONE line
@@ -170,7 +184,7 @@ def test_bench_rccl_calls_with_one_rank():
     env = dict(os.environ, ISS_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1",
-                          "--reads", "400000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-end-to-end",
+                          "--reads", "400000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-end-to-end",
                           "--no-other-workloads"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
