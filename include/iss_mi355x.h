@@ -352,6 +352,57 @@ int iss_fastq_write(int fd_r1, int fd_r2, const char *record_id, int64_t first_i
                     int64_t n_pairs, int32_t read_length, int32_t pitch, const uint8_t *r1_base,
                     const uint8_t *r1_qual, const uint8_t *r2_base, const uint8_t *r2_qual, int32_t n_threads);
 
+/*
+ * `model`: the reference's `iss model` (iss/app.py:147-169 -> iss/bam.py:103-227, iss/modeller.py) from a BAM file.  Additive to
+ * ABI 8.  The host inflates the BGZF blocks; these entries find the records, tally them on the device and evaluate the quality and
+ * insert-size kernel density estimates from the tallies.
+ *
+ * iss_bam_scan (host only, no GPU): the block_size chain of inflated record bytes -- the byte offsets of up to `capacity` whole
+ * records, how many were found and the bytes they cover (the rest starts the next chunk).  ISS_E_INVALID on a block_size under 32.
+ *
+ * The tally context: iss_bam_feed adds the records of one chunk (offsets from iss_bam_scan, select[r] != 0: the record is taken --
+ * mapped and in the subsample) to the device tallies; iss_bam_tally_download copies the ISS_BAM_TALLY_WORDS u64 words below and the
+ * first bad record (index over all fed records, -1: none) with its ISS_BAM_REC_* code; iss_bam_kde evaluates the 41-point quality
+ * CDFs of every (mate, bin, position) into qcdf[8][301][41] (NaN rows: fewer than two reads in the bin, or a position at or past the
+ * bin's shortest read) and, when with_isize, the 2000-point insert-size CDF for read_length (the caller checks there are two template
+ * lengths or more, not all equal).  iss_bam_reset zeroes the tallies.
+ *
+ * Tally words (u64): subst [2][301][16] at 0 (dispatch_subst's columns), indel [2][301][9] at ISS_BAM_OFF_INDEL (column 0 unused),
+ * quality histograms [2 mates][4 bins][301][94] at ISS_BAM_OFF_QHIST, template lengths [2000] at ISS_BAM_OFF_TLEN, reads per
+ * (mate, bin) [8] at ISS_BAM_OFF_NREAD, their shortest length [8] at ISS_BAM_OFF_MINLEN (~0: none), records tallied at ISS_BAM_OFF_TAKEN.
+ */
+#define ISS_BAM_MAX_LEN 301
+#define ISS_BAM_NQ 94
+#define ISS_BAM_NTLEN 2000
+#define ISS_BAM_OFF_INDEL 9632
+#define ISS_BAM_OFF_QHIST 15050
+#define ISS_BAM_OFF_TLEN 241402
+#define ISS_BAM_OFF_NREAD 243402
+#define ISS_BAM_OFF_MINLEN 243410
+#define ISS_BAM_OFF_TAKEN 243418
+#define ISS_BAM_TALLY_WORDS 243426
+#define ISS_BAM_QCDF_WORDS (8 * 301 * 41)
+
+#define ISS_BAM_REC_MALFORMED 1   /* record fields run past its block_size, or a broken optional field */
+#define ISS_BAM_REC_TOO_LONG 2    /* l_seq > 301 */
+#define ISS_BAM_REC_NO_QUAL 3     /* read1 / read2 without qualities (0xFF) or without bases */
+#define ISS_BAM_REC_CIGAR_OP 4    /* a CIGAR operation other than M, I, D, S, H */
+#define ISS_BAM_REC_NO_MD 5       /* no MD:Z tag */
+#define ISS_BAM_REC_BAD_MD 6      /* the MD tag does not cover the aligned columns */
+#define ISS_BAM_REC_INDEL_INDEX 7 /* dispatch_indels would index past the read (IndexError in the reference) */
+#define ISS_BAM_REC_QUAL_RANGE 8  /* a quality above 93 */
+#define ISS_BAM_REC_CIGAR_LEN 9   /* M + I + S lengths differ from l_seq */
+
+typedef struct iss_bam iss_bam;
+int iss_bam_scan(const uint8_t *data, int64_t n_bytes, int64_t *offsets, int64_t capacity, int64_t *n_records, int64_t *consumed);
+int iss_bam_create(int device_ordinal, iss_bam **out);
+void iss_bam_destroy(iss_bam *bam);
+const char *iss_bam_last_error(const iss_bam *bam);
+int iss_bam_reset(iss_bam *bam);
+int iss_bam_feed(iss_bam *bam, const uint8_t *data, int64_t n_bytes, const int64_t *offsets, const uint8_t *select, int64_t n_records);
+int iss_bam_tally_download(iss_bam *bam, uint64_t *tally, int64_t *bad_record, int32_t *bad_code);
+int iss_bam_kde(iss_bam *bam, int32_t read_length, int32_t with_isize, double *qcdf, double *isize_cdf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,19 @@ EXPORTS = (
     "iss_generate_batch", "iss_fastq_emit_batch", "iss_gen_phred_scores", "iss_mut_sequence", "iss_random_insert_size",
     "iss_introduce_indels", "iss_ev_step", "iss_mt_workers_seed", "iss_generate_mt_workers", "iss_mt_workers_peek",
     "iss_main_kernel", "iss_fastq_emit_scatter",
+    "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
+    "iss_bam_tally_download", "iss_bam_kde",
 )
+
+# `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
+BAM_MAX_LEN, BAM_NQ, BAM_NTLEN = 301, 94, 2000
+BAM_OFF_INDEL, BAM_OFF_QHIST, BAM_OFF_TLEN, BAM_OFF_NREAD, BAM_OFF_MINLEN, BAM_OFF_TAKEN, BAM_TALLY_WORDS = (
+    9632, 15050, 241402, 243402, 243410, 243418, 243426)
+BAM_REC_ERRORS = {
+    1: "malformed record", 2: "read longer than 301 bases", 3: "read without qualities", 4: "CIGAR operation other than M/I/D/S/H",
+    5: "mapped read without an MD tag", 6: "MD tag does not match the CIGAR", 7: "indel position outside the read",
+    8: "quality above 93", 9: "CIGAR length differs from the read length",
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -116,8 +128,18 @@ def lib():
     L.iss_introduce_indels.argtypes = [vp, i32, i64, u64, u64, vp, vp, vp, i64, vp, vp, vp]
     L.iss_ev_step.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp]
     L.iss_fastq_write.argtypes = [C.c_int, C.c_int, C.c_char_p, i64, i32, i64, i32, i32, vp, vp, vp, vp, i32]
+    L.iss_bam_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.iss_bam_create.argtypes = [C.c_int, C.POINTER(vp)]
+    L.iss_bam_destroy.argtypes = [vp]
+    L.iss_bam_destroy.restype = None
+    L.iss_bam_last_error.argtypes = [vp]
+    L.iss_bam_last_error.restype = C.c_char_p
+    L.iss_bam_reset.argtypes = [vp]
+    L.iss_bam_feed.argtypes = [vp, vp, i64, vp, vp, i64]
+    L.iss_bam_tally_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
+    L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
     for name in EXPORTS:
-        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id"):
+        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -1,4 +1,4 @@
-"""`generate`: the reference's ``iss generate`` flow (iss/app.py:23-144) on GPUs.
+"""`generate` and `model`.  `generate`: the reference's ``iss generate`` flow (iss/app.py:23-144) on GPUs.
 
 Same steps, same file names, same flag names for the options this engine supports: load the error
 model, concatenate the genome FASTA files, draw / read abundances (written to ``<out>_abundance.txt``),
@@ -303,6 +303,26 @@ def generate_reads(args):
     logger.info("Read generation complete")
 
 
+def model_from_bam(args):
+    """`model` (iss/app.py:147-169): errors are one line on stderr and exit status 1."""
+    from ._native import EngineError, NativeLibraryError
+    from .bam import BamError
+    from .modeller import to_model
+
+    logging.basicConfig(level=logging.ERROR if args.quiet else logging.DEBUG if args.debug else logging.INFO)
+    logger = logging.getLogger(__name__)
+    try:
+        timings = {}
+        logger.info("Starting model: %s" % args.bam)
+        path = to_model(args.bam, args.output, seed=args.seed, device=args.device, dense=args.dense, timings=timings)
+        logger.debug("seconds: %s" % ", ".join("%s %.3f" % kv for kv in sorted(timings.items())))
+        logger.info("Model written to %s" % path)
+    except (BamError, EngineError, NativeLibraryError, OSError) as e:
+        sys.stderr.write("ERROR: %s: %s\n" % (args.bam, str(e).splitlines()[0] if str(e) else type(e).__name__))
+        return 1
+    return 0
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="insilicoseq_amd", description="iss generate on MI355X")
     sub = p.add_subparsers(dest="cmd")
@@ -330,7 +350,17 @@ def main(argv=None):
                         "streams consumed sequentially on the GPU -- output identical to `iss generate` for the same --seed")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
+    m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")
+    m.add_argument("--bam", "-b", required=True, help="aligned reads (BAM with MD tags); no index needed")
+    m.add_argument("--output", "-o", required=True, help="output prefix: writes <prefix>.npz")
+    m.add_argument("--quiet", "-q", action="store_true")
+    m.add_argument("--debug", "-d", action="store_true")
+    m.add_argument("--seed", type=int, default=0, help="Philox key of the subsample (more than 1 000 000 mapped records)")
+    m.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    m.add_argument("--dense", action="store_true", help="also write <prefix>.dense.npz (this project's pickle-free form)")
     args = p.parse_args(argv)
+    if args.cmd == "model":
+        return model_from_bam(args)
     if args.cmd != "generate":
         p.print_help()
         return 1

@@ -3,7 +3,7 @@
 // stream for one record (iss_generate) or a whole work list (iss_generate_batch: records side by side in one arena),
 // HIP-event timing, downloads, the FASTQ pipeline (text or gzip members built on the device, copy stream, writer thread).
 // Device side: iss_kernels.hip.h (the Philox path), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
-// iss_fastq.hip.h, iss_deflate.hip.h.
+// iss_fastq.hip.h, iss_deflate.hip.h; `model` (BAM tallies, KDE): iss_bam.hip.h.
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@
 #include "iss_deflate.hip.h"
 #include "iss_mt_compat.hip.h"
 #include "iss_units.hip.h"
+#include "iss_bam.hip.h"        // `model`: BAM tallies and the KDE CDFs
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
@@ -40,3 +41,4 @@
 #include "iss_api_generate.hip.h"
 #include "iss_api_mt.hip.h"
 #include "iss_api_fastq.hip.h"
+#include "iss_api_bam.hip.h"

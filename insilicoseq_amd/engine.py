@@ -409,3 +409,66 @@ def fastq_write(fd_r1, fd_r2, record_id, first_i, cpu_number, n_pairs, read_leng
 
 
 __all__ = ["ReadEngine", "EngineError", "fastq_write"]
+
+
+class BamTally(object):
+    """Device tallies of `model` (include/iss_mi355x.h, iss_bam_*): feed record chunks, download the integer tallies, evaluate the
+    quality and insert-size KDE CDFs from them.  Replaces the per-read loop of iss/bam.py:125-170 and the scipy KDEs of
+    iss/modeller.py:12-38, 99-134."""
+
+    def __init__(self, device=0):
+        self._lib = _native.lib()
+        self._h = C.c_void_p()
+        rc = self._lib.iss_bam_create(int(device), C.byref(self._h))
+        if rc < 0:
+            msg = self._lib.iss_bam_last_error(self._h if self._h else None)
+            self.close()
+            raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.iss_bam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self._lib.iss_bam_last_error(self._h)
+            raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
+        return rc
+
+    def reset(self):
+        self._check(self._lib.iss_bam_reset(self._h))
+
+    def feed(self, data, offsets, select):
+        """Tally the selected records of one chunk (data: uint8 record bytes, offsets: int64 block_size offsets, select: uint8)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        select = np.ascontiguousarray(select, dtype=np.uint8)
+        assert offsets.size == select.size
+        self._check(self._lib.iss_bam_feed(self._h, data.ctypes.data, data.size, offsets.ctypes.data, select.ctypes.data, offsets.size))
+
+    def tallies(self):
+        """(flat u64 tally words, index of the first bad record or -1, its error code)."""
+        out = np.zeros(_native.BAM_TALLY_WORDS, dtype=np.uint64)
+        rec, code = C.c_int64(), C.c_int32()
+        self._check(self._lib.iss_bam_tally_download(self._h, out.ctypes.data, C.byref(rec), C.byref(code)))
+        return out, rec.value, code.value
+
+    def kde(self, read_length, with_isize=True):
+        """qcdf [2 mates][4 bins][301][41] (NaN rows where no CDF exists) and the 2000-point insert-size CDF (or None)."""
+        q = np.empty((2, 4, _native.BAM_MAX_LEN, 41), dtype=np.float64)
+        iz = np.empty(_native.BAM_NTLEN, dtype=np.float64)
+        self._check(self._lib.iss_bam_kde(self._h, int(read_length), 1 if with_isize else 0, q.ctypes.data, iz.ctypes.data))
+        return q, (iz if with_isize else None)

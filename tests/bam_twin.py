@@ -1,0 +1,75 @@
+"""A plain-Python twin of the `model` tallies for the tests: walks pysam-shim records (tests/golden/tooling/pysam_shim) the way
+iss/bam.py:125-170 and iss/modeller.py's dispatch functions use them and returns the arrays of insilicoseq_amd.modeller.unpack_tallies."""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SHIM = os.path.join(HERE, "golden", "tooling", "pysam_shim")
+
+SUBST = {"AA": 0, "aT": 1, "aG": 2, "aC": 3, "TT": 4, "tA": 5, "tG": 6, "tC": 7, "CC": 8, "cA": 9, "cT": 10, "cG": 11, "GG": 12,
+         "gA": 13, "gT": 14, "gC": 15}
+INDEL = {"A1": 1, "T1": 2, "C1": 3, "G1": 4, "A2": 5, "T2": 6, "C2": 7, "G2": 8}
+
+
+def shim():
+    if SHIM not in sys.path:
+        sys.path.insert(0, SHIM)
+    import pysam
+
+    return pysam
+
+
+def read_records(path):
+    return shim()._parse(path)[1]
+
+
+def tallies(reads):
+    """Tallies over the given records (every mapped one is taken)."""
+    M = 301
+    t = dict(subst=np.zeros((2, M, 16), np.uint64), indel=np.zeros((2, M, 9), np.uint64), qhist=np.zeros((2, 4, M, 94), np.uint64),
+             tlen=np.zeros(2000, np.uint64), nread=np.zeros((2, 4), np.uint64), minlen=np.full((2, 4), 2 ** 64 - 1, np.uint64), taken=0)
+    for r in reads:
+        if r.is_unmapped:
+            continue
+        t["taken"] += 1
+        if r.is_paired:
+            tl = abs(r.template_length)
+            if 0 < tl < 2000:
+                t["tlen"][tl] += 1
+        mate = 0 if r.is_read1 else 1 if r.is_read2 else None
+        if mate is not None:
+            q = list(r.query_qualities)
+            mean = int(np.mean(q))
+            if r.is_reverse:
+                q = q[::-1]
+            if mean < 40:
+                b = mean // 10
+                t["nread"][mate, b] += 1
+                t["minlen"][mate, b] = min(int(t["minlen"][mate, b]), len(q))
+                for p, v in enumerate(q):
+                    t["qhist"][mate, b, p, v] += 1
+        odd = False
+        for qp, _, ref in r.get_aligned_pairs(matches_only=True, with_seq=True):
+            key = ref + r.seq[qp]
+            if key not in SUBST:
+                odd = True
+            elif mate is not None:
+                t["subst"][mate, qp, SUBST[key]] += 1
+        if odd and mate is not None:
+            pos = 0
+            for op, ln in r.cigartuples:
+                if op == 0:
+                    pos += ln
+                elif op == 1:
+                    k = r.query_sequence[pos].upper() + "1"
+                    if k in INDEL:
+                        t["indel"][mate, pos, INDEL[k]] += 1
+                    pos += ln
+                elif op == 2:
+                    k = r.query_alignment_sequence[pos].upper() + "2"
+                    if k in INDEL:
+                        t["indel"][mate, pos, INDEL[k]] += 1
+                    pos -= ln
+    return t
