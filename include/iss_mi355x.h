@@ -92,9 +92,15 @@ typedef struct {
      * (n_q + 1 must cover the phreds: 41 -> 0..41).  The reference-compatible mode (iss_generate_mt) draws the
      * normal deviates in the reference's order; iss_generate / iss_generate_batch invert q_thr like a KDE row, so
      * the caller puts the distribution of that score there (the same row at every position, in every bin;
-     * insilicoseq_amd/model.py basic_phred_cdf).  The insert-size and bin tables are unused. */
-    int32_t quality_mode;        /* 0: KDE tables (kde.py), 1: basic                                     */
-    int32_t basic_insert_size;   /* basic.py:21 (200)                                                    */
+     * insilicoseq_amd/model.py basic_phred_cdf).  The insert-size and bin tables are unused.
+     * PerfectErrorModel (iss/error_models/perfect.py:14-52), quality_mode 2: constant insert size basic_insert_size (no
+     * draw), every phred 40 (no quality draw; n_q + 1 must cover 0..40), mut_sequence's per-base draws as usual -- the caller
+     * gives the substitution tables that make an error the base itself, upper-cased, and all-zero indel tables
+     * (insilicoseq_amd/model.py DenseModel.perfect).  iss_generate / iss_generate_batch run k_perfect (the environment
+     * switch ISS_PERFECT_KERNEL=0: k_main on the same tables, q_thr then all mass on 40); k_perfect writes no
+     * --store_mutations rows (the reference's perfect model records none).  basic_mean / sd / cap are unused. */
+    int32_t quality_mode;        /* 0: KDE tables (kde.py), 1: basic, 2: perfect                          */
+    int32_t basic_insert_size;   /* basic.py:21 / perfect.py:19 (200)                                    */
     double basic_mean;           /* util.phred_to_prob(30), basic.py:24, :52                             */
     double basic_sd;             /* 0.01, basic.py:52                                                     */
     double basic_cap;            /* 0.9999, basic.py:52                                                   */
@@ -241,7 +247,8 @@ int iss_timing_read(iss_ctx *ctx, double ms[4], int64_t *n_launches);
 int iss_stats_read(iss_ctx *ctx, int64_t *n_fixup_reads, int64_t *n_scripted_reads);
 
 /* Name of the kernel the last iss_generate / iss_generate_batch call launched for the hot path (simulate_read's per-base work,
- * iss/generator.py:146-180 + iss/error_models/kde.py:52-86): "k_main<mutations, plain, indel>" or "k_main_g<NI, NP>" -- what a
+ * iss/generator.py:146-180 + iss/error_models/kde.py:52-86): "k_main<mutations, plain, indel>", "k_main_g<NI, NP>" or, for
+ * quality mode 2, "k_perfect" -- what a
  * profile of the call lists, so that a measurement can name what it measured.  Returns the name's length (it is cut to
  * capacity - 1 characters and always closed by a NUL), 0 before the first call. */
 int iss_main_kernel(iss_ctx *ctx, char *name, int capacity);

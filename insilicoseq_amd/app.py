@@ -24,7 +24,7 @@ import numpy as np
 
 from .distributed import VCF_HEADER, concatenate_rank_files, temp_prefix
 from .generator import generate_work_divider, parse_fasta, worker_iterator, worker_set_iterator
-from .model import BasicErrorModel, KDErrorModel
+from .model import BasicErrorModel, KDErrorModel, PerfectErrorModel
 
 PROFILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
 # names of iss/generator.py:377-387 -> dense files converted from the reference's profiles
@@ -42,11 +42,8 @@ def convert_n_reads(unit):
 
 
 def load_error_model(mode, seed, model, fragment_length, fragment_length_sd, store_mutations, rng="philox"):
-    """iss/generator.py:359-421 for what the device path covers (kde)."""
+    """iss/generator.py:359-421: kde, basic and perfect."""
     logger = logging.getLogger(__name__)
-    if mode == "perfect":  # (the reference's PerfectErrorModel fails at its first error draw: SURVEY.md Appendix A-8)
-        logger.error("--mode perfect is not available on the GPU path")
-        sys.exit(1)
     if fragment_length is not None and fragment_length_sd is not None:
         logger.info("Using custom fragment length %s and default fragment length sd %s" % (fragment_length,
                                                                                            fragment_length_sd))
@@ -60,6 +57,10 @@ def load_error_model(mode, seed, model, fragment_length, fragment_length_sd, sto
         if model is not None:
             logger.warning("--model %s will be ignored in --mode %s" % (model, mode))
         return BasicErrorModel(fragment_length, fragment_length_sd, store_mutations)
+    if mode == "perfect":  # generator.py:417-421 (the reference's model with store_mutations = False supplied: SURVEY.md A-8)
+        if model is not None:
+            logger.warning("--model %s will be ignored in --mode %s" % (model, mode))
+        return PerfectErrorModel(fragment_length, fragment_length_sd, store_mutations)
     if model is None:
         logger.error("--model is required in --mode kde")
         sys.exit(1)
@@ -183,14 +184,18 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, records=None):
+            fragment, compress=False, mode=None, records=None):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over."""
     logging.basicConfig(level=logging.WARNING)
     # (records are identified by their ordinal in the concatenated FASTA, not by id: draft assemblies repeat ids)
     records = list(records if records is not None else parse_fasta(genome_file))
-    if npz is None:  # --mode basic
+    if mode is None:  # (callers that name no mode: a model file is kde, none is basic)
+        mode = "kde" if npz is not None else "basic"
+    if mode == "basic":
         model = BasicErrorModel(fragment[0], fragment[1], store_mutations)
+    elif mode == "perfect":
+        model = PerfectErrorModel(fragment[0], fragment[1], store_mutations)
     else:
         model = KDErrorModel(npz, fragment[0], fragment[1], store_mutations)
     work = [(records[idx], n, "default") for idx, n in work_spec]
@@ -275,7 +280,7 @@ def generate_reads(args):
         spec = [(ordinal_of[id(rec)], n) for rec, n, _ in chunk]
         jobs.append((rank, rank % max(args.devices, 1), genome_file, spec, error_model.npz_path, args.seed,
                      temp_prefix(args.output, rank), args.sequence_type, args.gc_bias, args.rng, args.store_mutations,
-                     (args.fragment_length, args.fragment_length_sd), device_gzip))
+                     (args.fragment_length, args.fragment_length_sd), device_gzip, args.mode))
     t_gen = time.perf_counter()
     in_place = None
     if workers == 1:

@@ -45,6 +45,9 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
     read_switches(ctx);
     const size_t lds_bytes = main_lds_bytes(M);
     const bool heavy = M.n_scan > 0 && !ctx->light;  // reads with an indel event are common: scan + edit scripts + k_main<.., INDEL>
+    // PerfectErrorModel (quality mode 2; no indels, so never heavy): k_perfect instead of k_main -- ISS_PERFECT_KERNEL=0 keeps k_main
+    // on the same (degenerate) tables, an A/B route
+    const bool perfect = M.quality_mode == 2 && ctx->env_perfect != 0 && !heavy;
     // k_main's deferred queue: 13 bits for (pass of a workgroup, iteration of the pass); the tile with the fewest
     // workgroups (a short last tile) makes the most passes
     const unsigned it_max = ((unsigned)M.TS + 3u) / 4u - 1u;
@@ -231,7 +234,13 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
             HIP_TRY(ctx, hipStreamWaitEvent(s_main, ctx->ev_setup_done[slot_i], 0));
         }
         HIP_TRY(ctx, mark(1, s_main));
-        {
+        if (perfect) {
+            // PerfectErrorModel: the genome windows straight into the rows (iss_perfect.hip.h); one lane per 16-byte piece
+            const int64_t ppp = iss::perfect_pairs_per_pass(M.row);
+            const unsigned blocks = (unsigned)std::min<int64_t>((n + ppp - 1) / ppp, 8 * (int64_t)ctx->n_cu);
+            hipLaunchKernelGGL(iss::k_perfect, dim3(blocks), dim3(iss::PERFECT_THREADS), 0, s_main, M, dg, A, desc);
+            ctx->main_kernel = "k_perfect";
+        } else {
             const uint64_t passes = ((uint64_t)n + iss::MAIN_PAIRS - 1) / iss::MAIN_PAIRS;  // a workgroup pass = 256 pairs
             // persistent grid, split over the position tiles in proportion to the tiles' work per pass -- a fixed part
             // (descriptor, addresses) + one part per iteration of 4 superitems, whether or not all four lanes of a pair have one

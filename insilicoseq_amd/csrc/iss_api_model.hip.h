@@ -42,7 +42,9 @@ int iss_model_upload(iss_ctx *ctx, const iss_model_tables *t) {
     iss::DevModel &M = ctx->M;
     M = iss::DevModel{};
     M.RL = RL; M.n_isize = t->n_isize; M.n_q = nq;
-    if (t->quality_mode != 0 && t->quality_mode != 1) return fail(ctx, ISS_E_INVALID, "quality_mode must be 0 (kde) or 1 (basic)");
+    if (t->quality_mode < 0 || t->quality_mode > 2) return fail(ctx, ISS_E_INVALID, "quality_mode must be 0 (kde), 1 (basic) or 2 (perfect)");
+    if (t->quality_mode == 2 && (nq < iss::PERFECT_PHRED + 1 || t->basic_insert_size < 0))
+        return fail(ctx, ISS_E_INVALID, "perfect model: needs phred thresholds 0..41, insert size >= 0");
     if (t->quality_mode == 1 && (nq < 41 || !(t->basic_sd >= 0.0) || !(t->basic_cap < 1.0) || t->basic_insert_size < 0))
         return fail(ctx, ISS_E_INVALID, "basic model: needs phred thresholds 0..41, sd >= 0, cap < 1, insert size >= 0");
     M.quality_mode = t->quality_mode;

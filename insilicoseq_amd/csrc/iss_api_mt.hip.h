@@ -72,7 +72,8 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     auto &m = ctx->mt;
     const int64_t CH = m.pool_ch ? m.pool_ch : 8192;  // (a worker of a set, lent for this call: its own turn length and buffers)
     const bool basic = M.quality_mode == 1;
-    const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, basic);
+    const bool kde = M.quality_mode == 0;  // (basic and perfect: walker only -- the resolver knows the KDE draws)
+    const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
     if (!m.pool_ch) { int rc_ = mt_reserve(ctx, 3 * ((size_t)(CH + 1) * py_need + 1248), 3 * ((size_t)(CH + 1) * np_need + 1248)); if (rc_) return rc_; }
     if (!(M.RL < G.L)) {
         // the reference draws the insert size BEFORE its assertion fails (generator.py:121-126, 130)
@@ -116,7 +117,7 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             return fail(ctx, ISS_E_SHORT_RECORD, "record shorter than read length for this ErrorModel");
         }
-        if (!basic) {  // (BasicErrorModel.random_insert_size is a constant: nothing is drawn)
+        if (kde) {  // (Basic / PerfectErrorModel.random_insert_size is a constant: nothing is drawn)
             const size_t want[2] = {0, 2};
             { int rc_ = mt_ensure(ctx, want); if (rc_) return rc_; }
             m.used[1] += 2;
@@ -127,7 +128,7 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     const iss::DevGenome dg{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0};
     const size_t fixed_lds = iss::mt_walk_fixed_lds_bytes(M.RL);
     const size_t rows_bytes = (((size_t)2 * M.NB * M.RL * M.mt_row_w + 1) & ~(size_t)1) * 4;  // 16-bit digit rows
-    const bool use_rows = !basic && rows_bytes + fixed_lds <= 150 * 1024;
+    const bool use_rows = kde && rows_bytes + fixed_lds <= 150 * 1024;
     const size_t lds_bytes = fixed_lds + (use_rows ? rows_bytes : 0);
     // Resolver path (k_mt_resolve + k_mt_emit) for plain runs; the sequential walker for indel-heavy models, the
     // BasicErrorModel, and for the single pairs the resolver hands back.
@@ -137,7 +138,7 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     {
         const char *force = getenv("ISS_MT_PATH");  // "walk": sequential walker only (testing aid)
         const bool allowed = !(force && !strcmp(force, "walk")) && ctx->mt_bounce_rate < 0.05 &&
-                             M.n_isize <= 4096 && !basic;
+                             M.n_isize <= 4096 && kde;
         const size_t budget = 160 * 1024 - 256;
         const uint32_t need_py = iss::mt_res_need_py(M.RL), need_np = iss::mt_res_need_np(M.RL);
         struct Cand { int pyv, npv; bool rows; resolve_fn fn; };
@@ -398,8 +399,7 @@ int mt_set_reserve(iss_ctx *ctx) {
     auto &t = ctx->mts;
     const iss::DevModel &M = ctx->M;
     const size_t W = (size_t)t.W;
-    const bool basic = M.quality_mode == 1;
-    const size_t need[2] = {iss::mt_py_need(M.RL), iss::mt_np_need(M.RL, basic)};
+    const size_t need[2] = {iss::mt_py_need(M.RL), iss::mt_np_need(M.RL, M.quality_mode)};
     if (!t.ch) {
         const char *e = getenv("ISS_MT_SET_TURN");  // pairs per worker and turn (tests: many turns)
         // (98 304 / W within 512 .. 4096: a worker whose resolver meets a pair for the walker loses the rest of its turn, a turn costs
@@ -575,6 +575,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     t.started = true;  // (from here on a failure leaves the set undefined)
     auto &m = ctx->mt;
     const bool basic = M.quality_mode == 1;
+    const bool kde = M.quality_mode == 0;  // (basic and perfect: walker only)
     // the resolver (k_mt_resolve_w + k_mt_emit_w) for plain runs, the walker for indel-heavy models and for the single pairs the
     // resolver hands back -- the choice of iss_generate_mt
     typedef void (*resolve_fn)(iss::DevModel, const iss::MtResolveJob *);
@@ -582,7 +583,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     size_t resolve_lds = 0;
     {
         const char *force = getenv("ISS_MT_PATH");  // "walk": sequential walker only (testing aid)
-        const bool allowed = !(force && !strcmp(force, "walk")) && ctx->mt_bounce_rate < 0.05 && M.n_isize <= 4096 && !basic;
+        const bool allowed = !(force && !strcmp(force, "walk")) && ctx->mt_bounce_rate < 0.05 && M.n_isize <= 4096 && kde;
         const size_t budget = 160 * 1024 - 256;
         const uint32_t need_py = iss::mt_res_need_py(M.RL), need_np = iss::mt_res_need_np(M.RL);
         struct Cand { int pyv, npv; bool rows; resolve_fn fn; };
@@ -622,7 +623,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         ws[w].gid = genome_ids[w];
         ws[w].boost = gc_bias ? 4 : 0;
     }
-    const size_t need[2] = {iss::mt_py_need(M.RL), iss::mt_np_need(M.RL, basic)};
+    const size_t need[2] = {iss::mt_py_need(M.RL), iss::mt_np_need(M.RL, M.quality_mode)};
     // Words a turn is given: `need` is the most ONE attempt at a pair can consume (the kernels stop in front of a pair they
     // might not finish: "starved"), but a turn of n pairs consumes n times the USUAL amount -- a plain pair takes 2 x (10 (RL - 1)
     // + 2 RL) + ~2 words of `random` and 2 + 2 x (2 + 2 RL + 2 per substitution) (+ 2) of numpy, a gc_bias rejection a whole
@@ -637,7 +638,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     };
     const size_t fixed_lds = iss::mt_walk_fixed_lds_bytes(M.RL);
     const size_t rows_bytes = (((size_t)2 * M.NB * M.RL * M.mt_row_w + 1) & ~(size_t)1) * 4;
-    const bool use_rows = !basic && rows_bytes + fixed_lds <= 150 * 1024;
+    const bool use_rows = kde && rows_bytes + fixed_lds <= 150 * 1024;
     const double guard = getenv("ISS_MT_GUARD") ? atof(getenv("ISS_MT_GUARD")) : 1e-6;
     if (!m.ev_main) {
         HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_main, hipEventDisableTiming));

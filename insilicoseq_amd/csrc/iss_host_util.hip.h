@@ -42,6 +42,7 @@ void read_switches(iss_ctx *ctx) {
     ctx->env_main_wgs = (e = getenv("ISS_MAIN_WGS")) ? std::max(1, atoi(e)) : 0;
     ctx->env_group = (e = getenv("ISS_MAIN_GROUP")) ? atoi(e) : -1;
     ctx->env_group_min = (e = getenv("ISS_MAIN_GROUP_MIN")) ? atoi(e) : 0;
+    ctx->env_perfect = (e = getenv("ISS_PERFECT_KERNEL")) ? atoi(e) : 1;
 }
 
 void free_model(iss_ctx *ctx) {

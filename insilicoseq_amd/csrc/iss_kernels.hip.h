@@ -206,8 +206,9 @@ struct DevModel {
     int32_t mt_row_w;             // 32-bit words per row of mt_rows (odd)
     const uint16_t *mt_rows;      // [2][NB][RL] rows of n_q leading digits min(q_thr >> 37, 0xffff) (no merging: index == phred)
     const uint32_t *mt_lim;       // [2][RL][5] ceil(thr / 2^26) of the 4 insertion thresholds and the largest deletion threshold    // BasicErrorModel (iss/error_models/basic.py)
-    int32_t quality_mode;         // 0 KDE tables; 1 basic: phred = round(-10 log10(1 - min(N(basic_mean, basic_sd), basic_cap)))
-    int32_t basic_insert_size;    // basic.py:21, :56-63 (no draw)
+    int32_t quality_mode;         // 0 KDE tables; 1 basic: phred = round(-10 log10(1 - min(N(basic_mean, basic_sd), basic_cap)));
+                                  // 2 perfect (perfect.py): every phred 40, no quality draw (Philox path: k_perfect, iss_perfect.hip.h)
+    int32_t basic_insert_size;    // basic.py:21, :56-63 / perfect.py:19, :45-52 (no draw)
     double basic_mean, basic_sd, basic_cap;
 };
 
@@ -613,8 +614,8 @@ __device__ __forceinline__ void setup_pair(const DevModel &M, const DevGenome &g
             frag = fabs(x) < 1e15 ? (int64_t)x : 0;  // int(): truncation toward zero
         }
         isz = frag - 2 * (int64_t)RL;
-    } else if (M.quality_mode == 1) {
-        isz = M.basic_insert_size;  // BasicErrorModel.random_insert_size: a constant, no draw (basic.py:56-63)
+    } else if (M.quality_mode != 0) {
+        isz = M.basic_insert_size;  // Basic / PerfectErrorModel.random_insert_size: a constant, no draw (basic.py:56-63, perfect.py:45-52)
         frag = isz + 2 * (int64_t)RL;
     } else {
         isz = count_lt(s_isize, M.n_isize, mk53(w0.x, w1.x));  // kde.py:97

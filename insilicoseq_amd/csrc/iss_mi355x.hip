@@ -2,7 +2,7 @@
 // Host side: context, HBM uploads (model tables, genomes; small records from an arena), launch sequencing on one HIP
 // stream for one record (iss_generate) or a whole work list (iss_generate_batch: records side by side in one arena),
 // HIP-event timing, downloads, the FASTQ pipeline (text or gzip members built on the device, copy stream, writer thread).
-// Device side: iss_kernels.hip.h (the Philox path), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
+// Device side: iss_kernels.hip.h (the Philox path), iss_perfect.hip.h (its perfect-model kernel), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
 // iss_fastq.hip.h, iss_deflate.hip.h; `model` (BAM tallies, KDE): iss_bam.hip.h.
 #include "iss_mi355x.h"
 
@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "iss_kernels.hip.h"
+#include "iss_perfect.hip.h"     // k_perfect: quality mode 2 (PerfectErrorModel)
 #include "iss_fastq.hip.h"
 #include "iss_deflate.hip.h"
 #include "iss_mt_compat.hip.h"

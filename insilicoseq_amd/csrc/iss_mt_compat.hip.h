@@ -225,10 +225,12 @@ __device__ __forceinline__ int wave_sum(int v) {
 // worst-case stream words one attempt at a pair can consume (randrange bounded at 64 words each)
 // (a randrange round: 64 candidates of one word, of two words once the bound passes 2^32 -- records of 2^32 bases and more)
 __host__ __device__ inline uint32_t mt_py_need(int RL) { return 256u + 2u * (10u * (uint32_t)(RL - 1) + 2u * (uint32_t)RL); }
-__host__ __device__ inline uint32_t mt_np_need(int RL, bool basic = false) {
-    // basic: the phreds of a mate are RL gaussians = RL/2 accepted polar candidates of 4 words (acceptance pi/4, expected
-    // 2.55 * RL words); 8 * RL + 1024 is tens of standard deviations above that (k_mt_walk also checks every round)
-    return 64u /* polar loop */ + 2u + 2u * (2u + 4u * (uint32_t)RL) + 2u + (basic ? 2u * (8u * (uint32_t)RL + 1024u) : 0u);
+__host__ __device__ inline uint32_t mt_np_need(int RL, int quality_mode = 0) {
+    // basic (1): the phreds of a mate are RL gaussians = RL/2 accepted polar candidates of 4 words (acceptance pi/4, expected
+    // 2.55 * RL words); 8 * RL + 1024 is tens of standard deviations above that (k_mt_walk also checks every round).
+    // perfect (2): no bin choice, no quality draw -- a mate's numpy words are its substitution picks only
+    if (quality_mode == 2) return 64u /* polar loop */ + 2u + 2u * (2u * (uint32_t)RL) + 2u;
+    return 64u /* polar loop */ + 2u + 2u * (2u + 4u * (uint32_t)RL) + 2u + (quality_mode == 1 ? 2u * (8u * (uint32_t)RL + 1024u) : 0u);
 }
 __host__ __device__ inline size_t mt_walk_fixed_lds_bytes(int RL) {
     const size_t rlp = (size_t)((RL + 63) & ~63);
@@ -309,7 +311,7 @@ __device__ __forceinline__ void mt_walk_body(const DevModel &M, const DevGenome 
     const uint32_t row_h = (uint32_t)M.mt_row_w * 2u;  // u16 entries per row
     for (int i = lane; i <= M.n_q; i += 64) mut_thr[i] = M.mut_thr[i];
     __syncthreads();
-    const uint32_t py_need = mt_py_need(RL), np_need = mt_np_need(RL, M.quality_mode == 1);
+    const uint32_t py_need = mt_py_need(RL), np_need = mt_np_need(RL, M.quality_mode);
     const uint32_t *py = A.py, *np = A.np;
     uint32_t opy = 0, onp = 0;
     const int64_t L = g.L;
@@ -445,8 +447,8 @@ __device__ __forceinline__ void mt_walk_body(const DevModel &M, const DevGenome 
                 frag = (int64_t)x;  // int(): truncation toward zero
             }
             isz = frag - 2 * (int64_t)RL;
-        } else if (M.quality_mode == 1) {
-            isz = M.basic_insert_size;  // BasicErrorModel.random_insert_size: a constant, no draw (basic.py:56-63)
+        } else if (M.quality_mode != 0) {
+            isz = M.basic_insert_size;  // Basic / PerfectErrorModel.random_insert_size: a constant, no draw (basic.py:56-63, perfect.py:45-52)
             frag = isz + 2 * (int64_t)RL;
         } else {
             // insert size: np.searchsorted(cdf, np.random.rand())  (kde.py:97)
@@ -564,6 +566,10 @@ __device__ __forceinline__ void mt_walk_body(const DevModel &M, const DevGenome 
                 abort_pair = basic_phreds(o, opy0 == 0u && onp0 == 0u);
                 if (!abort_pair && onp + 2u * (uint32_t)RL + 4u > A.np_avail) abort_pair = 1;  // room for the substitution picks
                 if (abort_pair) break;
+                __syncthreads();
+            } else if (M.quality_mode == 2) {
+                // PerfectErrorModel.gen_phred_scores: 40 everywhere, nothing drawn (perfect.py:36-43)
+                for (int p = lane; p < RL; p += 64) ql[p] = (uint8_t)PERFECT_PHRED;
                 __syncthreads();
             } else {
             // ---- gen_phred_scores: bin choice + one CDF inversion per position (kde.py:72-85)

@@ -258,6 +258,29 @@ class DenseModel(object):
         d.basic_mean_quality = int(mean_quality)
         return d
 
+    @classmethod
+    def perfect(cls, read_length=125, insert_size=200, quality=40):
+        """The tables of ``PerfectErrorModel`` (iss/error_models/perfect.py:14-52), shaped like ``basic()``'s: read length
+        125, insert size 200 (no draw), every phred 40 (the quality rows hold all their mass there), every substitution
+        "alternative" of a base the upper-case base itself (``np.random.choice`` over the identity distribution), no indels.
+        Quality mode 2: the engine draws no phred (k_perfect on the Philox path, no quality draw in the reference-compatible
+        mode); mut_sequence still runs on these tables, so a lower-case a/c/g/t is upper-cased where its error test fires."""
+        RL = int(read_length)
+        n_q = int(quality) + 1
+        qrow = np.zeros(n_q)
+        qrow[quality] = 1.0  # P(phred <= k): 0 below the quality, 1 from it on
+        subst_alt = np.zeros((2, RL, 4, 3), dtype=np.uint8)
+        for bi, b in enumerate(BASES):
+            subst_alt[:, :, bi, :] = ord(b)
+        d = cls(RL, np.array([1.0]), np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (2, 1)),
+                np.tile(np.array([0, 0, 0, 1], dtype=np.uint8), (2, 1)), np.tile(qrow, (2, N_BINS, RL, 1)),
+                np.tile(_choice_cdf([1 / 3, 1 / 3, 1 / 3]), (2, RL, 4, 1)), subst_alt, np.zeros((2, RL, 4)),
+                np.tile(np.frombuffer(BASES.encode(), dtype=np.uint8), (2, RL, 1)), np.zeros((2, RL, 4)),
+                np.array([phred_to_prob(q) for q in range(n_q + 1)]))
+        d.quality_mode = 2
+        d.basic_insert_size = int(insert_size)
+        return d
+
     # ----------------------------------------------------- dense (pickle-free) io
     def save(self, path):
         np.savez_compressed(
@@ -557,4 +580,39 @@ class BasicErrorModel(object):
         return DenseModel.basic(self.read_length, self.insert_size, self.quality_forward)
 
     def random_insert_size(self):
+        return self.insert_size
+
+
+class PerfectErrorModel(object):
+    """Host-side mirror of ``iss.error_models.perfect.PerfectErrorModel`` (perfect.py:7-52): same constructor and
+    attributes (every phred 40, insert size 200, identity substitutions, no indels); ``dense()`` gives the tables the engine
+    uploads (``DenseModel.perfect``, quality mode 2).  The pinned reference never sets ``store_mutations`` (its
+    ``mut_sequence`` then fails at the first error event); this mirror is that model with the
+    attribute supplied as False: ``store_mutations`` is accepted and ignored, a ``--store_mutations`` run records nothing."""
+
+    def __init__(self, fragment_length=None, fragment_sd=None, store_mutations=False):
+        self.read_length = 125
+        self.insert_size = 200
+        self.fragment_length = fragment_length
+        self.fragment_sd = fragment_sd
+        self.quality_forward = self.quality_reverse = 40
+        self.store_mutations = False
+        self.npz_path = None
+        self.subst_choices_for = self.subst_choices_rev = [
+            {b: (["A", "T", "C", "G"], [1 if b == x else 0 for x in "ATCG"]) for b in "ATCG"}
+            for _ in range(self.read_length)
+        ]
+        self.ins_for = self.ins_rev = self.del_for = self.del_rev = [
+            {"A": 0.0, "T": 0.0, "C": 0.0, "G": 0.0} for _ in range(self.read_length)
+        ]
+
+    def dense(self):
+        return DenseModel.perfect(self.read_length, self.insert_size, self.quality_forward)
+
+    def gen_phred_scores(self, mean_quality, orientation):
+        """perfect.py:36-43."""
+        return [40 for _ in range(self.read_length)]
+
+    def random_insert_size(self):
+        """perfect.py:45-52."""
         return self.insert_size
