@@ -123,6 +123,14 @@ int iss_genome_upload(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int32_
  * bits 2*(i%16).., A,T,C,G = 0..3), from host memory or -- codes_on_device != 0 -- from device memory of this GPU: what a
  * rank of a multi-GPU run receives in the one RCCL broadcast of the packed genomes (no ASCII, no host bounce). */
 int iss_genome_upload_packed(iss_ctx *ctx, const uint32_t *codes, int64_t length, int32_t codes_on_device, int32_t *genome_id);
+/* n records in one go (draft contigs: thousands of short records): the host stages their letters in iss_generate_batch's
+ * arena layout (the first record at coordinate 64, every record at a multiple of 32 bases, 64 bases of 'A' between records),
+ * one copy takes them to the device, one kernel (k_pack_group) packs the whole group, and one read-back of a per-record
+ * status table validates them.  genome_ids[k] is an ordinary genome id (every call takes it), or -1 for a record of no
+ * letters, of letters outside the rev_comp alphabet or longer than iss_genome_upload takes: its iss_genome_upload reports
+ * the error.  An iss_generate_batch call whose records are all of one group uses the group's buffers as its arena, with no
+ * copy.  Groups are freed by iss_genome_clear.  (Additive in ABI 8.) */
+int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii, const int64_t *lengths, int32_t *genome_ids);
 int iss_genome_clear(iss_ctx *ctx);
 
 /* Device output rows (R1 bases, R1 phred, R2 bases, R2 phred).  Reserve before generating.

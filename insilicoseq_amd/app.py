@@ -16,12 +16,12 @@ import random
 import logging
 import multiprocessing as mp
 import os
-import shutil
 import sys
 import time
 
 import numpy as np
 
+from . import drafts
 from .distributed import VCF_HEADER, concatenate_rank_files, temp_prefix
 from .generator import generate_work_divider, parse_fasta, worker_iterator, worker_set_iterator
 from .model import BasicErrorModel, KDErrorModel, PerfectErrorModel
@@ -225,47 +225,63 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
         raise
 
 
-def generate_reads(args):
+def load_readcount_or_abundance(args, records, error_model):
+    """load_readcount_or_abundance (iss/generator.py:497-594), in the reference's order of precedence, with --draft:
+    returns (readcount_dic, abundance_dic, n_reads) and writes _abundance.txt / _coverage.txt like the reference."""
     logger = logging.getLogger(__name__)
-    error_model = load_error_model(args.mode, args.seed, args.model, args.fragment_length, args.fragment_length_sd,
-                                   args.store_mutations, args.rng)
-    if not args.genomes:
-        logger.error("One of --genomes/-g is required")
-        sys.exit(1)
-    genome_file = args.output + ".iss.tmp.genomes.fasta"  # generator.py:468-469
-    with open(genome_file, "wb") as out:
-        for g in args.genomes:
-            with open(g, "rb") as fh:
-                shutil.copyfileobj(fh, out)
-    records = list(parse_fasta(genome_file))
-    if not records:
-        logger.error("Genome(s) file seems empty: %s" % genome_file)
-        sys.exit(1)
+    draft = args.draft or []
     ids = [r.id for r in records]
-    # load_readcount_or_abundance (iss/generator.py:497-594), in the reference's order of precedence
     readcount_dic = abundance_dic = None
     if args.readcount_file:
         logger.warning("--readcount_file disables --n_reads, n_reads will be calculated from the readcount file")
+        if draft:  # generator.py:519-520 (a RuntimeError there)
+            logger.error("readcount_file is only supported using --genomes, not --draft")
+            sys.exit(1)
         readcount_dic = parse_readcount_file(args.readcount_file)
         n_reads = sum(readcount_dic.values())
     else:
         n_reads = convert_n_reads(args.n_reads)
         if args.abundance_file:
             abundance_dic = parse_abundance_file(args.abundance_file)
+            if draft:  # file paths as keys: spread over the contigs by length
+                abundance_dic = drafts.expand_file_dic(abundance_dic, draft, "abundance")
         elif args.coverage_file:  # coverages instead of shares: the reads per record no longer depend on --n_reads
             logger.warning("--coverage_file disables --n_reads")
             abundance_dic = parse_abundance_file(args.coverage_file)
+            if draft:
+                abundance_dic = drafts.expand_file_dic(abundance_dic, draft, "coverage")
         elif args.coverage in ABUNDANCE:
-            abundance_dic = ABUNDANCE[args.coverage](ids)
+            if draft:  # drawn from the --abundance distribution (generator.py:554-561), _abundance.txt written on the way
+                abundance_dic = drafts.draft_abundance(ids, draft, ABUNDANCE[args.abundance],
+                                                       lambda d: _write_distribution(d, args.output, "abundance"), "coverage")
+            else:
+                abundance_dic = ABUNDANCE[args.coverage](ids)
             if args.n_reads:
                 abundance_dic = coverage_scaling(n_reads, abundance_dic, records, error_model.read_length)
             _write_distribution(abundance_dic, args.output, "coverage")
         elif args.abundance in ABUNDANCE:
-            abundance_dic = ABUNDANCE[args.abundance](ids)
-            _write_distribution(abundance_dic, args.output, "abundance")
+            if draft:
+                abundance_dic = drafts.draft_abundance(ids, draft, ABUNDANCE[args.abundance],
+                                                       lambda d: _write_distribution(d, args.output, "abundance"))
+            else:
+                abundance_dic = ABUNDANCE[args.abundance](ids)
+                _write_distribution(abundance_dic, args.output, "abundance")
         else:
             logger.error("Could not get abundance, or coverage or readcount information")
             sys.exit(1)
+    return readcount_dic, abundance_dic, n_reads
+
+
+def generate_reads(args):
+    logger = logging.getLogger(__name__)
+    error_model = load_error_model(args.mode, args.seed, args.model, args.fragment_length, args.fragment_length_sd,
+                                   args.store_mutations, args.rng)
+    # load_genomes (generator.py:424-494): --genomes then --draft into <out>.iss.tmp.genomes.fasta; --n_genomes (no --draft)
+    genome_file, records = drafts.load_genomes(args.genomes, args.draft, args.output, args.n_genomes)
+    if not records:
+        logger.error("Genome(s) file seems empty: %s" % genome_file)
+        sys.exit(1)
+    readcount_dic, abundance_dic, n_reads = load_readcount_or_abundance(args, records, error_model)
     workers = args.gpus
     # --compress: the workers' FASTQ files already hold gzip members built on the device (one per batch); concatenated
     # they are the .gz files util.compress would have made from the text (iss/util.py:255-268), which never exists
@@ -333,6 +349,9 @@ def main(argv=None):
     sub = p.add_subparsers(dest="cmd")
     g = sub.add_parser("generate")
     g.add_argument("--genomes", "-g", nargs="+")
+    g.add_argument("--draft", nargs="+", metavar="<draft.fasta>", help="draft genome(s): the contigs of a file are one genome")
+    g.add_argument("--n_genomes", "-u", type=int, metavar="<int>",
+                   help="take this many random records from the --genomes input (ignored with --draft)")
     g.add_argument("--model", "-m")
     g.add_argument("--mode", "-e", default="kde", choices=["kde", "basic", "perfect"])
     g.add_argument("--n_reads", "-n", default="1000000")

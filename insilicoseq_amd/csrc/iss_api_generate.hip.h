@@ -402,7 +402,21 @@ int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids,
         call_items.assign((size_t)n_items, iss::BatchItem{0, G.L, G.has_exceptions ? 1 : 0, 0});
         dg = iss::DevGenome{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0};
         any_exceptions = G.has_exceptions;
-    } else {
+    }
+    const int32_t group = single ? -1 : ctx->genomes[ids[0]].group;
+    bool direct = group >= 0;
+    for (int32_t k = 1; direct && k < n_items; ++k) direct = ctx->genomes[ids[(size_t)k]].group == group;
+    if (direct) {
+        // ---- every record of the call is of one group (iss_genome_upload_group): its buffers are the arena as they are
+        call_items.resize((size_t)n_items);
+        for (int32_t k = 0; k < n_items; ++k) {
+            const Genome &G = ctx->genomes[ids[(size_t)k]];
+            call_items[(size_t)k] = iss::BatchItem{G.coord, G.L, G.has_exceptions ? 1 : 0, 0};
+            any_exceptions |= G.has_exceptions;
+        }
+        const GenomeGroup &grp = ctx->groups[(size_t)group];
+        dg = iss::DevGenome{grp.packed, grp.mask, grp.ascii, 0, any_exceptions ? 1 : 0};
+    } else if (!single) {
         // ---- the records side by side in one arena (kept until another list of records is asked for; the buffers are
         // kept as long as they are large enough -- refilling them is ordered on the stream behind their last readers)
         if (ids != ctx->comm_ids) {

@@ -13,7 +13,19 @@ struct Genome {
     uint8_t *ascii = nullptr;
     int64_t L = 0;
     bool has_exceptions = false;
-    bool in_arena = false;  // small record: its three buffers are slices of a GenomeArena slab
+    bool in_arena = false;  // small record: its three buffers are slices of a GenomeArena slab (or of a GenomeGroup)
+    int32_t group = -1;     // iss_genome_upload_group: index into iss_ctx::groups; the buffers point into the group's arena
+    int64_t coord = 0;      //   at this coordinate
+};
+
+// iss_genome_upload_group: records packed side by side in iss_generate_batch's arena layout (coordinate 64 first, 32-base
+// aligned, 64 bases of padding between records); the arena iss_generate_batch uses as it is when a call's records are all
+// of one group.  `block` is a GenomeArena slice, or a hipMalloc of its own (`own`) for large groups.
+struct GenomeGroup {
+    uint8_t *block = nullptr;
+    bool own = false;
+    uint32_t *packed = nullptr, *mask = nullptr;  // word 0 = coordinate 0 (two readable words in front)
+    uint8_t *ascii = nullptr;
 };
 
 // Records of a long work list (draft genomes: thousands of contigs) are small: their buffers are cut from slabs
@@ -181,6 +193,9 @@ struct iss_ctx {
     std::vector<void *> model_allocs;
     // genomes
     std::vector<Genome> genomes;
+    std::vector<GenomeGroup> groups;
+    uint8_t *group_stage = nullptr;  // pinned staging of iss_genome_upload_group (letters, start coordinates, status read-back)
+    size_t group_stage_cap = 0;
     // outputs
     int64_t capacity = 0;
     uint8_t *out[4] = {nullptr, nullptr, nullptr, nullptr};  // ONE allocation of interleaved rows (iss::xp): out[k] = out[0] + iss::row_array_off(k)

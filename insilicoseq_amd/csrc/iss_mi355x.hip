@@ -26,6 +26,7 @@
 
 #include "iss_kernels.hip.h"
 #include "iss_perfect.hip.h"     // k_perfect: quality mode 2 (PerfectErrorModel)
+#include "iss_pack_group.hip.h"  // k_pack_group: records uploaded in groups (draft contigs)
 #include "iss_fastq.hip.h"
 #include "iss_deflate.hip.h"
 #include "iss_mt_compat.hip.h"

@@ -96,6 +96,30 @@ class ReadEngine(object):
         self._genome_lengths.append(int(a.size))
         return gid.value
 
+    def add_genomes(self, seqs):
+        """Upload several records in one group (iss_genome_upload_group: one copy, one pack kernel, one status read-back);
+        returns their genome ids, -1 for a record the group does not take (no letters, letters outside the rev_comp
+        alphabet): add_genome(seq) of that record raises the error."""
+        arrs = []
+        for seq in seqs:
+            if isinstance(seq, str):
+                seq = seq.encode("ascii")
+            arrs.append(np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else
+                        np.ascontiguousarray(seq, dtype=np.uint8))
+        n = len(arrs)
+        if not n:
+            return []
+        ptrs = np.array([a.ctypes.data if a.size else 0 for a in arrs], dtype=np.uint64)
+        lengths = np.array([a.size for a in arrs], dtype=np.int64)
+        ids = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.iss_genome_upload_group(self._ctx, n, ptrs.ctypes.data, lengths.ctypes.data, ids.ctypes.data))
+        # (ids are dense: the lengths of the records the group took, in order)
+        for gid, a in zip(ids.tolist(), arrs):
+            if gid >= 0:
+                assert gid == len(self._genome_lengths)
+                self._genome_lengths.append(int(a.size))
+        return ids.tolist()
+
     def add_genome_packed(self, codes, length, device_ptr=None):
         """Upload a record of plain A/C/G/T given as 2-bit codes (see distributed.pack_2bit): ``codes`` a uint32 array
         on the host, or ``device_ptr`` the address of the words in this GPU's memory (a slice of the broadcast buffer)."""

@@ -161,6 +161,15 @@ def worker_seed(seed, cpu_number):
     return int.from_bytes(os.urandom(8), "little")
 
 
+SMALL_RECORD = 1 << 20  # records of at most this many letters go into grouped uploads (the engine's SMALL_RECORD)
+
+
+def _seq_of(record):
+    """str / bytes / uint8 array as they are; Bio.Seq and the like through str()"""
+    seq = record.seq
+    return seq if isinstance(seq, (str, bytes, bytearray, np.ndarray)) else str(seq)
+
+
 class Worker(object):
     """State of one reference worker on one GPU: engine + uploaded genomes + running ordinal."""
 
@@ -168,6 +177,9 @@ class Worker(object):
     # kernels still run at their full rate, the (pinned) buffers are allocated in a quarter of the time of 2^20
     BATCH_PAIRS = int(os.environ.get("ISS_BATCH_PAIRS", 1 << 18))
     GENOME_BUDGET = 96 << 30  # letters kept resident in HBM (1.4 B each incl. the packed copies) before all are dropped
+    # records of at most SMALL_RECORD letters (draft contigs) are uploaded in groups of up to GROUP_BASES letters
+    # (ReadEngine.add_genomes: one copy, one pack kernel; a batch whose records are of one group needs no arena copies)
+    GROUP_BASES = 1 << 29
 
     def __init__(self, error_model, cpu_number, seed, device=None, rng="philox", compress=False):
         if rng not in ("philox", "mt"):
@@ -198,8 +210,16 @@ class Worker(object):
                              getattr(error_model, "fragment_sd", None) is not None)
         self.ordinal = 0
         self.timings = None
-        self._gids = {}  # id(record) -> (record, genome id on the device)
+        self._gids = {}  # id(record) -> (record, genome id on the device; -1: the group did not take it)
         self._resident = 0
+        self._plan, self._plan_at = [], {}  # the work list's records (plan()) and the first place of each
+
+    def plan(self, records):
+        """The records the work list will ask for, in order: a record's first genome_id() uploads it together with the
+        records after it that are not resident yet (upload_group)."""
+        self._plan, self._plan_at = list(records), {}
+        for i, record in enumerate(self._plan):
+            self._plan_at.setdefault(id(record), i)
 
     def close(self):
         self.engine.close()
@@ -213,17 +233,47 @@ class Worker(object):
         key = id(record)
         hit = self._gids.get(key)
         if hit is None or hit[0] is not record:
-            seq = record.seq  # str / bytes / uint8 array as they are; Bio.Seq and the like through str()
-            if not isinstance(seq, (str, bytes, bytearray, np.ndarray)):
-                seq = str(seq)
+            seq = _seq_of(record)
             if self._gids and self._resident + len(seq) > self.GENOME_BUDGET:
                 # a work list visits a record in one or two consecutive items: nothing uploaded so far is needed again
                 self.engine.clear_genomes()  # (waits for the device and the FASTQ pipeline first)
                 self._gids.clear()
                 self._resident = 0
+            at = self._plan_at.get(key)
+            if at is not None and self._plan[at] is record and len(seq) <= SMALL_RECORD:
+                self.upload_group(at)
+                hit = self._gids.get(key)
+        if hit is None or hit[0] is not record or hit[1] < 0:
+            # a large record, one outside the plan, or one its group did not take (the upload raises its error here)
+            seq = _seq_of(record)
             hit = self._gids[key] = (record, self.engine.add_genome(seq))
             self._resident += len(seq)
         return hit[1]
+
+    def upload_group(self, at):
+        """Upload the planned records from place `at` on that are not resident and small, in one group: up to GROUP_BASES
+        letters, and no further than GENOME_BUDGET (the record that would pass it is the next one to drop the others)."""
+        picked, seqs, size, seen = [], [], 0, set()
+        for record in self._plan[at:]:
+            key = id(record)
+            hit = self._gids.get(key)
+            if (hit is not None and hit[0] is record) or key in seen:
+                continue
+            if self.rng == "philox" and not (self.engine.read_length < len(record.seq)):
+                continue  # (skipped by the work loop: never uploaded)
+            seq = _seq_of(record)
+            if len(seq) > SMALL_RECORD:
+                continue
+            if self._resident + size + len(seq) > self.GENOME_BUDGET or (picked and size + len(seq) > self.GROUP_BASES):
+                break
+            seen.add(key)
+            picked.append(record)
+            seqs.append(seq)
+            size += len(seq)
+        for record, seq, gid in zip(picked, seqs, self.engine.add_genomes(seqs)):
+            self._gids[id(record)] = (record, gid)
+            if gid >= 0:
+                self._resident += len(seq)
 
     def simulate_reads(self, record, n_pairs, forward_handle, reverse_handle, mutations_handle, sequence_type,
                        gc_bias=False, writer_threads=4, flush=True):
@@ -437,6 +487,7 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
         sys.exit(1)
     w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
     w.timings = timings
+    w.plan(record for record, _n, _mode in work)
     if timings is not None:
         timings["t_ready"] = time.perf_counter()
     if store_mutations:
@@ -551,15 +602,46 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
 
         def gid_of(record):
             hit = gids.get(id(record))
-            if hit is None or hit[0] is not record:
-                seq = record.seq
-                if not isinstance(seq, (str, bytes, bytearray, np.ndarray)):
-                    seq = str(seq)
+            if hit is None or hit[0] is not record or hit[1] < 0:
+                # (a record its group did not take: the single upload raises its error here, where it always has)
+                seq = _seq_of(record)
                 if gids and resident[0] + len(seq) > budget:
                     over[0] = True  # (this round's pieces name the resident records: they go at the round's end)
                 hit = gids[id(record)] = (record, eng.add_genome(seq))
                 resident[0] += len(seq)
             return hit[1]
+
+        def upload_groups(records):
+            # the small records of the work lists in groups (Worker.upload_group), as far as the budget goes
+            picked, seqs, size, group = [], [], 0, [0]
+
+            def flush():
+                for record, seq, gid in zip(picked, seqs, eng.add_genomes(seqs)):
+                    gids[id(record)] = (record, gid)
+                    if gid >= 0:
+                        resident[0] += len(seq)
+                del picked[:], seqs[:]
+                group[0] = 0
+
+            for record in records:
+                if id(record) in gids:
+                    continue
+                seq = _seq_of(record)
+                if len(seq) > SMALL_RECORD:
+                    continue
+                if resident[0] + size + len(seq) > budget:
+                    break
+                if picked and group[0] + len(seq) > Worker.GROUP_BASES:
+                    flush()
+                gids[id(record)] = (record, -1)
+                picked.append(record)
+                seqs.append(seq)
+                size += len(seq)
+                group[0] += len(seq)
+            flush()
+
+        if hasattr(eng, "add_genomes"):  # (an engine that takes records one at a time gets them from gid_of)
+            upload_groups(record for work in works for record, _n, _m in work)
 
         def pieces(work, cpu):  # (record, genome id, pairs, id of the piece's first pair, short record?)
             for record, n_pairs, _mode in work:
