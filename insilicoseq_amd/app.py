@@ -207,7 +207,7 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
     the FINAL files were written (else the temp files were), or None when the set cannot be set up -- more workers than the engine takes, not enough memory for their stream buffers (three turns of
     stream words per worker and buffer: tens of GB from W = 512 on with long reads) -- BEFORE anything was written: the caller
     then takes the process pool, which has no such limit.  (ISS_HOST_FASTQ=1, the host formatter, is a Worker switch: the pool.)"""
-    from ._native import E_INVALID, E_NOMEM, EngineError
+    from ._native import EngineError
 
     logger = logging.getLogger(__name__)
     works = [[(records[idx], n, "default") for idx, n in j[3]] for j in jobs]
@@ -219,7 +219,7 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
             compress=device_gzip,
             final_prefix=args.output if len(jobs) == workers and os.environ.get("ISS_SET_TEMP_FILES", "") != "1" else None)
     except EngineError as e:
-        if e.code in (E_INVALID, E_NOMEM) and getattr(e, "before_output", False):
+        if getattr(e, "set_up_failed", False):  # (seeding, or the first call's stream buffers: nothing ran yet)
             logger.warning("%d workers side by side do not fit the device (%s): one process per worker instead" % (workers, e))
             return None
         raise
@@ -305,6 +305,8 @@ def generate_reads(args):
     elif args.rng == "mt" and args.devices == 1 and not args.store_mutations and args.seed is not None and workers <= 1024 \
             and os.environ.get("ISS_HOST_FASTQ", "") != "1":
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
+        if in_place is not None:
+            logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
             pool.starmap(_worker, jobs)

@@ -566,8 +566,9 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
     except PermissionError as e:
         logger.error("Failed to write %s output file(s): %s" % ("the" if final else "temporary", e))
         sys.exit(1)
-    eng = ReadEngine(0 if device is None else device)
+    eng, finished = None, False
     try:
+        eng = ReadEngine(0 if device is None else device)
         dense = _dense_of(error_model)
         eng.load_model(dense)
         at = [0] * W  # final files: where worker k's next byte goes
@@ -583,11 +584,13 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
                 os.ftruncate(fh.fileno(), total)
         if compress:
             eng.fastq_compress(True)
-        began = [False]  # (an engine error before the first round's rows exist leaves no output: the caller may take another path)
+        # e.set_up_failed: the set could not be set up (seeding, or no memory for the first call's stream buffers) -- nothing
+        # ran, and the caller may take the process pool instead; any other engine error is a failure of the set itself
+        began = [False]
         try:
             eng.seed_mt_workers([worker_seed(seed, c) for c in cpu_numbers])
         except _native.EngineError as e:
-            e.before_output = True
+            e.set_up_failed = True
             raise
         eng.mt_set_fragment(getattr(error_model, "fragment_length", None), getattr(error_model, "fragment_sd", None))
         # rows per worker and round (2^20 pairs per round for all workers together; 2^22 and 2^24 measured the same end to end:
@@ -597,7 +600,7 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
 
         # letters resident in HBM before all are dropped: Worker's budget less what the set itself holds on the device (stream
         # buffers, rows of a round -- up to a third of the memory)
-        budget = max(Worker.GENOME_BUDGET // 2, 1 << 30)
+        budget = Worker.GENOME_BUDGET // 2
         over = [False]
 
         def gid_of(record):
@@ -680,7 +683,7 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
             try:
                 done, status = eng.generate_mt_workers(g, n, row, sequence_type=sequence_type, gc_bias=gc_bias)
             except _native.EngineError as e:
-                e.before_output = not began[0]  # (the first call reserves the stream buffers: ISS_E_NOMEM comes from there)
+                e.set_up_failed = not began[0] and e.code == _native.E_NOMEM  # (the first call reserves the stream buffers)
                 raise
             began[0] = True
             scattered = []
@@ -703,12 +706,20 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
         eng.fastq_flush()
         if final and at != ends:  # every worker's text ends where the next one's starts
             raise RuntimeError("worker_set_iterator: a worker's text is not the size computed for it: %r / %r" % (at, ends))
+        finished = True
         return final
     finally:
-        eng.close()
+        if eng is not None:
+            eng.close()  # (waits for the writer thread)
         for fh3 in handles:
             for fh in fh3:
                 fh.close()
+        if final and not finished:  # the final files are full size from the start: a failed run must not leave them behind
+            for suffix in ("_R1.fastq", "_R2.fastq"):
+                try:
+                    os.remove("%s%s" % (final_prefix, suffix))
+                except FileNotFoundError:
+                    pass
 
 
 def lognormal_abundance(record_ids, rng):

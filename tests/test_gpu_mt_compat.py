@@ -23,6 +23,22 @@ def engine():
     eng.close()
 
 
+SET_RAN = b"workers side by side on one device"  # app.generate_reads: the worker set wrote the files
+SET_FELL_BACK = b"do not fit the device"  # app._run_worker_set: the set gave up, the process pool wrote them
+
+
+def _generate(argv, root, worker_set, env=None):
+    """`python -m insilicoseq_amd generate ARGV` (without --quiet); worker_set: the run must have taken the worker set --
+    its log line is there, the pool fallback's is not (the pool writes the same bytes)."""
+    p = subprocess.run([sys.executable, "-m", "insilicoseq_amd", "generate"] + list(argv), cwd=root, stderr=subprocess.PIPE,
+                       env=None if env is None else dict(os.environ, **env))
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-4000:]
+    if worker_set:
+        assert SET_FELL_BACK not in p.stderr, p.stderr.decode(errors="replace")[-4000:]
+        assert SET_RAN in p.stderr, p.stderr.decode(errors="replace")[-4000:]
+    return p.stderr
+
+
 def _res53(words):
     w = words.astype(np.uint64)
     return ((w[0::2] >> np.uint64(5)) * np.uint64(67108864) + (w[1::2] >> np.uint64(6))).astype(np.float64) / 9007199254740992.0
@@ -90,9 +106,8 @@ def test_generate_cli_basic_mode_equals_reference(tmp_path):
     """`--mode basic --rng mt` (BasicErrorModel on the device) == `iss generate --mode basic --cpus 2`."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path / "run")
-    subprocess.check_call([sys.executable, "-m", "insilicoseq_amd", "generate", "--genomes",
-                           os.path.join(GOLDEN, "genomes.fasta"), "--mode", "basic", "--rng", "mt", "-n", "400", "--seed", "42",
-                           "--cpus", "2", "--devices", "1", "-o", out, "--quiet"], cwd=root)
+    _generate(["--genomes", os.path.join(GOLDEN, "genomes.fasta"), "--mode", "basic", "--rng", "mt", "-n", "400", "--seed", "42",
+               "--cpus", "2", "--devices", "1", "-o", out], root, worker_set=True)
     z = np.load(os.path.join(GOLDEN, "generate", "genomes_basic_n400_seed42_cpus2.npz"))
     assert open(out + "_abundance.txt", "rb").read() == z["abundance"].tobytes()
     assert open(out + "_R1.fastq", "rb").read() == z["r1"].tobytes()
@@ -125,9 +140,9 @@ def test_generate_cli_equals_reference(cpus, tmp_path):
     """python -m insilicoseq_amd generate --rng mt == the reference's `iss generate --cpus N` output files."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path / "run")
-    subprocess.check_call([sys.executable, "-m", "insilicoseq_amd", "generate", "--genomes",
-                           os.path.join(GOLDEN, "genomes.fasta"), "--model", "hiseq", "-n", "600", "--seed", "42",
-                           "--cpus", str(cpus), "--devices", "1", "--rng", "mt", "-o", out, "--quiet"], cwd=root)
+    _generate(["--genomes", os.path.join(GOLDEN, "genomes.fasta"), "--model", "hiseq", "-n", "600", "--seed", "42",
+               "--cpus", str(cpus), "--devices", "1", "--rng", "mt", "-o", out] + (["--quiet"] if cpus == 1 else []), root,
+              worker_set=cpus > 1)
     z = np.load(os.path.join(GOLDEN, "generate", "genomes_hiseq_n600_seed42_cpus%d.npz" % cpus))
     assert open(out + "_abundance.txt", "rb").read() == z["abundance"].tobytes()
     assert open(out + "_R1.fastq", "rb").read() == z["r1"].tobytes()
@@ -150,11 +165,37 @@ def test_generate_cli_cpus8_equals_reference(case, tmp_path):
             fh.write(z["fasta"].tobytes())
     model, n, seed = case.split("_")[1], case.split("_")[2][1:], case.split("_")[3][4:]
     out = str(tmp_path / "run")
-    subprocess.check_call([sys.executable, "-m", "insilicoseq_amd", "generate", "--genomes", fasta, "--model", model, "-n", n,
-                           "--seed", seed, "--cpus", "8", "--devices", "1", "--rng", "mt", "-o", out, "--quiet"], cwd=root)
+    _generate(["--genomes", fasta, "--model", model, "-n", n, "--seed", seed, "--cpus", "8", "--devices", "1", "--rng", "mt",
+               "-o", out], root, worker_set=True)
     assert open(out + "_abundance.txt", "rb").read() == z["abundance"].tobytes()
     assert open(out + "_R1.fastq", "rb").read() == z["r1"].tobytes()
     assert open(out + "_R2.fastq", "rb").read() == z["r2"].tobytes()
+
+
+@pytest.mark.parametrize("temp_files", [False, True])
+@pytest.mark.parametrize("case", ["syn3_novaseq_n3000_seed7_cpus12", "genomes_hiseq_n1600_seed42_cpus11"])
+def test_generate_cli_two_digit_workers_equal_reference(case, temp_files, tmp_path):
+    """`iss generate --cpus 12` / `--cpus 11` (tests/golden/tooling/make_golden_cpus12.py): worker numbers 10 and 11 in the
+    same text job as 0 .. 9 -- the item sizes the host computes (fastq_text_bytes) and the text the device writes
+    (FastqItem.cpu_len) must agree for every width, in the final files (default) and, ISS_SET_TEMP_FILES=1, through the
+    workers' temp files and their concatenation.  cpus11 on data/genomes.fasta: uneven chunks, worker 10 alone at width 2."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    z = np.load(os.path.join(GOLDEN, "generate", case + ".npz"))
+    fasta = os.path.join(GOLDEN, "genomes.fasta")
+    if "fasta" in z.files:
+        fasta = str(tmp_path / "in.fasta")
+        with open(fasta, "wb") as fh:
+            fh.write(z["fasta"].tobytes())
+    model, n, seed, cpus = case.split("_")[1], case.split("_")[2][1:], case.split("_")[3][4:], case.split("_")[4][4:]
+    out = str(tmp_path / "run")
+    err = _generate(["--genomes", fasta, "--model", model, "-n", n, "--seed", seed, "--cpus", cpus, "--devices", "1", "--rng", "mt",
+                     "-o", out], root, worker_set=True, env={"ISS_SET_TEMP_FILES": "1"} if temp_files else None)
+    assert (b"(temporary files)" if temp_files else b"(final files)") in err
+    assert open(out + "_abundance.txt", "rb").read() == z["abundance"].tobytes()
+    assert open(out + "_R1.fastq", "rb").read() == z["r1"].tobytes()
+    assert open(out + "_R2.fastq", "rb").read() == z["r2"].tobytes()
+    assert sorted(os.listdir(str(tmp_path))) == sorted(["run_abundance.txt", "run_R1.fastq", "run_R2.fastq"] +
+                                                       (["in.fasta"] if "fasta" in z.files else []))
 
 
 @pytest.mark.parametrize("turn", [None, "37", "37/3"])
@@ -225,6 +266,23 @@ def test_generate_cli_compress_equals_reference(cpus, tmp_path):
     assert left == ["run.vcf.gz", "run_R1.fastq.gz", "run_R2.fastq.gz", "run_abundance.txt"], left
 
 
+def test_generate_cli_compress_worker_set_equals_reference(tmp_path):
+    """`--compress --cpus 2` without --store_mutations: the worker set writes gzip members into the workers' temp files
+    (a member's size is not known up front: no final-file mode), concatenated in worker order."""
+    import gzip
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "run")
+    err = _generate(["--genomes", os.path.join(GOLDEN, "genomes.fasta"), "--model", "hiseq", "-n", "600", "--seed", "42",
+                     "--cpus", "2", "--devices", "1", "--rng", "mt", "--compress", "-o", out], root, worker_set=True)
+    assert b"(temporary files)" in err
+    z = np.load(os.path.join(GOLDEN, "generate", "genomes_hiseq_n600_seed42_cpus2.npz"))
+    assert gzip.open(out + "_R1.fastq.gz", "rb").read() == z["r1"].tobytes()
+    assert gzip.open(out + "_R2.fastq.gz", "rb").read() == z["r2"].tobytes()
+    left = sorted(os.listdir(str(tmp_path)))
+    assert left == ["run_R1.fastq.gz", "run_R2.fastq.gz", "run_abundance.txt"], left
+
+
 @pytest.mark.parametrize("case", ["halfnormal", "zero_inflated_lognormal", "exponential", "uniform", "coverage_lognormal",
                                   "coverage_halfnormal", "abundance_file", "coverage_file", "readcount_file"])
 def test_generate_cli_abundance_inputs_equal_reference(case, tmp_path):
@@ -238,9 +296,8 @@ def test_generate_cli_abundance_inputs_equal_reference(case, tmp_path):
         fh.write(z["given"].tobytes())
     flags = [given if f.startswith("@") else f for f in flags]
     out = str(tmp_path / "run")
-    subprocess.check_call([sys.executable, "-m", "insilicoseq_amd", "generate", "--genomes",
-                           os.path.join(GOLDEN, "genomes.fasta"), "--model", "hiseq", "--seed", "42", "--cpus", "2",
-                           "--devices", "1", "--rng", "mt", "-o", out, "--quiet"] + flags, cwd=root)
+    _generate(["--genomes", os.path.join(GOLDEN, "genomes.fasta"), "--model", "hiseq", "--seed", "42", "--cpus", "2",
+               "--devices", "1", "--rng", "mt", "-o", out] + flags, root, worker_set=True)
     assert open(out + "_R1.fastq", "rb").read() == z["r1"].tobytes()
     assert open(out + "_R2.fastq", "rb").read() == z["r2"].tobytes()
     assert os.path.exists(out + "_abundance.txt") == bool(z["has_abundance"])
