@@ -1,102 +1,173 @@
 // iss_api_mt.hip.h -- C ABI: the reference-identical mode (rng="mt") -- one worker per context (iss_generate_mt) and W workers side by side
-// (iss_generate_mt_workers), custom fragment lengths, --store_mutations rows.
+// (iss_generate_mt_workers), custom fragment lengths, --store_mutations rows.  Both run a worker's chain (MtChain) through
+// the same rules: mt_chain_generate is the single-worker path, the set's turn loop takes its other workers side by side.
 #pragma once
 
-extern "C" {
+namespace {
 
-// ------------------------------------------------------------------ reference-compatible MT mode
-int iss_mt_seed(iss_ctx *ctx, uint64_t seed) {
-    if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    if (seed > 0xffffffffull) return fail(ctx, ISS_E_INVALID, "seed must be < 2^32 (numpy's legacy seeding raises)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    auto &m = ctx->mt;
-    if (!m.d_state) {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, 2 * sizeof(iss::MtState)));
-        m.d_state = static_cast<iss::MtState *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtWalkResult)));
-        m.d_res = static_cast<iss::MtWalkResult *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtGauss)));
-        m.d_gauss = static_cast<iss::MtGauss *>(p);
+iss::DevGenome dev_genome(const Genome &G) { return iss::DevGenome{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0}; }
+
+// ISS_MT_GUARD: how close to a rounding boundary the device still decides (tests widen it); read once per call
+double mt_guard_env() {
+    const char *e = getenv("ISS_MT_GUARD");
+    return e ? atof(e) : 1e-6;
+}
+
+// The resolver (k_mt_resolve / k_mt_resolve_w + k_mt_emit) for plain runs; the sequential walker for indel-heavy models, the
+// BasicErrorModel and perfect mode (walker only -- the resolver knows the KDE draws), and for the single pairs the resolver
+// hands back.  The candidates (py ring, numpy ring in KB, digit rows in LDS) in order of preference: digit rows in LDS first,
+// then the smallest rings that show a whole pair; each path maps the pick to its instantiation through this one list.
+#define ISS_MT_RESOLVERS(X) X(8, 2, true) X(4, 2, true) X(8, 4, true) X(4, 4, true) X(8, 2, false) X(4, 2, false) X(8, 4, false) X(4, 4, false)
+#define ISS_MT_RESOLVE_ONE(P_, N_, R_) iss::k_mt_resolve<P_, N_, R_>,
+#define ISS_MT_RESOLVE_SET(P_, N_, R_) iss::k_mt_resolve_w<P_, N_, R_>,
+constexpr size_t MT_LDS_BUDGET = 160 * 1024 - 256;
+struct MtResolverPick { int idx = -1; size_t lds = 0; };  // idx: position in ISS_MT_RESOLVERS (-1: the walker only)
+MtResolverPick mt_pick_resolver(const iss_ctx *ctx) {
+    const iss::DevModel &M = ctx->M;
+    const char *force = getenv("ISS_MT_PATH");  // "walk": sequential walker only (testing aid)
+    MtResolverPick pick;
+    if ((force && !strcmp(force, "walk")) || !(ctx->mt_bounce_rate < 0.05) || M.n_isize > 4096 || M.quality_mode != 0) return pick;
+    struct Cand { int pyv, npv; bool rows; };
+#define ISS_MT_CAND(P_, N_, R_) Cand{P_, N_, R_},
+    const Cand cands[] = {ISS_MT_RESOLVERS(ISS_MT_CAND)};
+#undef ISS_MT_CAND
+    const uint32_t need_py = iss::mt_res_need_py(M.RL), need_np = iss::mt_res_need_np(M.RL);
+    for (int i = 0; i < (int)(sizeof cands / sizeof cands[0]); ++i) {
+        const Cand &c = cands[i];
+        if (need_py > (uint32_t)c.pyv * 1024u || need_np > (uint32_t)c.npv * 1024u) continue;
+        const size_t b = iss::mt_res_lds_bytes(M, c.pyv, c.npv, c.rows);
+        if (b > MT_LDS_BUDGET) continue;
+        pick.idx = i;
+        pick.lds = b;
+        break;
     }
-    HIP_TRY(ctx, hipMemset(m.d_gauss, 0, sizeof(iss::MtGauss)));  // np.random.seed() drops the cached gaussian
-    iss::MtState st[2];
-    const uint32_t key[1] = {(uint32_t)seed};
-    mt_init_by_array(st[0].mt, key, 1);       // random.seed(seed)
-    mt_init_genrand(st[1].mt, (uint32_t)seed);  // np.random.seed(seed)
-    HIP_TRY(ctx, hipMemcpy(m.d_state, st, sizeof st, hipMemcpyHostToDevice));
-    m.fill[0] = m.fill[1] = m.used[0] = m.used[1] = 0;
-    m.seeded = true;
+    return pick;
+}
+
+// the walker's LDS: a fixed part, and the 16-bit digit rows (KDE models, where they fit) for turns of more than 64 pairs
+struct MtWalkLds { size_t fixed, rows; bool use_rows; };
+MtWalkLds mt_walk_lds(const iss::DevModel &M) {
+    MtWalkLds l;
+    l.fixed = iss::mt_walk_fixed_lds_bytes(M.RL);
+    l.rows = (((size_t)2 * M.NB * M.RL * M.mt_row_w + 1) & ~(size_t)1) * 4;
+    l.use_rows = M.quality_mode == 0 && l.rows + l.fixed <= 150 * 1024;
+    return l;
+}
+
+// what both paths give the resolver of one worker's turn: its words, the turn, its results
+iss::MtResolveArgs mt_resolve_args(const MtChain &c, int64_t n, int32_t sequence_type, int32_t gc_bias, iss::MtPairRec *rec, double guard) {
+    iss::MtResolveArgs R{};
+    R.py_base = c.buf[0][c.cur[0]];
+    R.np_base = c.buf[1][c.cur[1]];
+    R.py_off = (uint32_t)c.used[0];
+    R.np_off = (uint32_t)c.used[1];
+    R.py_fill = (uint32_t)c.fill[0];
+    R.np_fill = (uint32_t)c.fill[1];
+    R.py_cap = (uint32_t)c.cap[0];
+    R.np_cap = (uint32_t)c.cap[1];
+    R.n_pairs = n;
+    R.sequence_type = sequence_type;
+    R.gc_bias = gc_bias ? 1 : 0;
+    R.gc_thr = MT_GC_THR;
+    R.res = c.d_res;
+    R.rec = rec;
+    R.guard = guard;
+    R.gauss = c.d_gauss;
+    return R;
+}
+
+// ... and the walker: the words in front of the chain, the turn, its rows from row0
+iss::MtWalkArgs mt_walk_args(const iss_ctx *ctx, const MtChain &c, int64_t n, int64_t row0, int64_t pair_base, int32_t sequence_type,
+                             int32_t gc_bias, bool use_rows, double guard) {
+    iss::MtWalkArgs A{};
+    A.py = c.buf[0][c.cur[0]] + c.used[0];
+    A.np = c.buf[1][c.cur[1]] + c.used[1];
+    A.py_avail = (uint32_t)(c.fill[0] - c.used[0]);
+    A.np_avail = (uint32_t)(c.fill[1] - c.used[1]);
+    A.n_pairs = n;
+    A.sequence_type = sequence_type;
+    A.gc_bias = gc_bias ? 1 : 0;
+    A.gc_thr = MT_GC_THR;
+    for (int k = 0; k < 4; ++k) A.out[k] = ctx->out[k] + (size_t)row0 * ctx->M.row;
+    A.res = c.d_res;
+    A.use_rows = use_rows && n > 64 ? 1 : 0;  // staging the rows (one wavefront, tens of KB) only pays for a real batch
+    A.pair_base = pair_base;
+    A.guard = guard;
+    A.gauss = c.d_gauss;
+    return A;
+}
+
+// Words wanted for a turn: those of n + 1 pairs, plus `boost` more when a turn made no progress on them -- with gc_bias every
+// rejected candidate pair (generator.py:82-92) consumes a whole pair's draws, and a turn of one pair that meets three
+// rejections in a row needs more than two pairs' worth.  A turn that stopped starved with `want` words in front of it grows it.
+int mt_grow_boost(iss_ctx *ctx, const iss::MtWalkResult &res, size_t py_avail, size_t np_avail, const size_t want[2], int64_t &boost) {
+    if (res.n_done != 0 || !res.starved || py_avail < want[0] || np_avail < want[1]) return 0;
+    if (boost >= 256) return fail(ctx, ISS_E_INVALID, "MT stream buffers too small for one read pair");
+    boost = 2 * boost + 4;
     return 0;
 }
 
-static int mt_reserve(iss_ctx *ctx, size_t cap_py, size_t cap_np) {
-    auto &m = ctx->mt;
+// a context's own chain: buffers of at least cap_py / cap_np words, the unconsumed words carried over
+int mt_reserve(iss_ctx *ctx, MtChain &c, size_t cap_py, size_t cap_np) {
     const size_t want[2] = {cap_py, cap_np};
     for (int s = 0; s < 2; ++s) {
-        if (m.cap[s] >= want[s]) continue;
-        if (m.fill[s] != m.used[s]) {  // keep the unconsumed words
-            std::vector<uint32_t> keep(m.fill[s] - m.used[s]);
-            HIP_TRY(ctx, hipMemcpy(keep.data(), m.buf[s][m.cur[s]] + m.used[s], keep.size() * 4, hipMemcpyDeviceToHost));
-            for (auto &b : m.buf[s]) { if (b) (void)hipFree(b); b = nullptr; }
-            for (auto &b : m.buf[s]) { void *p = nullptr; HIP_TRY(ctx, hipMalloc(&p, want[s] * 4)); b = static_cast<uint32_t *>(p); }
-            HIP_TRY(ctx, hipMemcpy(m.buf[s][0], keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
-            m.fill[s] = keep.size();
-        } else {
-            for (auto &b : m.buf[s]) { if (b) (void)hipFree(b); b = nullptr; }
-            for (auto &b : m.buf[s]) { void *p = nullptr; HIP_TRY(ctx, hipMalloc(&p, want[s] * 4)); b = static_cast<uint32_t *>(p); }
-            m.fill[s] = 0;
-        }
-        m.cur[s] = 0;
-        m.used[s] = 0;
-        m.cap[s] = want[s];
+        if (c.cap[s] >= want[s]) continue;
+        std::vector<uint32_t> keep(c.fill[s] - c.used[s]);  // the unconsumed words
+        if (!keep.empty()) HIP_TRY(ctx, hipMemcpy(keep.data(), c.buf[s][c.cur[s]] + c.used[s], keep.size() * 4, hipMemcpyDeviceToHost));
+        for (auto &b : c.buf[s]) { if (b) (void)hipFree(b); b = nullptr; }
+        for (auto &b : c.buf[s]) { void *p = nullptr; HIP_TRY(ctx, hipMalloc(&p, want[s] * 4)); b = static_cast<uint32_t *>(p); }
+        if (!keep.empty()) HIP_TRY(ctx, hipMemcpy(c.buf[s][0], keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
+        c.fill[s] = keep.size();
+        c.cur[s] = 0;
+        c.used[s] = 0;
+        c.cap[s] = want[s];
     }
     return 0;
 }
 
-int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t sequence_type, int32_t gc_bias,
-                    int64_t out_first_pair, int64_t *n_done) {
-    if (n_done) *n_done = 0;
-    if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_generate_mt: upload a model first");
-    if (!ctx->mt.seeded) return fail(ctx, ISS_E_INVALID, "iss_generate_mt: call iss_mt_seed first");
-    if (genome_id < 0 || genome_id >= (int32_t)ctx->genomes.size()) return fail(ctx, ISS_E_INVALID, "unknown genome id");
-    if (sequence_type != ISS_SEQ_METAGENOMICS && sequence_type != ISS_SEQ_AMPLICON)
-        return fail(ctx, ISS_E_INVALID, "sequence type is not supported");
-    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->capacity)
-        return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
+int mt_chain_peek(iss_ctx *ctx, MtChain &c, uint32_t *py_words, uint32_t *np_words, int32_t n) {
+    const size_t want[2] = {(size_t)n, (size_t)n};
+    { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+    if (py_words) HIP_TRY(ctx, hipMemcpyAsync(py_words, c.buf[0][c.cur[0]] + c.used[0], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (np_words) HIP_TRY(ctx, hipMemcpyAsync(np_words, c.buf[1][c.cur[1]] + c.used[1], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The single-worker path: n_pairs pairs of genome_id into rows [out_first_pair, + n_pairs) from chain c's streams, in turns of
+// c.ch pairs, the pairs counted in n_resolved / n_walked.  The context's own chain (iss_generate_mt), or a worker of the set for
+// what its side-by-side loop does not do itself.  The chain's buffers are its owner's, reserved before the call.
+int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pairs, int32_t sequence_type, int32_t gc_bias,
+                      int64_t out_first_pair, double guard, int64_t *n_done, int64_t &n_resolved, int64_t &n_walked) {
     const Genome &G = ctx->genomes[genome_id];
     const iss::DevModel &M = ctx->M;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
     auto &m = ctx->mt;
-    const int64_t CH = m.pool_ch ? m.pool_ch : 8192;  // (a worker of a set, lent for this call: its own turn length and buffers)
+    const int64_t CH = c.ch;
     const bool basic = M.quality_mode == 1;
     const bool kde = M.quality_mode == 0;  // (basic and perfect: walker only -- the resolver knows the KDE draws)
     const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
-    if (!m.pool_ch) { int rc_ = mt_reserve(ctx, 3 * ((size_t)(CH + 1) * py_need + 1248), 3 * ((size_t)(CH + 1) * np_need + 1248)); if (rc_) return rc_; }
     if (!(M.RL < G.L)) {
         // the reference draws the insert size BEFORE its assertion fails (generator.py:121-126, 130)
         if (m.has_frag) {
             // np.random.normal(mu, sd) (generator.py:122): numpy's legacy polar Box-Muller -- a cached second value is used up,
             // else candidates of two doubles each are drawn until 0 < r2 < 1 and f * x1 is cached -- replayed on the host (libm)
             iss::MtGauss gs;
-            HIP_TRY(ctx, hipMemcpy(&gs, m.d_gauss, sizeof gs, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(&gs, c.d_gauss, sizeof gs, hipMemcpyDeviceToHost));
             if (gs.has_gauss) {
                 gs.has_gauss = 0;
             } else {
                 for (size_t used = 0;;) {
                     const size_t want[2] = {0, used + 256};
-                    { int rc_ = mt_ensure(ctx, want); if (rc_) return rc_; }
+                    { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
                     uint32_t w[256];
                     // (on the context's stream, which mt_ensure has made wait for the refill: the streams are non-blocking, a copy
                     //  on the null stream would not be ordered behind the fill kernel and the leftover copy)
-                    HIP_TRY(ctx, hipMemcpyAsync(w, m.buf[1][m.cur[1]] + m.used[1] + used, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
+                    HIP_TRY(ctx, hipMemcpyAsync(w, c.buf[1][c.cur[1]] + c.used[1] + used, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                     bool done = false;
-                    for (int c = 0; c < 64 && !done; ++c) {
+                    for (int k = 0; k < 64 && !done; ++k) {
                         auto res53 = [](uint32_t a, uint32_t b) { return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0); };
-                        volatile double x1 = 2.0 * res53(w[4 * c], w[4 * c + 1]) - 1.0, x2 = 2.0 * res53(w[4 * c + 2], w[4 * c + 3]) - 1.0;
+                        volatile double x1 = 2.0 * res53(w[4 * k], w[4 * k + 1]) - 1.0, x2 = 2.0 * res53(w[4 * k + 2], w[4 * k + 3]) - 1.0;
                         volatile double a2 = x1 * x1, b2 = x2 * x2;
                         volatile double r2 = a2 + b2;
                         used += 4;
@@ -110,66 +181,40 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
                         gs.x2 = x2;
                         done = true;
                     }
-                    if (done) { m.used[1] += used; break; }
+                    if (done) { c.used[1] += used; break; }
                 }
             }
-            HIP_TRY(ctx, hipMemcpyAsync(m.d_gauss, &gs, sizeof gs, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(c.d_gauss, &gs, sizeof gs, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             return fail(ctx, ISS_E_SHORT_RECORD, "record shorter than read length for this ErrorModel");
         }
         if (kde) {  // (Basic / PerfectErrorModel.random_insert_size is a constant: nothing is drawn)
             const size_t want[2] = {0, 2};
-            { int rc_ = mt_ensure(ctx, want); if (rc_) return rc_; }
-            m.used[1] += 2;
+            { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+            c.used[1] += 2;
         }
         return fail(ctx, ISS_E_SHORT_RECORD, "record shorter than read length for this ErrorModel");
     }
     if (n_pairs == 0) return 0;
-    const iss::DevGenome dg{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0};
-    const size_t fixed_lds = iss::mt_walk_fixed_lds_bytes(M.RL);
-    const size_t rows_bytes = (((size_t)2 * M.NB * M.RL * M.mt_row_w + 1) & ~(size_t)1) * 4;  // 16-bit digit rows
-    const bool use_rows = kde && rows_bytes + fixed_lds <= 150 * 1024;
-    const size_t lds_bytes = fixed_lds + (use_rows ? rows_bytes : 0);
-    // Resolver path (k_mt_resolve + k_mt_emit) for plain runs; the sequential walker for indel-heavy models, the
-    // BasicErrorModel, and for the single pairs the resolver hands back.
+    const iss::DevGenome dg = dev_genome(G);
+    const MtWalkLds lds = mt_walk_lds(M);
     typedef void (*resolve_fn)(iss::DevModel, iss::DevGenome, iss::MtResolveArgs, iss::PairDesc *);
-    resolve_fn resolve = nullptr;
-    size_t resolve_lds = 0;
-    {
-        const char *force = getenv("ISS_MT_PATH");  // "walk": sequential walker only (testing aid)
-        const bool allowed = !(force && !strcmp(force, "walk")) && ctx->mt_bounce_rate < 0.05 &&
-                             M.n_isize <= 4096 && kde;
-        const size_t budget = 160 * 1024 - 256;
-        const uint32_t need_py = iss::mt_res_need_py(M.RL), need_np = iss::mt_res_need_np(M.RL);
-        struct Cand { int pyv, npv; bool rows; resolve_fn fn; };
-        const Cand cands[8] = {  // digit rows in LDS first, then the smallest rings that show a whole pair
-            {8, 2, true, iss::k_mt_resolve<8, 2, true>},   {4, 2, true, iss::k_mt_resolve<4, 2, true>},
-            {8, 4, true, iss::k_mt_resolve<8, 4, true>},   {4, 4, true, iss::k_mt_resolve<4, 4, true>},
-            {8, 2, false, iss::k_mt_resolve<8, 2, false>}, {4, 2, false, iss::k_mt_resolve<4, 2, false>},
-            {8, 4, false, iss::k_mt_resolve<8, 4, false>}, {4, 4, false, iss::k_mt_resolve<4, 4, false>}};
-        for (const Cand &c : cands) {
-            if (!allowed || resolve) break;
-            if (need_py > (uint32_t)c.pyv * 1024u || need_np > (uint32_t)c.npv * 1024u) continue;
-            const size_t b = iss::mt_res_lds_bytes(M, c.pyv, c.npv, c.rows);
-            if (b > budget) continue;
-            resolve = c.fn;
-            resolve_lds = b;
+    static const resolve_fn resolvers[] = {ISS_MT_RESOLVERS(ISS_MT_RESOLVE_ONE)};
+    const MtResolverPick pick = mt_pick_resolver(ctx);
+    const resolve_fn resolve = pick.idx >= 0 ? resolvers[pick.idx] : nullptr;
+    if (resolve) {
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MT_LDS_BUDGET));
+        if (!c.d_rec) {  // (the context's own chain; a worker of the set has its records from mt_set_reserve)
+            void *p = nullptr;
+            HIP_TRY(ctx, hipMalloc(&p, (size_t)CH * sizeof(iss::MtPairRec)));
+            c.d_rec = static_cast<iss::MtPairRec *>(p);
         }
-        if (resolve) {
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(resolve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)budget));
-            if (!m.d_rec) {
-                void *p = nullptr;
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)CH * sizeof(iss::MtPairRec)));
-                m.d_rec = static_cast<iss::MtPairRec *>(p);
-            }
-            if (!m.d_mut_cnt) {  // (sized for the longest turn: a lent chain brings its own, shorter, d_rec)
-                void *p = nullptr;
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int32_t)));
-                m.d_mut_cnt = static_cast<int32_t *>(p);
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int64_t)));
-                m.d_mut_off = static_cast<int64_t *>(p);
-            }
+        if (!m.d_mut_cnt) {  // (sized for the longest turn: a set worker's chain takes shorter ones)
+            void *p = nullptr;
+            HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int32_t)));
+            m.d_mut_cnt = static_cast<int32_t *>(p);
+            HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int64_t)));
+            m.d_mut_off = static_cast<int64_t *>(p);
         }
     }
     if (basic && !m.d_amb) {  // phreds the host has to round, and its answers
@@ -182,52 +227,33 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     m.mut_n = 0;
     bool ov_valid = false, walk_one = false;
     int64_t ov_frag = 0;
-    // words wanted for a turn: those of n + 1 pairs, plus `boost` more when a turn made no progress on them -- with
-    // gc_bias every rejected candidate pair (generator.py:82-92) consumes a whole pair's draws, and a turn of one pair that
-    // meets three rejections in a row needs more than two pairs' worth
-    int64_t boost = gc_bias ? 4 : 0;
+    int64_t boost = gc_bias ? 4 : 0;  // (mt_grow_boost)
     while (done < n_pairs) {
         const int64_t n = walk_one ? 1 : std::min(CH, n_pairs - done);
-        const size_t want[2] = {std::min(m.cap[0] / 624 * 624 - 624, (size_t)(n + 1 + boost) * py_need),
-                                std::min(m.cap[1] / 624 * 624 - 624, (size_t)(n + 1 + boost) * np_need)};
-        { int rc_ = mt_ensure(ctx, want); if (rc_) return rc_; }
+        const size_t want[2] = {std::min(c.cap[0] / 624 * 624 - 624, (size_t)(n + 1 + boost) * py_need),
+                                std::min(c.cap[1] / 624 * 624 - 624, (size_t)(n + 1 + boost) * np_need)};
+        { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
         MtPrefetch pf;
         if (!walk_one && done + n < n_pairs) {  // produce the next chunk's words while this chunk runs
             const int64_t n_next = std::min(CH, n_pairs - done - n);
             const size_t want_next[2] = {(size_t)(n_next + 1) * py_need, (size_t)(n_next + 1) * np_need};
-            { int rc_ = mt_prefetch_begin(ctx, want, want_next, &pf); if (rc_) return rc_; }
+            { int rc_ = mt_prefetch_begin(ctx, c, want, want_next, &pf); if (rc_) return rc_; }
         }
         const int64_t row0 = out_first_pair + done;
         iss::MtWalkResult res{};
         if (resolve && !walk_one) {
-            iss::MtResolveArgs R{};
-            R.py_base = m.buf[0][m.cur[0]];
-            R.np_base = m.buf[1][m.cur[1]];
-            R.py_off = (uint32_t)m.used[0];
-            R.np_off = (uint32_t)m.used[1];
-            R.py_fill = (uint32_t)m.fill[0];
-            R.np_fill = (uint32_t)m.fill[1];
-            R.py_cap = (uint32_t)m.cap[0];
-            R.np_cap = (uint32_t)m.cap[1];
-            R.n_pairs = n;
-            R.sequence_type = sequence_type;
-            R.gc_bias = gc_bias ? 1 : 0;
-            R.gc_thr = 8106479329266893ull;
-            R.res = m.d_res;
-            R.rec = m.d_rec;
+            iss::MtResolveArgs R = mt_resolve_args(c, n, sequence_type, gc_bias, c.d_rec, guard);
             R.has_frag = m.has_frag ? 1 : 0;
             R.frag_mu = m.frag_mu;
             R.frag_sd = m.frag_sd;
-            R.guard = getenv("ISS_MT_GUARD") ? atof(getenv("ISS_MT_GUARD")) : 1e-6;
-            R.gauss = m.d_gauss;
-            hipLaunchKernelGGL(resolve, dim3(1), dim3(iss::RES_THREADS), resolve_lds, ctx->stream, M, dg, R, ctx->desc + row0);
-            HIP_TRY(ctx, hipMemcpyAsync(&res, m.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+            hipLaunchKernelGGL(resolve, dim3(1), dim3(iss::RES_THREADS), pick.lds, ctx->stream, M, dg, R, ctx->desc + row0);
+            HIP_TRY(ctx, hipMemcpyAsync(&res, c.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             HIP_TRY(ctx, hipGetLastError());
             if (res.n_done > 0) {
                 auto emit = [&](const iss::MtEmitMut &E) {
                     hipLaunchKernelGGL(iss::k_mt_emit, dim3((unsigned)((2 * res.n_done + 3) / 4)), dim3(256), 0, ctx->stream, M, dg,
-                                       R.py_base, R.np_base, res.n_done, ctx->desc + row0, m.d_rec,
+                                       R.py_base, R.np_base, res.n_done, ctx->desc + row0, c.d_rec,
                                        ctx->out[0] + (size_t)row0 * M.row, ctx->out[1] + (size_t)row0 * M.row,
                                        ctx->out[2] + (size_t)row0 * M.row, ctx->out[3] + (size_t)row0 * M.row, E);
                 };
@@ -256,59 +282,41 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
                     m.mut_n = at;
                 }
             }
-            m.used[0] += res.py_used;
-            m.used[1] += res.np_used;
-            { int rc_ = mt_prefetch_commit(ctx, pf); if (rc_) return rc_; }
+            c.used[0] += res.py_used;
+            c.used[1] += res.np_used;
+            { int rc_ = mt_prefetch_commit(ctx, c, pf); if (rc_) return rc_; }
             done += res.n_done;
-            m.n_resolved += res.n_done;
+            n_resolved += res.n_done;
             if (res.pad) { walk_one = true; continue; }  // the next pair is not plain: one turn of the walker
-            if (res.n_done == 0 && res.starved && (size_t)(R.py_fill - R.py_off) >= want[0] &&
-                (size_t)(R.np_fill - R.np_off) >= want[1]) {
-                if (boost >= 256) return fail(ctx, ISS_E_INVALID, "MT stream buffers too small for one read pair");
-                boost = 2 * boost + 4;
-            }
+            { int rc_ = mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, want, boost); if (rc_) return rc_; }
             continue;
         }
-        iss::MtWalkArgs A{};
-        A.py = m.buf[0][m.cur[0]] + m.used[0];
-        A.np = m.buf[1][m.cur[1]] + m.used[1];
-        A.py_avail = (uint32_t)(m.fill[0] - m.used[0]);
-        A.np_avail = (uint32_t)(m.fill[1] - m.used[1]);
-        A.n_pairs = n;
-        A.sequence_type = sequence_type;
-        A.gc_bias = gc_bias ? 1 : 0;
-        A.gc_thr = 8106479329266893ull;
-        for (int k = 0; k < 4; ++k) A.out[k] = ctx->out[k] + (size_t)row0 * M.row;
-        A.res = m.d_res;
-        A.use_rows = use_rows && n > 64 ? 1 : 0;  // staging the rows (one wavefront, tens of KB) only pays for a real batch
+        iss::MtWalkArgs A = mt_walk_args(ctx, c, n, row0, done, sequence_type, gc_bias, lds.use_rows, guard);
         A.mut = m.d_mut;
         A.mut_cap = m.mut_cap;
         A.mut_base = m.mut_n;
-        A.pair_base = done;
         A.has_frag = m.has_frag ? 1 : 0;
         A.frag_mu = m.frag_mu;
         A.frag_sd = m.frag_sd;
         A.ov_valid = ov_valid ? 1 : 0;
         A.ov_frag = ov_frag;
-        A.guard = getenv("ISS_MT_GUARD") ? atof(getenv("ISS_MT_GUARD")) : 1e-6;
         if (basic && A.guard > 0.45) A.guard = 0.45;  // (a test aid: > 0.5 would make every phred "ambiguous" twice over)
-        A.gauss = m.d_gauss;
         A.amb = m.d_amb;
         A.ovq = m.d_amb ? m.d_amb + iss::MT_AMB_CAP : nullptr;
         A.n_ovq = (int32_t)ovq.size();
         if (!ovq.empty())
             HIP_TRY(ctx, hipMemcpyAsync(m.d_amb + iss::MT_AMB_CAP, ovq.data(), ovq.size() * sizeof(iss::MtPhredAmb),
                                         hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(iss::k_mt_walk, dim3(1), dim3(64), A.use_rows ? lds_bytes : fixed_lds, ctx->stream, M, dg, A,
+        hipLaunchKernelGGL(iss::k_mt_walk, dim3(1), dim3(64), A.use_rows ? lds.fixed + lds.rows : lds.fixed, ctx->stream, M, dg, A,
                            ctx->desc + row0);
-        HIP_TRY(ctx, hipMemcpyAsync(&res, m.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&res, c.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipGetLastError());
-        m.used[0] += res.py_used;
-        m.used[1] += res.np_used;
-        { int rc_ = mt_prefetch_commit(ctx, pf); if (rc_) return rc_; }
+        c.used[0] += res.py_used;
+        c.used[1] += res.np_used;
+        { int rc_ = mt_prefetch_commit(ctx, c, pf); if (rc_) return rc_; }
         done += res.n_done;
-        m.n_walked += res.n_done;
+        n_walked += res.n_done;
         m.mut_n += res.n_mut;
         // host answers (phreds, fragment length) belong to the attempt that started the launch: they stay only if the
         // walk stopped again at that very attempt (gc_bias rejections move on to a new attempt of the same pair)
@@ -337,14 +345,60 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
             ov_valid = true;
             continue;
         }
-        if (res.n_done == 0 && res.starved && A.py_avail >= want[0] && A.np_avail >= want[1]) {
-            if (boost >= 256) return fail(ctx, ISS_E_INVALID, "MT stream buffers too small for one read pair");
-            boost = 2 * boost + 4;
-        }
+        { int rc_ = mt_grow_boost(ctx, res, A.py_avail, A.np_avail, want, boost); if (rc_) return rc_; }
         if (res.n_done > 0) walk_one = false;
     }
     if (n_done) *n_done = done;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ reference-compatible MT mode
+int iss_mt_seed(iss_ctx *ctx, uint64_t seed) {
+    if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
+    if (seed > 0xffffffffull) return fail(ctx, ISS_E_INVALID, "seed must be < 2^32 (numpy's legacy seeding raises)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    auto &c = ctx->mt.chain;
+    if (!c.d_state) {
+        void *p = nullptr;
+        HIP_TRY(ctx, hipMalloc(&p, 2 * sizeof(iss::MtState)));
+        c.d_state = static_cast<iss::MtState *>(p);
+        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtWalkResult)));
+        c.d_res = static_cast<iss::MtWalkResult *>(p);
+        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtGauss)));
+        c.d_gauss = static_cast<iss::MtGauss *>(p);
+    }
+    HIP_TRY(ctx, hipMemset(c.d_gauss, 0, sizeof(iss::MtGauss)));  // np.random.seed() drops the cached gaussian
+    iss::MtState st[2];
+    mt_seed_streams(st, (uint32_t)seed);
+    HIP_TRY(ctx, hipMemcpy(c.d_state, st, sizeof st, hipMemcpyHostToDevice));
+    c.fill[0] = c.fill[1] = c.used[0] = c.used[1] = 0;
+    ctx->mt.seeded = true;
+    return 0;
+}
+
+int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t sequence_type, int32_t gc_bias,
+                    int64_t out_first_pair, int64_t *n_done) {
+    if (n_done) *n_done = 0;
+    if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_generate_mt: upload a model first");
+    if (!ctx->mt.seeded) return fail(ctx, ISS_E_INVALID, "iss_generate_mt: call iss_mt_seed first");
+    if (genome_id < 0 || genome_id >= (int32_t)ctx->genomes.size()) return fail(ctx, ISS_E_INVALID, "unknown genome id");
+    if (sequence_type != ISS_SEQ_METAGENOMICS && sequence_type != ISS_SEQ_AMPLICON)
+        return fail(ctx, ISS_E_INVALID, "sequence type is not supported");
+    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->capacity)
+        return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
+    const iss::DevModel &M = ctx->M;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    auto &c = ctx->mt.chain;
+    const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
+    { int rc_ = mt_reserve(ctx, c, 3 * ((size_t)(c.ch + 1) * py_need + 1248), 3 * ((size_t)(c.ch + 1) * np_need + 1248)); if (rc_) return rc_; }
+    return mt_chain_generate(ctx, c, genome_id, n_pairs, sequence_type, gc_bias, out_first_pair, mt_guard_env(), n_done,
+                             ctx->mt.n_resolved, ctx->mt.n_walked);
 }
 
 // ------------------------------------------------------------------ MT mode: W workers per launch (round 5)
@@ -373,25 +427,23 @@ int iss_mt_workers_seed(iss_ctx *ctx, int32_t n_workers, const uint64_t *seeds) 
     HIP_TRY(ctx, hipHostMalloc(&p, W * sizeof(iss::MtWalkResult), hipHostMallocDefault));
     t.h_res = static_cast<iss::MtWalkResult *>(p);
     std::vector<iss::MtState> st(2 * W);
-    for (size_t w = 0; w < W; ++w) {
-        const uint32_t key[1] = {(uint32_t)seeds[w]};
-        mt_init_by_array(st[2 * w].mt, key, 1);               // random.seed(seed)
-        mt_init_genrand(st[2 * w + 1].mt, (uint32_t)seeds[w]);  // np.random.seed(seed)
-    }
+    for (size_t w = 0; w < W; ++w) mt_seed_streams(&st[2 * w], (uint32_t)seeds[w]);
     HIP_TRY(ctx, hipMemcpy(t.d_state, st.data(), st.size() * sizeof(iss::MtState), hipMemcpyHostToDevice));
     t.W = n_workers;
     t.started = t.poisoned = false;
-    t.cur.assign(2 * W, 0);
-    t.fill.assign(2 * W, 0);
-    t.used.assign(2 * W, 0);
-    t.last_read.assign(6 * W, -1);
+    t.chains.assign(W, MtChain{});
+    for (size_t w = 0; w < W; ++w) {
+        MtChain &c = t.chains[w];
+        c.d_state = t.d_state + 2 * w;
+        c.d_res = t.d_res + w;
+        c.d_gauss = t.d_gauss + w;
+    }
+    t.last_read.assign(4 * W, -1);
     t.n_resolved = t.n_walked = 0;
     return 0;
 }
 
 namespace {
-
-constexpr int MT_SET_BUFS = 2;  // stream buffers per (worker, stream) in rotation (see iss_ctx::MtSet::buf)
 
 // stream buffers, pair records and job tables of the set, sized for the model (called by every generate call; a model with longer
 // reads than the buffers were cut for is refused: seed the set again)
@@ -414,7 +466,7 @@ int mt_set_reserve(iss_ctx *ctx) {
     const size_t turn_words[2] = {(size_t)(t.ch + 1) * need[0] + 1248, (size_t)(t.ch + 1) * need[1] + 1248};
     if (!t.buf_turns) {
         const char *e = getenv("ISS_MT_SET_BUF_TURNS");  // (tests: 3 = a move every second turn)
-        const size_t per_k = W * MT_SET_BUFS * (turn_words[0] + turn_words[1]) * sizeof(uint32_t);
+        const size_t per_k = W * 2 * (turn_words[0] + turn_words[1]) * sizeof(uint32_t);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)64 << 30; }
         const size_t budget = std::min((size_t)32 << 30, free_b / 2);  // (half of what is free at most: other engines share the device)
@@ -441,7 +493,7 @@ int mt_set_reserve(iss_ctx *ctx) {
                                     W * (sizeof(iss::MtResolveJob) + sizeof(iss::MtWalkJob) + sizeof(iss::MtEmitJob))) + 255) & ~(size_t)255;
         bool ok = true;
         for (int s = 0; s < 2 && ok; ++s)
-            for (int b = 0; b < MT_SET_BUFS && ok; ++b) {
+            for (int b = 0; b < 2 && ok; ++b) {
                 void *p = nullptr;
                 ok = hipMalloc(&p, W * want[s] * sizeof(uint32_t)) == hipSuccess;
                 t.buf[s][b] = ok ? static_cast<uint32_t *>(p) : nullptr;
@@ -452,7 +504,7 @@ int mt_set_reserve(iss_ctx *ctx) {
         if (ok && (ok = hipMalloc(&p, 2 * jobs_bytes) == hipSuccess)) t.d_jobs = static_cast<uint8_t *>(p);
         if (!ok) {
             undo();
-            return fail(ctx, ISS_E_NOMEM, "iss_generate_mt_workers: no memory for the workers' stream buffers (W x " + std::to_string((want[0] + want[1]) * MT_SET_BUFS * 4) + " bytes)");
+            return fail(ctx, ISS_E_NOMEM, "iss_generate_mt_workers: no memory for the workers' stream buffers (W x " + std::to_string((want[0] + want[1]) * 2 * 4) + " bytes)");
         }
         hipError_t e = hipSuccess;
         for (auto &ev : t.ev_emit) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -462,70 +514,17 @@ int mt_set_reserve(iss_ctx *ctx) {
         t.jobs_bytes = jobs_bytes;
         t.cap[0] = want[0];
         t.cap[1] = want[1];
+        for (size_t w = 0; w < W; ++w) {  // the workers' slices
+            MtChain &c = t.chains[w];
+            for (int s = 0; s < 2; ++s) {
+                c.cap[s] = want[s];
+                for (int b = 0; b < 2; ++b) c.buf[s][b] = t.buf[s][b] + w * want[s];
+            }
+            c.d_rec = t.d_rec + w * (size_t)t.ch;  // (the first of its two sets of pair records: the single-worker path's)
+            c.ch = t.ch;
+        }
     }
     return 0;
-}
-
-// One worker of the set through the single-worker path (iss_generate_mt): its chain is lent to ctx->mt for the call.  For what
-// the side-by-side loop below does not do itself: records shorter than a read (the reference draws before its assertion
-// fails), custom fragment lengths and the BasicErrorModel (draws the host's libm has to settle).
-struct MtChainLoan {
-    struct Chain {
-        bool seeded; iss::MtState *d_state; uint32_t *buf[2][2]; int cur[2]; size_t cap[2], fill[2], used[2];
-        iss::MtWalkResult *d_res; iss::MtGauss *d_gauss; iss::MtPairRec *d_rec; int64_t pool_ch;
-    };
-    iss_ctx *ctx;
-    int w;
-    Chain own;
-    int64_t r0, w0;
-    int base[2];
-    typedef decltype(iss_ctx::mt) MtLegacy;
-    static Chain save(const MtLegacy &m) {
-        Chain c;
-        c.seeded = m.seeded; c.d_state = m.d_state; c.d_res = m.d_res; c.d_gauss = m.d_gauss; c.d_rec = m.d_rec; c.pool_ch = m.pool_ch;
-        for (int s = 0; s < 2; ++s) {
-            c.cur[s] = m.cur[s]; c.cap[s] = m.cap[s]; c.fill[s] = m.fill[s]; c.used[s] = m.used[s];
-            for (int b = 0; b < 2; ++b) c.buf[s][b] = m.buf[s][b];
-        }
-        return c;
-    }
-    static void load(MtLegacy &m, const Chain &c) {
-        m.seeded = c.seeded; m.d_state = c.d_state; m.d_res = c.d_res; m.d_gauss = c.d_gauss; m.d_rec = c.d_rec; m.pool_ch = c.pool_ch;
-        for (int s = 0; s < 2; ++s) {
-            m.cur[s] = c.cur[s]; m.cap[s] = c.cap[s]; m.fill[s] = c.fill[s]; m.used[s] = c.used[s];
-            for (int b = 0; b < 2; ++b) m.buf[s][b] = c.buf[s][b];
-        }
-    }
-    MtChainLoan(iss_ctx *ctx_, int w_) : ctx(ctx_), w(w_) {
-        auto &t = ctx->mts;
-        auto &m = ctx->mt;
-        own = save(m);
-        r0 = m.n_resolved; w0 = m.n_walked;
-        Chain c;
-        c.seeded = true; c.d_state = t.d_state + 2 * (size_t)w; c.d_res = t.d_res + w; c.d_gauss = t.d_gauss + w;
-        c.d_rec = t.d_rec + (size_t)w * (size_t)t.ch; c.pool_ch = t.ch;  // (the first of its two sets of pair records)
-        for (int s = 0; s < 2; ++s) {  // (the single-worker path ping-pongs between the current buffer and the next of the rotation)
-            base[s] = t.cur[2 * w + s];
-            c.cur[s] = 0; c.cap[s] = t.cap[s]; c.fill[s] = t.fill[2 * w + s]; c.used[s] = t.used[2 * w + s];
-            for (int b = 0; b < 2; ++b) c.buf[s][b] = t.buf[s][(base[s] + b) % MT_SET_BUFS] + (size_t)w * t.cap[s];
-        }
-        load(m, c);
-    }
-    ~MtChainLoan() {
-        auto &t = ctx->mts;
-        auto &m = ctx->mt;
-        for (int s = 0; s < 2; ++s) { t.cur[2 * w + s] = (base[s] + m.cur[s]) % MT_SET_BUFS; t.fill[2 * w + s] = m.fill[s]; t.used[2 * w + s] = m.used[s]; }
-        t.n_resolved += m.n_resolved - r0;
-        t.n_walked += m.n_walked - w0;
-        m.n_resolved = r0;
-        m.n_walked = w0;
-        load(m, own);
-    }
-};
-int mt_set_single(iss_ctx *ctx, int w, int32_t genome_id, int64_t n_pairs, int32_t sequence_type, int32_t gc_bias, int64_t out_first_pair,
-                  int64_t *n_done) {
-    MtChainLoan loan(ctx, w);
-    return iss_generate_mt(ctx, genome_id, n_pairs, sequence_type, gc_bias, out_first_pair, n_done);
 }
 
 }  // namespace
@@ -575,35 +574,18 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     t.started = true;  // (from here on a failure leaves the set undefined)
     auto &m = ctx->mt;
     const bool basic = M.quality_mode == 1;
-    const bool kde = M.quality_mode == 0;  // (basic and perfect: walker only)
+    const double guard = mt_guard_env();
     // the resolver (k_mt_resolve_w + k_mt_emit_w) for plain runs, the walker for indel-heavy models and for the single pairs the
-    // resolver hands back -- the choice of iss_generate_mt
+    // resolver hands back -- the choice of the single-worker path
     typedef void (*resolve_fn)(iss::DevModel, const iss::MtResolveJob *);
-    resolve_fn resolve = nullptr;
-    size_t resolve_lds = 0;
-    {
-        const char *force = getenv("ISS_MT_PATH");  // "walk": sequential walker only (testing aid)
-        const bool allowed = !(force && !strcmp(force, "walk")) && ctx->mt_bounce_rate < 0.05 && M.n_isize <= 4096 && kde;
-        const size_t budget = 160 * 1024 - 256;
-        const uint32_t need_py = iss::mt_res_need_py(M.RL), need_np = iss::mt_res_need_np(M.RL);
-        struct Cand { int pyv, npv; bool rows; resolve_fn fn; };
-        const Cand cands[8] = {
-            {8, 2, true, iss::k_mt_resolve_w<8, 2, true>},   {4, 2, true, iss::k_mt_resolve_w<4, 2, true>},
-            {8, 4, true, iss::k_mt_resolve_w<8, 4, true>},   {4, 4, true, iss::k_mt_resolve_w<4, 4, true>},
-            {8, 2, false, iss::k_mt_resolve_w<8, 2, false>}, {4, 2, false, iss::k_mt_resolve_w<4, 2, false>},
-            {8, 4, false, iss::k_mt_resolve_w<8, 4, false>}, {4, 4, false, iss::k_mt_resolve_w<4, 4, false>}};
-        for (const Cand &c : cands) {
-            if (!allowed || resolve) break;
-            if (need_py > (uint32_t)c.pyv * 1024u || need_np > (uint32_t)c.npv * 1024u) continue;
-            const size_t b = iss::mt_res_lds_bytes(M, c.pyv, c.npv, c.rows);
-            if (b > budget) continue;
-            resolve = c.fn;
-            resolve_lds = b;
-        }
-        if (resolve) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget));
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(iss::k_mt_walk_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget));
-    }
-    // ---- what the side-by-side loop does not do itself goes through the single-worker path, one worker after the other
+    static const resolve_fn resolvers[] = {ISS_MT_RESOLVERS(ISS_MT_RESOLVE_SET)};
+    const MtResolverPick pick = mt_pick_resolver(ctx);
+    const resolve_fn resolve = pick.idx >= 0 ? resolvers[pick.idx] : nullptr;
+    if (resolve) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MT_LDS_BUDGET));
+    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(iss::k_mt_walk_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MT_LDS_BUDGET));
+    // ---- what the side-by-side loop does not do itself goes through the single-worker path, one worker after the other: records
+    //      shorter than a read (the reference draws before its assertion fails), custom fragment lengths and the BasicErrorModel
+    //      (draws the host's libm has to settle)
     struct WS { int64_t n = 0, done = 0, row0 = 0; int32_t gid = 0; bool walk_one = false; int64_t boost = 0; };
     std::vector<WS> ws((size_t)W);
     const bool one_by_one = m.has_frag || basic;
@@ -612,7 +594,8 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         const Genome &G = ctx->genomes[genome_ids[w]];
         if (one_by_one || !(M.RL < G.L)) {
             int64_t dn = 0;
-            const int rc = mt_set_single(ctx, w, genome_ids[w], n_pairs[w], sequence_type, gc_bias, out_first_pair[w], &dn);
+            const int rc = mt_chain_generate(ctx, t.chains[w], genome_ids[w], n_pairs[w], sequence_type, gc_bias, out_first_pair[w], guard, &dn,
+                                             t.n_resolved, t.n_walked);
             if (n_done) n_done[w] = dn;
             if (rc == ISS_E_SHORT_RECORD) { if (status) status[w] = rc; continue; }
             if (rc) return rc;
@@ -636,15 +619,11 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     auto words_for = [&](int s, int64_t n, int64_t boost) {
         return std::min((size_t)(n + 1 + boost) * need[s], (size_t)((double)n * est[s]) + (size_t)(4 + boost) * need[s]);
     };
-    const size_t fixed_lds = iss::mt_walk_fixed_lds_bytes(M.RL);
-    const size_t rows_bytes = (((size_t)2 * M.NB * M.RL * M.mt_row_w + 1) & ~(size_t)1) * 4;
-    const bool use_rows = kde && rows_bytes + fixed_lds <= 150 * 1024;
-    const double guard = getenv("ISS_MT_GUARD") ? atof(getenv("ISS_MT_GUARD")) : 1e-6;
+    const MtWalkLds lds = mt_walk_lds(M);
     if (!m.ev_main) {
         HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_main, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_fill, hipEventDisableTiming));
     }
-    auto bufp = [&](int w, int s, int b) { return t.buf[s][b] + (size_t)w * t.cap[s]; };
     const size_t fm_sz = std::max(sizeof(iss::MtFillJob), sizeof(iss::MtMoveJob));
     std::vector<int64_t> n_w((size_t)W);
     std::vector<size_t> want(2 * (size_t)W);
@@ -665,7 +644,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         const int par = (int)(turn & 1);
         // a buffer about to be WRITTEN (produced into, moved into) may still be read by an emitter: the one of two turns ago has
         // been waited for at the top of the turn, the one of the turn before only if a target says so
-        auto read_by_last_turn = [&](int k, int b) { return t.last_read[(size_t)k * 3 + b] == turn - 1; };
+        auto read_by_last_turn = [&](int k, int b) { return t.last_read[(size_t)k * 2 + b] == turn - 1; };
         uint8_t *hj = t.h_jobs + (size_t)par * t.jobs_bytes, *dj = t.d_jobs + (size_t)par * t.jobs_bytes;
         auto tab = [&](size_t k, uint8_t *base) { return base + k * 2 * (size_t)W * fm_sz; };  // tables 0..3 (fill / move), then the rest
         iss::MtFillJob *h_fill_e = reinterpret_cast<iss::MtFillJob *>(tab(0, hj)), *h_fill_a = reinterpret_cast<iss::MtFillJob *>(tab(1, hj));
@@ -684,29 +663,30 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         for (int w = 0; w < W; ++w)
             for (int s = 0; s < 2; ++s) {
                 const int k = 2 * w + s;
+                MtChain &c = t.chains[w];
                 h_fill_e[k] = iss::MtFillJob{nullptr, nullptr, 0u, 0u};
                 h_move_e[k] = iss::MtMoveJob{nullptr, nullptr, 0u, 0u};
                 want[k] = n_w[w] ? std::min(t.cap[s] / 624 * 624 - 624, words_for(s, n_w[w], ws[w].boost)) : 0;
-                const size_t left = t.fill[k] - t.used[k];
+                const size_t left = c.fill[s] - c.used[s];
                 if (left >= want[k]) continue;
                 const size_t missing = (want[k] - left + 623) / 624;
                 ++dbg_ensure;
-                if (t.fill[k] + missing * 624 <= t.cap[s]) {  // appended in place: nothing moves, nobody reads behind `fill`
-                    h_fill_e[k] = iss::MtFillJob{t.d_state + k, bufp(w, s, t.cur[k]) + t.fill[k], (uint32_t)missing, 0u};
-                    t.fill[k] += missing * 624;
+                if (c.fill[s] + missing * 624 <= t.cap[s]) {  // appended in place: nothing moves, nobody reads behind `fill`
+                    h_fill_e[k] = iss::MtFillJob{c.d_state + s, c.buf[s][c.cur[s]] + c.fill[s], (uint32_t)missing, 0u};
+                    c.fill[s] += missing * 624;
                     fill_e = true;
                     continue;
                 }
                 move_e = true;
-                const int nxt = (t.cur[k] + 1) % MT_SET_BUFS;
-                h_move_e[k] = iss::MtMoveJob{bufp(w, s, t.cur[k]) + t.used[k], bufp(w, s, nxt), (uint32_t)left, 0u};
+                const int nxt = c.cur[s] ^ 1;
+                h_move_e[k] = iss::MtMoveJob{c.buf[s][c.cur[s]] + c.used[s], c.buf[s][nxt], (uint32_t)left, 0u};
                 const size_t room = (t.cap[s] - left) / 624;
                 const uint32_t blocks = (uint32_t)std::min(room, (want[k] - left + 623) / 624);
-                h_fill_e[k] = iss::MtFillJob{t.d_state + k, bufp(w, s, nxt) + left, blocks, 0u};
+                h_fill_e[k] = iss::MtFillJob{c.d_state + s, c.buf[s][nxt] + left, blocks, 0u};
                 wait_prev_e |= read_by_last_turn(k, nxt);
-                t.cur[k] = nxt;
-                t.used[k] = 0;
-                t.fill[k] = left + (size_t)blocks * 624;
+                c.cur[s] = nxt;
+                c.used[s] = 0;
+                c.fill[s] = left + (size_t)blocks * 624;
                 fill_e = true;
             }
         if (fill_e) {
@@ -727,24 +707,25 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         for (int w = 0; w < W; ++w)
             for (int s = 0; s < 2; ++s) {
                 const int k = 2 * w + s;
+                MtChain &c = t.chains[w];
                 pf[k] = PF{};
                 h_fill_a[k] = iss::MtFillJob{nullptr, nullptr, 0u, 0u};
                 if (!n_w[w] || ws[w].walk_one || ws[w].done + n_w[w] >= ws[w].n) continue;
                 const int64_t n_next = std::min(t.ch, ws[w].n - ws[w].done - n_w[w]);
                 const size_t want_next = words_for(s, n_next, 0);
-                const size_t avail = t.fill[k] - t.used[k];
+                const size_t avail = c.fill[s] - c.used[s];
                 if (avail >= want[k] + want_next) continue;
                 // (only what is missing: everything in front of the turn is moved behind it -- a backlog would be copied every turn)
                 const size_t blocks = (want[k] + want_next - avail + 623) / 624;
-                if (t.fill[k] + blocks * 624 <= t.cap[s]) {  // appended in place (committed in (f) by moving `fill` on: no copy)
+                if (c.fill[s] + blocks * 624 <= t.cap[s]) {  // appended in place (committed in (f) by moving `fill` on: no copy)
                     pf[k].on = true; pf[k].append = true; pf[k].blocks = (uint32_t)blocks;
-                    h_fill_a[k] = iss::MtFillJob{t.d_state + k, bufp(w, s, t.cur[k]) + t.fill[k], (uint32_t)blocks, 0u};
+                    h_fill_a[k] = iss::MtFillJob{c.d_state + s, c.buf[s][c.cur[s]] + c.fill[s], (uint32_t)blocks, 0u};
                     fill_a = true;
                     continue;
                 }
                 if (avail + blocks * 624 > t.cap[s]) continue;
                 pf[k].on = true; pf[k].at = avail; pf[k].blocks = (uint32_t)blocks;
-                h_fill_a[k] = iss::MtFillJob{t.d_state + k, bufp(w, s, (t.cur[k] + 1) % MT_SET_BUFS) + avail, (uint32_t)blocks, 0u};
+                h_fill_a[k] = iss::MtFillJob{c.d_state + s, c.buf[s][c.cur[s] ^ 1] + avail, (uint32_t)blocks, 0u};
                 fill_a = true;
             }
         if (fill_a) {  // (behind everything queued on the main stream so far -- incl. its wait for the emitter of two turns ago -- and
@@ -762,8 +743,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         // ---- (c) the turn: the resolver for the workers on the fast path, the walker for the others
         bool any_res = false, any_walk = false, walk_rows = false;
         for (int w = 0; w < W; ++w) {
-            const Genome &G = ctx->genomes[ws[w].gid];
-            const iss::DevGenome dg{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0};
+            const MtChain &c = t.chains[w];
             const int64_t row0 = ws[w].row0 + ws[w].done;
             const bool walker = n_w[w] > 0 && (!resolve || ws[w].walk_one);
             iss::MtResolveJob &rj = h_rj[w];
@@ -771,59 +751,28 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             iss::MtWalkJob &wj = h_wj[w];
             wj = iss::MtWalkJob{};
             if (n_w[w] > 0 && !walker) {
-                iss::MtResolveArgs &R = rj.A;
-                R.py_base = bufp(w, 0, t.cur[2 * w]);
-                R.np_base = bufp(w, 1, t.cur[2 * w + 1]);
-                res_buf[2 * w] = t.cur[2 * w];
-                res_buf[2 * w + 1] = t.cur[2 * w + 1];
-                R.py_off = (uint32_t)t.used[2 * w];
-                R.np_off = (uint32_t)t.used[2 * w + 1];
-                R.py_fill = (uint32_t)t.fill[2 * w];
-                R.np_fill = (uint32_t)t.fill[2 * w + 1];
-                R.py_cap = (uint32_t)t.cap[0];
-                R.np_cap = (uint32_t)t.cap[1];
-                R.n_pairs = n_w[w];
-                R.sequence_type = sequence_type;
-                R.gc_bias = gc_bias ? 1 : 0;
-                R.gc_thr = 8106479329266893ull;
-                R.res = t.d_res + w;
-                R.rec = t.d_rec + ((size_t)par * (size_t)W + (size_t)w) * (size_t)t.ch;
-                R.has_frag = 0;
-                R.guard = guard;
-                R.gauss = t.d_gauss + w;
-                rj.g = dg;
+                rj.A = mt_resolve_args(c, n_w[w], sequence_type, gc_bias, t.d_rec + ((size_t)par * (size_t)W + (size_t)w) * (size_t)t.ch, guard);
+                res_buf[2 * w] = c.cur[0];
+                res_buf[2 * w + 1] = c.cur[1];
+                rj.g = dev_genome(ctx->genomes[ws[w].gid]);
                 rj.desc = ctx->desc + row0;
                 any_res = true;
             } else if (walker) {
-                iss::MtWalkArgs &A = wj.A;
-                A.py = bufp(w, 0, t.cur[2 * w]) + t.used[2 * w];
-                A.np = bufp(w, 1, t.cur[2 * w + 1]) + t.used[2 * w + 1];
-                A.py_avail = (uint32_t)(t.fill[2 * w] - t.used[2 * w]);
-                A.np_avail = (uint32_t)(t.fill[2 * w + 1] - t.used[2 * w + 1]);
-                A.n_pairs = n_w[w];
-                A.sequence_type = sequence_type;
-                A.gc_bias = gc_bias ? 1 : 0;
-                A.gc_thr = 8106479329266893ull;
-                for (int k = 0; k < 4; ++k) A.out[k] = ctx->out[k] + (size_t)row0 * M.row;
-                A.res = t.d_res + w;
-                A.use_rows = use_rows && n_w[w] > 64 ? 1 : 0;
-                A.pair_base = ws[w].done;
-                A.guard = guard;
-                A.gauss = t.d_gauss + w;
-                wj.g = dg;
+                wj.A = mt_walk_args(ctx, c, n_w[w], row0, ws[w].done, sequence_type, gc_bias, lds.use_rows, guard);
+                wj.g = dev_genome(ctx->genomes[ws[w].gid]);
                 wj.desc = ctx->desc + row0;
                 any_walk = true;
-                walk_rows |= A.use_rows != 0;
+                walk_rows |= wj.A.use_rows != 0;
             }
         }
         HIP_TRY(ctx, hipMemcpyAsync(d_rest, h_rest, (size_t)W * (sizeof(iss::MtResolveJob) + sizeof(iss::MtWalkJob)), hipMemcpyHostToDevice, ctx->stream));
         if (any_walk) {  // (beside the resolver: other workers; behind the words and tables the main stream has waited for / copied)
             HIP_TRY(ctx, hipEventRecord(t.ev_turn, ctx->stream));
             HIP_TRY(ctx, hipStreamWaitEvent(s_side, t.ev_turn, 0));
-            hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), walk_rows ? fixed_lds + rows_bytes : fixed_lds, s_side, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
+            hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), walk_rows ? lds.fixed + lds.rows : lds.fixed, s_side, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
             HIP_TRY(ctx, hipEventRecord(t.ev_side, s_side));
         }
-        if (any_res) hipLaunchKernelGGL(resolve, dim3(W), dim3(iss::RES_THREADS), resolve_lds, ctx->stream, M, reinterpret_cast<const iss::MtResolveJob *>(dev_of(h_rj)));
+        if (any_res) hipLaunchKernelGGL(resolve, dim3(W), dim3(iss::RES_THREADS), pick.lds, ctx->stream, M, reinterpret_cast<const iss::MtResolveJob *>(dev_of(h_rj)));
         if (any_walk) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, t.ev_side, 0));
         HIP_TRY(ctx, hipMemcpyAsync(t.h_res, t.d_res, (size_t)W * sizeof(iss::MtWalkResult), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -843,7 +792,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             for (int k = 0; k < 4; ++k) ej.out[k] = ctx->out[k] + (size_t)row0 * M.row;
             ej.g = h_rj[w].g;
             emit_max = std::max(emit_max, ej.n_pairs);
-            for (int s = 0; s < 2; ++s) t.last_read[(size_t)(2 * w + s) * 3 + res_buf[2 * w + s]] = turn;
+            for (int s = 0; s < 2; ++s) t.last_read[(size_t)(2 * w + s) * 2 + res_buf[2 * w + s]] = turn;
         }
         if (emit_max > 0) {  // (on its own stream: the next turn's resolver does not wait for it.  Launched here, in front of the walk
                              //  behind the turn, not after it: the walk would run on a quiet chip -- 0.19 ms beside the emitter --
@@ -861,30 +810,28 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         bool any_odd = false;
         for (int w = 0; w < W; ++w) {
             if (!n_w[w]) continue;
+            MtChain &c = t.chains[w];
             const iss::MtWalkResult &res = t.h_res[w];
-            const bool walker = h_wj[w].A.n_pairs > 0;
             if (res.need_host) return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: a draw for the host's libm on the side-by-side path");
-            t.used[2 * w] += res.py_used;
-            t.used[2 * w + 1] += res.np_used;
+            c.used[0] += res.py_used;
+            c.used[1] += res.np_used;
             ws[w].done += res.n_done;
             if (dbg) { dbg_starved += res.starved != 0; dbg_own += ws[w].walk_one; }
-            if (walker) {
+            if (h_wj[w].A.n_pairs > 0) {  // (the walker's)
+                const iss::MtWalkArgs &A = h_wj[w].A;
                 t.n_walked += res.n_done;
-                if (res.n_done == 0 && res.starved && h_wj[w].A.py_avail >= want[2 * w] && h_wj[w].A.np_avail >= want[2 * w + 1]) {
-                    if (ws[w].boost >= 256) return fail(ctx, ISS_E_INVALID, "MT stream buffers too small for one read pair");
-                    ws[w].boost = 2 * ws[w].boost + 4;
-                }
+                { int rc_ = mt_grow_boost(ctx, res, A.py_avail, A.np_avail, &want[2 * w], ws[w].boost); if (rc_) return rc_; }
                 if (res.n_done > 0) ws[w].walk_one = false;
             } else {
+                const iss::MtResolveArgs &R = h_rj[w].A;
                 t.n_resolved += res.n_done;
                 if (res.pad) {
                     ++dbg_bounce;
                     ws[w].walk_one = true;  // (unless the walk behind this turn takes it)
                     any_odd = true;
-                } else if (res.n_done == 0 && res.starved && (size_t)(h_rj[w].A.py_fill - h_rj[w].A.py_off) >= want[2 * w] &&
-                           (size_t)(h_rj[w].A.np_fill - h_rj[w].A.np_off) >= want[2 * w + 1]) {
-                    if (ws[w].boost >= 256) return fail(ctx, ISS_E_INVALID, "MT stream buffers too small for one read pair");
-                    ws[w].boost = 2 * ws[w].boost + 4;
+                } else {
+                    int rc_ = mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, &want[2 * w], ws[w].boost);
+                    if (rc_) return rc_;
                 }
             }
         }
@@ -892,34 +839,22 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             int n_odd = 0;
             for (int w = 0; w < W; ++w) {
                 const bool odd = n_w[w] > 0 && h_rj[w].A.n_pairs > 0 && t.h_res[w].pad && ws[w].done < ws[w].n;
+                const MtChain &c = t.chains[w];
                 iss::MtWalkJob &wj = h_wj[w];
                 wj = iss::MtWalkJob{};
                 // (the words of one attempt at a pair must stand in front of the walker: else the pair waits for its own turn)
-                if (dbg && odd && (t.fill[2 * w] - t.used[2 * w] < 2 * need[0] || t.fill[2 * w + 1] - t.used[2 * w + 1] < 2 * need[1])) ++dbg_skip;
-                if (!odd || t.fill[2 * w] - t.used[2 * w] < 2 * need[0] || t.fill[2 * w + 1] - t.used[2 * w + 1] < 2 * need[1]) continue;
-                const Genome &G = ctx->genomes[ws[w].gid];
+                const bool short_of_words = c.fill[0] - c.used[0] < 2 * need[0] || c.fill[1] - c.used[1] < 2 * need[1];
+                if (dbg && odd && short_of_words) ++dbg_skip;
+                if (!odd || short_of_words) continue;
                 const int64_t row0 = ws[w].row0 + ws[w].done;
-                iss::MtWalkArgs &A = wj.A;
-                A.py = bufp(w, 0, t.cur[2 * w]) + t.used[2 * w];
-                A.np = bufp(w, 1, t.cur[2 * w + 1]) + t.used[2 * w + 1];
-                A.py_avail = (uint32_t)(t.fill[2 * w] - t.used[2 * w]);
-                A.np_avail = (uint32_t)(t.fill[2 * w + 1] - t.used[2 * w + 1]);
-                A.n_pairs = 1;
-                A.sequence_type = sequence_type;
-                A.gc_bias = gc_bias ? 1 : 0;
-                A.gc_thr = 8106479329266893ull;
-                for (int k = 0; k < 4; ++k) A.out[k] = ctx->out[k] + (size_t)row0 * M.row;
-                A.res = t.d_res + w;
-                A.pair_base = ws[w].done;
-                A.guard = guard;
-                A.gauss = t.d_gauss + w;
-                wj.g = iss::DevGenome{G.packed, G.mask, G.ascii, G.L, G.has_exceptions ? 1 : 0};
+                wj.A = mt_walk_args(ctx, c, 1, row0, ws[w].done, sequence_type, gc_bias, false, guard);
+                wj.g = dev_genome(ctx->genomes[ws[w].gid]);
                 wj.desc = ctx->desc + row0;
                 ++n_odd;
             }
             if (n_odd) {
                 HIP_TRY(ctx, hipMemcpyAsync(dev_of(h_wj), h_wj, (size_t)W * sizeof(iss::MtWalkJob), hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), fixed_lds, ctx->stream, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
+                hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), lds.fixed, ctx->stream, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
                 HIP_TRY(ctx, hipMemcpyAsync(t.h_res, t.d_res, (size_t)W * sizeof(iss::MtWalkResult), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 HIP_TRY(ctx, hipGetLastError());
@@ -927,8 +862,8 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                     if (h_wj[w].A.n_pairs <= 0) continue;
                     const iss::MtWalkResult &res = t.h_res[w];
                     if (res.need_host) return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: a draw for the host's libm on the side-by-side path");
-                    t.used[2 * w] += res.py_used;
-                    t.used[2 * w + 1] += res.np_used;
+                    t.chains[w].used[0] += res.py_used;
+                    t.chains[w].used[1] += res.np_used;
                     ws[w].done += res.n_done;
                     t.n_walked += res.n_done;
                     if (res.n_done > 0) ws[w].walk_one = false;  // (a gc_bias rejection, or starved: the pair takes a turn of its own)
@@ -940,21 +875,22 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         for (int w = 0; w < W; ++w)
             for (int s = 0; s < 2; ++s) {
                 const int k = 2 * w + s;
+                MtChain &c = t.chains[w];
                 h_move_c[k] = iss::MtMoveJob{nullptr, nullptr, 0u, 0u};
                 if (!n_w[w] || !pf[k].on) continue;
                 if (pf[k].append) {
-                    t.fill[k] += (size_t)pf[k].blocks * 624;
+                    c.fill[s] += (size_t)pf[k].blocks * 624;
                     if (dbg) { dbg_filled[s] += (uint64_t)pf[k].blocks * 624; ++dbg_appends; }
                     continue;
                 }
-                const size_t left = t.fill[k] - t.used[k];  // <= pf.at
-                const int nxt = (t.cur[k] + 1) % MT_SET_BUFS;
-                h_move_c[k] = iss::MtMoveJob{bufp(w, s, t.cur[k]) + t.used[k], bufp(w, s, nxt) + (pf[k].at - left), (uint32_t)left, 0u};
+                const size_t left = c.fill[s] - c.used[s];  // <= pf.at
+                const int nxt = c.cur[s] ^ 1;
+                h_move_c[k] = iss::MtMoveJob{c.buf[s][c.cur[s]] + c.used[s], c.buf[s][nxt] + (pf[k].at - left), (uint32_t)left, 0u};
                 wait_prev_c |= read_by_last_turn(k, nxt);
                 if (dbg) { dbg_moved[s] += left; dbg_filled[s] += (uint64_t)pf[k].blocks * 624; ++dbg_moves; dbg_big += left > want[k] / 4; }
-                t.cur[k] = nxt;
-                t.used[k] = pf[k].at - left;
-                t.fill[k] = pf[k].at + (size_t)pf[k].blocks * 624;
+                c.cur[s] = nxt;
+                c.used[s] = pf[k].at - left;
+                c.fill[s] = pf[k].at + (size_t)pf[k].blocks * 624;
                 move_c = true;
             }
         if (move_c) {
@@ -988,8 +924,7 @@ int iss_mt_workers_peek(iss_ctx *ctx, int32_t worker, uint32_t *py_words, uint32
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int rc_ = sync_all(ctx); if (rc_) return rc_; }
     { int rc_ = mt_set_reserve(ctx); if (rc_) return rc_; }
-    MtChainLoan loan(ctx, worker);
-    return iss_mt_peek(ctx, py_words, np_words, n);
+    return mt_chain_peek(ctx, ctx->mts.chains[worker], py_words, np_words, n);
 }
 
 int iss_set_fragment(iss_ctx *ctx, int32_t enabled, double fragment_length, double fragment_sd) {
@@ -1105,14 +1040,8 @@ int iss_mt_path_counts(iss_ctx *ctx, int64_t *n_resolved, int64_t *n_walked) {
 int iss_mt_peek(iss_ctx *ctx, uint32_t *py_words, uint32_t *np_words, int32_t n) {
     if (!ctx || !ctx->mt.seeded || n < 0 || n > 624) return fail(ctx, ISS_E_INVALID, "iss_mt_peek: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = mt_reserve(ctx, 4 * 624, 4 * 624); if (rc_) return rc_; }
-    const size_t want[2] = {(size_t)n, (size_t)n};
-    { int rc_ = mt_ensure(ctx, want); if (rc_) return rc_; }
-    auto &m = ctx->mt;
-    if (py_words) HIP_TRY(ctx, hipMemcpyAsync(py_words, m.buf[0][m.cur[0]] + m.used[0], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (np_words) HIP_TRY(ctx, hipMemcpyAsync(np_words, m.buf[1][m.cur[1]] + m.used[1], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    { int rc_ = mt_reserve(ctx, ctx->mt.chain, 4 * 624, 4 * 624); if (rc_) return rc_; }
+    return mt_chain_peek(ctx, ctx->mt.chain, py_words, np_words, n);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// iss_host_mt_streams.hip.h -- reference-compatible MT mode, host side of the streams: MT19937 seeding as CPython / numpy do it,
-// the fill kernel's launches one chunk ahead, libm evaluations the device hands back.
+// iss_host_mt_streams.hip.h -- reference-compatible MT mode, host side of a worker's streams (MtChain): MT19937 seeding as
+// CPython / numpy do it, the fill kernel's launches one chunk ahead, libm evaluations the device hands back.
 #pragma once
 
 namespace {
@@ -24,6 +24,15 @@ void mt_init_by_array(uint32_t *mt, const uint32_t *key, int len) {
     }
     mt[0] = 0x80000000u;
 }
+// random.seed(seed); np.random.seed(seed): the two streams of one worker
+void mt_seed_streams(iss::MtState st[2], uint32_t seed) {
+    const uint32_t key[1] = {seed};
+    mt_init_by_array(st[0].mt, key, 1);
+    mt_init_genrand(st[1].mt, seed);
+}
+
+// gc_bias: a candidate pair is kept iff the 53-bit integer of its uniform draw is below this (iss/generator.py:88)
+constexpr uint64_t MT_GC_THR = 8106479329266893ull;  // ceil(0.90 * 2^53), 0.90 being the f64 nearest to 0.9
 
 // int(loc + scale * gaussian) exactly as numpy's legacy_gauss / normal evaluate it (libm, no contraction):
 // f = sqrt(-2*log(r2)/r2); fresh value f*x2, cached value f*x1.
@@ -45,7 +54,7 @@ int64_t host_int_normal(double x1v, double x2v, bool cached, double loc, double 
 // produced while the current chunk is consumed on ctx->stream.  The fill first waits for everything queued on
 // ctx->stream so far (an earlier k_mt_emit may still read the target buffer); ctx->stream waits for ev_fill
 // before it touches the new words (mt_fill_join).
-int mt_fill_async(iss_ctx *ctx, uint32_t *const dst[2], const uint32_t blocks[2]) {
+int mt_fill_async(iss_ctx *ctx, const MtChain &c, uint32_t *const dst[2], const uint32_t blocks[2]) {
     auto &m = ctx->mt;
     if (!blocks[0] && !blocks[1]) return 0;
     if (!m.ev_main) {
@@ -54,7 +63,7 @@ int mt_fill_async(iss_ctx *ctx, uint32_t *const dst[2], const uint32_t blocks[2]
     }
     HIP_TRY(ctx, hipEventRecord(m.ev_main, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->fill_stream, m.ev_main, 0));
-    hipLaunchKernelGGL(iss::k_mt_fill, dim3(2), dim3(iss::FILL_THREADS), 0, ctx->fill_stream, m.d_state, dst[0], dst[1], blocks[0],
+    hipLaunchKernelGGL(iss::k_mt_fill, dim3(2), dim3(iss::FILL_THREADS), 0, ctx->fill_stream, c.d_state, dst[0], dst[1], blocks[0],
                        blocks[1]);
     HIP_TRY(ctx, hipEventRecord(m.ev_fill, ctx->fill_stream));
     return 0;
@@ -83,27 +92,26 @@ int host_basic_phred(double x1v, double x2v, bool cached, double loc, double sca
     return (int)nearbyint(x);  // round-half-even, like Python's round() on a float
 }
 
-// make at least `want[s]` unconsumed words available in stream s (capacity permitting)
-int mt_ensure(iss_ctx *ctx, const size_t want[2]) {
+// make at least `want[s]` unconsumed words available in stream s of chain c (capacity permitting)
+int mt_ensure(iss_ctx *ctx, MtChain &c, const size_t want[2]) {
     uint32_t blocks[2] = {0, 0};
     uint32_t *dst[2] = {nullptr, nullptr};
     { int rc_ = mt_fill_join(ctx); if (rc_) return rc_; }
     for (int s = 0; s < 2; ++s) {
-        auto &m = ctx->mt;
-        const size_t left = m.fill[s] - m.used[s];
+        const size_t left = c.fill[s] - c.used[s];
         if (left >= want[s]) continue;
-        const int nxt = m.cur[s] ^ 1;
+        const int nxt = c.cur[s] ^ 1;
         if (left)
-            HIP_TRY(ctx, hipMemcpyAsync(m.buf[s][nxt], m.buf[s][m.cur[s]] + m.used[s], left * sizeof(uint32_t),
+            HIP_TRY(ctx, hipMemcpyAsync(c.buf[s][nxt], c.buf[s][c.cur[s]] + c.used[s], left * sizeof(uint32_t),
                                         hipMemcpyDeviceToDevice, ctx->stream));
-        const size_t room = (m.cap[s] - left) / 624;
+        const size_t room = (c.cap[s] - left) / 624;
         blocks[s] = (uint32_t)std::min(room, (want[s] - left + 623) / 624);
-        dst[s] = m.buf[s][nxt] + left;
-        m.cur[s] = nxt;
-        m.used[s] = 0;
-        m.fill[s] = left + (size_t)blocks[s] * 624;
+        dst[s] = c.buf[s][nxt] + left;
+        c.cur[s] = nxt;
+        c.used[s] = 0;
+        c.fill[s] = left + (size_t)blocks[s] * 624;
     }
-    { int rc_ = mt_fill_async(ctx, dst, blocks); if (rc_) return rc_; }
+    { int rc_ = mt_fill_async(ctx, c, dst, blocks); if (rc_) return rc_; }
     return mt_fill_join(ctx);
 }
 
@@ -116,33 +124,31 @@ struct MtPrefetch {
     size_t at[2] = {0, 0};
     uint32_t blocks[2] = {0, 0};
 };
-int mt_prefetch_begin(iss_ctx *ctx, const size_t want_cur[2], const size_t want_next[2], MtPrefetch *pf) {
-    auto &m = ctx->mt;
+int mt_prefetch_begin(iss_ctx *ctx, const MtChain &c, const size_t want_cur[2], const size_t want_next[2], MtPrefetch *pf) {
     uint32_t *dst[2] = {nullptr, nullptr};
     for (int s = 0; s < 2; ++s) {
-        const size_t avail = m.fill[s] - m.used[s];
+        const size_t avail = c.fill[s] - c.used[s];
         if (avail >= want_cur[s] + want_next[s]) continue;  // enough for both chunks already
         const size_t blocks = (want_next[s] + 623) / 624;
-        if (avail + blocks * 624 > m.cap[s]) continue;       // no room: the next mt_ensure fills synchronously
+        if (avail + blocks * 624 > c.cap[s]) continue;       // no room: the next mt_ensure fills synchronously
         pf->on[s] = true;
         pf->at[s] = avail;
         pf->blocks[s] = (uint32_t)blocks;
-        dst[s] = m.buf[s][m.cur[s] ^ 1] + avail;
+        dst[s] = c.buf[s][c.cur[s] ^ 1] + avail;
     }
-    return mt_fill_async(ctx, dst, pf->blocks);
+    return mt_fill_async(ctx, c, dst, pf->blocks);
 }
-int mt_prefetch_commit(iss_ctx *ctx, const MtPrefetch &pf) {
-    auto &m = ctx->mt;
+int mt_prefetch_commit(iss_ctx *ctx, MtChain &c, const MtPrefetch &pf) {
     for (int s = 0; s < 2; ++s) {
         if (!pf.on[s]) continue;
-        const size_t left = m.fill[s] - m.used[s];  // <= pf.at[s]
-        const int nxt = m.cur[s] ^ 1;
+        const size_t left = c.fill[s] - c.used[s];  // <= pf.at[s]
+        const int nxt = c.cur[s] ^ 1;
         if (left)
-            HIP_TRY(ctx, hipMemcpyAsync(m.buf[s][nxt] + (pf.at[s] - left), m.buf[s][m.cur[s]] + m.used[s],
+            HIP_TRY(ctx, hipMemcpyAsync(c.buf[s][nxt] + (pf.at[s] - left), c.buf[s][c.cur[s]] + c.used[s],
                                         left * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        m.cur[s] = nxt;
-        m.used[s] = pf.at[s] - left;
-        m.fill[s] = pf.at[s] + (size_t)pf.blocks[s] * 624;
+        c.cur[s] = nxt;
+        c.used[s] = pf.at[s] - left;
+        c.fill[s] = pf.at[s] + (size_t)pf.blocks[s] * 624;
     }
     return 0;
 }

@@ -135,6 +135,20 @@ struct FastqPipe {
 };
 constexpr size_t FASTQ_ID_MAX = 4096;
 
+// MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's
+// own worker (iss_mt_seed / iss_generate_mt) owns its allocations; a worker of a set (iss_mt_workers_seed) holds slices of the
+// set's.  Only the owner allocates or frees them: the single-worker path (mt_chain_generate) works on whichever chain it is given.
+struct MtChain {
+    iss::MtState *d_state = nullptr;      // [2]: CPython random, numpy
+    uint32_t *buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // stream x ping-pong (the next buffer: cur ^ 1)
+    int cur[2] = {0, 0};
+    size_t cap[2] = {0, 0}, fill[2] = {0, 0}, used[2] = {0, 0};
+    iss::MtWalkResult *d_res = nullptr;
+    iss::MtGauss *d_gauss = nullptr;
+    iss::MtPairRec *d_rec = nullptr;  // k_mt_resolve -> k_mt_emit: stream offsets of one launch's pairs (`ch` of them)
+    int64_t ch = 8192;                // pairs per turn of the single-worker path
+};
+
 }  // namespace
 
 struct iss_ctx {
@@ -245,24 +259,16 @@ struct iss_ctx {
     // reference-compatible MT19937 mode (iss_mt_compat.hip.h)
     struct {
         bool seeded = false;
-        iss::MtState *d_state = nullptr;      // [2]: CPython random, numpy
-        uint32_t *buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // stream x ping-pong
-        int cur[2] = {0, 0};
-        size_t cap[2] = {0, 0}, fill[2] = {0, 0}, used[2] = {0, 0};
-        iss::MtWalkResult *d_res = nullptr;
-        iss::MtGauss *d_gauss = nullptr;
+        MtChain chain;  // the context's own worker
         bool has_frag = false;
         double frag_mu = 0, frag_sd = 0;
         iss::MutRecord *d_mut = nullptr;  // --store_mutations rows of the last iss_generate_mt call
         int64_t mut_cap = 0, mut_n = 0;
         hipEvent_t ev_main = nullptr, ev_fill = nullptr;  // ordering between ctx->stream and the fill stream
         iss::MtPhredAmb *d_amb = nullptr;  // BasicErrorModel: [0, CAP) phreds for the host, [CAP, 2 CAP) its answers
-        iss::MtPairRec *d_rec = nullptr;  // k_mt_resolve -> k_mt_emit: stream offsets of one launch's pairs
         int32_t *d_mut_cnt = nullptr;     // k_mt_emit, --store_mutations: rows per (pair, mate), then their offsets
         int64_t *d_mut_off = nullptr;
         int64_t n_resolved = 0, n_walked = 0;  // pairs by path (statistics, iss_mt_path_counts)
-        int64_t pool_ch = 0;  // != 0: the chain (streams, buffers, records) is a worker's of the set below, lent for one call:
-                              // iss_generate_mt takes turns of this many pairs and leaves the buffers as they are
     } mt;
     // MT mode, W workers per launch (iss_mt_workers_seed / iss_generate_mt_workers): the reference's N workers (seed + cpu_number,
     // iss/generator.py:234-236) as N chains side by side -- one workgroup per worker and kernel, job tables in HBM
@@ -273,20 +279,20 @@ struct iss_ctx {
         size_t cap[2] = {0, 0};              // words per (worker, stream, ping-pong buffer)
         int buf_turns = 0;                   // ... = this many turns' words (worst case)
         iss::MtState *d_state = nullptr;     // [W][2]: CPython random, numpy
-        // [stream][buffer]: W x cap[stream] words, MT_SET_BUFS buffers in rotation.  A stream's words are appended to its current
-        // buffer turn after turn; at the buffer's end the stream moves to the next one of the rotation (mt_set_reserve).  Two: the
-        // words of turn t + 1 then go into the buffer the emitter of turn t - 1 may still read, so that fill starts behind it.  (Three -- the
-        // fill never waits for an emitter -- were built and measured in round 5: 3.1e7 against 4.2e7 pairs/s at W = 256: fill,
-        // emitter and resolver then all start together and the resolver, the chain everything waits for, is the one that loses.)
-        uint32_t *buf[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // (the first MT_SET_BUFS of each are allocated)
-        std::vector<int64_t> last_read;      // [W * 2][3]: the turn whose emitter reads that buffer (-1: none in flight)
+        // [stream][buffer]: W x cap[stream] words, two buffers.  A stream's words are appended to its current buffer turn after
+        // turn; at the buffer's end the stream moves to the other one (mt_set_reserve).  Two: the words of turn t + 1 then go into
+        // the buffer the emitter of turn t - 1 may still read, so that fill starts behind it.  (Three -- the fill never waits for
+        // an emitter -- were built and measured in round 5: 3.1e7 against 4.2e7 pairs/s at W = 256: fill, emitter and resolver
+        // then all start together and the resolver, the chain everything waits for, is the one that loses.)
+        uint32_t *buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+        std::vector<int64_t> last_read;      // [W * 2][2]: the turn whose emitter reads that buffer (-1: none in flight)
         iss::MtWalkResult *d_res = nullptr;  // [W]
         iss::MtGauss *d_gauss = nullptr;     // [W]
         iss::MtPairRec *d_rec = nullptr;     // [2][W][ch]: the resolver of turn t + 1 runs beside the emitter of turn t
         hipEvent_t ev_emit[2] = {nullptr, nullptr};  // the emitter of the last turn of either parity
         hipEvent_t ev_side = nullptr, ev_turn = nullptr;  // side stream (the walker beside the resolver) <-> main stream
-        std::vector<int> cur;                // [W * 2]
-        std::vector<size_t> fill, used;      // [W * 2]
+        // [W]: the workers' chains, slices of the allocations above (iss_mt_workers_seed; buffers and records from mt_set_reserve)
+        std::vector<MtChain> chains;
         // job tables: pinned host staging + device copies, two sets (turn parity) of
         // [fill: ensure 2W | fill: ahead 2W | move: ensure 2W | move: commit 2W] and [resolve W | walk W | emit W]
         uint8_t *h_jobs = nullptr, *d_jobs = nullptr;

@@ -96,29 +96,28 @@ void free_mt_set(iss_ctx *ctx) {
     t.ev_side = t.ev_turn = nullptr;
     t.d_state = nullptr; t.d_res = nullptr; t.d_gauss = nullptr; t.d_rec = nullptr; t.h_jobs = nullptr; t.d_jobs = nullptr; t.h_res = nullptr;
     t.W = 0; t.ch = 0; t.buf_turns = 0; t.cap[0] = t.cap[1] = 0; t.jobs_bytes = 0;
-    t.cur.clear(); t.fill.clear(); t.used.clear(); t.last_read.clear();
+    t.chains.clear(); t.last_read.clear();
 }
 
 void free_mt(iss_ctx *ctx) {
     free_mt_set(ctx);
-    if (ctx->mt.d_state) (void)hipFree(ctx->mt.d_state);
-    if (ctx->mt.d_res) (void)hipFree(ctx->mt.d_res);
-    if (ctx->mt.d_mut) (void)hipFree(ctx->mt.d_mut);
-    if (ctx->mt.d_gauss) (void)hipFree(ctx->mt.d_gauss);
-    if (ctx->mt.d_rec) (void)hipFree(ctx->mt.d_rec);
-    if (ctx->mt.d_mut_cnt) (void)hipFree(ctx->mt.d_mut_cnt);
-    if (ctx->mt.d_mut_off) (void)hipFree(ctx->mt.d_mut_off);
-    ctx->mt.d_rec = nullptr; ctx->mt.d_mut_cnt = nullptr; ctx->mt.d_mut_off = nullptr;
-    if (ctx->mt.d_amb) (void)hipFree(ctx->mt.d_amb);
-    ctx->mt.d_amb = nullptr;
-    if (ctx->mt.ev_main) (void)hipEventDestroy(ctx->mt.ev_main);
-    if (ctx->mt.ev_fill) (void)hipEventDestroy(ctx->mt.ev_fill);
-    ctx->mt.ev_main = ctx->mt.ev_fill = nullptr;
-    ctx->mt.d_gauss = nullptr;
-    ctx->mt.d_mut = nullptr; ctx->mt.mut_cap = 0;
-    for (auto &st : ctx->mt.buf) for (auto &b : st) { if (b) (void)hipFree(b); b = nullptr; }
-    ctx->mt.d_state = nullptr; ctx->mt.d_res = nullptr; ctx->mt.seeded = false;
-    ctx->mt.cap[0] = ctx->mt.cap[1] = 0;
+    auto &m = ctx->mt;
+    auto &c = m.chain;
+    if (c.d_state) (void)hipFree(c.d_state);
+    if (c.d_res) (void)hipFree(c.d_res);
+    if (c.d_gauss) (void)hipFree(c.d_gauss);
+    if (c.d_rec) (void)hipFree(c.d_rec);
+    for (auto &st : c.buf) for (auto &b : st) if (b) (void)hipFree(b);
+    c = MtChain{};
+    if (m.d_mut) (void)hipFree(m.d_mut);
+    if (m.d_mut_cnt) (void)hipFree(m.d_mut_cnt);
+    if (m.d_mut_off) (void)hipFree(m.d_mut_off);
+    if (m.d_amb) (void)hipFree(m.d_amb);
+    m.d_mut = nullptr; m.mut_cap = 0; m.d_mut_cnt = nullptr; m.d_mut_off = nullptr; m.d_amb = nullptr;
+    if (m.ev_main) (void)hipEventDestroy(m.ev_main);
+    if (m.ev_fill) (void)hipEventDestroy(m.ev_fill);
+    m.ev_main = m.ev_fill = nullptr;
+    m.seeded = false;
 }
 
 // k_main_g: the instantiations (iterations per pass NI, passes per group NP) the library holds -- a group is at most five

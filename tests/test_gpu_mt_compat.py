@@ -583,3 +583,108 @@ def test_short_record_first_after_seeding_keeps_the_streams(n_short):
         assert np.array_equal(got[k], exp[k]), k
     assert [int(x) for x in py] == [rng.py_word() for _ in range(8)]  # both streams stand where the oracle's stand
     assert [int(x) for x in npw] == [rng.np_word() for _ in range(8)]
+
+
+def _mt_engine(case, genomes):
+    """A ReadEngine with the model of `case` (novaseq, basic, novaseq_frag, indel_heavy) and `genomes` added."""
+    from insilicoseq_amd.engine import ReadEngine
+
+    eng = ReadEngine(0)
+    eng.load_model(dense_model("basic" if case == "basic" else "novaseq", (0.01, 0.03) if case == "indel_heavy" else None))
+    if case == "novaseq_frag":
+        eng.mt_set_fragment(420.0, 35.0)
+    return eng, [eng.add_genome(g) for g in genomes]
+
+
+def _rows(eng, first, n):
+    got = eng.download(first, n)
+    return {k: got[k].copy() for k in ("r1_base", "r1_qual", "r2_base", "r2_qual")}
+
+
+def _generate_or_short(eng, gid, n):
+    """generate_mt's rows, or None for a record shorter than a read."""
+    from insilicoseq_amd._native import E_SHORT_RECORD, EngineError
+
+    try:
+        assert eng.generate_mt(gid, n) == n
+    except EngineError as e:
+        assert e.code == E_SHORT_RECORD
+        return None
+    return _rows(eng, 0, n)
+
+
+@pytest.mark.parametrize("case", ["novaseq", "basic", "novaseq_frag", "indel_heavy"])
+def test_worker_set_peek_equals_separate_workers(case, monkeypatch):
+    """iss_mt_workers_peek after several calls of a set over a plain, a short and a mixed-letter record, in many short turns
+    with buffers of three turns: every worker's rows and both of its streams' next words equal those of an engine of its own
+    given seed_mt(seed_w) and the same generate_mt calls.  basic / novaseq_frag: every worker takes the single-worker path;
+    the short record: that path in every case."""
+    from helpers import mixed_genome, random_genome
+    from insilicoseq_amd._native import E_SHORT_RECORD
+
+    monkeypatch.setenv("ISS_MT_SET_TURN", "37")
+    monkeypatch.setenv("ISS_MT_SET_BUF_TURNS", "3")
+    genomes = [random_genome(211, 30000), random_genome(213, 120), mixed_genome(212, 9000)]  # plain, short, mixed
+    seeds = [31, 32, 35, 40]
+    W, rounds, stride = len(seeds), 4, 400
+    r = np.random.RandomState(9)
+    plan = [[((w + k) % 3, int(r.randint(1, 300))) for w in range(W)] for k in range(rounds)]  # (record, pairs) per round, worker
+    set_rows = [[None] * W for _ in range(rounds)]
+    eng, gids = _mt_engine(case, genomes)
+    with eng:
+        eng.seed_mt_workers(seeds)
+        for k, calls in enumerate(plan):
+            done, status = eng.generate_mt_workers([gids[g] for g, _ in calls], [n for _, n in calls],
+                                                   [w * stride for w in range(W)])
+            for w, (g, n) in enumerate(calls):
+                assert status[w] == (E_SHORT_RECORD if g == 1 else 0), (case, k, w)
+                if status[w] == 0:
+                    assert done[w] == n
+                    set_rows[k][w] = _rows(eng, w * stride, n)
+        set_peek = [eng.mt_workers_peek(w, 16) for w in range(W)]
+    for w, seed in enumerate(seeds):
+        one, gids = _mt_engine(case, genomes)
+        with one:
+            one.seed_mt(seed)
+            for k, calls in enumerate(plan):
+                g, n = calls[w]
+                got = _generate_or_short(one, gids[g], n)
+                assert (got is None) == (set_rows[k][w] is None), (case, k, w)
+                for key in () if got is None else got:
+                    assert np.array_equal(got[key], set_rows[k][w][key]), (case, k, w, key)
+            py, npw = one.mt_peek(16)
+        assert np.array_equal(py, set_peek[w][0]) and np.array_equal(npw, set_peek[w][1]), (case, w)
+
+
+@pytest.mark.parametrize("case", ["novaseq", "basic"])
+def test_worker_set_leaves_the_context_chain_alone(case):
+    """One engine's own chain (seed_mt / generate_mt / mt_peek) goes on where it stood across calls of a worker set in the same
+    context -- set workers on the side-by-side path and on the single-worker path (a short record; basic: every worker) -- and
+    its rows equal those of an engine that never ran a set."""
+    from helpers import mixed_genome, random_genome
+
+    genomes = [random_genome(221, 30000), random_genome(223, 120), mixed_genome(222, 9000)]  # plain, short, mixed
+    singles = [(0, 200), (2, 150), (1, 7), (0, 90)]  # (record, pairs) of the context's own calls
+    sets = [([0, 1, 2], [300, 5, 120]), ([2, 0, 1], [80, 260, 3])]  # a set call after each of the first two
+    got, exp = [], []
+    eng, gids = _mt_engine(case, genomes)
+    with eng:
+        eng.seed_mt(123)
+        eng.seed_mt_workers([7, 8, 9])
+        for k, (g, n) in enumerate(singles):
+            got.append(_generate_or_short(eng, gids[g], n))
+            if k < len(sets):
+                recs, ns = sets[k]
+                eng.generate_mt_workers([gids[x] for x in recs], ns, [0, 400, 800])
+        got.append(eng.mt_peek(16))
+    ref, gids = _mt_engine(case, genomes)
+    with ref:
+        ref.seed_mt(123)
+        for g, n in singles:
+            exp.append(_generate_or_short(ref, gids[g], n))
+        exp.append(ref.mt_peek(16))
+    for k in range(len(singles)):
+        assert (got[k] is None) == (exp[k] is None), (case, k)
+        for key in () if got[k] is None else got[k]:
+            assert np.array_equal(got[k][key], exp[k][key]), (case, k, key)
+    assert np.array_equal(got[-1][0], exp[-1][0]) and np.array_equal(got[-1][1], exp[-1][1]), case
