@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-/* 8: iss_main_kernel (which instantiation of the hot kernel the last Philox-mode call launched: k_main or k_main_g -- the
+/* 8: (additive, like the three entries before them) iss_vcf_emit / iss_vcf_flush: the --store_mutations text built on the device.
+ *    iss_main_kernel (which instantiation of the hot kernel the last Philox-mode call launched: k_main or k_main_g -- the
  *    rows of a group of passes wait in registers for their byte patches).
  * 7: W workers of the reference-identical mode side by side in one context (iss_mt_workers_seed, iss_generate_mt_workers,
  *    iss_mt_workers_peek); 36-bit coordinates in MT mode and the batch arena.
@@ -334,6 +335,25 @@ int iss_fastq_emit_scatter(iss_ctx *ctx, int fd_r1, int fd_r2, int32_t n_items, 
                            const int64_t *first_pair, const int64_t *n_pairs, const int32_t *cpu_numbers, const int64_t *file_off,
                            int32_t n_threads);
 int iss_fastq_flush(iss_ctx *ctx);
+
+/*
+ * The --store_mutations VCF rows as text built ON THE DEVICE: what write_mutations (iss/generator.py:598-620) writes per
+ * mutation -- "{record.id}_{i}_{cpu}/{mate + 1}\t{position + 1}\t.\t{ref}\t{alt}\t{qual}\t\t\n", alt = ref + alt for an
+ * insertion (iss/error_models/__init__.py:203), qual = the phred of a substitution, '.' otherwise -- for the rows of the last
+ * generate call, appended to fd at its current position, in call order.  source 0: the rows of the last iss_generate /
+ * iss_generate_batch call (the filter and the order of iss_mutations_download, applied on the device); source 1: the rows of the
+ * last iss_generate_mt call.  Item k is output rows [first_pair[k], +n_pairs[k]) of that call under record_ids[k] with pair ids
+ * from first_i[k] (the item table of iss_fastq_emit_batch); the items stand in ascending row order and do not overlap, rows of
+ * pairs outside every item are left out.  Asynchronous like iss_fastq_emit: the kernels run on the context's stream behind the
+ * generation; a writer thread fetches the text and appends it (pwrite) behind the next batch.  Only text crosses to the host,
+ * apart from one counter: a Philox call that reserved more row slots than iss_mutations_reserve gave it returns ISS_E_NOMEM,
+ * *slots_needed = the slots it asked for, and appends nothing (reading that counter waits for the generation).  On success
+ * *slots_needed is 0.  source 1 with more rows than iss_mt_mutations_reserve holds: ISS_E_INVALID.
+ * iss_vcf_flush waits until every queued byte is in the file and leaves the descriptor at its end (iss_fastq_flush does not).
+ */
+int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
+                 const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number, int64_t *slots_needed);
+int iss_vcf_flush(iss_ctx *ctx);
 
 /*
  * `--compress` (iss/app.py:134-143 -> util.compress, iss/util.py:255-268: gzip of the finished FASTQ files) moved in

@@ -86,6 +86,7 @@ void iss_ctx_destroy(iss_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     fastq_shutdown(ctx);
+    vcf_shutdown(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->indel_stream) (void)hipStreamSynchronize(ctx->indel_stream);
     if (ctx->fill_stream) (void)hipStreamSynchronize(ctx->fill_stream);

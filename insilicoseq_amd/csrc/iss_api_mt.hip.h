@@ -225,6 +225,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
     std::vector<iss::MtPhredAmb> ovq;  // answers for the pair that restarts
     int64_t done = 0;
     m.mut_n = 0;
+    m.mut_row0 = out_first_pair;
     bool ov_valid = false, walk_one = false;
     int64_t ov_frag = 0;
     int64_t boost = gc_bias ? 4 : 0;  // (mt_grow_boost)

@@ -1,0 +1,212 @@
+// iss_api_vcf.hip.h -- C ABI: the --store_mutations VCF text built on the device (iss_vcf_emit, iss_vcf_flush).
+#pragma once
+
+extern "C" {
+
+int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
+                 const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number, int64_t *slots_needed) {
+    if (slots_needed) *slots_needed = 0;
+    if (!ctx || !ctx->have_model || fd < 0 || n_items < 0 || cpu_number < 0 || (source != 0 && source != 1) ||
+        (n_items && (!record_ids || !first_i || !first_pair || !n_pairs)))
+        return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    VcfPipe &q = ctx->vq;
+    if (!q.ready) {
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
+        for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &p : q.h_total) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); p = static_cast<uint64_t *>(v); }
+        { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); q.h_count = static_cast<uint32_t *>(v); }
+        { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 2 * sizeof(uint32_t))); q.d_stats = static_cast<uint32_t *>(v); }
+        q.stop = false;
+        q.writer = std::thread(vcf_writer_loop, ctx);
+        q.ready = true;
+    }
+    // the rows: how many slots to look at, and which output row pair 0 of the call is
+    const bool philox = source == 0;
+    int64_t n_slots = 0, row0 = 0, call_pairs = 0;
+    if (philox) {
+        if (!ctx->d_pmut || !ctx->d_pmut_count) return 0;  // (no rows are captured: like iss_mutations_download)
+        // the one value that comes back per call: the slots it reserved (this waits for the generation, not for the text)
+        HIP_TRY(ctx, hipMemcpyAsync(q.h_count, ctx->d_pmut_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        n_slots = (int64_t)*q.h_count;
+        if (n_slots > ctx->pmut_cap) {
+            if (slots_needed) *slots_needed = n_slots;  // (the slots the call asked for: what a retry has to reserve)
+            return fail(ctx, ISS_E_NOMEM, "mutation buffer too small for this call (reserve more with iss_mutations_reserve)");
+        }
+        row0 = ctx->last_row0;
+        call_pairs = ctx->last_n;
+    } else {
+        const auto &m = ctx->mt;
+        if (!m.d_mut) return 0;
+        if (m.mut_n > m.mut_cap) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: more rows than iss_mt_mutations_reserve holds");
+        n_slots = m.mut_n;
+        row0 = m.mut_row0;
+    }
+    // the items that hold pairs, as pairs of the call: ascending, apart
+    std::vector<iss::VcfItem> items;
+    std::string ids;
+    size_t longest = 0;  // of "{id}_{i}_" over the items
+    for (int32_t k = 0; k < n_items; ++k) {
+        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
+        const size_t idlen = strlen(record_ids[k]);
+        if (idlen > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: record id longer than 4096 bytes");
+        if (n_pairs[k] == 0) continue;
+        iss::VcfItem it{};
+        it.first_i = (uint64_t)first_i[k];
+        it.pair0 = first_pair[k] - row0;
+        it.n_pairs = n_pairs[k];
+        if (it.pair0 < 0 || (philox && it.pair0 + it.n_pairs > call_pairs))
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: an item lies outside the rows of the last generate call");
+        if (!items.empty() && it.pair0 < items.back().pair0 + items.back().n_pairs)
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: items must stand in ascending row order and not overlap");
+        it.id_off = (uint32_t)ids.size();
+        it.id_len = (int32_t)idlen;
+        ids.append(record_ids[k], idlen);
+        int dg = 1;
+        for (uint64_t v = it.first_i + (uint64_t)it.n_pairs - 1; v >= 10; v /= 10) ++dg;
+        longest = std::max(longest, idlen + (size_t)dg);
+        items.push_back(it);
+    }
+    if (items.empty() || n_slots == 0) return 0;
+    if (n_slots > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: too many rows");
+    if (q.fd != fd) {
+        { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }
+        const off_t at = lseek(fd, 0, SEEK_CUR);
+        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
+        q.fd = fd;
+        q.off = at;
+    }
+    iss::VcfArgs A{};
+    A.cpu_len = (int32_t)snprintf(A.cpu, sizeof A.cpu, "%d", cpu_number);
+    // bytes of a row at most: 14 fixed characters, position + 1 and the phred with up to 6 each, two letters of an insertion
+    const size_t row_max = longest + (size_t)A.cpu_len + 14 + 6 + 6 + 2;
+    const size_t bound = (size_t)n_slots * row_max;
+    // work arrays (one set: every kernel that touches them is on the context's stream)
+    const size_t n_tiles = std::max<size_t>(1, ((size_t)std::max<int64_t>(n_slots, call_pairs) + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
+    if ((size_t)n_slots > q.slots_cap || (size_t)call_pairs > q.pairs_cap || n_tiles > q.tiles_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the kernels of the emit before may still read them)
+        const size_t sc = std::max(q.slots_cap, (size_t)n_slots + (size_t)n_slots / 4 + 4096);
+        const size_t pc = std::max(q.pairs_cap, (size_t)call_pairs + (size_t)call_pairs / 4 + 4096);
+        const size_t tc = (std::max(sc, pc) + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE + 1;
+        vcf_free_work(ctx);
+        void *v = nullptr;
+        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_key = static_cast<uint32_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_slot = static_cast<uint32_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_order = static_cast<uint32_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_len = static_cast<uint32_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, (sc + 1) * 8)); q.d_off = static_cast<uint64_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, pc * 4)); q.d_cnt = static_cast<uint32_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, (pc + 1) * 8)); q.d_seg = static_cast<uint64_t *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, tc * 8)); q.d_tiles = static_cast<uint64_t *>(v);
+        q.slots_cap = sc; q.pairs_cap = pc; q.tiles_cap = tc;
+    }
+    const int slot = q.next;
+    {
+        std::unique_lock<std::mutex> lk(q.mu);
+        q.cv.wait(lk, [&] { return !q.busy[slot]; });
+        if (!q.error.empty()) { const std::string e = q.error; q.error.clear(); return fail(ctx, ISS_E_IO, e); }
+    }
+    // (the slot is free: nothing reads its text or its tables)
+    if (bound > q.text_cap[slot]) {
+        if (q.d_text[slot]) (void)hipFree(q.d_text[slot]);
+        q.d_text[slot] = nullptr;
+        q.text_cap[slot] = 0;
+        const size_t cap = bound + bound / 8 + (1u << 20);
+        void *v = nullptr;
+        if (hipMalloc(&v, cap) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, ISS_E_NOMEM, "iss_vcf_emit: no device memory for the text"); }
+        q.d_text[slot] = static_cast<uint8_t *>(v);
+        q.text_cap[slot] = cap;
+    }
+    if (items.size() > q.items_cap[slot] || ids.size() + 1 > q.ids_cap[slot]) {
+        if (q.h_items[slot]) (void)hipHostFree(q.h_items[slot]);
+        if (q.d_items[slot]) (void)hipFree(q.d_items[slot]);
+        if (q.h_ids[slot]) (void)hipHostFree(q.h_ids[slot]);
+        if (q.d_ids[slot]) (void)hipFree(q.d_ids[slot]);
+        q.h_items[slot] = q.d_items[slot] = nullptr;
+        q.h_ids[slot] = q.d_ids[slot] = nullptr;
+        q.items_cap[slot] = q.ids_cap[slot] = 0;
+        const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
+        void *v = nullptr;
+        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(iss::VcfItem), hipHostMallocDefault)); q.h_items[slot] = static_cast<iss::VcfItem *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(iss::VcfItem))); q.d_items[slot] = static_cast<iss::VcfItem *>(v);
+        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault)); q.h_ids[slot] = static_cast<char *>(v);
+        HIP_TRY(ctx, hipMalloc(&v, dc)); q.d_ids[slot] = static_cast<char *>(v);
+        q.items_cap[slot] = ic;
+        q.ids_cap[slot] = dc;
+    }
+    memcpy(q.h_items[slot], items.data(), items.size() * sizeof(iss::VcfItem));
+    memcpy(q.h_ids[slot], ids.data(), ids.size());
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::VcfItem), hipMemcpyHostToDevice, st));
+    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, st));
+    A.mut = philox ? ctx->d_pmut : ctx->mt.d_mut;
+    A.n_slots = (uint32_t)n_slots;
+    A.n_pairs = call_pairs;
+    A.cnt = q.d_cnt;
+    A.seg = q.d_seg;
+    A.key = q.d_key;
+    A.slot = q.d_slot;
+    A.len = q.d_len;
+    A.off = q.d_off;
+    A.text = q.d_text[slot];
+    A.text_cap = q.text_cap[slot];
+    A.items = q.d_items[slot];
+    A.ids = q.d_ids[slot];
+    A.n_items = (int32_t)items.size();
+    auto grid_for = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>(2048, (n + iss::VCF_THREADS - 1) / iss::VCF_THREADS)); };
+    auto scan = [&](const uint32_t *in, uint64_t n, uint64_t *out) {
+        const unsigned tiles = (unsigned)((n + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
+        hipLaunchKernelGGL(iss::k_vcf_scan_sums, dim3(tiles), dim3(iss::VSCAN_THREADS), 0, st, in, n, q.d_tiles);
+        hipLaunchKernelGGL(iss::k_vcf_scan_tiles, dim3(1), dim3(iss::VSCAN_THREADS), 0, st, q.d_tiles, (uint64_t)tiles, out + n);
+        hipLaunchKernelGGL(iss::k_vcf_scan_apply, dim3(tiles), dim3(iss::VSCAN_THREADS), 0, st, in, n, (const uint64_t *)q.d_tiles, out);
+    };
+    const dim3 grid = grid_for((uint64_t)n_slots), block(iss::VCF_THREADS);
+    q.job_debug[slot] = false;
+    if (philox) {  // a, b: the slots that stay, in the order of iss_mutations_download
+        A.flags = ctx->flags + ctx->last_row0;
+        A.order = q.d_order;
+        A.n_rows = q.d_seg + call_pairs;
+        HIP_TRY(ctx, hipMemsetAsync(q.d_cnt, 0, (size_t)call_pairs * 4, st));
+        HIP_TRY(ctx, hipMemsetAsync(q.d_order, 0, (size_t)n_slots * 4, st));
+        // ISS_VCF_DEBUG: the writer thread reports how many slots held a row and how many of those stayed (the rest are stale)
+        const bool debug = getenv("ISS_VCF_DEBUG") != nullptr;
+        q.job_debug[slot] = debug;
+        if (debug) {
+            A.stats = q.d_stats;
+            HIP_TRY(ctx, hipMemsetAsync(q.d_stats, 0, 2 * sizeof(uint32_t), st));
+        }
+        hipLaunchKernelGGL(iss::k_vcf_count, grid, block, 0, st, A);
+        if (debug) HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot] + 1, q.d_stats, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        scan(q.d_cnt, (uint64_t)call_pairs, q.d_seg);
+        hipLaunchKernelGGL(iss::k_vcf_scatter, grid, block, 0, st, A);
+        hipLaunchKernelGGL(iss::k_vcf_rank, grid, block, 0, st, A);
+        // the flag words are this call's set: k_setup of the call after the next rewrites it once this event has passed
+        if (ctx->call_seq) {
+            const int par = (int)((ctx->call_seq - 1) & 1u);
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_call_done[par], st));
+        }
+    }
+    hipLaunchKernelGGL(iss::k_vcf_len, grid, block, 0, st, A);  // c
+    scan(q.d_len, (uint64_t)n_slots, q.d_off);
+    hipLaunchKernelGGL(iss::k_vcf_format, grid, block, 0, st, A);  // d
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot], q.d_off + n_slots, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipEventRecord(q.ev_fmt[slot], st));
+    {
+        std::lock_guard<std::mutex> lk(q.mu);
+        q.job_fd[slot] = fd;
+        q.jobs.push_back(slot);
+        q.busy[slot] = true;
+    }
+    q.cv.notify_all();
+    q.next ^= 1;
+    return 0;
+}
+
+int iss_vcf_flush(iss_ctx *ctx) {
+    if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
+    return vcf_flush(ctx);
+}
+
+}  // extern "C"

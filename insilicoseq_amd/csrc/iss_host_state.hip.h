@@ -135,6 +135,41 @@ struct FastqPipe {
 };
 constexpr size_t FASTQ_ID_MAX = 4096;
 
+// Device-formatted VCF text (--store_mutations) on its way to the file: the kernels of iss_vcf.hip.h run on the context's stream
+// behind the generation, the writer thread fetches the text once it knows its size and appends it.  Two slots of text; the work
+// arrays are one set (only kernels of the context's stream touch them, in order).
+struct VcfPipe {
+    bool ready = false;
+    hipStream_t data_stream = nullptr;   // the writer thread's copies
+    hipEvent_t ev_fmt[2] = {nullptr, nullptr};
+    uint8_t *d_text[2] = {nullptr, nullptr};
+    size_t text_cap[2] = {0, 0};
+    uint8_t *h_text[2] = {nullptr, nullptr};  // pinned; grown by the writer thread to the size a text has
+    size_t h_cap[2] = {0, 0};
+    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value: bytes of the slot's text
+    iss::VcfItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
+    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
+    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    uint32_t *h_count = nullptr;         // pinned: the slots a Philox call reserved
+    uint32_t *d_stats = nullptr;         // ISS_VCF_DEBUG: k_vcf_count's two counters (they come back behind h_total)
+    bool job_debug[2] = {false, false};
+    // work arrays: [slots_cap] key, slot, order, len; [slots_cap + 1] off; [pairs_cap] cnt; [pairs_cap + 1] seg; tile sums of the scans
+    uint32_t *d_key = nullptr, *d_slot = nullptr, *d_order = nullptr, *d_len = nullptr, *d_cnt = nullptr;
+    uint64_t *d_off = nullptr, *d_seg = nullptr, *d_tiles = nullptr;
+    size_t slots_cap = 0, pairs_cap = 0, tiles_cap = 0;
+    int next = 0;
+    int fd = -1;
+    int64_t off = 0;                     // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
+    std::thread writer;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<int> jobs;                // slots, in call order
+    int job_fd[2] = {-1, -1};
+    bool busy[2] = {false, false};
+    bool stop = false;
+    std::string error;
+};
+
 // MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's
 // own worker (iss_mt_seed / iss_generate_mt) owns its allocations; a worker of a set (iss_mt_workers_seed) holds slices of the
 // set's.  Only the owner allocates or frees them: the single-worker path (mt_chain_generate) works on whichever chain it is given.
@@ -264,6 +299,7 @@ struct iss_ctx {
         double frag_mu = 0, frag_sd = 0;
         iss::MutRecord *d_mut = nullptr;  // --store_mutations rows of the last iss_generate_mt call
         int64_t mut_cap = 0, mut_n = 0;
+        int64_t mut_row0 = 0;             // ... whose pair 0 is this output row
         hipEvent_t ev_main = nullptr, ev_fill = nullptr;  // ordering between ctx->stream and the fill stream
         iss::MtPhredAmb *d_amb = nullptr;  // BasicErrorModel: [0, CAP) phreds for the host, [CAP, 2 CAP) its answers
         int32_t *d_mut_cnt = nullptr;     // k_mt_emit, --store_mutations: rows per (pair, mate), then their offsets
@@ -302,6 +338,7 @@ struct iss_ctx {
         int64_t n_resolved = 0, n_walked = 0;
     } mts;
     FastqPipe fq;
+    VcfPipe vq;
     // timing
     bool timing = false, timing_main_only = false;
     std::vector<TimedLaunch> timed;

@@ -3,7 +3,7 @@
 // stream for one record (iss_generate) or a whole work list (iss_generate_batch: records side by side in one arena),
 // HIP-event timing, downloads, the FASTQ pipeline (text or gzip members built on the device, copy stream, writer thread).
 // Device side: iss_kernels.hip.h (the Philox path), iss_perfect.hip.h (its perfect-model kernel), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
-// iss_fastq.hip.h, iss_deflate.hip.h; `model` (BAM tallies, KDE): iss_bam.hip.h.
+// iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h.
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -32,15 +32,18 @@
 #include "iss_mt_compat.hip.h"
 #include "iss_units.hip.h"
 #include "iss_bam.hip.h"        // `model`: BAM tallies and the KDE CDFs
+#include "iss_vcf.hip.h"        // --store_mutations: the VCF text (last: the kernels before it keep their places in the code object)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
 #include "iss_host_util.hip.h"        // errors, uploads, switches, frees, kernel choice, timing, synchronisation
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
 #include "iss_host_fastq_pipe.hip.h"  // writer thread, flush
+#include "iss_host_vcf_pipe.hip.h"    // the VCF text's writer thread, flush
 #include "iss_api_context.hip.h"
 #include "iss_api_model.hip.h"
 #include "iss_api_generate.hip.h"
 #include "iss_api_mt.hip.h"
 #include "iss_api_fastq.hip.h"
+#include "iss_api_vcf.hip.h"
 #include "iss_api_bam.hip.h"

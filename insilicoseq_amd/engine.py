@@ -360,6 +360,34 @@ class ReadEngine(object):
         self._check(self._lib.iss_fastq_emit_scatter(self._ctx, int(fd_r1), int(fd_r2), n, ids, cols[0].ctypes.data, cols[1].ctypes.data,
                                                      cols[2].ctypes.data, cpus.ctypes.data, cols[3].ctypes.data, int(n_threads)))
 
+    def vcf_emit(self, fd, items, cpu_number, source="philox"):
+        """The --store_mutations rows of the last generate() / generate_batch() call (``source="philox"``) or generate_mt() call
+        (``"mt"``) as VCF text built on the device, appended to ``fd`` (asynchronous; ``vcf_flush`` before the file is used).
+        items: the tuples of fastq_emit_batch -- (record id, first pair id, first output row, pairs), in ascending row order.  A
+        Philox call that overflowed its row buffer raises E_NOMEM and leaves ``mutation_slots_needed`` like mutations()."""
+        if source not in ("philox", "mt"):
+            raise ValueError("source must be 'philox' or 'mt'")
+        self._need_vcf_entries()
+        n = len(items)
+        ids = (C.c_char_p * n)(*[str(it[0]).encode() for it in items])
+        first_i = np.array([it[1] for it in items], dtype=np.int64)
+        first_pair = np.array([it[2] for it in items], dtype=np.int64)
+        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
+        need = C.c_int64(0)
+        rc = self._lib.iss_vcf_emit(self._ctx, int(fd), 0 if source == "philox" else 1, n, ids, first_i.ctypes.data,
+                                    first_pair.ctypes.data, n_pairs.ctypes.data, int(cpu_number), C.byref(need))
+        self.mutation_slots_needed = need.value if rc == _native.E_NOMEM else 0  # (what a retry has to reserve)
+        self._check(rc)
+
+    def vcf_flush(self):
+        self._need_vcf_entries()
+        self._check(self._lib.iss_vcf_flush(self._ctx))
+
+    def _need_vcf_entries(self):
+        if not hasattr(self._lib, "iss_vcf_emit"):  # (no fall-back: a library from before these entries cannot take this route)
+            raise _native.NativeLibraryError("%s does not export iss_vcf_emit / iss_vcf_flush: rebuild it, or set ISS_HOST_VCF=1 "
+                                             "for the rows-to-host route" % _native.LIB_PATH)
+
     def fastq_compress(self, on=True):
         """`--compress` on the device: every fastq_emit appends one gzip member per file instead of text."""
         self._check(self._lib.iss_fastq_compress(self._ctx, 1 if on else 0))

@@ -192,6 +192,8 @@ class Worker(object):
         self.engine.load_model(self.dense)
         self.store_mutations = False
         self.device_fastq = os.environ.get("ISS_HOST_FASTQ", "") != "1"  # ISS_HOST_FASTQ=1: host formatter (iss_fastq_write)
+        # the --store_mutations text is built on the device too (ReadEngine.vcf_emit); ISS_HOST_VCF=1: rows to the host, write_mutations
+        self.device_vcf = self.device_fastq and os.environ.get("ISS_HOST_VCF", "") != "1"
         self.compress = bool(compress)
         if self.compress:
             if not self.device_fastq:
@@ -299,19 +301,26 @@ class Worker(object):
         gid = self.genome_id(record)
         for fh in (forward_handle, reverse_handle):
             fh.flush()
+        device_vcf = self.store_mutations and self.device_vcf
+        if device_vcf:
+            mutations_handle.flush()  # (the device's text follows what the handle has written)
         done = 0
         while done < n_pairs:
             n = min(self.BATCH_PAIRS, n_pairs - done)
             if self.rng == "mt":
                 assert eng.generate_mt(gid, n, sequence_type=sequence_type, gc_bias=gc_bias, out_first_pair=0) == n
-                if self.store_mutations:
+                if device_vcf:
+                    eng.vcf_emit(mutations_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number, source="mt")
+                elif self.store_mutations:
                     write_mutations(eng.mt_mutations(), mutations_handle, record.id, done, self.cpu_number)
             else:
                 def gen():
                     eng.generate(gid, n, first_ordinal=self.ordinal, seed=self.seed, sequence_type=sequence_type,
                                  gc_bias=gc_bias, out_first_pair=0)
                 gen()
-                if self.store_mutations:
+                if device_vcf:
+                    emit_mutations(eng, gen, mutations_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number)
+                elif self.store_mutations:
                     write_mutations(mutation_rows(eng, gen), mutations_handle, record.id, done, self.cpu_number)
             if self.device_fastq:
                 # text built on the device, copied and written behind the next batch's generation
@@ -327,17 +336,19 @@ class Worker(object):
             done += n
         if self.device_fastq and flush:
             eng.fastq_flush()  # the handles are the caller's again
+            if device_vcf:
+                eng.vcf_flush()
         return done
 
 
-def mutation_rows(eng, regenerate):
-    """--store_mutations rows of the generate call just made (Philox path).  The row buffer is sized from the model's
-    expected rows; when a batch overflows it (ISS_E_NOMEM: a heavy-indel or edited model, rows written twice for reads
+def _retry_on_row_overflow(eng, regenerate, take):
+    """``take()`` turns the --store_mutations rows of the generate call just made (Philox path) into what its caller wants:
+    rows on the host, or text on the device.  The row buffer is sized from the model's expected rows; when a batch overflows it (ISS_E_NOMEM: a heavy-indel or edited model, rows written twice for reads
     the indel kernels rebuild) the reservation doubles and ``regenerate()`` repeats the call -- generation is a pure
     function of seed and ordinal, so the rows and the reads are the same ones."""
     while True:
         try:
-            return eng.mutations()
+            return take()
         except _native.EngineError as e:
             if e.code != _native.E_NOMEM:
                 raise
@@ -354,6 +365,18 @@ def mutation_rows(eng, regenerate):
             regenerate()
 
 
+def mutation_rows(eng, regenerate):
+    """--store_mutations rows of the generate call just made (Philox path), on the host; an overflowing call is repeated
+    (_retry_on_row_overflow)."""
+    return _retry_on_row_overflow(eng, regenerate, eng.mutations)
+
+
+def emit_mutations(eng, regenerate, fd, items, cpu_number):
+    """The same rows as VCF text built on the device and appended to ``fd`` (ReadEngine.vcf_emit; ``items`` as for
+    fastq_emit_batch), with the same rule for a call that overflows its row buffer."""
+    _retry_on_row_overflow(eng, regenerate, lambda: eng.vcf_emit(fd, items, cpu_number))
+
+
 def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_handle, sequence_type, gc_bias):
     """The worker's loop over its work items (iss/generator.py:245-249) with the parallel path's batches cut across
     items: up to BATCH_PAIRS pairs of consecutive items go through ONE set of launches (engine.generate_batch; the
@@ -368,12 +391,19 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         if not pending:
             return
         rows = None
+        device_vcf = w.store_mutations and getattr(w, "device_vcf", False)  # the text on the device; else rows -> write_mutations
+        row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
+        for rid, _gid, n, first_i in pending:
+            emit.append((rid, first_i, row, n))
+            row += n
         try:
             def gen():
                 eng.generate_batch([p[1] for p in pending], [p[2] for p in pending], first_ordinal=w.ordinal, seed=w.seed,
                                    sequence_type=sequence_type, gc_bias=gc_bias, out_first_pair=0)
             gen()
-            if w.store_mutations:
+            if device_vcf:
+                emit_mutations(eng, gen, mutations_handle.fileno(), emit, w.cpu_number)
+            elif w.store_mutations:
                 rows = mutation_rows(eng, gen)
         except _native.EngineError as e:
             if e.code != _native.E_INVALID or "records of one call must stay below" not in str(e):
@@ -386,23 +416,24 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                     eng.generate(gid, n, first_ordinal=ordinal, seed=w.seed, sequence_type=sequence_type, gc_bias=gc_bias,
                                  out_first_pair=row)
                 gen1()
-                if w.store_mutations:
+                if device_vcf:  # one emit per call, at the call's rows
+                    emit_mutations(eng, gen1, mutations_handle.fileno(), [(_rid, _first_i, row, n)], w.cpu_number)
+                elif w.store_mutations:
                     part = mutation_rows(eng, gen1)
                     part["pair"] += row
                     parts.append(part)
                 row += n
                 ordinal += n
-            if w.store_mutations:
+            if w.store_mutations and not device_vcf:
                 rows = np.concatenate(parts) if parts else None
         pairs = rows["pair"] if rows is not None else None  # ascending: the rows come back in (pair, mate, ...) order
-        row, emit = 0, []
+        row = 0
         for rid, _gid, n, first_i in pending:
             if rows is not None:  # this item's rows are contiguous
                 lo, hi = np.searchsorted(pairs, row, "left"), np.searchsorted(pairs, row + n, "left")
                 sel = rows[lo:hi].copy()
                 sel["pair"] -= row
                 write_mutations(sel, mutations_handle, rid, first_i, w.cpu_number)
-            emit.append((rid, first_i, row, n))
             row += n
         eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
         w.ordinal += row
@@ -501,6 +532,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
             w.engine.mutations_reserve(int(Worker.BATCH_PAIRS * per_pair) + (1 << 21))
     try:
         with forward_handle, reverse_handle, mutation_handle:
+            if store_mutations and w.device_vcf:
+                mutation_handle.flush()  # the device's text goes to the descriptor, behind what the handle holds (nothing)
             if rng == "philox" and w.device_fastq and os.environ.get("ISS_ITEMWISE", "") != "1":
                 _simulate_work_batched(w, work, forward_handle, reverse_handle, mutation_handle, sequence_type, gc_bias)
             else:
@@ -508,6 +541,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                     w.simulate_reads(record, n_pairs, forward_handle, reverse_handle, mutation_handle, sequence_type,
                                      gc_bias, flush=False)  # keep the text pipeline running across work items
             w.engine.fastq_flush()
+            if store_mutations and w.device_vcf:
+                w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
             if timings is not None:
                 timings["t_end"] = time.perf_counter()
     finally:

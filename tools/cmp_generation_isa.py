@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""Are the generation kernels (k_main*, k_setup, k_indel_*, k_perfect, k_mt_*) of two device assembly files the same code?
+A change that adds kernels of its own must leave them alone.  Compared per kernel: every instruction, directive and label, with
+comments dropped and the function number taken out of the basic-block labels (.LBB<function>_<block>: hipcc numbers the
+functions of a translation unit in order, so a kernel added in front of another renumbers labels and nothing else).
+
+Usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -I include -S --cuda-device-only -o new.s insilicoseq_amd/csrc/iss_mi355x.hip
+       (the same on the parent commit -> parent.s);  python tools/cmp_generation_isa.py parent.s new.s"""
+import re
+import sys
+
+GENERATION = re.compile(r"k_main|k_setup|k_indel_|k_perfect|k_mt_")
+
+
+def kernels(path):
+    out, name = {}, None
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1)
+            out[name] = []
+        elif name is not None:
+            if line.startswith(".Lfunc_end"):
+                name = None
+                continue
+            line = line.split(";", 1)[0].rstrip()
+            if line:
+                out[name].append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+    return out
+
+
+def main():
+    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    names = [k for k in a if GENERATION.search(k)]
+    bad = [k for k in names if a[k] != b.get(k)]
+    for k in bad:
+        print("differs: %s" % k)
+    print("%d generation kernels compared, %d differ (%d instructions and labels in all); kernels only in the second file: %d" % (
+        len(names), len(bad), sum(len(a[k]) for k in names), len(set(b) - set(a))))
+    return 1 if bad or not names else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
