@@ -23,7 +23,7 @@ import numpy as np
 
 from . import drafts
 from .distributed import VCF_HEADER, concatenate_rank_files, temp_prefix
-from .generator import generate_work_divider, parse_fasta, worker_iterator, worker_set_iterator
+from .generator import WorkerSetNotSetUp, generate_work_divider, parse_fasta, worker_iterator, worker_set_iterator
 from .model import BasicErrorModel, KDErrorModel, PerfectErrorModel
 
 PROFILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
@@ -207,8 +207,6 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
     the FINAL files were written (else the temp files were), or None when the set cannot be set up -- more workers than the engine takes, not enough memory for their stream buffers (three turns of
     stream words per worker and buffer: tens of GB from W = 512 on with long reads) -- BEFORE anything was written: the caller
     then takes the process pool, which has no such limit.  (ISS_HOST_FASTQ=1, the host formatter, is a Worker switch: the pool.)"""
-    from ._native import EngineError
-
     logger = logging.getLogger(__name__)
     works = [[(records[idx], n, "default") for idx, n in j[3]] for j in jobs]
     try:
@@ -218,11 +216,9 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
             works, error_model, [j[0] for j in jobs], [j[6] for j in jobs], args.seed, args.sequence_type, args.gc_bias, device=0,
             compress=device_gzip,
             final_prefix=args.output if len(jobs) == workers and os.environ.get("ISS_SET_TEMP_FILES", "") != "1" else None)
-    except EngineError as e:
-        if getattr(e, "set_up_failed", False):  # (seeding, or the first call's stream buffers: nothing ran yet)
-            logger.warning("%d workers side by side do not fit the device (%s): one process per worker instead" % (workers, e))
-            return None
-        raise
+    except WorkerSetNotSetUp as e:  # (seeding, or the first call's stream buffers: nothing ran yet)
+        logger.warning("%d workers side by side do not fit the device (%s): one process per worker instead" % (workers, e))
+        return None
 
 
 def load_readcount_or_abundance(args, records, error_model):

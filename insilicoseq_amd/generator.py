@@ -170,6 +170,122 @@ def _seq_of(record):
     return seq if isinstance(seq, (str, bytes, bytearray, np.ndarray)) else str(seq)
 
 
+def _warn_short_record(eng, record):
+    """True for a record not longer than the model's reads, with the reference's two warnings: its simulate_read fails an
+    assertion and the record is skipped (iss/generator.py:77-80).  (An MT caller still consumes the reference's draw.)"""
+    if eng.read_length < len(record.seq):
+        return False
+    logger = logging.getLogger(__name__)
+    logger.warning("%s shorter than read length for this ErrorModel" % record.id)
+    logger.warning("Skipping %s. You will have less reads than specified" % record.id)
+    return True
+
+
+class GenomeStore(object):
+    """Which records are resident in one engine's HBM: id(record) -> (record, genome id), the letters they take, and the three
+    operations of the work loops: gid() (look up, else upload), the grouped uploads (plan() / upload_groups()), drop().
+
+    ``limits`` has GENOME_BUDGET and GROUP_BASES (Worker, or a Worker: read at every call), the store keeps
+    GENOME_BUDGET // ``budget_divisor`` letters.  ``drop_on_upload``: gid() drops the resident genomes itself before an upload that
+    would pass the budget; otherwise it only notes it (``over``) and the caller drops at a point where nothing names them
+    (drop_if_over()).  ``skip_short``: records not longer than the reads are left out of groups."""
+
+    def __init__(self, engine, limits, budget_divisor, drop_on_upload, skip_short):
+        self.engine, self.limits, self.budget_divisor = engine, limits, budget_divisor
+        self.drop_on_upload, self.skip_short = drop_on_upload, skip_short
+        self._gids = {}  # id(record) -> (record, genome id on the device; -1: the group did not take it)
+        self.resident, self.over = 0, False
+        self._plan, self._plan_at = [], {}  # the work list's records (plan()) and the first place of each
+
+    @property
+    def budget(self):
+        return self.limits.GENOME_BUDGET // self.budget_divisor
+
+    def _hit(self, record):
+        hit = self._gids.get(id(record))
+        return hit if hit is not None and hit[0] is record else None
+
+    def plan(self, records):
+        """Lazy grouping.  The records the work list will ask for, in order: a record's first gid() uploads it in one group
+        with the small records after it that are not resident yet."""
+        self._plan, self._plan_at = list(records), {}
+        for i, record in enumerate(self._plan):
+            self._plan_at.setdefault(id(record), i)
+
+    def needs_room_for(self, record):
+        """Would uploading this record pass the budget?"""
+        return self._hit(record) is None and bool(self._gids) and self.resident + len(record.seq) > self.budget
+
+    def gid(self, record):
+        hit = self._hit(record)
+        if hit is None:
+            if self._gids and self.resident + len(record.seq) > self.budget:
+                if self.drop_on_upload:
+                    self.drop()
+                else:
+                    self.over = True
+            at = self._plan_at.get(id(record))
+            if at is not None and self._plan[at] is record and len(record.seq) <= SMALL_RECORD:
+                self.upload_groups(self._plan[at:], one_group=True)
+                hit = self._hit(record)
+        if hit is None or hit[1] < 0:
+            # a large record, one outside the groups, or one its group did not take (the upload raises its error here)
+            seq = _seq_of(record)
+            hit = self._gids[id(record)] = (record, self.engine.add_genome(seq))
+            self.resident += len(seq)
+        return hit[1]
+
+    def upload_groups(self, records, one_group=False):
+        """Eager grouping.  Upload those of ``records`` that are not resident and small (SMALL_RECORD) in groups of up to
+        GROUP_BASES letters each (ReadEngine.add_genomes), in order, and no further than the budget: the record that would pass
+        it comes through gid().  ``one_group``: stop where the first group is full."""
+        if not hasattr(self.engine, "add_genomes"):
+            return  # (an engine that takes records one at a time gets them from gid())
+        picked, seqs, seen = [], [], set()
+        size = group = 0  # letters picked by this call; letters of the group being filled
+
+        def flush():
+            for record, seq, gid in zip(picked, seqs, self.engine.add_genomes(seqs)):
+                self._gids[id(record)] = (record, gid)
+                if gid >= 0:
+                    self.resident += len(seq)
+            del picked[:], seqs[:]
+
+        for record in records:
+            if self._hit(record) is not None or id(record) in seen:
+                continue
+            if self.skip_short and not (self.engine.read_length < len(record.seq)):
+                continue  # (skipped by the work loop: never uploaded)
+            seq = _seq_of(record)
+            if len(seq) > SMALL_RECORD:
+                continue
+            # (`resident` holds the groups flushed so far and `size` counts them again: a call that makes several groups stops
+            # at about half the budget.  Kept as it was; what it leaves out is uploaded alone.)
+            if self.resident + size + len(seq) > self.budget:
+                break
+            if picked and group + len(seq) > self.limits.GROUP_BASES:
+                if one_group:
+                    break
+                flush()
+                group = 0
+            seen.add(id(record))
+            picked.append(record)
+            seqs.append(seq)
+            size += len(seq)
+            group += len(seq)
+        flush()
+
+    def drop(self):
+        self.engine.clear_genomes()  # (waits for the device and the FASTQ pipeline first)
+        self._gids.clear()
+        self.resident, self.over = 0, False
+
+    def drop_if_over(self):
+        """For a caller without drop_on_upload, where nothing names an uploaded record."""
+        if self.over or self.resident > self.budget:
+            self.drop()
+
+
 class Worker(object):
     """State of one reference worker on one GPU: engine + uploaded genomes + running ordinal."""
 
@@ -211,86 +327,39 @@ class Worker(object):
         self.has_fragment = (getattr(error_model, "fragment_length", None) is not None and
                              getattr(error_model, "fragment_sd", None) is not None)
         self.ordinal = 0
-        self.timings = None
-        self._gids = {}  # id(record) -> (record, genome id on the device; -1: the group did not take it)
-        self._resident = 0
-        self._plan, self._plan_at = [], {}  # the work list's records (plan()) and the first place of each
+        self.genomes = GenomeStore(
+            self.engine, self,
+            budget_divisor=1,     # the whole GENOME_BUDGET: beside the genomes a worker holds one batch of rows and its text
+            drop_on_upload=True,  # a work list visits a record in one or two consecutive items: nothing uploaded so far is needed again
+            skip_short=rng == "philox")  # the Philox loops skip a short record before any upload; the MT engine needs it for its draw
 
     def plan(self, records):
-        """The records the work list will ask for, in order: a record's first genome_id() uploads it together with the
-        records after it that are not resident yet (upload_group)."""
-        self._plan, self._plan_at = list(records), {}
-        for i, record in enumerate(self._plan):
-            self._plan_at.setdefault(id(record), i)
+        """The records the work list will ask for, in order (GenomeStore.plan: groups are made lazily, from a record's place
+        in the list, so that a drop is followed by a new group and not by single uploads)."""
+        self.genomes.plan(records)
 
     def close(self):
         self.engine.close()
 
     def needs_room_for(self, record):
         """Would uploading this record drop the resident genomes (GENOME_BUDGET)?"""
-        hit = self._gids.get(id(record))
-        return (hit is None or hit[0] is not record) and bool(self._gids) and self._resident + len(record.seq) > self.GENOME_BUDGET
+        return self.genomes.needs_room_for(record)
 
     def genome_id(self, record):
-        key = id(record)
-        hit = self._gids.get(key)
-        if hit is None or hit[0] is not record:
-            seq = _seq_of(record)
-            if self._gids and self._resident + len(seq) > self.GENOME_BUDGET:
-                # a work list visits a record in one or two consecutive items: nothing uploaded so far is needed again
-                self.engine.clear_genomes()  # (waits for the device and the FASTQ pipeline first)
-                self._gids.clear()
-                self._resident = 0
-            at = self._plan_at.get(key)
-            if at is not None and self._plan[at] is record and len(seq) <= SMALL_RECORD:
-                self.upload_group(at)
-                hit = self._gids.get(key)
-        if hit is None or hit[0] is not record or hit[1] < 0:
-            # a large record, one outside the plan, or one its group did not take (the upload raises its error here)
-            seq = _seq_of(record)
-            hit = self._gids[key] = (record, self.engine.add_genome(seq))
-            self._resident += len(seq)
-        return hit[1]
-
-    def upload_group(self, at):
-        """Upload the planned records from place `at` on that are not resident and small, in one group: up to GROUP_BASES
-        letters, and no further than GENOME_BUDGET (the record that would pass it is the next one to drop the others)."""
-        picked, seqs, size, seen = [], [], 0, set()
-        for record in self._plan[at:]:
-            key = id(record)
-            hit = self._gids.get(key)
-            if (hit is not None and hit[0] is record) or key in seen:
-                continue
-            if self.rng == "philox" and not (self.engine.read_length < len(record.seq)):
-                continue  # (skipped by the work loop: never uploaded)
-            seq = _seq_of(record)
-            if len(seq) > SMALL_RECORD:
-                continue
-            if self._resident + size + len(seq) > self.GENOME_BUDGET or (picked and size + len(seq) > self.GROUP_BASES):
-                break
-            seen.add(key)
-            picked.append(record)
-            seqs.append(seq)
-            size += len(seq)
-        for record, seq, gid in zip(picked, seqs, self.engine.add_genomes(seqs)):
-            self._gids[id(record)] = (record, gid)
-            if gid >= 0:
-                self._resident += len(seq)
+        return self.genomes.gid(record)
 
     def simulate_reads(self, record, n_pairs, forward_handle, reverse_handle, mutations_handle, sequence_type,
                        gc_bias=False, writer_threads=4, flush=True):
-        """iss/generator.py:21-66 for one work item, streamed in batches: generate on the GPU, copy
-        back, format FASTQ on host threads."""
+        """iss/generator.py:21-66 for one work item, streamed in batches of BATCH_PAIRS: generate on the GPU, then hand the rows
+        to the device's text pipeline, which builds the FASTQ (and, with --store_mutations, the VCF) text and writes it behind
+        the next batch's generation.  ISS_HOST_FASTQ=1 / ISS_HOST_VCF=1: rows copied back and formatted on the host instead."""
         logger = logging.getLogger(__name__)
         logger.debug("Cpu #%s: Generating %s read pairs" % (self.cpu_number, n_pairs))
         eng = self.engine
-        if not (eng.read_length < len(record.seq)):
-            # AssertionError in simulate_read -> warning + record skipped (generator.py:77-80)
-            logger.warning("%s shorter than read length for this ErrorModel" % record.id)
-            logger.warning("Skipping %s. You will have less reads than specified" % record.id)
+        if _warn_short_record(eng, record):
             if self.rng == "mt" and n_pairs > 0:
-                # the reference has already drawn the insert size (or, with --fragment-length, its gaussian) when its
-                # assertion fails (generator.py:121-130): the engine consumes the same draw and reports the short record
+                # the reference has already drawn the insert size (or, with --fragment-length, its gaussian) when its assertion
+                # fails (generator.py:121-130): the engine consumes the same draw and reports the short record
                 gid = self.genome_id(record)  # (upload errors -- letters outside the alphabet, an empty record -- propagate)
                 try:
                     eng.generate_mt(gid, 1)
@@ -301,27 +370,21 @@ class Worker(object):
         gid = self.genome_id(record)
         for fh in (forward_handle, reverse_handle):
             fh.flush()
-        device_vcf = self.store_mutations and self.device_vcf
-        if device_vcf:
+        route = _mutation_route(self)
+        if route == "device":
             mutations_handle.flush()  # (the device's text follows what the handle has written)
         done = 0
         while done < n_pairs:
             n = min(self.BATCH_PAIRS, n_pairs - done)
-            if self.rng == "mt":
-                assert eng.generate_mt(gid, n, sequence_type=sequence_type, gc_bias=gc_bias, out_first_pair=0) == n
-                if device_vcf:
-                    eng.vcf_emit(mutations_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number, source="mt")
-                elif self.store_mutations:
-                    write_mutations(eng.mt_mutations(), mutations_handle, record.id, done, self.cpu_number)
-            else:
-                def gen():
+
+            def gen():
+                if self.rng == "mt":
+                    assert eng.generate_mt(gid, n, sequence_type=sequence_type, gc_bias=gc_bias, out_first_pair=0) == n
+                else:
                     eng.generate(gid, n, first_ordinal=self.ordinal, seed=self.seed, sequence_type=sequence_type,
                                  gc_bias=gc_bias, out_first_pair=0)
-                gen()
-                if device_vcf:
-                    emit_mutations(eng, gen, mutations_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number)
-                elif self.store_mutations:
-                    write_mutations(mutation_rows(eng, gen), mutations_handle, record.id, done, self.cpu_number)
+            gen()
+            _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
             if self.device_fastq:
                 # text built on the device, copied and written behind the next batch's generation
                 # (one pwrite stream per file: tmpfs gets slower with concurrent writers to one file)
@@ -336,7 +399,7 @@ class Worker(object):
             done += n
         if self.device_fastq and flush:
             eng.fastq_flush()  # the handles are the caller's again
-            if device_vcf:
+            if route == "device":
                 eng.vcf_flush()
         return done
 
@@ -377,21 +440,48 @@ def emit_mutations(eng, regenerate, fd, items, cpu_number):
     _retry_on_row_overflow(eng, regenerate, lambda: eng.vcf_emit(fd, items, cpu_number))
 
 
-def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_handle, sequence_type, gc_bias):
+def _mutation_route(w):
+    """Where a worker's --store_mutations rows go: "device" (VCF text built there), "host" (rows copied back), None."""
+    return ("device" if w.device_vcf else "host") if w.store_mutations else None
+
+
+def _take_mutations(route, eng, regenerate, handle, items, cpu_number, source):
+    """The --store_mutations rows of the generate call just made -- ``source`` "philox" or "mt"; ``items`` as for
+    fastq_emit_batch, the call's rows numbered from its first pair -- to the .vcf ``handle`` by ``route``: text built on the
+    device, or rows fetched and written item by item.  A Philox call that overflows its row buffer is repeated with
+    ``regenerate`` (_retry_on_row_overflow); an MT call cannot be (its streams have moved on) and never is."""
+    if route == "device":
+        if source == "mt":
+            eng.vcf_emit(handle.fileno(), items, cpu_number, source="mt")
+        else:
+            emit_mutations(eng, regenerate, handle.fileno(), items, cpu_number)
+    elif route == "host":
+        rows = eng.mt_mutations() if source == "mt" else mutation_rows(eng, regenerate)
+        if len(items) == 1:  # all rows are the item's, numbered from its first pair wherever its output rows start (no copy)
+            write_mutations(rows, handle, items[0][0], items[0][1], cpu_number)
+            return
+        pairs = rows["pair"]  # ascending: the rows come back in (pair, mate, ...) order, so every item's rows are contiguous
+        for rid, first_i, row, n in items:
+            lo, hi = np.searchsorted(pairs, row, "left"), np.searchsorted(pairs, row + n, "left")
+            sel = rows[lo:hi].copy()
+            sel["pair"] -= row
+            write_mutations(sel, handle, rid, first_i, cpu_number)
+
+
+def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_handle, sequence_type, gc_bias, timings=None):
     """The worker's loop over its work items (iss/generator.py:245-249) with the parallel path's batches cut across
     items: up to BATCH_PAIRS pairs of consecutive items go through ONE set of launches (engine.generate_batch; the
     rows are those of one call per item), then every item's rows are handed to the FASTQ pipeline under its own record
-    id.  Same files as simulate_reads item by item."""
+    id.  Same files as simulate_reads item by item.  ``timings``: worker_iterator's dict, for its ``batches``."""
     logger = logging.getLogger(__name__)
     eng = w.engine
+    route = _mutation_route(w)
     pending, cur = [], 0  # (record id, genome id, pairs, id of the item's first pair in this piece)
 
     def run():
         nonlocal pending, cur
         if not pending:
             return
-        rows = None
-        device_vcf = w.store_mutations and getattr(w, "device_vcf", False)  # the text on the device; else rows -> write_mutations
         row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
         for rid, _gid, n, first_i in pending:
             emit.append((rid, first_i, row, n))
@@ -401,53 +491,31 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                 eng.generate_batch([p[1] for p in pending], [p[2] for p in pending], first_ordinal=w.ordinal, seed=w.seed,
                                    sequence_type=sequence_type, gc_bias=gc_bias, out_first_pair=0)
             gen()
-            if device_vcf:
-                emit_mutations(eng, gen, mutations_handle.fileno(), emit, w.cpu_number)
-            elif w.store_mutations:
-                rows = mutation_rows(eng, gen)
+            _take_mutations(route, eng, gen, mutations_handle, emit, w.cpu_number, "philox")
         except _native.EngineError as e:
             if e.code != _native.E_INVALID or "records of one call must stay below" not in str(e):
                 raise
-            # records too long to stand side by side in one arena: the same rows from one call per item
-            eng.reserve(sum(p[2] for p in pending))
-            parts, row, ordinal = [], 0, w.ordinal
-            for _rid, gid, n, _first_i in pending:
-                def gen1(gid=gid, n=n, ordinal=ordinal, row=row):
+            # records too long to stand side by side in one arena: the same rows, the same call, one item at a time
+            eng.reserve(row)
+            ordinal = w.ordinal
+            for (_rid, gid, n, _first_i), item in zip(pending, emit):
+                def gen1():
                     eng.generate(gid, n, first_ordinal=ordinal, seed=w.seed, sequence_type=sequence_type, gc_bias=gc_bias,
-                                 out_first_pair=row)
+                                 out_first_pair=item[2])
                 gen1()
-                if device_vcf:  # one emit per call, at the call's rows
-                    emit_mutations(eng, gen1, mutations_handle.fileno(), [(_rid, _first_i, row, n)], w.cpu_number)
-                elif w.store_mutations:
-                    part = mutation_rows(eng, gen1)
-                    part["pair"] += row
-                    parts.append(part)
-                row += n
+                _take_mutations(route, eng, gen1, mutations_handle, [item], w.cpu_number, "philox")
                 ordinal += n
-            if w.store_mutations and not device_vcf:
-                rows = np.concatenate(parts) if parts else None
-        pairs = rows["pair"] if rows is not None else None  # ascending: the rows come back in (pair, mate, ...) order
-        row = 0
-        for rid, _gid, n, first_i in pending:
-            if rows is not None:  # this item's rows are contiguous
-                lo, hi = np.searchsorted(pairs, row, "left"), np.searchsorted(pairs, row + n, "left")
-                sel = rows[lo:hi].copy()
-                sel["pair"] -= row
-                write_mutations(sel, mutations_handle, rid, first_i, w.cpu_number)
-            row += n
         eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
         w.ordinal += row
-        if getattr(w, "timings", None) is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
-            w.timings.setdefault("batches", []).append((time.perf_counter(), row))
+        if timings is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
+            timings.setdefault("batches", []).append((time.perf_counter(), row))
         pending, cur = [], 0
 
     for fh in (forward_handle, reverse_handle):
         fh.flush()
     for record, n_pairs, _mode in work:
         logger.debug("Cpu #%s: Generating %s read pairs" % (w.cpu_number, n_pairs))
-        if not (eng.read_length < len(record.seq)):  # AssertionError in simulate_read -> record skipped (generator.py:77-80)
-            logger.warning("%s shorter than read length for this ErrorModel" % record.id)
-            logger.warning("Skipping %s. You will have less reads than specified" % record.id)
+        if _warn_short_record(eng, record):
             continue
         if w.needs_room_for(record):
             run()  # (the genomes about to be dropped are still named by the pending items)
@@ -517,7 +585,6 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
         logger.error("Failed to write temporary output file(s): %s" % e)
         sys.exit(1)
     w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
-    w.timings = timings
     w.plan(record for record, _n, _mode in work)
     if timings is not None:
         timings["t_ready"] = time.perf_counter()
@@ -535,7 +602,7 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
             if store_mutations and w.device_vcf:
                 mutation_handle.flush()  # the device's text goes to the descriptor, behind what the handle holds (nothing)
             if rng == "philox" and w.device_fastq and os.environ.get("ISS_ITEMWISE", "") != "1":
-                _simulate_work_batched(w, work, forward_handle, reverse_handle, mutation_handle, sequence_type, gc_bias)
+                _simulate_work_batched(w, work, forward_handle, reverse_handle, mutation_handle, sequence_type, gc_bias, timings)
             else:
                 for record, n_pairs, _mode in work:
                     w.simulate_reads(record, n_pairs, forward_handle, reverse_handle, mutation_handle, sequence_type,
@@ -565,6 +632,93 @@ def fastq_text_bytes(record_id, n_pairs, cpu_number, read_length):
     return n_pairs * (len(str(record_id).encode()) + len(str(int(cpu_number))) + 2 * read_length + 10) + _digits_before(n_pairs)
 
 
+class WorkerSetNotSetUp(_native.EngineError):
+    """The worker set could not be set up -- seeding failed, or there is no memory for the first call's stream buffers: nothing
+    ran, and the caller may take the process pool instead.  Any other engine error is a failure of the set itself."""
+
+
+def _open_set_files(worker_prefixes, final_prefix):
+    """The set's handles: [(R1, R2)] of the final files, or (R1, R2, vcf) of every worker's temp files."""
+    try:
+        if final_prefix is not None:
+            return [(open("%s_R1.fastq" % final_prefix, "w"), open("%s_R2.fastq" % final_prefix, "w"))]
+        return [(open("%s_R1.fastq" % prefix, "w"), open("%s_R2.fastq" % prefix, "w"), open("%s.vcf" % prefix, "w"))
+                for prefix in worker_prefixes]
+    except PermissionError as e:
+        logging.getLogger(__name__).error("Failed to write %s output file(s): %s" % (
+            "the" if final_prefix is not None else "temporary", e))
+        sys.exit(1)
+
+
+def _final_offsets(works, cpu_numbers, read_length):
+    """Where every worker's text starts and ends in either final file: worker k starts where workers 0 .. k-1 end, and a
+    worker's text size is arithmetic (fastq_text_bytes; short records give no text)."""
+    starts, ends, total = [], [], 0
+    for work, cpu in zip(works, cpu_numbers):
+        starts.append(total)
+        total += sum(fastq_text_bytes(rec.id, n, cpu, read_length) for rec, n, _m in work if read_length < len(rec.seq))
+        ends.append(total)
+    return starts, ends
+
+
+def _set_pieces(genomes, work, cpu, per):
+    """One worker's work list as the pieces its rounds take, at most ``per`` pairs each: (record, genome id, pairs, id of the
+    piece's first pair, short record?).  The genome id is looked up (or the record uploaded) when the piece's round comes."""
+    for record, n_pairs, _mode in work:
+        logging.getLogger(__name__).debug("Cpu #%s: Generating %s read pairs" % (cpu, n_pairs))
+        if _warn_short_record(genomes.engine, record):
+            # the reference has drawn the insert size (or its gaussian) by then (generator.py:121-130): a piece of one pair
+            # makes the engine consume that draw
+            if n_pairs > 0:
+                yield record, genomes.gid(record), 1, 0, True
+            continue
+        done = 0
+        while done < n_pairs:
+            n = min(per, n_pairs - done)
+            yield record, genomes.gid(record), n, done, False
+            done += n
+
+
+def _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, read_length, sequence_type, gc_bias):
+    """Rounds of one piece per worker (``its``: _set_pieces of every worker) until every work list is done: one
+    generate_mt_workers call, then the pieces' text -- one scattered job into the final files at the workers' places ``at``
+    (moved on by what is written: fastq_text_bytes at the model's ``read_length``), or with ``at`` None one job per worker into
+    its temp files."""
+    began = False
+    while True:
+        genomes.drop_if_over()  # between rounds nothing names an uploaded record (a round uploads what its pieces need again)
+        cur = [next(it, None) for it in its]
+        if all(c is None for c in cur):
+            break
+        g = [c[1] if c else 0 for c in cur]
+        n = [c[2] if c else 0 for c in cur]
+        row = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
+        try:
+            done, status = eng.generate_mt_workers(g, n, row, sequence_type=sequence_type, gc_bias=gc_bias)
+        except _native.EngineError as e:
+            if not began and e.code == _native.E_NOMEM:  # (the first call reserves the stream buffers)
+                raise WorkerSetNotSetUp(e.code, e.message) from e
+            raise
+        began = True
+        scattered = []
+        for k, c in enumerate(cur):
+            if c is None:
+                continue
+            if c[4]:
+                assert status[k] == _native.E_SHORT_RECORD and done[k] == 0, (k, int(status[k]), int(done[k]))
+                continue
+            assert status[k] == 0 and done[k] == c[2], (k, int(status[k]), int(done[k]), c[2])
+            if at is not None:  # (the piece's bytes: pairs c[3] .. c[3] + c[2] - 1 of the work item)
+                scattered.append((c[0].id, c[3], int(row[k]), c[2], cpu_numbers[k], at[k]))
+                at[k] += fastq_text_bytes(c[0].id, c[3] + c[2], cpu_numbers[k], read_length) - \
+                    fastq_text_bytes(c[0].id, c[3], cpu_numbers[k], read_length)
+            else:
+                eng.fastq_emit(handles[k][0].fileno(), handles[k][1].fileno(), c[0].id, c[3], cpu_numbers[k], int(row[k]), c[2],
+                               n_threads=1)
+        if scattered:  # ONE text job per round: the next round's kernels run beside its copy and its writes
+            eng.fastq_emit_scatter(handles[0][0].fileno(), handles[0][1].fileno(), scattered, n_threads=1)
+
+
 def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, sequence_type, gc_bias, device=None,
                         compress=False, batch_pairs=None, final_prefix=None):
     """W reference workers (``rng="mt"``) on ONE GPU, side by side: the files of ``worker_iterator(works[k], error_model,
@@ -578,8 +732,8 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
     parent's concatenation of the temp files in worker order would hold (iss/app.py:123-127, iss/util.py:213-234): a worker's
     text size is arithmetic (fastq_text_bytes), so worker k starts where workers 0 .. k-1 end, a round is ONE text job whose
     pieces are written at their places (ReadEngine.fastq_emit_scatter), and no temp file is made.  Returns True when the final
-    files were written, False when the temp files were (the caller concatenates them)."""
-    logger = logging.getLogger(__name__)
+    files were written, False when the temp files were (the caller concatenates them).  Raises WorkerSetNotSetUp when the set
+    could not be set up (nothing ran)."""
     W = len(works)
     if not (W == len(cpu_numbers) == len(worker_prefixes)) or W < 1:
         raise ValueError("worker_set_iterator: one work list, cpu number and file prefix per worker")
@@ -591,153 +745,41 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
             worker_iterator(work, error_model, cpu, prefix, seed, sequence_type, gc_bias, device=device, rng="mt", compress=compress)
         return False
     final = final_prefix is not None and not compress
-    handles = []
-    try:
-        if final:
-            handles.append((open("%s_R1.fastq" % final_prefix, "w"), open("%s_R2.fastq" % final_prefix, "w")))
-        else:
-            for prefix in worker_prefixes:
-                handles.append((open("%s_R1.fastq" % prefix, "w"), open("%s_R2.fastq" % prefix, "w"), open("%s.vcf" % prefix, "w")))
-    except PermissionError as e:
-        logger.error("Failed to write %s output file(s): %s" % ("the" if final else "temporary", e))
-        sys.exit(1)
+    handles = _open_set_files(worker_prefixes, final_prefix if final else None)
     eng, finished = None, False
     try:
         eng = ReadEngine(0 if device is None else device)
         dense = _dense_of(error_model)
         eng.load_model(dense)
-        at = [0] * W  # final files: where worker k's next byte goes
+        at = ends = None  # final files: where worker k's next byte goes, and where its text has to end
         if final:
-            RL, total = dense.read_length, 0
-            ends = [0] * W
-            for k, (work, cpu) in enumerate(zip(works, cpu_numbers)):
-                at[k] = total
-                total += sum(fastq_text_bytes(rec.id, n, cpu, RL) for rec, n, _m in work if RL < len(rec.seq))
-                ends[k] = total
+            at, ends = _final_offsets(works, cpu_numbers, dense.read_length)
             for fh in handles[0]:
                 fh.flush()
-                os.ftruncate(fh.fileno(), total)
+                os.ftruncate(fh.fileno(), ends[-1])
         if compress:
             eng.fastq_compress(True)
-        # e.set_up_failed: the set could not be set up (seeding, or no memory for the first call's stream buffers) -- nothing
-        # ran, and the caller may take the process pool instead; any other engine error is a failure of the set itself
-        began = [False]
         try:
             eng.seed_mt_workers([worker_seed(seed, c) for c in cpu_numbers])
         except _native.EngineError as e:
-            e.set_up_failed = True
-            raise
+            raise WorkerSetNotSetUp(e.code, e.message) from e
         eng.mt_set_fragment(getattr(error_model, "fragment_length", None), getattr(error_model, "fragment_sd", None))
         # rows per worker and round (2^20 pairs per round for all workers together; 2^22 and 2^24 measured the same end to end:
         # 16 M pairs at W = 64 in 2.6-2.8 s incl. 0.5 s of engine start -- generation and text take turns)
         per = int(batch_pairs or max(1024, min(Worker.BATCH_PAIRS, (1 << 20) // W)))
-        gids, resident = {}, [0]
-
-        # letters resident in HBM before all are dropped: Worker's budget less what the set itself holds on the device (stream
-        # buffers, rows of a round -- up to a third of the memory)
-        budget = Worker.GENOME_BUDGET // 2
-        over = [False]
-
-        def gid_of(record):
-            hit = gids.get(id(record))
-            if hit is None or hit[0] is not record or hit[1] < 0:
-                # (a record its group did not take: the single upload raises its error here, where it always has)
-                seq = _seq_of(record)
-                if gids and resident[0] + len(seq) > budget:
-                    over[0] = True  # (this round's pieces name the resident records: they go at the round's end)
-                hit = gids[id(record)] = (record, eng.add_genome(seq))
-                resident[0] += len(seq)
-            return hit[1]
-
-        def upload_groups(records):
-            # the small records of the work lists in groups (Worker.upload_group), as far as the budget goes
-            picked, seqs, size, group = [], [], 0, [0]
-
-            def flush():
-                for record, seq, gid in zip(picked, seqs, eng.add_genomes(seqs)):
-                    gids[id(record)] = (record, gid)
-                    if gid >= 0:
-                        resident[0] += len(seq)
-                del picked[:], seqs[:]
-                group[0] = 0
-
-            for record in records:
-                if id(record) in gids:
-                    continue
-                seq = _seq_of(record)
-                if len(seq) > SMALL_RECORD:
-                    continue
-                if resident[0] + size + len(seq) > budget:
-                    break
-                if picked and group[0] + len(seq) > Worker.GROUP_BASES:
-                    flush()
-                gids[id(record)] = (record, -1)
-                picked.append(record)
-                seqs.append(seq)
-                size += len(seq)
-                group[0] += len(seq)
-            flush()
-
-        if hasattr(eng, "add_genomes"):  # (an engine that takes records one at a time gets them from gid_of)
-            upload_groups(record for work in works for record, _n, _m in work)
-
-        def pieces(work, cpu):  # (record, genome id, pairs, id of the piece's first pair, short record?)
-            for record, n_pairs, _mode in work:
-                logger.debug("Cpu #%s: Generating %s read pairs" % (cpu, n_pairs))
-                if not (eng.read_length < len(record.seq)):
-                    # AssertionError in simulate_read -> warning + record skipped (generator.py:77-80); the reference has
-                    # drawn the insert size (or its gaussian) by then (generator.py:121-130): the engine consumes that draw
-                    logger.warning("%s shorter than read length for this ErrorModel" % record.id)
-                    logger.warning("Skipping %s. You will have less reads than specified" % record.id)
-                    if n_pairs > 0:
-                        yield record, gid_of(record), 1, 0, True
-                    continue
-                done = 0
-                while done < n_pairs:
-                    n = min(per, n_pairs - done)
-                    yield record, gid_of(record), n, done, False
-                    done += n
-
-        its = [pieces(work, cpu) for work, cpu in zip(works, cpu_numbers)]
+        genomes = GenomeStore(
+            eng, Worker,
+            budget_divisor=2,      # Worker's budget less what the set itself holds on the device (stream buffers, rows of a round -- up to a third of the memory)
+            drop_on_upload=False,  # a round's pieces name the resident records: they go between rounds (_run_set_rounds)
+            skip_short=False)      # the engine consumes a short record's draw: it needs the record
+        # eager grouping, once: the workers' lists advance side by side, so there is no one place in a plan to group from, and
+        # after a drop the records still to come are uploaded alone as their pieces come up
+        genomes.upload_groups(record for work in works for record, _n, _m in work)
+        its = [_set_pieces(genomes, work, cpu, per) for work, cpu in zip(works, cpu_numbers)]
         for fh3 in handles:
             for fh in fh3[:2]:
                 fh.flush()
-        while True:
-            if over[0] or resident[0] > budget:
-                over[0] = False
-                # between rounds nothing names an uploaded record: drop them all (a round uploads what its pieces need again)
-                eng.clear_genomes()  # (waits for the device and the FASTQ pipeline first)
-                gids.clear()
-                resident[0] = 0
-            cur = [next(it, None) for it in its]
-            if all(c is None for c in cur):
-                break
-            g = [c[1] if c else 0 for c in cur]
-            n = [c[2] if c else 0 for c in cur]
-            row = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
-            try:
-                done, status = eng.generate_mt_workers(g, n, row, sequence_type=sequence_type, gc_bias=gc_bias)
-            except _native.EngineError as e:
-                e.set_up_failed = not began[0] and e.code == _native.E_NOMEM  # (the first call reserves the stream buffers)
-                raise
-            began[0] = True
-            scattered = []
-            for k, c in enumerate(cur):
-                if c is None:
-                    continue
-                if c[4]:
-                    assert status[k] == _native.E_SHORT_RECORD and done[k] == 0, (k, int(status[k]), int(done[k]))
-                    continue
-                assert status[k] == 0 and done[k] == c[2], (k, int(status[k]), int(done[k]), c[2])
-                if final:  # (the piece's bytes: pairs c[3] .. c[3] + c[2] - 1 of the work item)
-                    scattered.append((c[0].id, c[3], int(row[k]), c[2], cpu_numbers[k], at[k]))
-                    at[k] += fastq_text_bytes(c[0].id, c[3] + c[2], cpu_numbers[k], dense.read_length) - \
-                        fastq_text_bytes(c[0].id, c[3], cpu_numbers[k], dense.read_length)
-                else:
-                    eng.fastq_emit(handles[k][0].fileno(), handles[k][1].fileno(), c[0].id, c[3], cpu_numbers[k], int(row[k]), c[2],
-                                   n_threads=1)
-            if scattered:  # ONE text job per round: the next round's kernels run beside its copy and its writes
-                eng.fastq_emit_scatter(handles[0][0].fileno(), handles[0][1].fileno(), scattered, n_threads=1)
+        _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, dense.read_length, sequence_type, gc_bias)
         eng.fastq_flush()
         if final and at != ends:  # every worker's text ends where the next one's starts
             raise RuntimeError("worker_set_iterator: a worker's text is not the size computed for it: %r / %r" % (at, ends))

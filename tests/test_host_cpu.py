@@ -576,6 +576,7 @@ def test_batched_worker_loop_falls_back_to_single_calls():
 
     class FakeWorker:
         BATCH_PAIRS = 1000
+        device_vcf = False
 
         def __init__(self):
             self.engine = FakeEngine()

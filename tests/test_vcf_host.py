@@ -117,8 +117,8 @@ def test_another_error_propagates():
     assert e.value.code == _native.E_IO
 
 
-def test_host_route_without_the_attribute():
-    """A worker without `device_vcf` (the stand-ins of test_host_cpu.py) keeps the host route."""
+def test_host_route_with_device_vcf_off():
+    """A worker whose `device_vcf` is False (ISS_HOST_VCF=1; the stand-ins of test_host_cpu.py) takes the host route."""
     from insilicoseq_amd.engine import MUT_DTYPE
     import numpy as np
 
