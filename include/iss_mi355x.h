@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive, like the three entries before them) iss_vcf_emit / iss_vcf_flush: the --store_mutations text built on the device.
+/* 8: (additive) iss_mt_workers_mutations_reserve / iss_mt_workers_mutations_download / iss_vcf_emit_workers: --store_mutations for
+ *    the W workers of a set (rows per worker, placed on the device; one text job per call).
+ *    (additive, like the three entries before them) iss_vcf_emit / iss_vcf_flush: the --store_mutations text built on the device.
  *    iss_main_kernel (which instantiation of the hot kernel the last Philox-mode call launched: k_main or k_main_g -- the
  *    rows of a group of passes wait in registers for their byte patches).
  * 7: W workers of the reference-identical mode side by side in one context (iss_mt_workers_seed, iss_generate_mt_workers,
@@ -288,7 +290,8 @@ int iss_mt_path_counts(iss_ctx *ctx, int64_t *n_resolved, int64_t *n_walked);
  * per worker (n_pairs[w] == 0: the worker sits this call out).  status[w] (may be NULL): 0, or ISS_E_SHORT_RECORD for a worker whose
  * record is not longer than a read (its draw is consumed like iss_generate_mt does); any other failure fails the call.  The
  * workers' row ranges must not overlap.  Custom fragment lengths and the BasicErrorModel run the workers one after the other
- * through iss_generate_mt (draws the host's libm settles); --store_mutations rows are per context (ISS_E_INVALID here).
+ * through iss_generate_mt (draws the host's libm settles); --store_mutations rows of the set: iss_mt_workers_mutations_reserve below
+ * (a context that holds single-worker rows, iss_mt_mutations_reserve, is refused here: ISS_E_INVALID).
  * iss_mt_workers_peek: iss_mt_peek for worker w.  iss_mt_path_counts counts the set's pairs too.
  */
 int iss_mt_workers_seed(iss_ctx *ctx, int32_t n_workers, const uint64_t *seeds);
@@ -306,6 +309,14 @@ int iss_mt_set_fragment(iss_ctx *ctx, int32_t enabled, double fragment_length, d
  * min(rows, capacity) of them and reports the total row count. */
 int iss_mt_mutations_reserve(iss_ctx *ctx, int64_t capacity);
 int iss_mt_mutations_download(iss_ctx *ctx, iss_mutation *out, int64_t capacity, int64_t *n_total);
+/* --store_mutations for the workers of a set: after iss_mt_workers_mutations_reserve with rows_per_worker > 0 every
+ * iss_generate_mt_workers call records each worker's rows from index 0 of the worker's own region, in the reference's order -- the
+ * rows iss_generate_mt records for that worker in a context of its own; 0 frees the storage and switches the capture off.  The
+ * request outlives iss_mt_workers_seed (the new workers get their regions).  A worker that makes more rows than its region holds:
+ * the surplus is dropped, the call returns ISS_E_NOMEM and the set is poisoned like after any failure half way (seed it again).
+ * iss_mt_workers_mutations_download copies min(rows, capacity) rows of one worker of the last call and reports its row count. */
+int iss_mt_workers_mutations_reserve(iss_ctx *ctx, int64_t rows_per_worker);
+int iss_mt_workers_mutations_download(iss_ctx *ctx, int32_t worker, iss_mutation *out, int64_t capacity, int64_t *n_total);
 
 /*
  * FASTQ text built ON THE DEVICE (the host formatter below tops out near 3 GB/s of text, four hundred times
@@ -353,6 +364,13 @@ int iss_fastq_flush(iss_ctx *ctx);
  */
 int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
                  const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number, int64_t *slots_needed);
+/* The same for the rows of the last iss_generate_mt_workers call, ALL workers in one text job (one sequence of the kernels, one
+ * copy): entry k is worker k's piece -- output rows [first_pair[k], +n_pairs[k]), which must start at the worker's first row of that
+ * call, under record_ids[k] with pair ids from first_i[k] and worker number cpu_numbers[k]; n_pairs[k] == 0: the worker sat the call
+ * out.  Worker k's byte range of the text is appended to fds[k] at its current position by the writer thread, the descriptors are
+ * left at their ends. */
+int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const char *const *record_ids, const int64_t *first_i,
+                         const int64_t *first_pair, const int64_t *n_pairs, const int32_t *cpu_numbers);
 int iss_vcf_flush(iss_ctx *ctx);
 
 /*

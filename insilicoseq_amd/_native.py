@@ -24,6 +24,7 @@ EXPORTS = (
     "iss_generate_batch", "iss_fastq_emit_batch", "iss_gen_phred_scores", "iss_mut_sequence", "iss_random_insert_size",
     "iss_introduce_indels", "iss_ev_step", "iss_mt_workers_seed", "iss_generate_mt_workers", "iss_mt_workers_peek",
     "iss_main_kernel", "iss_fastq_emit_scatter", "iss_vcf_emit", "iss_vcf_flush",
+    "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download", "iss_vcf_emit_workers",
     "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
     "iss_bam_tally_download", "iss_bam_kde",
 )
@@ -129,6 +130,11 @@ def lib():
     if hasattr(L, "iss_vcf_emit") and hasattr(L, "iss_vcf_flush"):
         L.iss_vcf_emit.argtypes = [vp, C.c_int, i32, i32, vp, vp, vp, vp, i32, C.POINTER(i64)]
         L.iss_vcf_flush.argtypes = [vp]
+    # (additive to ABI 8 as well: --store_mutations for the workers of a set)
+    if hasattr(L, "iss_vcf_emit_workers"):
+        L.iss_mt_workers_mutations_reserve.argtypes = [vp, i64]
+        L.iss_mt_workers_mutations_download.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+        L.iss_vcf_emit_workers.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -151,7 +157,8 @@ def lib():
     L.iss_bam_tally_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
     L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
     for name in EXPORTS:
-        if name in ("iss_vcf_emit", "iss_vcf_flush") and not hasattr(L, name):
+        if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
+                    "iss_vcf_emit_workers") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

@@ -214,9 +214,9 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
         # chunks than workers: the reference fails on the missing temp file, util.py:233 -- that path keeps the temp files)
         return worker_set_iterator(
             works, error_model, [j[0] for j in jobs], [j[6] for j in jobs], args.seed, args.sequence_type, args.gc_bias, device=0,
-            compress=device_gzip,
+            compress=device_gzip, vcf_files=bool(getattr(args, "store_mutations", False)),
             final_prefix=args.output if len(jobs) == workers and os.environ.get("ISS_SET_TEMP_FILES", "") != "1" else None)
-    except WorkerSetNotSetUp as e:  # (seeding, or the first call's stream buffers: nothing ran yet)
+    except WorkerSetNotSetUp as e:  # (seeding, the row pool of --store_mutations, or the first call's stream buffers: nothing ran yet)
         logger.warning("%d workers side by side do not fit the device (%s): one process per worker instead" % (workers, e))
         return None
 
@@ -298,7 +298,7 @@ def generate_reads(args):
     if workers == 1:
         for j in jobs:
             _worker(*j, records=records)
-    elif args.rng == "mt" and args.devices == 1 and not args.store_mutations and args.seed is not None and workers <= 1024 \
+    elif args.rng == "mt" and args.devices == 1 and args.seed is not None and workers <= 1024 \
             and os.environ.get("ISS_HOST_FASTQ", "") != "1":
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
@@ -308,7 +308,8 @@ def generate_reads(args):
             pool.starmap(_worker, jobs)
     t_cat = time.perf_counter()
     if in_place:
-        pass
+        if args.store_mutations:  # the FASTQ files are final; a VCF's size is not arithmetic: the workers' .vcf behind the header
+            concatenate_rank_files(args.output, workers, suffixes=(".vcf",), headers={".vcf": VCF_HEADER})
     elif args.store_mutations:  # app.py:128-133
         concatenate_rank_files(args.output, workers, suffixes=("_R1.fastq", "_R2.fastq", ".vcf"),
                                headers={".vcf": VCF_HEADER}, out_suffixes=gz)

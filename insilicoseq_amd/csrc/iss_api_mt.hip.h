@@ -134,11 +134,15 @@ int mt_chain_peek(iss_ctx *ctx, MtChain &c, uint32_t *py_words, uint32_t *np_wor
     return 0;
 }
 
+// where a chain's --store_mutations rows go (mut NULL: nowhere): the context's own buffer (iss_generate_mt), or the region of a
+// worker of the set; n: rows of the call so far, row0: the output row of the call's pair 0
+struct MtRowSink { iss::MutRecord *mut; int64_t cap, n, row0; };
+
 // The single-worker path: n_pairs pairs of genome_id into rows [out_first_pair, + n_pairs) from chain c's streams, in turns of
 // c.ch pairs, the pairs counted in n_resolved / n_walked.  The context's own chain (iss_generate_mt), or a worker of the set for
 // what its side-by-side loop does not do itself.  The chain's buffers are its owner's, reserved before the call.
 int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pairs, int32_t sequence_type, int32_t gc_bias,
-                      int64_t out_first_pair, double guard, int64_t *n_done, int64_t &n_resolved, int64_t &n_walked) {
+                      int64_t out_first_pair, double guard, int64_t *n_done, int64_t &n_resolved, int64_t &n_walked, MtRowSink &rows) {
     const Genome &G = ctx->genomes[genome_id];
     const iss::DevModel &M = ctx->M;
     auto &m = ctx->mt;
@@ -224,8 +228,8 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
     }
     std::vector<iss::MtPhredAmb> ovq;  // answers for the pair that restarts
     int64_t done = 0;
-    m.mut_n = 0;
-    m.mut_row0 = out_first_pair;
+    rows.n = 0;
+    rows.row0 = out_first_pair;
     bool ov_valid = false, walk_one = false;
     int64_t ov_frag = 0;
     int64_t boost = gc_bias ? 4 : 0;  // (mt_grow_boost)
@@ -259,7 +263,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
                                        ctx->out[2] + (size_t)row0 * M.row, ctx->out[3] + (size_t)row0 * M.row, E);
                 };
                 iss::MtEmitMut E{};
-                if (!m.d_mut) {
+                if (!rows.mut) {
                     emit(E);
                 } else {
                     // --store_mutations: count the rows of every mate, place them with a prefix sum, write them in order
@@ -270,17 +274,17 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
                     HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), m.d_mut_cnt, items * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                     std::vector<int64_t> off(items);
-                    int64_t at = m.mut_n;
+                    int64_t at = rows.n;
                     for (size_t k = 0; k < items; ++k) { off[k] = at; at += cnt[k]; }
                     HIP_TRY(ctx, hipMemcpyAsync(m.d_mut_off, off.data(), items * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
                     E.mut_cnt = nullptr;
                     E.mut_off = m.d_mut_off;
-                    E.mut = m.d_mut;
-                    E.mut_cap = m.mut_cap;
+                    E.mut = rows.mut;
+                    E.mut_cap = rows.cap;
                     E.pair_base = done;
                     emit(E);
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `off` is pageable host memory
-                    m.mut_n = at;
+                    rows.n = at;
                 }
             }
             c.used[0] += res.py_used;
@@ -293,9 +297,9 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             continue;
         }
         iss::MtWalkArgs A = mt_walk_args(ctx, c, n, row0, done, sequence_type, gc_bias, lds.use_rows, guard);
-        A.mut = m.d_mut;
-        A.mut_cap = m.mut_cap;
-        A.mut_base = m.mut_n;
+        A.mut = rows.mut;
+        A.mut_cap = rows.cap;
+        A.mut_base = rows.n;
         A.has_frag = m.has_frag ? 1 : 0;
         A.frag_mu = m.frag_mu;
         A.frag_sd = m.frag_sd;
@@ -318,7 +322,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
         { int rc_ = mt_prefetch_commit(ctx, c, pf); if (rc_) return rc_; }
         done += res.n_done;
         n_walked += res.n_done;
-        m.mut_n += res.n_mut;
+        rows.n += res.n_mut;
         // host answers (phreds, fragment length) belong to the attempt that started the launch: they stay only if the
         // walk stopped again at that very attempt (gc_bias rejections move on to a new attempt of the same pair)
         const bool same_attempt = res.n_done == 0 && res.py_used == 0 && res.np_used == 0;
@@ -398,8 +402,13 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     auto &c = ctx->mt.chain;
     const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
     { int rc_ = mt_reserve(ctx, c, 3 * ((size_t)(c.ch + 1) * py_need + 1248), 3 * ((size_t)(c.ch + 1) * np_need + 1248)); if (rc_) return rc_; }
-    return mt_chain_generate(ctx, c, genome_id, n_pairs, sequence_type, gc_bias, out_first_pair, mt_guard_env(), n_done,
-                             ctx->mt.n_resolved, ctx->mt.n_walked);
+    auto &m = ctx->mt;
+    MtRowSink rows{m.d_mut, m.mut_cap, m.mut_n, m.mut_row0};
+    const int rc = mt_chain_generate(ctx, c, genome_id, n_pairs, sequence_type, gc_bias, out_first_pair, mt_guard_env(), n_done,
+                                     m.n_resolved, m.n_walked, rows);
+    m.mut_n = rows.n;
+    m.mut_row0 = rows.row0;
+    return rc;
 }
 
 // ------------------------------------------------------------------ MT mode: W workers per launch (round 5)
@@ -408,6 +417,36 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
 // a set of W workers is W chains side by side: per turn ONE launch of each kernel of the path with one workgroup (k_mt_fill_w,
 // k_mt_resolve_w, k_mt_walk_w) or one grid row (k_mt_emit_w) per worker, the jobs in tables in HBM.  Every worker's rows and
 // stream positions are exactly those of iss_mt_seed(seed_w) + iss_generate_mt(...) in a context of its own.
+namespace {
+
+// the rows of a seeded set's workers, where iss_mt_workers_mutations_reserve asked for them: the pool, the counts (zero), the
+// events of the ordering rule (mt_workers_generate).  The per-turn counts and places follow with the first call (they need the
+// turn length).
+int mt_set_rows_alloc(iss_ctx *ctx) {
+    auto &t = ctx->mts;
+    if (!t.W || !t.mut_rows || t.d_mut) return 0;
+    const size_t W = (size_t)t.W;
+    void *p = nullptr;
+    if (hipMalloc(&p, W * (size_t)t.mut_rows * sizeof(iss::MutRecord)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, ISS_E_NOMEM, "iss_mt_workers_mutations_reserve: no device memory for " + std::to_string(t.W) + " x " + std::to_string(t.mut_rows) + " rows");
+    }
+    t.d_mut = static_cast<iss::MutRecord *>(p);
+    HIP_TRY(ctx, hipMalloc(&p, W * sizeof(int64_t)));
+    t.d_mut_n = static_cast<int64_t *>(p);
+    HIP_TRY(ctx, hipMemset(t.d_mut_n, 0, W * sizeof(int64_t)));
+    HIP_TRY(ctx, hipHostMalloc(&p, W * sizeof(int64_t), hipHostMallocDefault));
+    t.h_mut_n = static_cast<int64_t *>(p);
+    HIP_TRY(ctx, hipEventCreateWithFlags(&t.ev_place, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&t.ev_walk, hipEventDisableTiming));
+    t.mut_n.assign(W, 0);
+    t.mut_row0.assign(W, 0);
+    t.mut_pairs.assign(W, 0);
+    return 0;
+}
+
+}  // namespace
+
 int iss_mt_workers_seed(iss_ctx *ctx, int32_t n_workers, const uint64_t *seeds) {
     if (!ctx || n_workers < 1 || n_workers > 1024 || !seeds) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_seed: 1 .. 1024 workers");
     for (int32_t w = 0; w < n_workers; ++w)
@@ -441,7 +480,7 @@ int iss_mt_workers_seed(iss_ctx *ctx, int32_t n_workers, const uint64_t *seeds) 
     }
     t.last_read.assign(4 * W, -1);
     t.n_resolved = t.n_walked = 0;
-    return 0;
+    return mt_set_rows_alloc(ctx);  // (a standing iss_mt_workers_mutations_reserve: the new workers' regions, their counts zero)
 }
 
 namespace {
@@ -555,7 +594,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: call iss_mt_workers_seed for this many workers first");
     if (sequence_type != ISS_SEQ_METAGENOMICS && sequence_type != ISS_SEQ_AMPLICON)
         return fail(ctx, ISS_E_INVALID, "sequence type is not supported");
-    if (ctx->mt.d_mut) return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: --store_mutations rows are per context (one context per worker)");
+    if (ctx->mt.d_mut) return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: this context holds single-worker --store_mutations rows (iss_mt_mutations_reserve): free them, the set's rows are iss_mt_workers_mutations_reserve");
     const int W = n_workers;
     const iss::DevModel &M = ctx->M;
     for (int w = 0; w < W; ++w) {
@@ -572,6 +611,25 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int rc_ = sync_all(ctx); if (rc_) return rc_; }
     { int rc_ = mt_set_reserve(ctx); if (rc_) return rc_; }
+    // --store_mutations (iss_mt_workers_mutations_reserve): the rows of this call, per worker from 0
+    const bool rows_on = t.d_mut != nullptr;
+    if (rows_on && !t.d_mut_cnt) {  // (a worker's counts and places of one turn; the stride keeps them 16-byte aligned)
+        const size_t stride = ((size_t)2 * (size_t)t.ch + 7) & ~(size_t)7;
+        void *p = nullptr;
+        HIP_TRY(ctx, hipMalloc(&p, (size_t)W * stride * sizeof(int32_t)));
+        t.d_mut_cnt = static_cast<int32_t *>(p);
+        HIP_TRY(ctx, hipMalloc(&p, (size_t)W * stride * sizeof(int64_t)));
+        t.d_mut_off = static_cast<int64_t *>(p);
+        t.mut_stride = stride;
+    }
+    if (rows_on)
+        for (int w = 0; w < W; ++w) {
+            t.h_mut_n[w] = 0;
+            t.mut_n[w] = 0;
+            t.mut_row0[w] = out_first_pair[w];
+            t.mut_pairs[w] = n_pairs[w];
+        }
+    auto region = [&](int w) { return rows_on ? t.d_mut + (size_t)w * (size_t)t.mut_rows : nullptr; };
     t.started = true;  // (from here on a failure leaves the set undefined)
     auto &m = ctx->mt;
     const bool basic = M.quality_mode == 1;
@@ -595,8 +653,10 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         const Genome &G = ctx->genomes[genome_ids[w]];
         if (one_by_one || !(M.RL < G.L)) {
             int64_t dn = 0;
+            MtRowSink rows{region(w), t.mut_rows, 0, 0};  // (its own region of the pool, through the single-worker path's host placement)
             const int rc = mt_chain_generate(ctx, t.chains[w], genome_ids[w], n_pairs[w], sequence_type, gc_bias, out_first_pair[w], guard, &dn,
-                                             t.n_resolved, t.n_walked);
+                                             t.n_resolved, t.n_walked, rows);
+            if (rows_on) t.h_mut_n[w] = rows.n;
             if (n_done) n_done[w] = dn;
             if (rc == ISS_E_SHORT_RECORD) { if (status) status[w] = rc; continue; }
             if (rc) return rc;
@@ -634,6 +694,18 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     const bool dbg = getenv("ISS_MT_SET_DEBUG") != nullptr;  // per call: turns, words produced / moved, pairs handed to the walker
     uint64_t dbg_turns = 0, dbg_moved[2] = {0, 0}, dbg_filled[2] = {0, 0}, dbg_bounce = 0, dbg_moves = 0, dbg_big = 0, dbg_pairs = 0, dbg_appends = 0, dbg_starved = 0, dbg_own = 0, dbg_skip = 0, dbg_ensure = 0;
     std::fill(t.last_read.begin(), t.last_read.end(), (int64_t)-1);  // (everything before this call has been waited for: sync_all above)
+    // The running row counts live in device memory (zero; the rows of the workers that went one by one).  ORDER OF A WORKER'S ROWS
+    // (the reference's: pairs in order, mate 0 before mate 1, positions ascending) -- whoever appends to a worker's region takes
+    // its place from the worker's count and moves the count on, so the appenders of one worker must follow one another:
+    //     place + write of turn t (emit stream)  ->  the walker behind turn t (main stream), or the worker's walker turn t + 1
+    //     (side stream)  ->  place of turn t + 1 (emit stream).
+    // Two events say so, and nothing else does: ev_place, recorded on the emit stream behind k_mt_mut_place_w (in front of the
+    // writing pass: that one only reads the places), is waited for by the stream of every walker launch; ev_walk, recorded on the
+    // main stream behind its walker (and behind its wait for the side stream's), is waited for by the emit stream in front of the
+    // next k_mt_mut_place_w.  An event is re-recorded every turn and a wait takes its latest record: the one before in stream order.
+    // A wait for an event that has no record yet (the first turn, or a walker before any emitter ran) is a no-op by HIP's rule:
+    // nothing has been appended then, and the counts' upload below is on the main stream, in front of every launch of this call.
+    if (rows_on) HIP_TRY(ctx, hipMemcpyAsync(t.d_mut_n, t.h_mut_n, (size_t)W * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     for (;;) {
         bool any = false;
         for (int w = 0; w < W; ++w) {
@@ -760,6 +832,9 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                 any_res = true;
             } else if (walker) {
                 wj.A = mt_walk_args(ctx, c, n_w[w], row0, ws[w].done, sequence_type, gc_bias, lds.use_rows, guard);
+                wj.A.mut = region(w);
+                wj.A.mut_cap = t.mut_rows;
+                wj.A.mut_count = rows_on ? t.d_mut_n + w : nullptr;
                 wj.g = dev_genome(ctx->genomes[ws[w].gid]);
                 wj.desc = ctx->desc + row0;
                 any_walk = true;
@@ -770,11 +845,13 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         if (any_walk) {  // (beside the resolver: other workers; behind the words and tables the main stream has waited for / copied)
             HIP_TRY(ctx, hipEventRecord(t.ev_turn, ctx->stream));
             HIP_TRY(ctx, hipStreamWaitEvent(s_side, t.ev_turn, 0));
+            if (rows_on) HIP_TRY(ctx, hipStreamWaitEvent(s_side, t.ev_place, 0));  // (the rows of the turn before have their places)
             hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), walk_rows ? lds.fixed + lds.rows : lds.fixed, s_side, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
             HIP_TRY(ctx, hipEventRecord(t.ev_side, s_side));
         }
         if (any_res) hipLaunchKernelGGL(resolve, dim3(W), dim3(iss::RES_THREADS), pick.lds, ctx->stream, M, reinterpret_cast<const iss::MtResolveJob *>(dev_of(h_rj)));
         if (any_walk) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, t.ev_side, 0));
+        if (any_walk && rows_on) HIP_TRY(ctx, hipEventRecord(t.ev_walk, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(t.h_res, t.d_res, (size_t)W * sizeof(iss::MtWalkResult), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipGetLastError());
@@ -792,6 +869,13 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             ej.rec = h_rj[w].A.rec;
             for (int k = 0; k < 4; ++k) ej.out[k] = ctx->out[k] + (size_t)row0 * M.row;
             ej.g = h_rj[w].g;
+            if (rows_on) {
+                ej.mut_cnt = t.d_mut_cnt + (size_t)w * t.mut_stride;
+                ej.mut_off = t.d_mut_off + (size_t)w * t.mut_stride;
+                ej.mut = region(w);
+                ej.mut_cap = t.mut_rows;
+                ej.pair_base = ws[w].done;
+            }
             emit_max = std::max(emit_max, ej.n_pairs);
             for (int s = 0; s < 2; ++s) t.last_read[(size_t)(2 * w + s) * 2 + res_buf[2 * w + s]] = turn;
         }
@@ -802,6 +886,14 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             HIP_TRY(ctx, hipMemcpyAsync(dev_of(h_ej), h_ej, (size_t)W * sizeof(iss::MtEmitJob), hipMemcpyHostToDevice, s_emit));
             hipLaunchKernelGGL(iss::k_mt_emit_w, dim3((unsigned)((2 * emit_max + 3) / 4), (unsigned)W), dim3(256), 0, s_emit, M,
                                reinterpret_cast<const iss::MtEmitJob *>(dev_of(h_ej)));
+            if (rows_on) {  // the counts of the pass above -> places (one workgroup per worker) -> the rows, and only the rows
+                HIP_TRY(ctx, hipStreamWaitEvent(s_emit, t.ev_walk, 0));
+                hipLaunchKernelGGL(iss::k_mt_mut_place_w, dim3((unsigned)W), dim3(iss::PLACE_THREADS), 0, s_emit,
+                                   reinterpret_cast<const iss::MtEmitJob *>(dev_of(h_ej)), t.d_mut_n);
+                HIP_TRY(ctx, hipEventRecord(t.ev_place, s_emit));
+                hipLaunchKernelGGL(iss::k_mt_emit_rows_w, dim3((unsigned)((2 * emit_max + 3) / 4), (unsigned)W), dim3(256), 0, s_emit, M,
+                                   reinterpret_cast<const iss::MtEmitJob *>(dev_of(h_ej)));
+            }
         }
         HIP_TRY(ctx, hipEventRecord(t.ev_emit[par], s_emit));
         // ---- (e) what the turn consumed and produced; a resolver that stopped in front of a pair for the walker (an indel candidate,
@@ -849,13 +941,18 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                 if (!odd || short_of_words) continue;
                 const int64_t row0 = ws[w].row0 + ws[w].done;
                 wj.A = mt_walk_args(ctx, c, 1, row0, ws[w].done, sequence_type, gc_bias, false, guard);
+                wj.A.mut = region(w);
+                wj.A.mut_cap = t.mut_rows;
+                wj.A.mut_count = rows_on ? t.d_mut_n + w : nullptr;
                 wj.g = dev_genome(ctx->genomes[ws[w].gid]);
                 wj.desc = ctx->desc + row0;
                 ++n_odd;
             }
             if (n_odd) {
                 HIP_TRY(ctx, hipMemcpyAsync(dev_of(h_wj), h_wj, (size_t)W * sizeof(iss::MtWalkJob), hipMemcpyHostToDevice, ctx->stream));
+                if (rows_on) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, t.ev_place, 0));  // (this turn's rows have their places: the walked pair's come behind them)
                 hipLaunchKernelGGL(iss::k_mt_walk_w, dim3(W), dim3(64), lds.fixed, ctx->stream, M, reinterpret_cast<const iss::MtWalkJob *>(dev_of(h_wj)));
+                if (rows_on) HIP_TRY(ctx, hipEventRecord(t.ev_walk, ctx->stream));
                 HIP_TRY(ctx, hipMemcpyAsync(t.h_res, t.d_res, (size_t)W * sizeof(iss::MtWalkResult), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 HIP_TRY(ctx, hipGetLastError());
@@ -915,6 +1012,40 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     for (auto &e : t.ev_emit) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, e, 0));  // (the rows are complete once the main stream is)
     for (int w = 0; w < W; ++w)
         if (n_done && ws[w].n) n_done[w] = ws[w].done;
+    if (rows_on) {  // the workers' row counts: what iss_vcf_emit_workers / iss_mt_workers_mutations_download take, and the overflow check
+        HIP_TRY(ctx, hipMemcpyAsync(t.h_mut_n, t.d_mut_n, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int w = 0; w < W; ++w) t.mut_n[w] = t.h_mut_n[w];
+        for (int w = 0; w < W; ++w)
+            if (t.mut_n[w] > t.mut_rows)  // (the rows past the region were dropped, never written elsewhere: the call fails, the set is poisoned)
+                return fail(ctx, ISS_E_NOMEM, "iss_generate_mt_workers: worker " + std::to_string(w) + " made " + std::to_string(t.mut_n[w]) +
+                                                  " mutation rows, iss_mt_workers_mutations_reserve holds " + std::to_string(t.mut_rows) + " per worker");
+    }
+    return 0;
+}
+
+int iss_mt_workers_mutations_reserve(iss_ctx *ctx, int64_t rows_per_worker) {
+    if (!ctx || rows_per_worker < 0 || rows_per_worker > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_mutations_reserve: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }  // (a queued text's kernels read the pool)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    free_mt_set_rows(ctx);
+    ctx->mts.mut_rows = rows_per_worker;
+    return mt_set_rows_alloc(ctx);  // (a set seeded later gets its rows then)
+}
+
+int iss_mt_workers_mutations_download(iss_ctx *ctx, int32_t worker, iss_mutation *out, int64_t capacity, int64_t *n_total) {
+    if (n_total) *n_total = 0;
+    if (!ctx || worker < 0 || worker >= ctx->mts.W || capacity < 0) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_mutations_download: bad argument");
+    const auto &t = ctx->mts;
+    if (!t.d_mut) return 0;
+    if (n_total) *n_total = t.mut_n[(size_t)worker];
+    const int64_t n = std::min(std::min(t.mut_n[(size_t)worker], t.mut_rows), capacity);
+    if (n > 0 && out) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemcpy(out, t.d_mut + (size_t)worker * (size_t)t.mut_rows, (size_t)n * sizeof(iss::MutRecord), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -1,86 +1,66 @@
 // iss_api_vcf.hip.h -- C ABI: the --store_mutations VCF text built on the device (iss_vcf_emit, iss_vcf_flush).
 #pragma once
 
-extern "C" {
+namespace {
 
-int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
-                 const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number, int64_t *slots_needed) {
-    if (slots_needed) *slots_needed = 0;
-    if (!ctx || !ctx->have_model || fd < 0 || n_items < 0 || cpu_number < 0 || (source != 0 && source != 1) ||
-        (n_items && (!record_ids || !first_i || !first_pair || !n_pairs)))
-        return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    VcfPipe &q = ctx->vq;
-    if (!q.ready) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
-        for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &p : q.h_total) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); p = static_cast<uint64_t *>(v); }
-        { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); q.h_count = static_cast<uint32_t *>(v); }
-        { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 2 * sizeof(uint32_t))); q.d_stats = static_cast<uint32_t *>(v); }
-        q.stop = false;
-        q.writer = std::thread(vcf_writer_loop, ctx);
-        q.ready = true;
-    }
-    // the rows: how many slots to look at, and which output row pair 0 of the call is
-    const bool philox = source == 0;
-    int64_t n_slots = 0, row0 = 0, call_pairs = 0;
-    if (philox) {
-        if (!ctx->d_pmut || !ctx->d_pmut_count) return 0;  // (no rows are captured: like iss_mutations_download)
-        // the one value that comes back per call: the slots it reserved (this waits for the generation, not for the text)
-        HIP_TRY(ctx, hipMemcpyAsync(q.h_count, ctx->d_pmut_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        n_slots = (int64_t)*q.h_count;
-        if (n_slots > ctx->pmut_cap) {
-            if (slots_needed) *slots_needed = n_slots;  // (the slots the call asked for: what a retry has to reserve)
-            return fail(ctx, ISS_E_NOMEM, "mutation buffer too small for this call (reserve more with iss_mutations_reserve)");
-        }
-        row0 = ctx->last_row0;
-        call_pairs = ctx->last_n;
-    } else {
-        const auto &m = ctx->mt;
-        if (!m.d_mut) return 0;
-        if (m.mut_n > m.mut_cap) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: more rows than iss_mt_mutations_reserve holds");
-        n_slots = m.mut_n;
-        row0 = m.mut_row0;
-    }
-    // the items that hold pairs, as pairs of the call: ascending, apart
+// one text job: the rows, their items, where the text goes
+struct VcfJob {
+    int fd = -1;                   // one file ...
+    std::vector<int> wfds;         // ... or one per item: a worker set (wbase below)
+    bool philox = false;
+    const iss::MutRecord *mut = nullptr;
+    int64_t n_slots = 0, call_pairs = 0;
     std::vector<iss::VcfItem> items;
     std::string ids;
-    size_t longest = 0;  // of "{id}_{i}_" over the items
-    for (int32_t k = 0; k < n_items; ++k) {
-        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
-        const size_t idlen = strlen(record_ids[k]);
-        if (idlen > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: record id longer than 4096 bytes");
-        if (n_pairs[k] == 0) continue;
-        iss::VcfItem it{};
-        it.first_i = (uint64_t)first_i[k];
-        it.pair0 = first_pair[k] - row0;
-        it.n_pairs = n_pairs[k];
-        if (it.pair0 < 0 || (philox && it.pair0 + it.n_pairs > call_pairs))
-            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: an item lies outside the rows of the last generate call");
-        if (!items.empty() && it.pair0 < items.back().pair0 + items.back().n_pairs)
-            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: items must stand in ascending row order and not overlap");
-        it.id_off = (uint32_t)ids.size();
-        it.id_len = (int32_t)idlen;
-        ids.append(record_ids[k], idlen);
-        int dg = 1;
-        for (uint64_t v = it.first_i + (uint64_t)it.n_pairs - 1; v >= 10; v /= 10) ++dg;
-        longest = std::max(longest, idlen + (size_t)dg);
-        items.push_back(it);
-    }
-    if (items.empty() || n_slots == 0) return 0;
-    if (n_slots > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: too many rows");
-    if (q.fd != fd) {
-        { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }
-        const off_t at = lseek(fd, 0, SEEK_CUR);
-        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
-        q.fd = fd;
-        q.off = at;
-    }
+    size_t longest = 0;            // of "{id}_{i}_" over the items
+    std::vector<uint64_t> wbase;   // a worker set: [n_items + 1] first row of item k's worker in the text
+    uint64_t wstride = 0;          // ... whose rows stand at mut + k * wstride
+};
+
+int vcf_pipe_init(iss_ctx *ctx) {
+    VcfPipe &q = ctx->vq;
+    if (q.ready) return 0;
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
+    for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &p : q.h_total) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); p = static_cast<uint64_t *>(v); }
+    { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); q.h_count = static_cast<uint32_t *>(v); }
+    { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 2 * sizeof(uint32_t))); q.d_stats = static_cast<uint32_t *>(v); }
+    q.stop = false;
+    q.writer = std::thread(vcf_writer_loop, ctx);
+    q.ready = true;
+    return 0;
+}
+
+// an item of the table: the id's place in `ids`, the worker's number, the longest "{id}_{i}_" so far
+int vcf_add_item(iss_ctx *ctx, VcfJob &J, const char *record_id, int64_t first_i, int64_t pair0, int64_t n_pairs, int32_t cpu_number) {
+    const size_t idlen = strlen(record_id);
+    if (idlen > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: record id longer than 4096 bytes");
+    iss::VcfItem it{};
+    it.first_i = (uint64_t)first_i;
+    it.pair0 = pair0;
+    it.n_pairs = n_pairs;
+    it.id_off = (uint32_t)J.ids.size();
+    it.id_len = (int32_t)idlen;
+    it.cpu_len = (int32_t)snprintf(it.cpu, sizeof it.cpu, "%d", cpu_number);
+    J.ids.append(record_id, idlen);
+    int dg = 1;
+    for (uint64_t v = it.first_i + (uint64_t)std::max<int64_t>(it.n_pairs, 1) - 1; v >= 10; v /= 10) ++dg;
+    J.longest = std::max(J.longest, idlen + (size_t)dg);
+    J.items.push_back(it);
+    return 0;
+}
+
+// the kernels of DESIGN.md section 14 for one job, on the context's stream; the job queued for the writer thread
+int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
+    VcfPipe &q = ctx->vq;
+    const bool philox = J.philox;
+    const int64_t n_slots = J.n_slots, call_pairs = J.call_pairs;
+    const std::vector<iss::VcfItem> &items = J.items;
+    const std::string &ids = J.ids;
+    const size_t longest = J.longest;
     iss::VcfArgs A{};
-    A.cpu_len = (int32_t)snprintf(A.cpu, sizeof A.cpu, "%d", cpu_number);
     // bytes of a row at most: 14 fixed characters, position + 1 and the phred with up to 6 each, two letters of an insertion
-    const size_t row_max = longest + (size_t)A.cpu_len + 14 + 6 + 6 + 2;
+    const size_t row_max = longest + 12 /* the worker's number */ + 14 + 6 + 6 + 2;
     const size_t bound = (size_t)n_slots * row_max;
     // work arrays (one set: every kernel that touches them is on the context's stream)
     const size_t n_tiles = std::max<size_t>(1, ((size_t)std::max<int64_t>(n_slots, call_pairs) + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
@@ -140,7 +120,7 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::VcfItem), hipMemcpyHostToDevice, st));
     if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, st));
-    A.mut = philox ? ctx->d_pmut : ctx->mt.d_mut;
+    A.mut = J.mut;
     A.n_slots = (uint32_t)n_slots;
     A.n_pairs = call_pairs;
     A.cnt = q.d_cnt;
@@ -154,6 +134,25 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
     A.items = q.d_items[slot];
     A.ids = q.d_ids[slot];
     A.n_items = (int32_t)items.size();
+    const bool set = !J.wbase.empty();  // a worker set: item k = worker k, its rows from wbase[k] (the table behind the items' copy)
+    if (set) {
+        const size_t nw = J.wbase.size();  // n_items + 1
+        if (2 * nw > q.wb_cap[slot]) {
+            if (q.h_wb[slot]) (void)hipHostFree(q.h_wb[slot]);
+            if (q.d_wb[slot]) (void)hipFree(q.d_wb[slot]);
+            q.h_wb[slot] = q.d_wb[slot] = nullptr;
+            q.wb_cap[slot] = 0;
+            void *v = nullptr;
+            HIP_TRY(ctx, hipHostMalloc(&v, 4 * nw * sizeof(uint64_t), hipHostMallocDefault)); q.h_wb[slot] = static_cast<uint64_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, 4 * nw * sizeof(uint64_t))); q.d_wb[slot] = static_cast<uint64_t *>(v);
+            q.wb_cap[slot] = 4 * nw;
+        }
+        memcpy(q.h_wb[slot], J.wbase.data(), nw * sizeof(uint64_t));
+        HIP_TRY(ctx, hipMemcpyAsync(q.d_wb[slot], q.h_wb[slot], nw * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        A.wbase = q.d_wb[slot];
+        A.wstride = J.wstride;
+        A.wbytes = q.d_wb[slot] + nw;
+    }
     auto grid_for = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>(2048, (n + iss::VCF_THREADS - 1) / iss::VCF_THREADS)); };
     auto scan = [&](const uint32_t *in, uint64_t n, uint64_t *out) {
         const unsigned tiles = (unsigned)((n + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
@@ -191,17 +190,124 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
     scan(q.d_len, (uint64_t)n_slots, q.d_off);
     hipLaunchKernelGGL(iss::k_vcf_format, grid, block, 0, st, A);  // d
     HIP_TRY(ctx, hipGetLastError());
+    if (set) {
+        hipLaunchKernelGGL(iss::k_vcf_worker_bytes, dim3((unsigned)(J.wbase.size() + iss::VCF_THREADS - 1) / iss::VCF_THREADS), block, 0, st, A);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(q.h_wb[slot] + J.wbase.size(), A.wbytes, J.wbase.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot], q.d_off + n_slots, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipEventRecord(q.ev_fmt[slot], st));
     {
         std::lock_guard<std::mutex> lk(q.mu);
-        q.job_fd[slot] = fd;
+        q.job_fd[slot] = J.fd;
+        q.job_wfds[slot] = J.wfds;
         q.jobs.push_back(slot);
         q.busy[slot] = true;
     }
     q.cv.notify_all();
     q.next ^= 1;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
+                 const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number, int64_t *slots_needed) {
+    if (slots_needed) *slots_needed = 0;
+    if (!ctx || !ctx->have_model || fd < 0 || n_items < 0 || cpu_number < 0 || (source != 0 && source != 1) ||
+        (n_items && (!record_ids || !first_i || !first_pair || !n_pairs)))
+        return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    VcfPipe &q = ctx->vq;
+    { int rc_ = vcf_pipe_init(ctx); if (rc_) return rc_; }
+    // the rows: how many slots to look at, and which output row pair 0 of the call is
+    const bool philox = source == 0;
+    int64_t n_slots = 0, row0 = 0, call_pairs = 0;
+    if (philox) {
+        if (!ctx->d_pmut || !ctx->d_pmut_count) return 0;  // (no rows are captured: like iss_mutations_download)
+        // the one value that comes back per call: the slots it reserved (this waits for the generation, not for the text)
+        HIP_TRY(ctx, hipMemcpyAsync(q.h_count, ctx->d_pmut_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        n_slots = (int64_t)*q.h_count;
+        if (n_slots > ctx->pmut_cap) {
+            if (slots_needed) *slots_needed = n_slots;  // (the slots the call asked for: what a retry has to reserve)
+            return fail(ctx, ISS_E_NOMEM, "mutation buffer too small for this call (reserve more with iss_mutations_reserve)");
+        }
+        row0 = ctx->last_row0;
+        call_pairs = ctx->last_n;
+    } else {
+        const auto &m = ctx->mt;
+        if (!m.d_mut) return 0;
+        if (m.mut_n > m.mut_cap) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: more rows than iss_mt_mutations_reserve holds");
+        n_slots = m.mut_n;
+        row0 = m.mut_row0;
+    }
+    // the items that hold pairs, as pairs of the call: ascending, apart
+    VcfJob J;
+    for (int32_t k = 0; k < n_items; ++k) {
+        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
+        if (strlen(record_ids[k]) > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: record id longer than 4096 bytes");
+        if (n_pairs[k] == 0) continue;
+        const int64_t pair0 = first_pair[k] - row0;
+        if (pair0 < 0 || (philox && pair0 + n_pairs[k] > call_pairs))
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: an item lies outside the rows of the last generate call");
+        if (!J.items.empty() && pair0 < J.items.back().pair0 + J.items.back().n_pairs)
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: items must stand in ascending row order and not overlap");
+        { int rc_ = vcf_add_item(ctx, J, record_ids[k], first_i[k], pair0, n_pairs[k], cpu_number); if (rc_) return rc_; }
+    }
+    if (J.items.empty() || n_slots == 0) return 0;
+    if (n_slots > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: too many rows");
+    if (q.fd != fd) {
+        { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }
+        const off_t at = lseek(fd, 0, SEEK_CUR);
+        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
+        q.fd = fd;
+        q.off = at;
+    }
+    J.fd = fd;
+    J.philox = philox;
+    J.mut = philox ? ctx->d_pmut : ctx->mt.d_mut;
+    J.n_slots = n_slots;
+    J.call_pairs = call_pairs;
+    return vcf_queue(ctx, J);
+}
+
+int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const char *const *record_ids, const int64_t *first_i,
+                         const int64_t *first_pair, const int64_t *n_pairs, const int32_t *cpu_numbers) {
+    if (!ctx || !ctx->have_model || n_workers < 1 || !fds || !record_ids || !first_i || !first_pair || !n_pairs || !cpu_numbers)
+        return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: bad argument");
+    const auto &t = ctx->mts;
+    if (n_workers != t.W) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: one entry per worker of the seeded set");
+    if (t.poisoned) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: the last iss_generate_mt_workers call failed (its rows are undefined)");
+    if (!t.d_mut) return 0;  // (no rows are captured: like iss_vcf_emit)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc_ = vcf_pipe_init(ctx); if (rc_) return rc_; }
+    VcfPipe &q = ctx->vq;
+    // item k = worker k (a worker that sits the round out, or made no row, has an empty range); the text's rows are the workers' rows
+    // one worker after the other
+    VcfJob J;
+    uint64_t rows = 0;
+    for (int32_t k = 0; k < n_workers; ++k) {
+        if (!record_ids[k] || first_i[k] < 0 || n_pairs[k] < 0 || cpu_numbers[k] < 0 || (n_pairs[k] > 0 && fds[k] < 0))
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: bad argument");
+        if (n_pairs[k] > 0 && (first_pair[k] != t.mut_row0[(size_t)k] || n_pairs[k] > t.mut_pairs[(size_t)k]))
+            return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: a worker's item is not its rows of the last iss_generate_mt_workers call");
+        if (t.mut_n[(size_t)k] > t.mut_rows) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: more rows than iss_mt_workers_mutations_reserve holds");
+        { int rc_ = vcf_add_item(ctx, J, record_ids[k], first_i[k], 0, n_pairs[k], cpu_numbers[k]); if (rc_) return rc_; }
+        J.wbase.push_back(rows);
+        J.wfds.push_back(fds[k]);
+        if (n_pairs[k] > 0) rows += (uint64_t)t.mut_n[(size_t)k];
+    }
+    J.wbase.push_back(rows);
+    if (rows == 0) return 0;
+    if (rows > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: too many rows");
+    if (q.fd >= 0) { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }  // (a single file's running offset ends here)
+    J.mut = t.d_mut;
+    J.wstride = (uint64_t)t.mut_rows;
+    J.n_slots = (int64_t)rows;
+    return vcf_queue(ctx, J);
 }
 
 int iss_vcf_flush(iss_ctx *ctx) {

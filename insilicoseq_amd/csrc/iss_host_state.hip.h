@@ -165,6 +165,10 @@ struct VcfPipe {
     std::condition_variable cv;
     std::deque<int> jobs;                // slots, in call order
     int job_fd[2] = {-1, -1};
+    // iss_vcf_emit_workers: the text of a slot is W byte ranges, range k appended to job_wfds[k] (empty: one file, job_fd)
+    std::vector<int> job_wfds[2];
+    uint64_t *h_wb[2] = {nullptr, nullptr}, *d_wb[2] = {nullptr, nullptr};  // [2][wb_cap]: the workers' first rows (wbase), then their byte offsets
+    size_t wb_cap[2] = {0, 0};
     bool busy[2] = {false, false};
     bool stop = false;
     std::string error;
@@ -336,6 +340,19 @@ struct iss_ctx {
         iss::MtWalkResult *h_res = nullptr;  // pinned [W]
         int64_t turns = 0;
         int64_t n_resolved = 0, n_walked = 0;
+        // --store_mutations in the set (iss_mt_workers_mutations_reserve): worker w owns rows
+        // [w * mut_rows, + mut_rows) of ONE pool and a running row count in device memory.  The request (mut_rows) outlives a
+        // re-seeding, the storage is the set's.
+        int64_t mut_rows = 0;                // rows per worker (0: off)
+        iss::MutRecord *d_mut = nullptr;     // [W][mut_rows]
+        int64_t *d_mut_n = nullptr;          // [W]: rows of the running call so far
+        int64_t *h_mut_n = nullptr;          // pinned [W]: set at a call's start, read back at its end
+        int32_t *d_mut_cnt = nullptr;        // [W][mut_stride]: k_mt_emit_w's rows per (pair, mate) of a turn
+        int64_t *d_mut_off = nullptr;        // [W][mut_stride]: their places (k_mt_mut_place_w)
+        size_t mut_stride = 0;
+        hipEvent_t ev_place = nullptr;       // emit stream: the last k_mt_mut_place_w -> the walkers of the main and side streams
+        hipEvent_t ev_walk = nullptr;        // main stream: the last walker -> the next k_mt_mut_place_w
+        std::vector<int64_t> mut_n, mut_row0, mut_pairs;  // [W]: rows, first output row and pairs of the last call's workers
     } mts;
     FastqPipe fq;
     VcfPipe vq;

@@ -80,8 +80,25 @@ void free_outputs(iss_ctx *ctx) {
     ctx->capacity = 0;
 }
 
+// the set's --store_mutations storage (the request, MtSet::mut_rows, stays)
+void free_mt_set_rows(iss_ctx *ctx) {
+    auto &t = ctx->mts;
+    if (t.d_mut) (void)hipFree(t.d_mut);
+    if (t.d_mut_n) (void)hipFree(t.d_mut_n);
+    if (t.h_mut_n) (void)hipHostFree(t.h_mut_n);
+    if (t.d_mut_cnt) (void)hipFree(t.d_mut_cnt);
+    if (t.d_mut_off) (void)hipFree(t.d_mut_off);
+    if (t.ev_place) (void)hipEventDestroy(t.ev_place);
+    if (t.ev_walk) (void)hipEventDestroy(t.ev_walk);
+    t.d_mut = nullptr; t.d_mut_n = nullptr; t.h_mut_n = nullptr; t.d_mut_cnt = nullptr; t.d_mut_off = nullptr;
+    t.ev_place = t.ev_walk = nullptr;
+    t.mut_stride = 0;
+    t.mut_n.clear(); t.mut_row0.clear(); t.mut_pairs.clear();
+}
+
 void free_mt_set(iss_ctx *ctx) {
     auto &t = ctx->mts;
+    free_mt_set_rows(ctx);
     if (t.d_state) (void)hipFree(t.d_state);
     if (t.d_res) (void)hipFree(t.d_res);
     if (t.d_gauss) (void)hipFree(t.d_gauss);

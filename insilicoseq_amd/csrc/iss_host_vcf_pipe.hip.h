@@ -10,12 +10,14 @@ void vcf_writer_loop(iss_ctx *ctx) {
     for (;;) {
         int slot, fd;
         int64_t at;
+        std::vector<int> wfds;
         {
             std::unique_lock<std::mutex> lk(q.mu);
             q.cv.wait(lk, [&] { return q.stop || !q.jobs.empty(); });
             if (q.jobs.empty()) return;
             slot = q.jobs.front();
             fd = q.job_fd[slot];
+            wfds = q.job_wfds[slot];
             at = q.off;  // (only this thread moves it while jobs are queued)
         }
         std::string err;
@@ -44,14 +46,27 @@ void vcf_writer_loop(iss_ctx *ctx) {
                 err = "device copy of the VCF text failed";
             // invariant: the text is whole rows (the lengths the device summed are the bytes it wrote)
             else if (q.h_text[slot][total - 1] != '\n') err = "VCF text does not end with a row";
-            else if (pwrite_all(fd, q.h_text[slot], total, at)) err = std::string("write failed: ") + strerror(errno);
+            else if (wfds.empty()) { if (pwrite_all(fd, q.h_text[slot], total, at)) err = std::string("write failed: ") + strerror(errno); }
+            else {
+                // a worker set's text: range k behind what worker k's file holds (only this thread writes to it: the descriptor
+                // stands at its end, and is left there)
+                const uint64_t *wb = q.h_wb[slot] + wfds.size() + 1;
+                for (size_t k = 0; k < wfds.size() && err.empty(); ++k) {
+                    const uint64_t lo = wb[k], hi = wb[k + 1];
+                    if (lo > hi || hi > total || (k + 1 == wfds.size() && hi != total)) { err = "VCF text: the workers' byte ranges do not tile it"; break; }
+                    if (hi == lo) continue;
+                    const off_t end = lseek(wfds[k], 0, SEEK_CUR);
+                    if (end < 0 || pwrite_all(wfds[k], q.h_text[slot] + lo, hi - lo, (int64_t)end) || lseek(wfds[k], end + (off_t)(hi - lo), SEEK_SET) < 0)
+                        err = std::string("write failed: ") + strerror(errno);
+                }
+            }
         }
         {
             std::lock_guard<std::mutex> lk(q.mu);
             q.jobs.pop_front();
             q.busy[slot] = false;
-            if (err.empty()) q.off += (int64_t)total;
-            else if (q.error.empty()) q.error = err;
+            if (!err.empty()) { if (q.error.empty()) q.error = err; }
+            else if (wfds.empty()) q.off += (int64_t)total;  // (a worker set's descriptors were moved as they were written)
         }
         q.cv.notify_all();
     }
@@ -101,6 +116,10 @@ void vcf_shutdown(iss_ctx *ctx) {
         if (q.d_items[sl]) (void)hipFree(q.d_items[sl]);
         if (q.h_ids[sl]) (void)hipHostFree(q.h_ids[sl]);
         if (q.d_ids[sl]) (void)hipFree(q.d_ids[sl]);
+        if (q.h_wb[sl]) (void)hipHostFree(q.h_wb[sl]);
+        if (q.d_wb[sl]) (void)hipFree(q.d_wb[sl]);
+        q.h_wb[sl] = q.d_wb[sl] = nullptr;
+        q.wb_cap[sl] = 0;
         q.d_text[sl] = q.h_text[sl] = nullptr;
         q.h_total[sl] = nullptr;
         q.h_items[sl] = q.d_items[sl] = nullptr;

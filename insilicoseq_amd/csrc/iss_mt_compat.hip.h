@@ -16,6 +16,8 @@
 //   k_mt_resolve / k_mt_emit : the fast path for plain pairs (see below): only the stream offsets are
 //               chained, by one workgroup working from LDS; the reads are then built in parallel.
 //
+//   k_mt_mut_place_w / k_mt_emit_rows_w: --store_mutations rows of a set's turn -- placed by a scan per worker on the device, then
+//               written by a rows-only pass of the emitter.
 //   k_mt_fill_w / k_mt_resolve_w / k_mt_walk_w / k_mt_emit_w / k_mt_move_w (round 5): the same bodies for W workers per
 //               launch -- the reference's own parallelism is N workers with seeds seed + cpu_number (iss/app.py:99-106,
 //               iss/generator.py:234-236): one workgroup (wavefront, grid row) per worker, the jobs in a table in HBM.
@@ -213,6 +215,8 @@ struct MtWalkArgs {
     MtPhredAmb *amb;            // out: ambiguous phreds of the pair that stopped the walk (capacity MT_AMB_CAP)
     const MtPhredAmb *ovq;      // in: the host's answers for the FIRST pair of this launch
     int32_t n_ovq;
+    int64_t *mut_count;         // a worker of the set: its running row count in device memory -- read as mut_base when the walk
+                                // begins, moved on by n_mut when it ends (NULL: mut_base above, a host value)
 };
 constexpr int MT_AMB_CAP = 512;
 
@@ -320,12 +324,13 @@ __device__ __forceinline__ void mt_walk_body(const DevModel &M, const DevGenome 
     double host_x1 = 0, host_x2 = 0;
     MtGauss gs = *A.gauss;  // wave-uniform copy; written back at the end
     int64_t n_mut = 0;  // wave-uniform
+    const int64_t mut_base = A.mut_count ? *A.mut_count : A.mut_base;
     auto put_mut = [&](int mate, int type, int pos, int ref, int alt, int qual, int64_t at) {
-        if (A.mut && A.mut_base + at < A.mut_cap) {
+        if (A.mut && mut_base + at < A.mut_cap) {
             MutRecord r;
             r.pair = (int32_t)(A.pair_base + i); r.mate = (int8_t)mate; r.type = (int8_t)type; r.position = (int16_t)pos;
             r.ref = (uint8_t)ref; r.alt = (uint8_t)alt; r.quality = (int16_t)qual;
-            A.mut[A.mut_base + at] = r;
+            A.mut[mut_base + at] = r;
         }
     };
     int n_amb = 0, abort_pair = 0;  // wave-uniform
@@ -658,6 +663,7 @@ __device__ __forceinline__ void mt_walk_body(const DevModel &M, const DevGenome 
         A.res->host_x2 = host_x2;
         A.res->n_amb = n_amb;
         *A.gauss = gs;
+        if (A.mut_count) *A.mut_count = mut_base + n_mut;  // (past mut_cap: the host sees the overflow, the rows were dropped)
     }
 }
 __global__ __launch_bounds__(64) void k_mt_walk(DevModel M, DevGenome g, MtWalkArgs A, PairDesc *desc) { mt_walk_body(M, g, A, desc); }
@@ -673,6 +679,7 @@ __global__ __launch_bounds__(64) void k_mt_walk_w(DevModel M, const MtWalkJob *j
 #pragma unroll
     for (int k = 0; k < 4; ++k) j.A.out[k] = as_global(j.A.out[k], jobs);
     j.A.mut = as_global(j.A.mut, jobs); j.A.amb = as_global(j.A.amb, jobs); j.A.ovq = as_global(j.A.ovq, jobs);
+    j.A.mut_count = as_global(j.A.mut_count, jobs);
     mt_walk_body(M, genome_as_global(j.g, jobs), j.A, as_global(j.desc, jobs));
 }
 
@@ -1050,8 +1057,10 @@ __global__ __launch_bounds__(RES_THREADS) void k_mt_resolve_w(DevModel M, const 
 // reads of the pairs k_mt_resolve resolved: one wavefront per (pair, mate); the read is the template
 // (no indel, only ACGT), phred scores and substitutions come from the recorded stream offsets
 // --store_mutations: the rows of a (pair, mate) are its substituted positions in ascending order, and the file
-// lists the mates in order.  Pass 1 (mut_cnt != NULL) only counts the rows of every mate; the host turns the counts
-// into offsets; pass 2 (mut != NULL) writes each row at its final place mut_off[item] + rank.
+// lists the mates in order.  Pass 1 (mut_cnt != NULL) only counts the rows of every mate; the counts become offsets (one
+// worker: a prefix sum on the host; the set: k_mt_mut_place_w); pass 2 (mut != NULL) writes each row at its final place
+// mut_off[item] + rank.  ROWS_ONLY (the set's pass 2): the read's bytes are in place since pass 1 and are not stored again,
+// and a mate that pass 1 counted no row for (mut_cnt, read here) leaves at once.
 struct MtEmitMut {
     int32_t *mut_cnt;         // pass 1: [2 * n_pairs] rows per (pair, mate)
     const int64_t *mut_off;   // pass 2: [2 * n_pairs] first row of (pair, mate) in `mut`
@@ -1060,6 +1069,7 @@ struct MtEmitMut {
     int64_t pair_base;        // pair index (within the call) of this launch's first pair
 };
 
+template <bool ROWS_ONLY = false>
 __device__ __forceinline__ void mt_emit_body(const DevModel &M, const DevGenome &g, const uint32_t *py, const uint32_t *np,
                                              int64_t n_pairs, const PairDesc *desc, const MtPairRec *rec, uint8_t *out0,
                                              uint8_t *out1, uint8_t *out2, uint8_t *out3, const MtEmitMut &E) {
@@ -1069,6 +1079,7 @@ __device__ __forceinline__ void mt_emit_body(const DevModel &M, const DevGenome 
     const int64_t i = item >> 1;
     const int o = (int)(item & 1);
     const int RL = M.RL;
+    if (ROWS_ONLY && E.mut_cnt[item] == 0) return;  // (uniform: one wavefront per item)
     const PairDesc d = desc[i];
     const MtPairRec r = rec[i];
     const uint32_t onp_q = r.onp_bin[o] + 2u, onp_s = onp_q + 2u * (uint32_t)RL, opy_e = r.opy_err[o];
@@ -1117,8 +1128,9 @@ __device__ __forceinline__ void mt_emit_body(const DevModel &M, const DevGenome 
             }
         }
         n_rows += (uint32_t)__popcll(rm);
-        if (p < RL) { ob[xp(p)] = (uint8_t)ch; oq[xp(p)] = (uint8_t)q; }
+        if (!ROWS_ONLY && p < RL) { ob[xp(p)] = (uint8_t)ch; oq[xp(p)] = (uint8_t)q; }
     }
+    if (ROWS_ONLY) return;
     if (E.mut_cnt && lane == 0) E.mut_cnt[item] = (int32_t)n_rows;
     for (int p = RL + lane; p < M.pitch; p += 64) { ob[xp(p)] = 0; oq[xp(p)] = 0; }
 }
@@ -1127,20 +1139,96 @@ __global__ __launch_bounds__(256) void k_mt_emit(DevModel M, DevGenome g, const 
                                                  uint8_t *out1, uint8_t *out2, uint8_t *out3, MtEmitMut E) {
     mt_emit_body(M, g, py, np, n_pairs, desc, rec, out0, out1, out2, out3, E);
 }
-struct MtEmitJob {  // (grid.y = worker; no --store_mutations rows on this path)
+struct MtEmitJob {  // (grid.y = worker)
     const uint32_t *py, *np;
     int64_t n_pairs;
     const PairDesc *desc;
     const MtPairRec *rec;
     uint8_t *out[4];
     DevGenome g;
+    // --store_mutations (NULL: off): what MtEmitMut holds, per worker -- the worker's [2 * n_pairs] counts and offsets, its
+    // region of the set's row pool and the region's capacity
+    int32_t *mut_cnt;
+    int64_t *mut_off;
+    MutRecord *mut;
+    int64_t mut_cap;
+    int64_t pair_base;
 };
+// the reads of the turn; with rows on, pass 1: the rows of every mate counted
 __global__ __launch_bounds__(256) void k_mt_emit_w(DevModel M, const MtEmitJob *jobs) {
     const MtEmitJob j = jobs[blockIdx.y];
     if ((int64_t)blockIdx.x * 4 >= 2 * j.n_pairs) return;
-    const MtEmitMut none{};
+    MtEmitMut E{};
+    E.mut_cnt = as_global(j.mut_cnt, jobs);
     mt_emit_body(M, genome_as_global(j.g, jobs), as_global(j.py, jobs), as_global(j.np, jobs), j.n_pairs, as_global(j.desc, jobs), as_global(j.rec, jobs),
-                 as_global(j.out[0], jobs), as_global(j.out[1], jobs), as_global(j.out[2], jobs), as_global(j.out[3], jobs), none);
+                 as_global(j.out[0], jobs), as_global(j.out[1], jobs), as_global(j.out[2], jobs), as_global(j.out[3], jobs), E);
+}
+// pass 2 of the set: the rows at the places k_mt_mut_place_w gave them, nothing else stored
+__global__ __launch_bounds__(256) void k_mt_emit_rows_w(DevModel M, const MtEmitJob *jobs) {
+    const MtEmitJob j = jobs[blockIdx.y];
+    if ((int64_t)blockIdx.x * 4 >= 2 * j.n_pairs || !j.mut) return;
+    MtEmitMut E{};
+    E.mut_cnt = as_global(j.mut_cnt, jobs);
+    E.mut_off = as_global(j.mut_off, jobs);
+    E.mut = as_global(j.mut, jobs);
+    E.mut_cap = j.mut_cap;
+    E.pair_base = j.pair_base;
+    mt_emit_body<true>(M, genome_as_global(j.g, jobs), as_global(j.py, jobs), as_global(j.np, jobs), j.n_pairs, as_global(j.desc, jobs), as_global(j.rec, jobs),
+                       nullptr, nullptr, nullptr, nullptr, E);
+}
+
+// Between the two passes: one workgroup per worker turns the worker's [2 * n_pairs] counts into the places of its rows -- an
+// exclusive scan that starts at the worker's running row count mut_n[worker] (device memory: the walker behind a turn reads
+// and moves the same count, MtWalkArgs::mut_count) and moves the count on by the turn's rows.  A tile of 2048 counts per
+// step: eight per lane, the lanes' sums scanned inside a wavefront by shuffles, the four wavefronts' totals through LDS; the
+// tiles of a longer turn follow one another with the carry.  No atomics, nothing for the host to do.
+constexpr int PLACE_THREADS = 256, PLACE_PER = 8;
+__global__ __launch_bounds__(PLACE_THREADS) void k_mt_mut_place_w(const MtEmitJob *jobs, int64_t *mut_n) {
+    __shared__ int32_t wave_total[PLACE_THREADS / 64];
+    const int64_t n_items = 2 * jobs[blockIdx.x].n_pairs;
+    if (n_items <= 0 || !jobs[blockIdx.x].mut) return;  // (uniform)
+    const int32_t *cnt = as_global(jobs[blockIdx.x].mut_cnt, jobs);  // (16-byte aligned: the host's stride per worker)
+    int64_t *off = as_global(jobs[blockIdx.x].mut_off, jobs);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t carry = mut_n[blockIdx.x];
+    for (int64_t base = 0; base < n_items; base += PLACE_THREADS * PLACE_PER) {  // (uniform)
+        const int64_t at = base + (int64_t)tid * PLACE_PER;
+        int32_t v[PLACE_PER];
+        if (at + PLACE_PER <= n_items) {
+            const int4 a = *reinterpret_cast<const int4 *>(cnt + at), b = *reinterpret_cast<const int4 *>(cnt + at + 4);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < PLACE_PER; ++k) v[k] = at + k < n_items ? cnt[at + k] : 0;
+        }
+        int32_t s = 0;
+#pragma unroll
+        for (int k = 0; k < PLACE_PER; ++k) s += v[k];
+        int32_t incl = s;  // inclusive scan over the wavefront's lanes
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int32_t x = __shfl_up(incl, d);
+            if (lane >= d) incl += x;
+        }
+        if (lane == 63) wave_total[wave] = incl;
+        __syncthreads();
+        int32_t before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < PLACE_THREADS / 64; ++w) {
+            const int32_t x = wave_total[w];
+            total += x;
+            before += w < wave ? x : 0;
+        }
+        int64_t run = carry + (int64_t)before + (int64_t)(incl - s);
+#pragma unroll
+        for (int k = 0; k < PLACE_PER; ++k) {
+            if (at + k < n_items) off[at + k] = run;
+            run += v[k];
+        }
+        carry += total;
+        __syncthreads();  // (wave_total is written again by the next tile)
+    }
+    if (tid == 0) mut_n[blockIdx.x] = carry;
 }
 
 }  // namespace iss

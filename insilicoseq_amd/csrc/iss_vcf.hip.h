@@ -86,13 +86,17 @@ __global__ __launch_bounds__(VSCAN_THREADS) void k_vcf_scan_apply(const uint32_t
 
 // ------------------------------------------------------------------ rows -> text
 // One emit call formats the rows of several work items: item k = pairs [pair0, pair0 + n_pairs) of the generate call, under
-// "{id_k}_{first_i + (pair - pair0)}_{cpu}".  Items stand in ascending pair order and do not overlap.
+// "{id_k}_{first_i + (pair - pair0)}_{cpu_k}".  Items stand in ascending pair order and do not overlap.
+// The rows of a worker set (VcfArgs::wbase): item k is worker k's piece, the rows of the text are the
+// workers' rows one worker after the other, and a row's item is its worker -- pair numbers start at 0 in every worker.
 struct VcfItem {
     uint64_t first_i;   // pair id of the item's first pair
     int64_t pair0;      // the item's first pair, counted from the call's first pair
     int64_t n_pairs;
     uint32_t id_off;    // of the record id in `ids`
     int32_t id_len;
+    int32_t cpu_len;
+    char cpu[12];       // the worker's number in decimal
 };
 
 struct VcfArgs {
@@ -112,8 +116,11 @@ struct VcfArgs {
     const VcfItem *items;
     const char *ids;
     int32_t n_items;
-    int32_t cpu_len;
-    char cpu[12];             // the worker's number in decimal
+    // a worker set: row j of the text is row j - wbase[k] of worker k = the last k with wbase[k] <= j, whose rows start at
+    // mut + k * wstride ([n_items + 1], wbase[n_items] = n_slots; NULL: one worker, or the Philox slots)
+    const uint64_t *wbase;
+    uint64_t wstride;
+    uint64_t *wbytes;         // out [n_items + 1]: byte offset of worker k's first row in the text (k_vcf_worker_bytes)
     uint32_t *stats;          // ISS_VCF_DEBUG (else NULL): [0] slots that hold a row, [1] rows that stay
 };
 
@@ -201,6 +208,23 @@ __device__ __forceinline__ int vcf_item_of(const VcfArgs &A, int64_t p) {
     return p >= it.pair0 && p < it.pair0 + it.n_pairs ? lo : -1;
 }
 
+// row j of the text and its item (-1: none)
+__device__ __forceinline__ MutRecord vcf_row(const VcfArgs &A, uint64_t j, int *item) {
+    if (A.wbase) {
+        int lo = 0, hi = A.n_items;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (A.wbase[mid] <= j) lo = mid; else hi = mid;
+        }
+        const MutRecord r = A.mut[(uint64_t)lo * A.wstride + (j - A.wbase[lo])];
+        *item = r.pair >= 0 && (int64_t)r.pair < A.items[lo].n_pairs ? lo : -1;
+        return r;
+    }
+    const MutRecord r = A.mut[A.order ? A.order[j] : (uint32_t)j];
+    *item = vcf_item_of(A, r.pair);
+    return r;
+}
+
 __device__ __forceinline__ uint64_t vcf_rows(const VcfArgs &A) {
     if (!A.n_rows) return A.n_slots;
     return *A.n_rows < A.n_slots ? *A.n_rows : A.n_slots;
@@ -212,12 +236,12 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_len(VcfArgs A) {
     for (uint64_t j = (uint64_t)blockIdx.x * VCF_THREADS + threadIdx.x; j < A.n_slots; j += (uint64_t)gridDim.x * VCF_THREADS) {
         uint32_t len = 0;
         if (j < n_rows) {
-            const MutRecord r = A.mut[A.order ? A.order[j] : (uint32_t)j];
-            const int k = vcf_item_of(A, r.pair);
+            int k;
+            const MutRecord r = vcf_row(A, j, &k);
             if (k >= 0) {
                 const VcfItem &it = A.items[k];
                 const int type = r.type & 3;
-                len = (uint32_t)it.id_len + (uint32_t)A.cpu_len + 14u + (uint32_t)vcf_digits(it.first_i + (uint64_t)(r.pair - it.pair0)) +
+                len = (uint32_t)it.id_len + (uint32_t)it.cpu_len + 14u + (uint32_t)vcf_digits(it.first_i + (uint64_t)(r.pair - it.pair0)) +
                       (uint32_t)vcf_signed_len((int32_t)r.position + 1) + (type == 1 ? 2u : 1u) +
                       (type == 0 ? (uint32_t)vcf_signed_len(r.quality) : 1u);
             }
@@ -233,8 +257,9 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_format(VcfArgs A) {
         const uint32_t len = A.len[j];
         const uint64_t at = A.off[j];
         if (!len || at + len > A.text_cap) continue;  // (a row of no item; the second test cannot fail: the host sized the text)
-        const MutRecord r = A.mut[A.order ? A.order[j] : (uint32_t)j];
-        const VcfItem it = A.items[vcf_item_of(A, r.pair)];
+        int ki;
+        const MutRecord r = vcf_row(A, j, &ki);
+        const VcfItem it = A.items[ki];
         uint8_t *w = A.text + at;
         const char *id = A.ids + it.id_off;
         for (int k = 0; k < it.id_len; ++k) w[k] = (uint8_t)id[k];
@@ -245,8 +270,8 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_format(VcfArgs A) {
         vcf_put_u64(w, g, n);
         w += n;
         *w++ = '_';
-        for (int k = 0; k < A.cpu_len; ++k) w[k] = (uint8_t)A.cpu[k];
-        w += A.cpu_len;
+        for (int k = 0; k < it.cpu_len; ++k) w[k] = (uint8_t)it.cpu[k];
+        w += it.cpu_len;
         *w++ = '/';
         *w++ = (uint8_t)('1' + (r.mate & 1));
         *w++ = '\t';
@@ -269,6 +294,11 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_format(VcfArgs A) {
         }
         *w++ = '\t'; *w++ = '\t'; *w++ = '\n';
     }
+}
+
+// a worker set: where every worker's rows start in the text (the writer thread appends each range to its worker's file)
+__global__ __launch_bounds__(VCF_THREADS) void k_vcf_worker_bytes(VcfArgs A) {
+    for (int k = blockIdx.x * VCF_THREADS + threadIdx.x; k <= A.n_items; k += gridDim.x * VCF_THREADS) A.wbytes[k] = A.off[A.wbase[k]];
 }
 
 }  // namespace iss

@@ -325,6 +325,44 @@ class ReadEngine(object):
             raise EngineError(_native.E_INVALID, "mutation buffer too small: %d rows, capacity %d" % (n.value, cap))
         return out[: n.value]
 
+    def mt_workers_mutations_reserve(self, rows_per_worker):
+        """Enable (rows_per_worker > 0) / disable --store_mutations row capture of generate_mt_workers: every worker of the set
+        owns a region of that many rows.  A worker that makes more rows fails the call with E_NOMEM (the set must be seeded
+        again)."""
+        self._need_set_rows_entries()
+        self._check(self._lib.iss_mt_workers_mutations_reserve(self._ctx, int(rows_per_worker)))
+        self._set_mut_cap = int(rows_per_worker)
+
+    def mt_workers_mutations(self, worker):
+        """Rows of worker ``worker`` in the last generate_mt_workers call as a structured array (see mt_mutations)."""
+        self._need_set_rows_entries()
+        cap = getattr(self, "_set_mut_cap", 0)
+        out = np.zeros(cap, dtype=MUT_DTYPE)
+        n = C.c_int64(0)
+        self._check(self._lib.iss_mt_workers_mutations_download(self._ctx, int(worker), out.ctypes.data, cap, C.byref(n)))
+        if n.value > cap:
+            raise EngineError(_native.E_INVALID, "mutation buffer too small: %d rows, capacity %d" % (n.value, cap))
+        return out[: n.value]
+
+    def vcf_emit_workers(self, items):
+        """The --store_mutations rows of the last generate_mt_workers call as VCF text built on the device in ONE job for all
+        workers.  items: one entry per worker of the set, (fd, record id, first pair id, first output row, pairs, cpu number) --
+        pairs 0: the worker sat the call out.  Worker k's text is appended to its fd (asynchronous; ``vcf_flush`` before the
+        files are used)."""
+        self._need_set_rows_entries()
+        n = len(items)
+        fds = np.array([it[0] for it in items], dtype=np.int32)
+        ids = (C.c_char_p * n)(*[str(it[1]).encode() for it in items])
+        cols = [np.array([it[k] for it in items], dtype=np.int64) for k in (2, 3, 4)]
+        cpus = np.array([it[5] for it in items], dtype=np.int32)
+        self._check(self._lib.iss_vcf_emit_workers(self._ctx, n, fds.ctypes.data, ids, cols[0].ctypes.data, cols[1].ctypes.data,
+                                                   cols[2].ctypes.data, cpus.ctypes.data))
+
+    def _need_set_rows_entries(self):
+        if not hasattr(self._lib, "iss_vcf_emit_workers"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_mt_workers_mutations_reserve / iss_vcf_emit_workers: "
+                                             "rebuild it" % _native.LIB_PATH)
+
     def mt_peek(self, n=8):
         """The next n 32-bit words of (CPython random, numpy) -- not consumed."""
         a = np.zeros(n, dtype=np.uint32)

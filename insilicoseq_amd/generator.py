@@ -679,11 +679,13 @@ def _set_pieces(genomes, work, cpu, per):
             done += n
 
 
-def _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, read_length, sequence_type, gc_bias):
+def _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, read_length, sequence_type, gc_bias, vcf=None):
     """Rounds of one piece per worker (``its``: _set_pieces of every worker) until every work list is done: one
     generate_mt_workers call, then the pieces' text -- one scattered job into the final files at the workers' places ``at``
     (moved on by what is written: fastq_text_bytes at the model's ``read_length``), or with ``at`` None one job per worker into
-    its temp files."""
+    its temp files.  ``vcf`` (--store_mutations): (route, the workers' .vcf handles) -- after every round the rows of all
+    workers become ONE text job on the device (ReadEngine.vcf_emit_workers), worker k's bytes appended to handle k; route
+    "host": the rows fetched worker by worker and written by write_mutations."""
     began = False
     while True:
         genomes.drop_if_over()  # between rounds nothing names an uploaded record (a round uploads what its pieces need again)
@@ -717,37 +719,55 @@ def _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, read_length, se
                                n_threads=1)
         if scattered:  # ONE text job per round: the next round's kernels run beside its copy and its writes
             eng.fastq_emit_scatter(handles[0][0].fileno(), handles[0][1].fileno(), scattered, n_threads=1)
+        if vcf is not None:
+            route, vcf_handles = vcf
+            live = [c is not None and not c[4] for c in cur]  # (a short record makes no row: its worker sits the text out)
+            if route == "device":
+                eng.vcf_emit_workers([(vcf_handles[k].fileno(), c[0].id, c[3], int(row[k]), c[2], cpu_numbers[k]) if live[k]
+                                      else (-1, "", 0, 0, 0, cpu_numbers[k]) for k, c in enumerate(cur)])
+            else:
+                for k, c in enumerate(cur):
+                    if live[k]:
+                        write_mutations(eng.mt_workers_mutations(k), vcf_handles[k], c[0].id, c[3], cpu_numbers[k])
 
 
 def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, sequence_type, gc_bias, device=None,
-                        compress=False, batch_pairs=None, final_prefix=None):
+                        compress=False, batch_pairs=None, final_prefix=None, vcf_files=False):
     """W reference workers (``rng="mt"``) on ONE GPU, side by side: the files of ``worker_iterator(works[k], error_model,
     cpu_numbers[k], worker_prefixes[k], seed, ..., rng="mt")`` for every k -- byte for byte the reference's
     ``iss generate --cpus W`` temp files (iss/app.py:99-106, iss/generator.py:223-251) -- but the workers' chains run in the
     same kernel launches, one workgroup per worker (ReadEngine.generate_mt_workers).  A worker is a sequential chain over its
     two MT19937 streams (seed + cpu_number, generator.py:234-236); W of them are what the reference itself runs in parallel.
-    ``--store_mutations`` rows are per engine: such a run takes one worker after the other through worker_iterator.
+    ``--store_mutations``: every worker owns a region of the engine's row pool (ReadEngine.mt_workers_mutations_reserve, sized
+    by worker_iterator's rule at the set's pairs per round); after each round the rows of all workers become one VCF text job
+    (vcf_emit_workers; ISS_HOST_VCF=1: rows to the host, write_mutations) appended to the workers' ``{prefix}.vcf`` files -- a
+    VCF's size is not arithmetic, so those stay temp files in either mode and the caller concatenates them behind the header.
+    ``vcf_files``: the command asked for --store_mutations, so the caller will concatenate the workers' ``.vcf`` files -- they
+    are made with ``final_prefix`` too when the model records nothing (PerfectErrorModel: empty files, the header alone).
 
     ``final_prefix`` (text mode): the workers' text goes straight to ``{final_prefix}_R1.fastq`` / ``_R2.fastq`` -- what the
     parent's concatenation of the temp files in worker order would hold (iss/app.py:123-127, iss/util.py:213-234): a worker's
     text size is arithmetic (fastq_text_bytes), so worker k starts where workers 0 .. k-1 end, a round is ONE text job whose
     pieces are written at their places (ReadEngine.fastq_emit_scatter), and no temp file is made.  Returns True when the final
     files were written, False when the temp files were (the caller concatenates them).  Raises WorkerSetNotSetUp when the set
-    could not be set up (nothing ran)."""
+    could not be set up (nothing ran: seeding, no room for the stream buffers or for the row pool of --store_mutations)."""
     W = len(works)
     if not (W == len(cpu_numbers) == len(worker_prefixes)) or W < 1:
         raise ValueError("worker_set_iterator: one work list, cpu number and file prefix per worker")
     if sequence_type not in _native.SEQ_TYPES:
         raise RuntimeError("sequence type '%s' is not supported" % sequence_type)  # generator.py:139
-    if bool(getattr(error_model, "store_mutations", False)) or seed is None:
+    store_mutations = bool(getattr(error_model, "store_mutations", False))
+    if seed is None:
         # (unseeded workers draw their seeds from the OS one by one, like the reference's processes)
         for work, cpu, prefix in zip(works, cpu_numbers, worker_prefixes):
             worker_iterator(work, error_model, cpu, prefix, seed, sequence_type, gc_bias, device=device, rng="mt", compress=compress)
         return False
     final = final_prefix is not None and not compress
     handles = _open_set_files(worker_prefixes, final_prefix if final else None)
-    eng, finished = None, False
+    eng, finished, vcf_handles = None, False, None
     try:
+        if store_mutations or vcf_files:  # (the temp-file layout opens a worker's .vcf beside its FASTQ files)
+            vcf_handles = [open("%s.vcf" % prefix, "w") for prefix in worker_prefixes] if final else [h[2] for h in handles]
         eng = ReadEngine(0 if device is None else device)
         dense = _dense_of(error_model)
         eng.load_model(dense)
@@ -767,6 +787,16 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
         # rows per worker and round (2^20 pairs per round for all workers together; 2^22 and 2^24 measured the same end to end:
         # 16 M pairs at W = 64 in 2.6-2.8 s incl. 0.5 s of engine start -- generation and text take turns)
         per = int(batch_pairs or max(1024, min(Worker.BATCH_PAIRS, (1 << 20) // W)))
+        vcf = None
+        if store_mutations:
+            # a worker's rows of one round, by worker_iterator's rule (twice the model's expectation + slack per pair)
+            try:
+                eng.mt_workers_mutations_reserve(int(per * (2.0 * dense.expected_mutation_rows_per_pair() + 4.0)))
+            except _native.EngineError as e:
+                if e.code != _native.E_NOMEM:
+                    raise
+                raise WorkerSetNotSetUp(e.code, e.message) from e  # (no room for the row pool: nothing ran, like the stream buffers)
+            vcf = ("device" if os.environ.get("ISS_HOST_VCF", "") != "1" else "host", vcf_handles)
         genomes = GenomeStore(
             eng, Worker,
             budget_divisor=2,      # Worker's budget less what the set itself holds on the device (stream buffers, rows of a round -- up to a third of the memory)
@@ -779,8 +809,10 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
         for fh3 in handles:
             for fh in fh3[:2]:
                 fh.flush()
-        _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, dense.read_length, sequence_type, gc_bias)
+        _run_set_rounds(eng, genomes, its, cpu_numbers, handles, at, dense.read_length, sequence_type, gc_bias, vcf)
         eng.fastq_flush()
+        if vcf is not None and vcf[0] == "device":
+            eng.vcf_flush()  # (before the handles close: the text is appended to their descriptors)
         if final and at != ends:  # every worker's text ends where the next one's starts
             raise RuntimeError("worker_set_iterator: a worker's text is not the size computed for it: %r / %r" % (at, ends))
         finished = True
@@ -791,10 +823,14 @@ def worker_set_iterator(works, error_model, cpu_numbers, worker_prefixes, seed, 
         for fh3 in handles:
             for fh in fh3:
                 fh.close()
-        if final and not finished:  # the final files are full size from the start: a failed run must not leave them behind
-            for suffix in ("_R1.fastq", "_R2.fastq"):
+        for fh in (vcf_handles or []) if final else []:
+            fh.close()
+        if not finished:
+            # the final files are full size from the start: a failed run must not leave them behind, nor the workers' .vcf files
+            gone = ["%s%s" % (final_prefix, suffix) for suffix in ("_R1.fastq", "_R2.fastq")] if final else []
+            for path in gone + (["%s.vcf" % prefix for prefix in worker_prefixes] if store_mutations or vcf_files else []):
                 try:
-                    os.remove("%s%s" % (final_prefix, suffix))
+                    os.remove(path)
                 except FileNotFoundError:
                     pass
 
