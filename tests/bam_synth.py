@@ -7,6 +7,9 @@ block, the 28-byte EOF block) holding paired records with CIGAR, MD, flags, temp
 move dispatch_indels' position below zero), N bases and N reference letters, unmapped / secondary / supplementary
 records, records flagged neither read1 nor read2, unpaired records, reversed reads and mean qualities in every bin
 (and at 40 and above, which lands in no bin).  ``records(...)`` returns the same records as dicts without writing them.
+
+``edge_table()`` is the table of named hand-built records of the edge tests (one branch of the tally kernel each), ``edge_bad_records()``
+the records every error code is reported for, ``edge_fillers()`` what golden case d adds so that the reference finishes on them.
 """
 import hashlib
 import random
@@ -15,6 +18,7 @@ import zlib
 
 SEQ_CODES = "=ACMGRSVTWYHKDBN"
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+_SCALAR = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}
 
 
 def bgzf_block(payload, level=6):
@@ -47,18 +51,21 @@ def encode_record(r):
     cig = b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in r["cigar"])
     aux = b""
     for tag, typ, val in r.get("tags", ()):
-        if typ == "Z":
-            aux += tag.encode() + b"Z" + val.encode() + b"\0"
-        elif typ == "i":
-            aux += tag.encode() + b"i" + struct.pack("<i", val)
-        elif typ == "C":
-            aux += tag.encode() + b"C" + struct.pack("<B", val)
-        elif typ == "B":
-            aux += tag.encode() + b"BC" + struct.pack("<i", len(val)) + bytes(val)
+        if typ in ("Z", "H"):
+            aux += tag.encode() + typ.encode() + val.encode() + b"\0"
+        elif typ == "A":
+            aux += tag.encode() + b"A" + val.encode()
+        elif typ in _SCALAR:
+            aux += tag.encode() + typ.encode() + struct.pack("<" + _SCALAR[typ], val)
+        elif typ == "B":  # a list: a C array; (subtype, list): an array of that subtype
+            sub, vals = val if isinstance(val, tuple) else ("C", val)
+            aux += tag.encode() + b"B" + sub.encode() + struct.pack("<i%d%s" % (len(vals), _SCALAR[sub]), len(vals), *vals)
+    aux += r.get("raw_aux", b"")  # bytes behind the tags as they are (malformed optional fields)
     ref_id = -1 if r.get("unplaced") else 0
     body = struct.pack("<iiBBHHHiiii", ref_id, r.get("pos", 0), len(name), 60, 4680, len(r["cigar"]), r["flag"], l_seq,
                        ref_id, r.get("mpos", 0), r.get("tlen", 0))
     body += name + cig + packed + qb + aux
+    body = body[:len(body) - r.get("truncate", 0)]  # a block_size smaller than the fields claim; the record shrinks with it
     return struct.pack("<i", len(body)) + body
 
 
@@ -222,11 +229,194 @@ def records(seed, n_pairs=2000, read_length=151, var_lengths=None, p_indel=0.01,
     return out
 
 
+R1, R2R = 1 | 2 | 32 | 64, 1 | 2 | 16 | 128  # read1 forward, read2 reverse
+
+
+def alt_cigar(n_ops, other, l_seq, lead=()):
+    """`lead`, then 1M 1<other> 1M ... over n_ops - len(lead) operations; the last M takes what is left of the l_seq query bases."""
+    ops = list(lead) + [(0, 1) if k % 2 == 0 else (other, 1) for k in range(n_ops - len(lead))]
+    assert ops[-1][0] == 0
+    used = sum(ln for op, ln in ops if op in (0, 1, 4))
+    ops[-1] = (0, 1 + l_seq - used)
+    return ops
+
+
+def edge_read(name, cigar, seq=None, qual=None, flag=R1, tlen=0, mism=None, md=None, dels=None, front=(), back=(), trigger=False,
+              **more):
+    """One hand-built record.  mism: {aligned column: reference letter, or None for a letter that differs from the read's};
+    trigger: the last aligned column gets the reference letter N, which flags the read for dispatch_indels (iss/modeller.py:186-188);
+    dels: the deleted letters of each D; md: the MD string as is; front / back: tags in front of and behind MD:Z."""
+    l_seq = sum(ln for op, ln in cigar if op in (0, 1, 4))
+    rnd = random.Random(zlib.crc32(name.encode()))
+    if seq is None:
+        seq = "".join(rnd.choice("ACGT") for _ in range(l_seq))
+    if qual is None:
+        qual = [(7 * i + 3) % 40 for i in range(len(seq))]
+    qpos, q = [], 0  # query position of every aligned column
+    for op, ln in cigar:
+        if op == 0:
+            qpos.extend(range(q, q + ln))
+        if op in (0, 1, 4):
+            q += ln
+    ref_cols = [None] * len(qpos)
+    for col, letter in (mism or {}).items():
+        col %= len(qpos)
+        ref_cols[col] = letter or "ACGT"[("ACGT".find(seq[qpos[col]]) + 1) % 4]
+    if trigger and ref_cols[-1] is None:
+        ref_cols[-1] = "N"
+    dels = list(dels or [])
+    ops = [(op, ln, (dels.pop(0) if dels else "A" * ln) if op == 2 else "") for op, ln in cigar]
+    tags = list(front) + [("MD", "Z", _md(ref_cols, ops) if md is None else md)] + list(back)
+    return dict(name=name, flag=flag, pos=100, tlen=tlen, cigar=list(cigar), seq=seq, qual=list(qual), tags=tags, **more)
+
+
+def _qual_sum(l, total):
+    """l qualities in 0..93 that add up to total, not all alike."""
+    q = [total // l] * l
+    for i in range(total - sum(q)):
+        q[i] += 1
+    if l > 2 and 0 < q[0] < 93 and 0 < q[-1] < 93:
+        q[0] += 1
+        q[-1] -= 1
+    return q
+
+
+def edge_table():
+    """The named valid records of the `model` edge tests, in a fixed order (tests/test_gpu_model_edges.py tallies each alone and all
+    together; golden case d holds them too).  Every record is one the reference's `iss model` accepts."""
+    t = []
+    add = lambda *a, **kw: t.append(edge_read(*a, **kw))
+    # CIGAR with many operations: the lanes stride over more than 64 of them
+    add("ops301_MI", alt_cigar(301, 1, 301), trigger=True, mism={0: None, 77: None})
+    add("ops301_MD", alt_cigar(301, 2, 301), trigger=True, flag=R2R)
+    add("ops65_MI", alt_cigar(65, 1, 90), trigger=True)
+    add("ops65_MD", alt_cigar(65, 2, 90), trigger=True, flag=R2R)
+    add("ops64_SMI", alt_cigar(64, 1, 70, lead=[(4, 1)]), trigger=True)
+    add("ops64_HMD", alt_cigar(64, 2, 70, lead=[(5, 9)]), trigger=True)
+    add("ops129_MI_plain", alt_cigar(129, 1, 200), mism={5: None})  # not flagged: the indels are not dispatched
+    # read length, forward and reverse
+    for l in (1, 2, 63, 64, 65, 300, 301):
+        for tag, flag in (("f", R1), ("r", R1 | 16), ("f2", R2R & ~16), ("r2", R2R)):
+            add("len%d_%s" % (l, tag), [(0, l)], flag=flag, mism={0: None, -1: None} if l > 1 and tag in ("f", "r2") else None)
+    # clips
+    add("clip_HSMSH", [(5, 5), (4, 3), (0, 10), (2, 2), (0, 5), (1, 1), (0, 4), (4, 2), (5, 4)], trigger=True, dels=["GT"])
+    add("clip_all_one", [(4, 6)])
+    add("clip_all_two", [(4, 3), (4, 4)], flag=R2R)
+    add("clip_all_hard", [(5, 2), (4, 5), (5, 2)])
+    add("clip_then_I", [(4, 3), (1, 2), (0, 10)], trigger=True)
+    add("clip_H_then_I", [(5, 7), (1, 2), (0, 10)], trigger=True, flag=R2R)
+    add("D_then_clip_plain", [(0, 10), (2, 2), (4, 3)])
+    add("D_then_clip", [(0, 6), (2, 3), (0, 4), (2, 1), (4, 3)], trigger=True)
+    add("D_then_clip_SH", [(4, 2), (0, 6), (2, 3), (0, 4), (2, 1), (4, 3), (5, 8)], trigger=True, flag=R2R)
+    # dispatch_indels below zero: rows pos + 301, letters from pos + len (iss/modeller.py:281-313)
+    add("neg_I_D", [(0, 2), (2, 10), (1, 1), (0, 3), (2, 2), (0, 5)], trigger=True)
+    add("neg_I_D_r2", [(0, 2), (2, 10), (1, 1), (0, 3), (2, 2), (0, 5)], trigger=True, flag=R2R)
+    add("neg_clipped", [(4, 2), (0, 2), (2, 10), (1, 1), (0, 3), (2, 2), (0, 5), (4, 3)], trigger=True)
+    add("neg_far", [(0, 1), (2, 40), (1, 2), (0, 30), (2, 1), (0, 20)], trigger=True)
+    add("neg_301", [(0, 3), (2, 250), (1, 1), (0, 200), (2, 1), (0, 97)], trigger=True)
+    add("indel_at_N", [(0, 4), (1, 1), (0, 4), (2, 1), (0, 4)], seq="ACGTNACGTNACG", trigger=True, dels=["N"])
+    add("indel_query_N", [(0, 4), (1, 2), (0, 6)], seq="ACGTACNTACGT", mism={9: None})  # an aligned N in the read flags it
+    # MD tag
+    add("md_lower", [(0, 12)], seq="ACGTACGTACGT", md="2t3g5")
+    add("md_lower_del", [(0, 6), (2, 2), (0, 6)], seq="ACGTACGTACGT", md="1g4^ac3a2", trigger=False)
+    add("md_N", [(0, 12)], seq="ACGTACGTACGT", md="3N4n3")
+    add("md_same_letter", [(0, 12)], seq="ACGTACGTACGT", md="1C10")  # "cC" is no key of dispatch_dict: flags the read
+    add("md_runs", [(0, 12)], seq="ACGTACGTACGT", md="0C0A0T0A8")
+    add("md_runs_I", [(0, 3), (1, 2), (0, 7)], seq="ACGTACGTACGT", md="0C0A0N7")
+    add("md_leading_zeros", [(0, 12)], seq="ACGTACGTACGT", md="003A0008")
+    add("md_zero_only", [(4, 5)], md="000")
+    add("md_first_last", [(0, 70)], mism={0: None, 69: None})
+    add("md_after_I", [(0, 5), (1, 3), (0, 5)], mism={5: None})
+    add("md_after_S", [(4, 4), (0, 9)], mism={0: None})
+    add("md_after_SI", [(5, 1), (4, 4), (1, 1), (0, 66), (1, 2), (0, 9)], mism={0: None, 66: None, 74: None}, flag=R2R)
+    # optional fields in front of MD:Z
+    scalars = [("XA", "A", "q"), ("Xc", "c", -7), ("XC", "C", 200), ("Xs", "s", -300), ("XS", "S", 60000), ("Xi", "i", -70000),
+               ("XI", "I", 4000000000), ("Xf", "f", 1.5)]
+    add("tags_scalars", [(0, 20)], front=scalars, mism={3: None})
+    add("tags_strings", [(0, 20)], front=[("XZ", "Z", "MD:Z:7"), ("XH", "H", "1AE301"), ("XE", "Z", "")], mism={3: None})
+    arrays = [("Ba", "B", ("c", [])), ("Bb", "B", ("S", [])), ("Bc", "B", ("f", [])), ("Bd", "B", ("c", [-1, 2, -3])),
+              ("Be", "B", ("S", [1, 65535, 77, 0, 5])), ("Bf", "B", ("f", [0.5, -2.0])), ("Bg", "B", ("C", [77, 68, 90])),
+              ("Bh", "B", ("s", [-5])), ("Bi", "B", ("i", [1, -2])), ("Bj", "B", ("I", [4000000000]))]
+    add("tags_arrays", [(0, 20)], front=arrays, mism={3: None})
+    add("tags_all_md_last", [(0, 20)], front=scalars + arrays + [("XZ", "Z", "x")], mism={19: None}, flag=R2R)
+    add("tags_md_first", [(0, 20)], back=scalars + arrays, mism={0: None})
+    # mean-quality bins: int(np.mean(q)) at 9 | 10 and 39 | 40 (iss/modeller.py:56-61), l no power of two
+    for l in (7, 301):
+        for what, total in (("9", 10 * l - 1), ("10", 10 * l), ("39", 40 * l - 1), ("40", 40 * l), ("19", 20 * l - 1), ("30", 30 * l)):
+            add("mean%s_l%d" % (what, l), [(0, l)], qual=_qual_sum(l, total), flag=R1 if l == 7 else R2R)
+    add("qual_all_93", [(0, 11)], qual=[93] * 11)
+    add("qual_all_0", [(0, 11)], qual=[0] * 11)
+    add("qual_all_0_r2", [(0, 301)], qual=[0] * 301, flag=R2R)
+    add("qual_93_and_0", [(0, 11)], qual=[93] + [0] * 10, flag=R1 | 16)
+    # template length: 0 < |tlen| < 2000 of the paired reads (iss/bam.py:127-130, iss/modeller.py:24-29)
+    for tl in (0, 1, -1, 1999, -1999, 2000, -2000, -2 ** 31, 2 ** 31 - 1):
+        add("tlen%d_paired" % tl, [(0, 9)], tlen=tl)
+        add("tlen%d_unpaired" % tl, [(0, 9)], tlen=tl, flag=64)
+    # flags
+    add("flag_neither", [(0, 9), (1, 1), (0, 9)], flag=1 | 2, tlen=333, trigger=True)
+    add("flag_neither_unpaired", [(0, 19)], flag=0, tlen=333)
+    add("flag_both", [(0, 9), (1, 1), (0, 9)], flag=1 | 2 | 64 | 128, tlen=-444, trigger=True)
+    add("flag_both_reverse", [(0, 19)], flag=1 | 16 | 64 | 128, mism={4: None})
+    add("flag_secondary", [(0, 19)], flag=R1 | 256, mism={4: None})
+    add("flag_supplementary", [(0, 19)], flag=R2R | 2048, mism={4: None})
+    t.append(dict(edge_read("flag_unmapped_bare", [], seq="ACGTA", flag=R1 | 4, tlen=555), qual=None, tags=[]))  # never looked at
+    add("flag_live_between", [(0, 19)], flag=R2R, tlen=-556, mism={18: None})
+    add("flag_unmapped_full", [(0, 19)], flag=R2R | 4, tlen=557, mism={1: None})
+    names = [r["name"] for r in t]
+    assert len(set(names)) == len(names)
+    for r in t:
+        if r["flag"] & 4:
+            continue
+        assert sum(ln for op, ln in r["cigar"] if op in (0, 1, 4)) == len(r["seq"]) <= 301, r["name"]
+        assert r["name"].endswith("_plain") or _indel_positions_ok(r["cigar"], len(r["seq"])), r["name"]
+    return t
+
+
+def edge_fillers():
+    """Pairs of short reads that put two reads or more into every (mate, bin) slice the edge table uses and give the template
+    lengths a spread: what the reference's `iss model` needs to finish on golden case d."""
+    out = []
+    for k, level in enumerate((4, 4, 14, 14, 25, 25, 34, 34)):
+        for mate, flag in ((0, R1), (1, R2R)):
+            qual = [level + (i + k) % 5 for i in range(12)]
+            out.append(edge_read("fill%d_%d" % (k, mate), [(0, 12)], qual=qual, flag=flag, tlen=(300 + 7 * k) * (1 - 2 * mate),
+                                 mism={k: None}))
+    return out
+
+
+def edge_bad_records():
+    """(error code of insilicoseq_amd/csrc/iss_bam.hip.h, record) for records the reference fails on, two ways or more per code where
+    the kernel has them.  Every record lies inside its own bytes: a malformed one has a block_size smaller than its fields claim."""
+    big = struct.pack("<i", 100)
+    return [
+        (1, edge_read("bad_block_short", [(0, 20)], truncate=30)),                                  # ends inside the qualities
+        (1, dict(edge_read("bad_Z_open", [(0, 20)]), tags=[("XX", "i", 5)], raw_aux=b"MDZ20")),     # no NUL before block_size ends
+        (1, dict(edge_read("bad_B_long", [(0, 20)]), tags=[], raw_aux=b"XBBc" + big + b"\1\2\3")),  # 100 elements claimed, 3 there
+        (2, edge_read("bad_too_long", [(0, 302)])),
+        (3, dict(edge_read("bad_no_qual", [(0, 20)]), qual=None)),
+        (4, edge_read("bad_cigar_op", [(0, 10), (3, 5), (0, 10)])),                                 # N (skipped region)
+        (4, edge_read("bad_cigar_op_eq", [(0, 10), (7, 10)], seq="ACGTACGTACGTACGTACGT", qual=[30] * 20, md="20")),  # =
+        (5, dict(edge_read("bad_no_md", [(0, 20)]), tags=[("NM", "i", 0), ("XZ", "Z", "MD")])),
+        (6, edge_read("bad_md_many", [(0, 20)], md="25")),
+        (6, edge_read("bad_md_few", [(0, 20)], md="7A7")),
+        (6, edge_read("bad_md_letters_many", [(0, 3)], md="0A0C0G0T0")),
+        (7, edge_read("bad_indel_D_at_clip", [(0, 10), (2, 2), (4, 3)], trigger=True)),             # query_alignment_sequence[10] of 10
+        (7, edge_read("bad_indel_I_below", [(0, 1), (2, 30), (1, 1), (0, 8)], trigger=True)),       # query_sequence[-29] of 10
+        (8, edge_read("bad_qual_94", [(0, 20)], qual=[30] * 19 + [94])),
+        (9, edge_read("bad_cigar_len", [(0, 19)], seq="ACGTACGTACGTACGTACGT", qual=[30] * 20, md="19")),
+        (9, edge_read("bad_cigar_len_long", [(0, 21)], seq="ACGTACGTACGTACGTACGT", qual=[30] * 20, md="21")),
+    ]
+
+
 def case_records(parts):
     """The records of a golden case (tests/golden/bam/cases.json), in file order: parts of records(**kw) with two edits --
-    neither: read1 / read2 flags cleared; read1_level: read1's qualities at that level past position 4, read2 unmapped."""
+    neither: read1 / read2 flags cleared; read1_level: read1's qualities at that level past position 4, read2 unmapped.
+    A part {"edge_table": true} is edge_table() followed by edge_fillers()."""
     out = []
     for part in parts:
+        if part.get("edge_table"):
+            out.extend(edge_table() + edge_fillers())
+            continue
         kw = dict(part)
         neither = kw.pop("neither", False)
         level = kw.pop("read1_level", None)

@@ -25,6 +25,13 @@ def read_records(path):
     return shim()._parse(path)[1]
 
 
+def from_dicts(recs):
+    """pysam-shim records of bam_synth record dicts, without a file."""
+    import bam_synth
+
+    return [shim().AlignedSegment(bam_synth.encode_record(r)[4:]) for r in recs]
+
+
 def tallies(reads):
     """Tallies over the given records (every mapped one is taken)."""
     M = 301

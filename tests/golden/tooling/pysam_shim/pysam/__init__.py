@@ -115,9 +115,18 @@ class AlignedSegment(object):
     is_read2 = property(lambda self: bool(self.flag & 128))
 
     @property
-    def query_alignment_sequence(self):  # without soft-clipped ends
-        lo = self.cigartuples[0][1] if self.cigartuples and self.cigartuples[0][0] == 4 else 0
-        hi = self.cigartuples[-1][1] if len(self.cigartuples) > 1 and self.cigartuples[-1][0] == 4 else 0
+    def query_alignment_sequence(self):  # without soft-clipped ends; hard clips outside them are passed over like pysam does
+        lo = hi = 0
+        for op, ln in self.cigartuples:  # pysam's getQueryStart: every leading S, behind any H
+            if op == 4:
+                lo += ln
+            elif op != 5:
+                break
+        for op, ln in self.cigartuples[:0:-1]:  # getQueryEnd: walks back to the second operation
+            if op == 4:
+                hi += ln
+            elif op != 5:
+                break
         return self.query_sequence[lo:len(self.query_sequence) - hi]
 
     def get_aligned_pairs(self, matches_only=False, with_seq=False):

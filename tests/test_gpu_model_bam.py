@@ -85,7 +85,7 @@ def _cdf_rows(x):
     return [np.asarray(r, dtype=np.float64) for r in x]
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c"])
+@pytest.mark.parametrize("name", ["a", "b", "c", "d"])
 def test_golden_cases_match_reference_npz(dev, tmp_path, name):
     from insilicoseq_amd.modeller import to_model
 

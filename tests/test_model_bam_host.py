@@ -45,7 +45,7 @@ def reader_records(path, chunk_bytes):
     return out
 
 
-@pytest.mark.parametrize("name", ["ecoli", "a", "b", "c"])
+@pytest.mark.parametrize("name", ["ecoli", "a", "b", "c", "d"])
 def test_reader_agrees_with_pysam_shim(native, tmp_path, name):
     path = ECOLI_BAM if name == "ecoli" else case_bam(tmp_path, name)
     pysam = bam_twin.shim()
@@ -95,7 +95,7 @@ def _finish_from_golden(name, tmp_path):
     return f, z
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c"])
+@pytest.mark.parametrize("name", ["a", "b", "c", "d"])
 def test_finish_matches_reference_on_count_inputs(tmp_path, name):
     f, z = _finish_from_golden(name, tmp_path)
     assert f["read_length"] == int(z["read_length"])
