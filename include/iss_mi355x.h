@@ -245,6 +245,30 @@ int iss_output_download(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint8
  * [first_pair, first_pair+n_pairs) as int64[n][4] -- iss/generator.py:135, 165-176. */
 int iss_output_download_coords(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int64_t *coords);
 
+/*
+ * Rows [first_pair, first_pair + n_pairs) as dense arrays in DEVICE memory the caller owns (a consumer that stays on the GPU: a
+ * training or evaluation loop; additive in ABI 8).  Any of the four pointers may be NULL:
+ *   d_bases  uint8 [n_pairs][2][read_length]  mate 1, then mate 2, bases as sequenced, no pitch padding -- a pair's 2 * read_length
+ *            bytes start wherever they fall, no alignment is asked of the pointer.  ISS_EXPORT_ASCII: the bytes
+ *            iss_output_download returns; ISS_EXPORT_CODES: A, C, G, T -> 0, 1, 2, 3 (alphabetical -- not the engine's A, T, C, G),
+ *            upper or lower case, every other letter 4
+ *   d_qual   uint8 [n_pairs][2][read_length]  the phred scores iss_output_download returns
+ *   d_coords int64 [n_pairs][4]               what iss_output_download_coords returns (record coordinates, not arena coordinates)
+ *   d_item   int32 [n_pairs]                  the pair's item in the last iss_generate_batch call; 0 for every other row (those of
+ *                                             iss_generate, iss_generate_mt, older calls)
+ * Asynchronous on the context's current stream -- the caller's after iss_ctx_set_stream / iss_ctx_set_stream_ordered -- behind the
+ * generation it reads: no wait on the host, no device allocation.  The arrays are ready when that stream reaches the end of the
+ * call's kernel; the rows may be generated anew as soon as the call returns (the next call is ordered behind it on the stream).
+ * Rows outside the reserved range or an unknown encoding: ISS_E_INVALID, nothing launched.  n_pairs == 0: 0, nothing launched.
+ */
+#define ISS_EXPORT_ASCII 0
+#define ISS_EXPORT_CODES 1
+int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t encoding, void *d_bases, void *d_qual,
+                      int64_t *d_coords, int32_t *d_item);
+/* iss_ctx_set_stream without the wait on the host (additive in ABI 8): everything queued on the context's streams so far is
+ * ordered in front of what the context queues on `hip_stream` from now on, by events.  NULL: back to the context's own stream. */
+int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream);
+
 /* HIP-event timing of the kernels launched by iss_generate (on the launch stream).
  * enable: 0 off, 1 every kernel, 2 k_main only (an event is a bubble in the stream: the five-kernel timing costs
  * about 6 % of a step).  iss_timing_read synchronises, returns accumulated milliseconds per kernel

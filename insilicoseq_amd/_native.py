@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ISS_MI355X_LIB") or os.path.join(_HERE, LIB_NAME)  # 
 
 E_INVALID, E_HIP, E_NOMEM, E_SHORT_RECORD, E_IO = -1, -2, -3, -4, -5
 SEQ_TYPES = {"metagenomics": 0, "amplicon": 1}
+EXPORT_ENCODINGS = {"ascii": 0, "codes": 1}  # ISS_EXPORT_ASCII / ISS_EXPORT_CODES
 
 # every symbol include/iss_mi355x.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -27,6 +28,7 @@ EXPORTS = (
     "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download", "iss_vcf_emit_workers",
     "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
     "iss_bam_tally_download", "iss_bam_kde",
+    "iss_output_export", "iss_ctx_set_stream_ordered",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -135,6 +137,10 @@ def lib():
         L.iss_mt_workers_mutations_reserve.argtypes = [vp, i64]
         L.iss_mt_workers_mutations_download.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
         L.iss_vcf_emit_workers.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    # (additive to ABI 8: the rows as dense device arrays; a build from before them still loads and ReadEngine.export raises)
+    if hasattr(L, "iss_output_export"):
+        L.iss_output_export.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
+        L.iss_ctx_set_stream_ordered.argtypes = [vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -158,7 +164,7 @@ def lib():
     L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
     for name in EXPORTS:
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
-                    "iss_vcf_emit_workers") and not hasattr(L, name):
+                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

@@ -114,6 +114,7 @@ void iss_ctx_destroy(iss_ctx *ctx) {
     for (auto &e : ctx->ev_fork) if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->ev_join) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_inputs) (void)hipEventDestroy(ctx->ev_inputs);
+    for (auto &e : ctx->ev_handover) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 

@@ -399,6 +399,8 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     const iss::DevModel &M = ctx->M;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ctx->last_first.clear();  // (this call's descriptors carry record coordinates: no batch's arena offsets apply to the rows any more)
+    ctx->last_off.clear();
     auto &c = ctx->mt.chain;
     const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
     { int rc_ = mt_reserve(ctx, c, 3 * ((size_t)(c.ch + 1) * py_need + 1248), 3 * ((size_t)(c.ch + 1) * np_need + 1248)); if (rc_) return rc_; }
@@ -581,6 +583,7 @@ int iss_generate_mt_workers(iss_ctx *ctx, int32_t n_workers, const int32_t *geno
     if (ctx && ctx->mts.poisoned)
         return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: an earlier call failed half way (the workers' streams and rows are undefined): call iss_mt_workers_seed again");
     if (ctx) ctx->mts.started = false;
+    if (ctx) { ctx->last_first.clear(); ctx->last_off.clear(); }  // (record coordinates, as in iss_generate_mt)
     const int rc = mt_workers_generate(ctx, n_workers, genome_ids, n_pairs, out_first_pair, sequence_type, gc_bias, n_done, status);
     if (rc < 0 && ctx && ctx->mts.started) ctx->mts.poisoned = true;
     return rc;

@@ -222,6 +222,7 @@ struct iss_ctx {
     hipEvent_t ev_slot_done[FIX_SLOTS_C] = {};          // the last kernel of the chunk that used a counter slot: the setup stream waits
     bool ev_slot_valid[FIX_SLOTS_C] = {};               //   for it before the slot's next user clears the counters
     hipEvent_t ev_inputs = nullptr;                     // tables / arena copies queued on the main stream for this call's k_setup
+    hipEvent_t ev_handover[5] = {};                     // iss_ctx_set_stream_ordered: the tails of the five streams, for the new main stream to wait for
     uint64_t call_seq = 0;
     bool inputs_pending = false;  // copies for this call's k_setup were queued on the main stream (ev_inputs)
     bool timing_all = false;      // HIP events around every kernel: one stream

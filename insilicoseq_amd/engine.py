@@ -31,6 +31,7 @@ class ReadEngine(object):
         self.pitch = None
         self._capacity = 0
         self._genome_lengths = []
+        self.stream_ptr = 0  # the hipStream_t set_stream() was given last (0: the context's own stream)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -461,8 +462,32 @@ class ReadEngine(object):
         self._check(self._lib.iss_output_device_ptrs(self._ctx, *[C.byref(x) for x in p]))
         return [x.value for x in p]
 
-    def set_stream(self, hip_stream_ptr):
-        self._check(self._lib.iss_ctx_set_stream(self._ctx, C.c_void_p(hip_stream_ptr)))
+    def set_stream(self, hip_stream_ptr, wait=True):
+        """Launch on the caller's hipStream_t from now on (None / 0: the context's own stream again).  ``wait=False``: no wait on
+        the host -- what the context has queued so far is ordered in front of the new stream's work by events."""
+        if wait:
+            self._check(self._lib.iss_ctx_set_stream(self._ctx, C.c_void_p(hip_stream_ptr or None)))
+        else:
+            self._need_export_entries()
+            self._check(self._lib.iss_ctx_set_stream_ordered(self._ctx, C.c_void_p(hip_stream_ptr or None)))
+        self.stream_ptr = int(hip_stream_ptr or 0)
+
+    def export(self, first_pair, n_pairs, bases_ptr=None, qual_ptr=None, coords_ptr=None, item_ptr=None, encoding="ascii"):
+        """Rows [first_pair, +n_pairs) as dense arrays in device memory of the caller (raw device addresses, any array library's):
+        bases / qual uint8 [n_pairs, 2, read_length], coords int64 [n_pairs, 4] (record coordinates), item int32 [n_pairs] (the
+        pair's item of the last generate_batch(); 0 elsewhere); None: not wanted.  ``encoding``: "ascii" (the bytes of
+        download()) or "codes" (A, C, G, T -> 0..3, anything else 4).  Asynchronous on the engine's current stream, behind the
+        generation; nothing waits on the host (include/iss_mi355x.h: iss_output_export)."""
+        if encoding not in _native.EXPORT_ENCODINGS:
+            raise EngineError(_native.E_INVALID, "export: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
+        self._need_export_entries()
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (bases_ptr, qual_ptr, coords_ptr, item_ptr)]
+        self._check(self._lib.iss_output_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding], *ptrs))
+
+    def _need_export_entries(self):
+        if not hasattr(self._lib, "iss_output_export"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_output_export / iss_ctx_set_stream_ordered: rebuild it"
+                                             % _native.LIB_PATH)
 
     # ------------------------------------------------------------------ measurement
     def timing_enable(self, on=True):
