@@ -78,3 +78,124 @@ def synthetic_model(read_length, n_q, n_isize, seed, indel=(1e-3, 2e-3), nonempt
     phred_thr = 1.0 - 10.0 ** (-np.arange(n_q + 1) / 10.0)
     return DenseModel(RL, isize, bin_cdf, np.asarray(nonempty, dtype=np.uint8), qcdf, subst_cdf, subst_alt, ins, ins_letter,
                       dele, phred_thr)
+
+
+# ------------------------------------------------------------------ the plain formatters (no library code: the expected text)
+def fastq_text(record_id, first_i, cpu_number, mate, bases, quals):
+    """FASTQ text of one mate's reads (uint8 [n, read_length] letters and phreds), pair k named record_id_(first_i + k)_cpu/mate
+    (SeqIO.write(..., 'fastq-sanger'), iss/generator.py:64-65)."""
+    out = []
+    for k in range(len(bases)):
+        out.append(b"@%s_%d_%d/%d\n" % (record_id.encode(), first_i + k, cpu_number, mate) + bases[k].tobytes() + b"\n+\n"
+                   + (quals[k].astype(np.uint8) + 33).tobytes() + b"\n")
+    return b"".join(out)
+
+
+def vcf_lines(record_id, first_i, cpu_number, mutations):
+    """The --store_mutations lines of the oracle's mutation rows (iss/generator.py:598-620): an insertion's alt is ref + the
+    inserted letter, only a substitution carries its phred."""
+    lines = []
+    for m in mutations:
+        ref, alt = chr(m["ref"]), chr(m["alt"])
+        alt = ref + alt if m["type"] == 1 else alt
+        qual = str(int(m["quality"])) if m["type"] == 0 else "."
+        lines.append("\t".join(["%s_%d_%d/%d" % (record_id, first_i + int(m["pair"]), cpu_number, 1 + int(m["mate"])),
+                                str(int(m["position"]) + 1), ".", ref, alt, qual, "", ""]) + "\n")
+    return lines
+
+
+# ------------------------------------------------------------------ the read-length sweep of the row readers
+# 2, 5, 7: one partial piece; 8, 16: pitch == RL; 32, 64, 128, 256, 1024: no padding in the last line; 9, 31, 33, 100, 250,
+# 997: a partial last piece; 997, 1024: the engine's limit (128 pieces a mate)
+ROW_SWEEP = (2, 5, 7, 8, 9, 16, 31, 32, 33, 64, 100, 128, 250, 256, 997, 1024)
+ROW_SWEEP_PAIRS = 205  # rows of a case: 200 pairs from first pair 5
+ROW_SWEEP_SEED, ROW_SWEEP_FIRST_ORDINAL, ROW_SWEEP_MT_SEED = 31, 3, 4321
+ROW_SWEEP_WORK = (70, 0, 130)  # pairs of the --store_mutations work list's three records
+ROW_SWEEP_WORKER_SEED, ROW_SWEEP_CPU = 11, 2
+
+
+def row_sweep_model(RL):
+    """The sweep's model at read length RL (random tables with indels, two empty mean-quality bins).  Few phreds: a
+    substitution at every third position or so (from 100 positions on a few more phreds, to keep the VCF of a case below a
+    megabyte or two).  Below 100 positions the default indel rates would leave the 200 pairs of a case with a handful of
+    insertions and deletions at best, so they are raised there."""
+    n_q = 1 if RL == 2 else 3 if RL < 8 else 9 if RL < 100 else 30
+    return synthetic_model(RL, n_q, 7, seed=4000 + RL, indel=(0.02, 0.04) if RL < 100 else (1e-3, 2e-3))
+
+
+def row_sweep_genome(RL, k=0):
+    return mixed_genome(50 * RL + k, max(8 * RL + 7, 64) + 100 * k)
+
+
+def row_sweep_oracle_rows(dense, rng, genome, n, first_ordinal=0, oracle_kw=None):
+    """The oracle's reads as (bases [n, 2, RL], phreds [n, 2, RL], coordinates [n, 4])."""
+    from oracle import oracle as O
+
+    res = O.Oracle(dense, **(oracle_kw or {})).simulate(rng, genome, n, first_ordinal=first_ordinal, want_coords=True)
+    assert res["status"] == 0 and res["n_done"] == n
+    return {"bases": np.stack([res["r1_base"], res["r2_base"]], axis=1), "qual": np.stack([res["r1_qual"], res["r2_qual"]], axis=1),
+            "coords": res["coords"]}
+
+
+def row_sweep_worker_files(dense, RL):
+    """The sweep's --store_mutations work list (three records, the second with no pairs) and what worker_iterator has to write
+    for it in Philox mode: (record ids, sequences, pair counts), R1 text, R2 text, VCF text, the rows' types."""
+    from oracle import oracle as O
+
+    ids = ["w%d.%d" % (RL, k) for k in range(3)]
+    seqs = [row_sweep_genome(RL, 1 + k) for k in range(3)]
+    orc, rng = O.Oracle(dense), O.Rng().seed_philox(ROW_SWEEP_WORKER_SEED + ROW_SWEEP_CPU)
+    r1, r2, lines, types, ordinal = [], [], [], [], 0
+    for rid, seq, n in zip(ids, seqs, ROW_SWEEP_WORK):
+        res = orc.simulate(rng, seq, n, first_ordinal=ordinal, store_mutations=True)
+        assert res["status"] == 0 and res["n_done"] == n
+        ordinal += n
+        r1.append(fastq_text(rid, 0, ROW_SWEEP_CPU, 1, res["r1_base"], res["r1_qual"]))
+        r2.append(fastq_text(rid, 0, ROW_SWEEP_CPU, 2, res["r2_base"], res["r2_qual"]))
+        lines += vcf_lines(rid, 0, ROW_SWEEP_CPU, res["mutations"])
+        types += res["mutations"]["type"].tolist()
+    return (ids, seqs, ROW_SWEEP_WORK), b"".join(r1), b"".join(r2), "".join(lines), types
+
+
+def export_tile_pairs(RL, max_tile=64, lds_budget=48 * 1024):
+    """Pairs of a k_rows_export workgroup, by the rule of iss_export.hip.h: at most 64, both dense images of the tile (each
+    tile * 2 RL bytes rounded up to 16, + 16 for the offset of its first byte) within 48 KB of LDS."""
+    def region(t):
+        return ((t * 2 * RL + 15) // 16 + 1) * 16
+
+    t = min(max_tile, (lds_budget - 64) // (4 * RL))
+    while t > 0 and 2 * region(t) > lds_budget:
+        t -= 1
+    return t
+
+
+def export_tile_alignments(RL, n_pairs, shift):
+    """Addresses mod 16 at which the tiles of one export of n_pairs pairs start in an output array that begins at ``shift``."""
+    tile = export_tile_pairs(RL)
+    return [(shift + t0 * 2 * RL) % 16 for t0 in range(0, n_pairs, tile)]
+
+
+GUARD = 64
+
+
+class Guarded(object):
+    """A device buffer of ``nbytes`` with GUARD bytes of 0xA5 on either side (``shift``: the payload's address mod 16)."""
+
+    def __init__(self, nbytes, dtype, shape, shift=0, fill=0xA5):
+        import torch
+
+        self.torch, self.dtype, self.shape, self.nbytes = torch, dtype, shape, nbytes
+        self.buf = torch.full((GUARD + shift + nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda:0")
+        self.at = GUARD + shift
+        assert (self.buf.data_ptr() + self.at) % 16 == shift % 16
+        self.ptr = self.buf.data_ptr() + self.at
+
+    def guards_intact(self):
+        b = self.buf.cpu().numpy()
+        return bool((b[:self.at] == 0xA5).all() and (b[self.at + self.nbytes:] == 0xA5).all())
+
+    def untouched(self):
+        return bool((self.buf.cpu().numpy() == 0xA5).all())
+
+    def value(self):
+        return self.buf.cpu().numpy()[self.at:self.at + self.nbytes].view(self.dtype).reshape(self.shape)

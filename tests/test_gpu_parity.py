@@ -1136,6 +1136,7 @@ def test_mt_single_pairs_with_gc_bias_rejections():
 
 def _expected_worker_files(dense, recs, counts, seed, cpu, rng_mode, seq_type, gc_bias, frag, tmp_path):
     """worker_iterator's three files as the oracle + the host formatter + the reference's VCF line format give them."""
+    from helpers import vcf_lines
     from insilicoseq_amd.engine import fastq_write
     from oracle import oracle as O
 
@@ -1157,12 +1158,7 @@ def _expected_worker_files(dense, recs, counts, seed, cpu, rng_mode, seq_type, g
                 fastq_write(f1.fileno(), f2.fileno(), r.id, 0, cpu, k, dense.read_length, dense.read_length, res["r1_base"],
                             res["r1_qual"], res["r2_base"], res["r2_qual"], 1)
             ordinal += n
-            for m in res["mutations"]:
-                ref, alt = chr(m["ref"]), chr(m["alt"])
-                alt = ref + alt if m["type"] == 1 else alt
-                qual = str(int(m["quality"])) if m["type"] == 0 else "."
-                lines.append("\t".join(["%s_%d_%d/%d" % (r.id, m["pair"], cpu, 1 + int(m["mate"])), str(int(m["position"]) + 1),
-                                        ".", ref, alt, qual, "", ""]) + "\n")
+            lines += vcf_lines(r.id, 0, cpu, res["mutations"])
     return p1.read_bytes(), p2.read_bytes(), "".join(lines)
 
 

@@ -6,11 +6,10 @@ import pytest
 import torch  # noqa: F401  (here, when the module is collected: torch's HIP runtime has to be the process's first -- the engine's
               #  library then binds to it; torch imported behind a ReadEngine would start a second runtime that finds no GPU)
 
-from helpers import dense_model, mixed_genome, random_genome
+from helpers import Guarded, dense_model, mixed_genome, random_genome
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 N_ROWS = 7 + 257  # first_pair 7, 257 pairs: the largest case
 
 
@@ -44,26 +43,6 @@ def teardown_module(module):
     for eng, _ in _state.values():
         eng.close()
     _state.clear()
-
-
-class Guarded(object):
-    """A device buffer of ``nbytes`` with GUARD bytes of 0xA5 on either side (``shift``: the payload's address mod 16)."""
-
-    def __init__(self, nbytes, dtype, shape, shift=0, fill=0xA5):
-        import torch
-
-        self.torch, self.dtype, self.shape, self.nbytes = torch, dtype, shape, nbytes
-        self.buf = torch.full((GUARD + shift + nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda:0")
-        self.at = GUARD + shift
-        assert (self.buf.data_ptr() + self.at) % 16 == shift % 16
-        self.ptr = self.buf.data_ptr() + self.at
-
-    def guards_intact(self):
-        b = self.buf.cpu().numpy()
-        return bool((b[:self.at] == 0xA5).all() and (b[self.at + self.nbytes:] == 0xA5).all())
-
-    def value(self):
-        return self.buf.cpu().numpy()[self.at:self.at + self.nbytes].view(self.dtype).reshape(self.shape)
 
 
 def _outputs(n, RL, shift=0):
