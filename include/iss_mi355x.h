@@ -265,6 +265,36 @@ int iss_output_download_coords(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs
 #define ISS_EXPORT_CODES 1
 int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t encoding, void *d_bases, void *d_qual,
                       int64_t *d_coords, int32_t *d_item);
+/*
+ * The mutation rows of the last iss_generate / iss_generate_batch call (Philox path, after iss_mutations_reserve: "source 0" of
+ * iss_vcf_emit) as dense arrays in DEVICE memory the caller owns: per-base truth for a quality or error-correction model that
+ * stays on the GPU (additive in ABI 8).  The labels are the reference's VCF rows (iss/error_models/__init__.py:98-108, 197-221)
+ * and nothing more.  Window: output rows [first_pair, first_pair + n_pairs).
+ *   truth    uint8 [n_pairs][2][read_length]  shape and `encoding` of iss_output_export's d_bases: at every position that carries
+ *            a substitution row (type 0) the row's `ref` letter -- what stood there before mut_sequence changed it; under
+ *            ISS_EXPORT_CODES recoded like the bases, in either letter case (ASCII keeps the case: a lower-case record gives a
+ *            lower-case ref) -- and the exported base everywhere else.  NULL: not wanted
+ *   events   int32 [capacity][6]  (pair - first_pair, mate, type, position, ref, alt) of every row of the window's pairs, in the
+ *            order of iss_mutations_download (pair, mate, indel rows in loop order, then substitution rows by position); ref and
+ *            alt are ASCII whatever the encoding, alt of a deletion is '.'.  Rows from `capacity` on are not written
+ *   n_events int64 [1]  the rows of the window -- it may exceed `capacity`.  events and n_events go together (both, or both NULL)
+ * Two quirks come with the reference's rows:
+ *   1. a substitution whose new letter equals annotations["original"][position] is applied but not recorded (:98): truth then
+ *      shows the base as read, not the one it replaced (after an indel shifted the read "original" is another base's letter);
+ *   2. an indel row's position is a position in the sequence as it stood when the event fired (:201, :215), not in the read as
+ *      it came out: indels are delivered as rows and never painted into the dense image.
+ * A call that asked for more row slots than iss_mutations_reserve gave it has no row that can be trusted: the device itself
+ * writes n_events = -1 then and leaves the plain bases in truth (iss_mutations_download and iss_vcf_emit say ISS_E_NOMEM behind a
+ * wait on the host; this entry has no such wait).
+ * Stream and ownership as for iss_output_export: asynchronous on the context's current stream behind the generation, no wait on
+ * the host; the arrays are the caller's, ready when that stream reaches the end of the call's last kernel; the rows may be
+ * generated anew as soon as the call returns.  (The first call that asks for events under a reservation allocates work arrays
+ * of the reservation's size; a call after the reservation or the output rows grew waits for the stream to replace them.)
+ * ISS_E_INVALID, nothing launched: no reservation in force, no Philox generate call since it was made, a window outside the
+ * reserved output rows, an unknown encoding, events without n_events or the other way round.  MT mode's rows are not served.
+ */
+int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t encoding, uint8_t *truth, int32_t *events,
+                         int64_t capacity, int64_t *n_events);
 /* iss_ctx_set_stream without the wait on the host (additive in ABI 8): everything queued on the context's streams so far is
  * ordered in front of what the context queues on `hip_stream` from now on, by events.  NULL: back to the context's own stream. */
 int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream);

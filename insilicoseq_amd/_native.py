@@ -28,7 +28,7 @@ EXPORTS = (
     "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download", "iss_vcf_emit_workers",
     "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
     "iss_bam_tally_download", "iss_bam_kde",
-    "iss_output_export", "iss_ctx_set_stream_ordered",
+    "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -141,6 +141,9 @@ def lib():
     if hasattr(L, "iss_output_export"):
         L.iss_output_export.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
         L.iss_ctx_set_stream_ordered.argtypes = [vp, vp]
+    # (additive to ABI 8 again: the mutation rows as dense device arrays; without it ReadEngine.export_mutations raises)
+    if hasattr(L, "iss_mutations_export"):
+        L.iss_mutations_export.argtypes = [vp, i64, i64, i32, vp, vp, i64, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -164,7 +167,7 @@ def lib():
     L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
     for name in EXPORTS:
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
-                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered") and not hasattr(L, name):
+                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

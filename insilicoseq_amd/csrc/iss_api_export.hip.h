@@ -1,5 +1,6 @@
 // iss_api_export.hip.h -- C ABI: the output rows as dense arrays in the caller's device memory (iss_output_export, k_rows_export)
-// and the hand-over of the context to another stream without a wait on the host (iss_ctx_set_stream_ordered).
+// their mutation rows likewise (iss_mutations_export, iss_truth.hip.h), and the hand-over of the context to another stream without
+// a wait on the host (iss_ctx_set_stream_ordered).
 #pragma once
 
 extern "C" {
@@ -44,6 +45,110 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
     HIP_TRY(ctx, hipGetLastError());
     // (iss_generate_batch refills a set of tables once the event of its last reader has passed: this launch is that reader now)
     if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], ctx->stream));
+    return 0;
+}
+
+int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t encoding, uint8_t *truth, int32_t *events,
+                         int64_t capacity, int64_t *n_events) {
+    if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: upload a model first");
+    if (encoding != ISS_EXPORT_ASCII && encoding != ISS_EXPORT_CODES) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: unknown encoding");
+    if ((events != nullptr) != (n_events != nullptr) || capacity < 0 || capacity > ((int64_t)1 << 40))
+        return fail(ctx, ISS_E_INVALID, "iss_mutations_export: events and n_events go together, with a capacity of 0 or more");
+    if (!ctx->d_pmut || ctx->pmut_cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: no rows are reserved (iss_mutations_reserve)");
+    if (!ctx->pmut_call || !ctx->d_pmut_count)
+        return fail(ctx, ISS_E_INVALID, "iss_mutations_export: no iss_generate / iss_generate_batch call since the rows were reserved");
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+        return fail(ctx, ISS_E_INVALID, "iss_mutations_export: rows out of range");
+    const iss::DevModel &M = ctx->M;
+    const bool want_truth = truth && n_pairs;
+    if (want_truth) {  // (what iss_output_export would refuse, said before anything is launched)
+        const int tile = iss::export_tile_pairs(M.RL);
+        if (tile < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: read length beyond the export kernel's tile");
+        if ((n_pairs + tile - 1) / tile > (int64_t)0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: too many rows for one call");
+    }
+    if (!want_truth && !events) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t call_pairs = ctx->last_n;
+    iss::TruthArgs T{};
+    T.mut = ctx->d_pmut;
+    T.count = ctx->d_pmut_count;
+    T.cap = (uint32_t)ctx->pmut_cap;
+    T.flags = ctx->flags + ctx->last_row0;
+    T.call_pairs = call_pairs;
+    T.rel0 = first_pair - ctx->last_row0;
+    T.n_pairs = n_pairs;
+    T.RL = M.RL;
+    T.encoding = encoding;
+    T.w0 = std::min(std::max<int64_t>(T.rel0, 0), call_pairs);
+    T.w1 = std::min(std::max<int64_t>(T.rel0 + n_pairs, T.w0), call_pairs);
+    auto grid_for = [](uint64_t n, int threads) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (n + threads - 1) / threads))); };
+    if (events && T.w0 < T.w1) {  // the work arrays: sized once per reservation (a larger one waits for the kernels that read the old set)
+        auto &w = ctx->tw;
+        const size_t n_slots = (size_t)ctx->pmut_cap;
+        const size_t n_tiles = ((size_t)call_pairs + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE;
+        if (n_slots > w.slots_cap || (size_t)call_pairs > w.pairs_cap || n_tiles > w.tiles_cap) {
+            if (w.slots_cap || w.pairs_cap) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            const size_t sc = std::max(w.slots_cap, n_slots);
+            const size_t pc = std::max(w.pairs_cap, std::max((size_t)call_pairs, (size_t)ctx->capacity));
+            const size_t tc = (pc + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE + 1;
+            truth_free_work(ctx);
+            void *v = nullptr;
+            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_key = static_cast<uint32_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_slot = static_cast<uint32_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_order = static_cast<uint32_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, pc * 4)); w.d_cnt = static_cast<uint32_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, (pc + 1) * 8)); w.d_seg = static_cast<uint64_t *>(v);
+            HIP_TRY(ctx, hipMalloc(&v, tc * 8)); w.d_tiles = static_cast<uint64_t *>(v);
+            w.slots_cap = sc; w.pairs_cap = pc; w.tiles_cap = tc;
+        }
+    }
+    hipStream_t st = ctx->stream;
+    if (want_truth) {
+        // the bases a second time, then the substitutions' ref letters over them -- behind the copy, on the same stream
+        { int rc_ = iss_output_export(ctx, first_pair, n_pairs, encoding, truth, nullptr, nullptr, nullptr); if (rc_) return rc_; }
+        T.truth = truth;
+        hipLaunchKernelGGL(iss::k_truth_scatter, grid_for((uint64_t)ctx->pmut_cap, iss::TRUTH_THREADS), dim3(iss::TRUTH_THREADS), 0, st, T);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (events) {
+        T.events = events;
+        T.capacity = capacity;
+        T.n_events = n_events;
+        uint64_t rows_max = 0;
+        if (T.w0 < T.w1) {  // stages a and b of the VCF text (iss_vcf.hip.h) over every reserved slot: unused ones hold pair -1
+            auto &w = ctx->tw;
+            iss::VcfArgs A{};
+            A.mut = ctx->d_pmut;
+            A.n_slots = (uint32_t)ctx->pmut_cap;
+            A.n_pairs = call_pairs;
+            A.flags = T.flags;
+            A.cnt = w.d_cnt;
+            A.seg = w.d_seg;
+            A.key = w.d_key;
+            A.slot = w.d_slot;
+            A.order = w.d_order;
+            A.n_rows = w.d_seg + call_pairs;
+            HIP_TRY(ctx, hipMemsetAsync(w.d_cnt, 0, (size_t)call_pairs * 4, st));
+            HIP_TRY(ctx, hipMemsetAsync(w.d_order, 0, (size_t)ctx->pmut_cap * 4, st));
+            const dim3 grid = grid_for((uint64_t)ctx->pmut_cap, iss::VCF_THREADS), block(iss::VCF_THREADS);
+            const unsigned tiles = (unsigned)(((uint64_t)call_pairs + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
+            hipLaunchKernelGGL(iss::k_vcf_count, grid, block, 0, st, A);
+            hipLaunchKernelGGL(iss::k_vcf_scan_sums, dim3(tiles), dim3(iss::VSCAN_THREADS), 0, st, (const uint32_t *)w.d_cnt, (uint64_t)call_pairs, w.d_tiles);
+            hipLaunchKernelGGL(iss::k_vcf_scan_tiles, dim3(1), dim3(iss::VSCAN_THREADS), 0, st, w.d_tiles, (uint64_t)tiles, w.d_seg + call_pairs);
+            hipLaunchKernelGGL(iss::k_vcf_scan_apply, dim3(tiles), dim3(iss::VSCAN_THREADS), 0, st, (const uint32_t *)w.d_cnt, (uint64_t)call_pairs,
+                               (const uint64_t *)w.d_tiles, w.d_seg);
+            hipLaunchKernelGGL(iss::k_vcf_scatter, grid, block, 0, st, A);
+            hipLaunchKernelGGL(iss::k_vcf_rank, grid, block, 0, st, A);
+            HIP_TRY(ctx, hipGetLastError());
+            T.seg = w.d_seg;
+            T.order = w.d_order;
+            rows_max = (uint64_t)std::min<int64_t>(ctx->pmut_cap, capacity);
+        }
+        hipLaunchKernelGGL(iss::k_truth_events, grid_for(rows_max, iss::TRUTH_THREADS), dim3(iss::TRUTH_THREADS), 0, st, T);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // the flag words are this call's set: k_setup of the call after the next rewrites it once this event has passed (iss_vcf_emit)
+    if (ctx->call_seq) HIP_TRY(ctx, hipEventRecord(ctx->ev_call_done[(int)((ctx->call_seq - 1) & 1u)], st));
     return 0;
 }
 

@@ -73,6 +73,7 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         ctx->d_pmut_count = reinterpret_cast<uint32_t *>(ctx->fix_count) + 60;  // +240 B of the scratch block
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pmut, 0xff, (size_t)ctx->pmut_cap * sizeof(iss::MutRecord), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pmut_count, 0, sizeof(uint32_t), ctx->stream));
+        ctx->pmut_call = true;
     }
     ctx->last_row0 = out_first_pair;
     ctx->last_n = n_pairs;

@@ -1077,6 +1077,7 @@ int iss_mutations_reserve(iss_ctx *ctx, int64_t capacity) {
     if (ctx->d_pmut) (void)hipFree(ctx->d_pmut);
     ctx->d_pmut = nullptr;
     ctx->pmut_cap = 0;
+    ctx->pmut_call = false;
     if (capacity) {
         void *p = nullptr;
         HIP_TRY(ctx, hipMalloc(&p, (size_t)capacity * sizeof(iss::MutRecord)));

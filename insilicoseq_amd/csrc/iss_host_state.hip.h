@@ -290,6 +290,14 @@ struct iss_ctx {
     iss::MutRecord *d_pmut = nullptr;
     uint32_t *d_pmut_count = nullptr;
     int64_t pmut_cap = 0;
+    bool pmut_call = false;              // a generate call has recorded rows under the reservation in force (iss_mutations_export)
+    // iss_mutations_export's work arrays for the event rows (stages a and b of iss_vcf.hip.h): [slots] key, slot, order;
+    // [pairs] cnt; [pairs + 1] seg; tile sums of the scan.  Only kernels of the context's stream touch them, in order.
+    struct TruthWork {
+        uint32_t *d_key = nullptr, *d_slot = nullptr, *d_order = nullptr, *d_cnt = nullptr;
+        uint64_t *d_seg = nullptr, *d_tiles = nullptr;
+        size_t slots_cap = 0, pairs_cap = 0, tiles_cap = 0;
+    } tw;
     int64_t last_row0 = 0, last_n = 0;  // rows of the last iss_generate call (their flags tell which rows are stale)
     std::vector<int64_t> last_first;     // the last call was a batch: its item_first (rows last_row0 + ...), else empty
     std::vector<int64_t> last_off;       // ... and the arena offsets its descriptors carry

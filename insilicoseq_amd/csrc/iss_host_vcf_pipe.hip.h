@@ -96,6 +96,14 @@ void vcf_free_work(iss_ctx *ctx) {
     q.slots_cap = q.pairs_cap = q.tiles_cap = 0;
 }
 
+// the same arrays of iss_mutations_export (its own set: that entry shares nothing with the text's writer thread)
+void truth_free_work(iss_ctx *ctx) {
+    auto &w = ctx->tw;
+    for (uint32_t **p : {&w.d_key, &w.d_slot, &w.d_order, &w.d_cnt}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    for (uint64_t **p : {&w.d_seg, &w.d_tiles}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    w.slots_cap = w.pairs_cap = w.tiles_cap = 0;
+}
+
 void vcf_shutdown(iss_ctx *ctx) {
     VcfPipe &q = ctx->vq;
     if (!q.ready) return;

@@ -125,13 +125,16 @@ struct VcfArgs {
 };
 
 // does the row in this slot stay?  (iss_mutations_download: used slots; k_main's rows only for mates the fix-up did not rebuild)
-__device__ __forceinline__ bool vcf_keep(const VcfArgs &A, const MutRecord &r) {
-    if (r.pair < 0 || (int64_t)r.pair >= A.n_pairs) return false;
+// `n_pairs`, `flags`: the pairs of the generate call and its flag words.  The one statement of the filter on the device: the VCF
+// text and the truth arrays (iss_truth.hip.h) both go through it.
+__device__ __forceinline__ bool mut_row_stays(const MutRecord &r, int64_t n_pairs, const uint32_t *flags) {
+    if (r.pair < 0 || (int64_t)r.pair >= n_pairs) return false;
     if ((uint8_t)r.type & 32) return true;
-    const uint32_t f = A.flags[r.pair];
+    const uint32_t f = flags[r.pair];
     const int mate = r.mate & 1;
     return (((f >> mate) | (f >> (2 + mate))) & 1u) == 0;
 }
+__device__ __forceinline__ bool vcf_keep(const VcfArgs &A, const MutRecord &r) { return mut_row_stays(r, A.n_pairs, A.flags); }
 
 // the low half of iss_mutations_download's key: mate, indel rows (loop order) before substitution rows, position, slot of the step
 __device__ __forceinline__ uint32_t vcf_key(const MutRecord &r) {

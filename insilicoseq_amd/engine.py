@@ -484,6 +484,22 @@ class ReadEngine(object):
         ptrs = [C.c_void_p(int(p)) if p else None for p in (bases_ptr, qual_ptr, coords_ptr, item_ptr)]
         self._check(self._lib.iss_output_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding], *ptrs))
 
+    def export_mutations(self, first_pair, n_pairs, truth_ptr=None, events_ptr=None, capacity=0, n_events_ptr=None, encoding="ascii"):
+        """The mutation rows of the last generate() / generate_batch() (after mutations_reserve()) as dense arrays in device
+        memory of the caller (raw device addresses), for output rows [first_pair, +n_pairs): truth uint8 [n_pairs, 2,
+        read_length] -- the exported bases with every recorded substitution's ``ref`` letter put back, in ``encoding``; events
+        int32 [capacity, 6] (pair - first_pair, mate, type, position, ref, alt) in the order of mutations(), with their number
+        (int64, one word; -1: the call overflowed the reserved slots, truth is then the plain bases) at n_events_ptr; None: not
+        wanted, events and n_events go together.  Asynchronous on the engine's current stream, behind the generation; nothing
+        waits on the host (include/iss_mi355x.h: iss_mutations_export)."""
+        if encoding not in _native.EXPORT_ENCODINGS:
+            raise EngineError(_native.E_INVALID, "export_mutations: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
+        if not hasattr(self._lib, "iss_mutations_export"):  # (no fall-back, like _need_export_entries)
+            raise _native.NativeLibraryError("%s does not export iss_mutations_export: rebuild it" % _native.LIB_PATH)
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (truth_ptr, events_ptr, n_events_ptr)]
+        self._check(self._lib.iss_mutations_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding],
+                                                   ptrs[0], ptrs[1], int(capacity), ptrs[2]))
+
     def _need_export_entries(self):
         if not hasattr(self._lib, "iss_output_export"):  # (no fall-back, like _need_vcf_entries)
             raise _native.NativeLibraryError("%s does not export iss_output_export / iss_ctx_set_stream_ordered: rebuild it"

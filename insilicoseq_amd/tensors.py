@@ -5,21 +5,30 @@ read classifier, a quality model, a k-mer sketch).  Nothing here touches the hos
     for batch in ReadTensorStream(records, dense_model, work, batch_pairs=1 << 20, seed=7):
         loss = net(batch.bases, batch.qual, batch.record)     # uint8 [N, 2, L], uint8 [N, 2, L], int32 [N]
 
+With ``truth=True`` every batch also carries per-base truth -- ``batch.truth``: the bases as they stood before the simulator's
+substitutions -- and, with ``events_capacity``, the mutation rows themselves (``batch.events``, ``batch.n_events``): the engine's
+--store_mutations rows exported on the device (iss_mutations_export).
+
 torch is imported when a tensor is first needed (the package itself does not import it); the pure parts -- the cutting of a work
-list into batches, the numpy twin of the export kernel, ``multinomial_work`` -- need numpy only."""
+list into batches, the numpy twins of the export kernels, ``multinomial_work`` -- need numpy only."""
 import collections
 import logging
 
 import numpy as np
 
 from . import _native
-from ._native import EXPORT_ENCODINGS, EngineError, E_INVALID
+from ._native import EXPORT_ENCODINGS, EngineError, E_INVALID, E_NOMEM
 
-ReadBatch = collections.namedtuple("ReadBatch", ["bases", "qual", "coords", "record"])
+ReadBatch = collections.namedtuple("ReadBatch", ["bases", "qual", "coords", "record", "truth", "events", "n_events"],
+                                   defaults=(None, None, None))
 ReadBatch.__doc__ = """bases, qual: torch.uint8 [N, 2, L] (mate 1, mate 2; read length L, no padding); coords: torch.int64 [N, 4]
 (forward_start, reverse_start, reverse_end, insert_size in the record's own coordinates); record: torch.int32 [N] (the index of
-the pair's record in the list the stream was given; the work item for export_tensors).  All on the engine's device, owned by the
-caller: the engine keeps no reference and never writes to them again."""
+the pair's record in the list the stream was given; the work item for export_tensors).  Only when asked for (else None) --
+truth: torch.uint8 [N, 2, L], ``bases`` with the ``ref`` letter of every recorded substitution put back, same encoding; events:
+torch.int32 [capacity, 6], rows (pair within the batch, mate, type 0 substitution / 1 insertion / 2 deletion, position, ref,
+alt -- ASCII) in the order of ReadEngine.mutations(); n_events: 0-dim torch.int64, the batch's rows (rows from ``capacity`` on
+are not in ``events``; -1: the engine's row slots overflowed).  All on the engine's device, owned by the caller: the engine keeps
+no reference and never writes to them again."""
 
 
 def _torch():
@@ -75,6 +84,64 @@ def export_rows_host(rows, read_length, encoding="ascii"):
     bases = np.stack([arrays[0], arrays[2]], axis=1)
     qual = np.stack([arrays[1], arrays[3]], axis=1)
     return (recode(bases) if encoding == "codes" else bases), qual
+
+
+def truth_host(bases, rows, encoding="ascii"):
+    """The numpy twin of k_truth_scatter: ``bases`` uint8 [n, 2, L] as exported in ``encoding``, ``rows`` the structured array of
+    ReadEngine.mutations() or any other with its fields (``pair`` counted from bases[0]; rows of other pairs are passed over) -> truth uint8
+    [n, 2, L]: the ``ref`` letter (recoded under "codes", in either letter case) at every position with a substitution row
+    (type 0), the base everywhere else.  Indel rows are not painted: their positions are positions of the sequence as it stood
+    when the event fired."""
+    if encoding not in EXPORT_ENCODINGS:
+        raise ValueError("encoding must be 'ascii' or 'codes'")
+    truth = np.array(bases, dtype=np.uint8, copy=True)
+    assert truth.ndim == 3 and truth.shape[1] == 2
+    rows = np.asarray(rows)
+    sub = rows[(rows["type"] == 0) & (rows["pair"] >= 0) & (rows["pair"] < truth.shape[0])]
+    ref = sub["ref"].astype(np.uint8)
+    truth[sub["pair"].astype(np.int64), sub["mate"].astype(np.int64) & 1, sub["position"].astype(np.int64)] = \
+        recode(ref) if encoding == "codes" else ref
+    return truth
+
+
+def events_host(rows, first_pair, n_pairs):
+    """The numpy twin of k_truth_events: the rows of pairs [first_pair, first_pair + n_pairs), in the order they stand in
+    (ReadEngine.mutations(): pair, mate, indel rows in loop order, substitution rows by position) -> int32 [k, 6]
+    (pair - first_pair, mate, type, position, ref, alt)."""
+    rows = np.asarray(rows)
+    sel = rows[(rows["pair"] >= int(first_pair)) & (rows["pair"] < int(first_pair) + int(n_pairs))]
+    out = np.empty((sel.shape[0], 6), dtype=np.int32)
+    out[:, 0] = sel["pair"].astype(np.int64) - int(first_pair)
+    for k, f in enumerate(("mate", "type", "position", "ref", "alt"), start=1):
+        out[:, k] = sel[f]
+    return out
+
+
+MUT_CHUNK_SLOTS = 256         # slots a wavefront reserves at a time (iss_kernels.hip.h: MUT_CHUNK)
+MAIN_LAUNCH_PAIRS = 12582912  # pairs of one launch of a generate call at most (iss_host_util.hip.h: MAIN_CHUNK_PAIRS)
+
+
+def default_mutation_slots(error_model, batch_pairs, compute_units=256):
+    """Row slots to reserve (ReadEngine.mutations_reserve) for generate calls of ``batch_pairs`` pairs, by the advice of
+    include/iss_mi355x.h (iss_mutations_reserve): the kernels reserve slots in 256-slot chunks per wavefront, so
+
+        slots = 256 * wavefronts + batch_pairs * (2 * expected rows of a pair + 4)
+
+    * wavefronts: every wavefront that records a row leaves one chunk partly used.  Per launch the main kernel runs one
+      16-wavefront workgroup per compute unit and the indel fix-up at most 8 four-wavefront workgroups per compute unit, one
+      wavefront per read (2 * batch_pairs reads): 16 CU + min(32 CU, 2 * batch_pairs); a call of more than 12 582 912 pairs
+      is several launches.
+    * expected rows of a pair: DenseModel.expected_mutation_rows_per_pair() -- substitutions from the model's phred tables
+      (sum over positions of P(phred) * 10 ** (-phred / 10), the quality bins weighted) plus its indel rates.  Twice that: a
+      wavefront that needs n <= 64 slots when fewer are left in its chunk takes a new chunk (a chunk may end a quarter
+      empty), and the reads the fix-up rebuilds leave their first rows behind as stale ones; + 4 per pair keeps small batches
+      of a clean model above their own scatter (generator.py sizes the --store_mutations buffers the same way)."""
+    n = max(int(batch_pairs), 1)
+    cu = max(int(compute_units), 1)
+    launches = -(-n // MAIN_LAUNCH_PAIRS)
+    wavefronts = launches * (16 * cu + min(32 * cu, 2 * n))
+    per_pair = 2.0 * float(error_model.expected_mutation_rows_per_pair()) + 4.0
+    return int(MUT_CHUNK_SLOTS * wavefronts + np.ceil(n * per_pair))
 
 
 def coords_from_descriptors(fs, re, meta, isz, read_length, arena_off=0):
@@ -175,33 +242,51 @@ class _EngineOnCurrentStream(object):
             self.engine.set_stream(self.previous, wait=False)
 
 
-def _empty_batch(engine, n_pairs):
+def _empty_batch(engine, n_pairs, truth=False, events_capacity=0):
     torch = _torch()
     dev = torch.device("cuda", engine.device)
     L = engine.read_length
-    return ReadBatch(torch.empty((n_pairs, 2, L), dtype=torch.uint8, device=dev), torch.empty((n_pairs, 2, L), dtype=torch.uint8, device=dev),
-                     torch.empty((n_pairs, 4), dtype=torch.int64, device=dev), torch.empty((n_pairs,), dtype=torch.int32, device=dev))
+    out = ReadBatch(torch.empty((n_pairs, 2, L), dtype=torch.uint8, device=dev), torch.empty((n_pairs, 2, L), dtype=torch.uint8, device=dev),
+                    torch.empty((n_pairs, 4), dtype=torch.int64, device=dev), torch.empty((n_pairs,), dtype=torch.int32, device=dev))
+    if truth:
+        out = out._replace(truth=torch.empty((n_pairs, 2, L), dtype=torch.uint8, device=dev))
+    if events_capacity > 0:
+        out = out._replace(events=torch.empty((int(events_capacity), 6), dtype=torch.int32, device=dev),
+                           n_events=torch.empty((), dtype=torch.int64, device=dev))
+    return out
 
 
 def _check_out(engine, out, n_pairs):
     torch = _torch()
     L = engine.read_length
-    want = ((n_pairs, 2, L), torch.uint8), ((n_pairs, 2, L), torch.uint8), ((n_pairs, 4), torch.int64), ((n_pairs,), torch.int32)
+    want = (((n_pairs, 2, L), torch.uint8), ((n_pairs, 2, L), torch.uint8), ((n_pairs, 4), torch.int64), ((n_pairs,), torch.int32),
+            ((n_pairs, 2, L), torch.uint8), (("capacity >= 1", 6), torch.int32), ((), torch.int64))
+    if (out.events is None) != (out.n_events is None):
+        raise ValueError("out.events and out.n_events go together")
     for name, t, (shape, dtype) in zip(ReadBatch._fields, out, want):
         if t is None:
             continue
+        if name == "events" and t.dim() == 2 and t.shape[0] >= 1:
+            shape = (int(t.shape[0]), 6)
         if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != torch.device("cuda", engine.device):
             raise ValueError("out.%s: a contiguous %s tensor of shape %s on cuda:%d" % (name, dtype, shape, engine.device))
 
 
 def _export_into(engine, first_pair, n_pairs, encoding, out):
-    engine.export(first_pair, n_pairs, *[t.data_ptr() if t is not None and n_pairs else None for t in out], encoding=encoding)
+    engine.export(first_pair, n_pairs, *[t.data_ptr() if t is not None and n_pairs else None for t in out[:4]], encoding=encoding)
+    if out.truth is not None or out.events is not None:
+        ev = out.events is not None
+        engine.export_mutations(first_pair, n_pairs, truth_ptr=out.truth.data_ptr() if out.truth is not None and n_pairs else None,
+                                events_ptr=out.events.data_ptr() if ev else None, capacity=out.events.shape[0] if ev else 0,
+                                n_events_ptr=out.n_events.data_ptr() if ev else None, encoding=encoding)
 
 
-def export_tensors(engine, first_pair, n_pairs, encoding="codes", out=None):
+def export_tensors(engine, first_pair, n_pairs, encoding="codes", out=None, truth=False, events_capacity=0):
     """Rows [first_pair, +n_pairs) of ``engine`` as a ReadBatch on its device; ``record`` holds the pair's item of the last
     generate_batch() (0 for other rows).  The tensors are allocated by torch, or ``out`` (a ReadBatch; a field may be None: not
-    wanted) is written.  Stream rule: the export runs on torch's current stream -- behind everything the engine has queued (its
+    wanted) is written.  ``truth`` / ``events_capacity`` > 0: the fields ``truth`` / ``events`` and ``n_events`` as well, from
+    the mutation rows of the last generate call -- the engine must hold a reservation (ReadEngine.mutations_reserve) made before
+    that call, and the rows must be that call's; an ``out`` that carries these fields asks for them too.  Stream rule: the export runs on torch's current stream -- behind everything the engine has queued (its
     generation) and in front of whatever the caller queues on that stream next; afterwards the engine is back on the stream it
     had, ordered behind the export, so that generating into the same rows right away is safe.  Nothing waits on the host."""
     if encoding not in EXPORT_ENCODINGS:
@@ -210,7 +295,7 @@ def export_tensors(engine, first_pair, n_pairs, encoding="codes", out=None):
     torch = _torch()
     with torch.cuda.device(engine.device):
         if out is None:
-            out = _empty_batch(engine, n_pairs)
+            out = _empty_batch(engine, n_pairs, truth, int(events_capacity))
         else:
             out = ReadBatch(*out)
             _check_out(engine, out, n_pairs)
@@ -229,14 +314,32 @@ class ReadTensorStream(object):
     ``fragment_length`` / ``fragment_sd``: custom fragment lengths (both or none).
 
     Every batch is a new set of tensors that belongs to the caller.  A batch is generated and exported on torch's current
-    stream at the time it is asked for; nothing waits on the host."""
+    stream at the time it is asked for; nothing waits on the host.
+
+    ``truth=True``: the engine's mutation rows are reserved once, here (``mutation_slots`` row slots; default:
+    default_mutation_slots() for the model, the batch size and the device's compute units), and every batch carries ``truth``;
+    with ``events_capacity`` > 0 also ``events`` [events_capacity, 6] and ``n_events``, an event's pair counted from the batch's
+    first pair.  The contract extends to them: concatenated over the batches (the pairs rebased by the batches' first
+    ordinals), ``truth`` and the valid event rows do not depend on ``batch_pairs``.  ``truth=False`` (the default): no
+    reservation, the same kernels and tensors as before, the three fields None.
+
+    Overflow rule.  A batch whose generate call asked for more row slots than ``mutation_slots`` has no row that can be
+    trusted: the device writes n_events = -1 and leaves ``truth`` equal to ``bases``.  The stream learns of it without a wait
+    of its own: each batch's count is also copied, asynchronously, into a pinned host word with an event recorded behind the
+    copy; the word of a batch is looked at when the NEXT batch is asked for (by then the event has normally passed; if not,
+    that one event is waited for), the last batch's when the iteration ends.  On -1 the stream raises EngineError(E_NOMEM)
+    naming the batch and ``mutation_slots`` -- so the batch in question has already been handed out when the error comes:
+    do not keep results of an iteration that raised."""
 
     def __init__(self, records, error_model, work, batch_pairs, seed=0, device=0, encoding="codes", sequence_type="metagenomics",
-                 gc_bias=False, fragment_length=None, fragment_sd=None):
+                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None):
         from .engine import ReadEngine
 
         if encoding not in EXPORT_ENCODINGS:
             raise EngineError(E_INVALID, "ReadTensorStream: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
+        self.truth, self.events_capacity = bool(truth), int(events_capacity)
+        if self.events_capacity < 0 or (self.events_capacity and not self.truth):
+            raise EngineError(E_INVALID, "ReadTensorStream: events_capacity needs truth=True and must not be negative")
         torch = _torch()
         self.batch_pairs, self.seed, self.encoding = int(batch_pairs), int(seed), encoding
         self.sequence_type, self.gc_bias = sequence_type, bool(gc_bias)
@@ -262,9 +365,19 @@ class ReadTensorStream(object):
         self._batches = cut_batches([n for _, n in self.work], self.batch_pairs)
         self.n_pairs = sum(n for _, n in self.work)
         self.engine.reserve(min(self.batch_pairs, max(self.n_pairs, 1)))
+        self.mutation_slots = 0
         with torch.cuda.device(self.engine.device):
+            dev = torch.device("cuda", self.engine.device)
             # the record of every work item, on the device once: a batch's labels are a gather from its slice
-            self._work_record = torch.tensor([k for k, _ in self.work], dtype=torch.int32, device=torch.device("cuda", self.engine.device))
+            self._work_record = torch.tensor([k for k, _ in self.work], dtype=torch.int32, device=dev)
+            if self.truth:
+                if mutation_slots is None:
+                    mutation_slots = default_mutation_slots(error_model, min(self.batch_pairs, max(self.n_pairs, 1)),
+                                                            torch.cuda.get_device_properties(self.engine.device).multi_processor_count)
+                self.mutation_slots = int(mutation_slots)
+                self.engine.mutations_reserve(self.mutation_slots)
+                self._words = torch.zeros(2, dtype=torch.int64).pin_memory()  # the counts of the last two batches, as they arrive
+                self._no_events = torch.empty((1, 6), dtype=torch.int32, device=dev)  # (never written: capacity 0)
 
     def __len__(self):
         return len(self._batches)
@@ -278,22 +391,47 @@ class ReadTensorStream(object):
     def __exit__(self, *exc):
         self.close()
 
+    def _check_overflow(self, pending):
+        """The pinned word of a batch handed out before: -1 says its generate call overflowed the reserved row slots."""
+        index, event, word = pending
+        event.synchronize()  # (normally passed long ago)
+        if int(word.item()) < 0:
+            raise EngineError(E_NOMEM, "ReadTensorStream: batch %d asked for more mutation row slots than mutation_slots=%d holds; "
+                                       "its truth and events are not valid (pass a larger mutation_slots)" % (index, self.mutation_slots))
+
     def __iter__(self):
         torch = _torch()
         eng = self.engine
-        for first_ordinal, first_item, counts in self._batches:
+        pending = None
+        for index, (first_ordinal, first_item, counts) in enumerate(self._batches):
+            if pending is not None:
+                self._check_overflow(pending)
+                pending = None
             n = sum(counts)
             with torch.cuda.device(eng.device):
-                out = _empty_batch(eng, n)
+                out = _empty_batch(eng, n, self.truth, self.events_capacity)
                 with _EngineOnCurrentStream(eng, restore=False) as on:
                     eng.generate_batch(self._gids[first_item:first_item + len(counts)], counts, first_ordinal=first_ordinal, seed=self.seed,
                                        sequence_type=self.sequence_type, gc_bias=self.gc_bias, out_first_pair=0)
                     on.join_inputs()
                     _export_into(eng, 0, n, self.encoding, out)
+                    count = out.n_events
+                    if self.truth and count is None:
+                        # no events wanted: the overflow word alone, from an empty window (one small kernel, no row is ordered)
+                        count = torch.empty((), dtype=torch.int64, device=out.bases.device)
+                        eng.export_mutations(0, 0, events_ptr=self._no_events.data_ptr(), capacity=0, n_events_ptr=count.data_ptr())
+                if self.truth:
+                    word = self._words[index & 1]
+                    word.copy_(count, non_blocking=True)
+                    event = torch.cuda.Event()
+                    event.record()
+                    pending = (index, event, word)
                 # (item -> record on the device, in place: the slice of the work list's records this batch's items index)
                 record = torch.index_select(self._work_record[first_item:first_item + len(counts)], 0, out.record.long())
             yield out._replace(record=record)
+        if pending is not None:
+            self._check_overflow(pending)
 
 
 __all__ = ["ReadBatch", "ReadTensorStream", "export_tensors", "multinomial_work", "cut_batches", "export_rows_host", "recode",
-           "row_byte_index", "coords_from_descriptors"]
+           "row_byte_index", "coords_from_descriptors", "truth_host", "events_host", "default_mutation_slots"]

@@ -4,6 +4,7 @@ traffic, and ReadTensorStream next to the same work as bare generate_batch() cal
 
     python tools/tensor_bench.py                          # everything, one JSON line per figure
     ISS_MI355X_LIB=<older build> python tools/tensor_bench.py --bare-only    # the bare calls on another build of the library
+    python tools/tensor_bench.py --truth                  # only: ReadTensorStream with truth=True next to truth=False (section 17)
 
 Times are medians of --reps runs after a warm-up; the two routes of a comparison alternate run by run in one process."""
 import argparse
@@ -69,8 +70,8 @@ def export_alone(dense, recs, n, reps):
             tb_per_s=round((read_b + write_b if what == "export" else 2 * half) / t / 1e9, 3))
 
 
-def run_stream(dense, recs, work, batch_pairs):
-    with T.ReadTensorStream(recs, dense, work, batch_pairs, seed=3) as s:
+def run_stream(dense, recs, work, batch_pairs, **kw):
+    with T.ReadTensorStream(recs, dense, work, batch_pairs, seed=3, **kw) as s:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for batch in s:
@@ -93,21 +94,45 @@ def run_bare(dense, recs, work, batch_pairs):
         return time.perf_counter() - t0
 
 
+def truth_leg(dense, recs, work, total, batch_pairs, reps, events_capacity):
+    """DESIGN.md section 17, "Measured: not yet": the stream with and without truth, alternating run by run in one process."""
+    legs = {"truth=False": {}, "truth=True": {"truth": True}}
+    if events_capacity:
+        legs["truth=True, events"] = {"truth": True, "events_capacity": events_capacity}
+    secs = {k: [] for k in legs}
+    for rep in range(reps + 1):
+        for k, kw in legs.items():
+            t = run_stream(dense, recs, work, batch_pairs, **kw)
+            if rep:
+                secs[k].append(t)
+    for k in legs:
+        t = statistics.median(secs[k])
+        out(what="ReadTensorStream " + k, batch_pairs=batch_pairs, pairs=total, s=round(t, 5), pairs_per_s=round(total / t, 1),
+            s_all=[round(x, 5) for x in secs[k]],
+            mutation_slots=T.default_mutation_slots(dense, batch_pairs, torch.cuda.get_device_properties(0).multi_processor_count) if legs[k] else 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=5000000)
     ap.add_argument("--total", type=int, default=20000000, help="pairs of a stream run")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bare-only", action="store_true")
+    ap.add_argument("--truth", action="store_true", help="only the truth=True / truth=False comparison of the stream")
+    ap.add_argument("--batch-pairs", type=int, default=1 << 20, help="--truth: pairs of a batch")
+    ap.add_argument("--events-capacity", type=int, default=0, help="--truth: a third leg with this many event rows per batch")
     a = ap.parse_args()
     dense = DenseModel.load(os.path.join(ROOT, "insilicoseq_amd", "profiles", "novaseq.dense.npz"))
     recs = records()
     from insilicoseq_amd import _native
 
     out(library=_native.LIB_PATH, build_id=_native.lib().iss_build_id().decode(), device=torch.cuda.get_device_name(0))
-    if not a.bare_only:
+    if not a.bare_only and not a.truth:
         export_alone(dense, recs, a.pairs, a.reps)
     work = T.multinomial_work([1.0 / (k + 1) for k in range(len(recs))], a.total, seed=9)
+    if a.truth:
+        truth_leg(dense, recs, work, a.total, a.batch_pairs, a.reps, a.events_capacity)
+        return
     for batch_pairs in (1 << 16, 1 << 20, 5000000):
         routes = ("bare",) if a.bare_only else ("stream", "bare")
         secs = {r: [] for r in routes}
