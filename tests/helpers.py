@@ -83,10 +83,11 @@ def synthetic_model(read_length, n_q, n_isize, seed, indel=(1e-3, 2e-3), nonempt
 # ------------------------------------------------------------------ the plain formatters (no library code: the expected text)
 def fastq_text(record_id, first_i, cpu_number, mate, bases, quals):
     """FASTQ text of one mate's reads (uint8 [n, read_length] letters and phreds), pair k named record_id_(first_i + k)_cpu/mate
-    (SeqIO.write(..., 'fastq-sanger'), iss/generator.py:64-65)."""
+    (SeqIO.write(..., 'fastq-sanger'), iss/generator.py:64-65).  record_id: str, or bytes as the C ABI takes them."""
     out = []
+    rid = record_id if isinstance(record_id, bytes) else record_id.encode()
     for k in range(len(bases)):
-        out.append(b"@%s_%d_%d/%d\n" % (record_id.encode(), first_i + k, cpu_number, mate) + bases[k].tobytes() + b"\n+\n"
+        out.append(b"@%s_%d_%d/%d\n" % (rid, first_i + k, cpu_number, mate) + bases[k].tobytes() + b"\n+\n"
                    + (quals[k].astype(np.uint8) + 33).tobytes() + b"\n")
     return b"".join(out)
 

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+from deflate_twin import _deflate_block, _length_code, _tokens  # noqa: F401  (the tokenizer and block packer twins)
 from helpers import GOLDEN, dense_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -190,88 +191,6 @@ def test_compress_file_is_one_gzip_stream(tmp_path):
         assert gz == path + ".gz" and not os.path.exists(path)
         with gzip.open(gz, "rb") as fh:
             assert fh.read() == data
-
-
-def _length_code(n):
-    """RFC 1951 3.2.5 for match lengths 3..32: (symbol, extra bits, their value)"""
-    if n <= 10:
-        return 254 + n, 0, 0
-    k = n - 11
-    if k < 8:
-        return 265 + (k >> 1), 1, k & 1
-    return 269 + ((k - 8) >> 2), 2, (k - 8) & 3
-
-
-def _tokens(data, dist=0):
-    """The device's tokens (iss_deflate.hip.h, deflate_tokens): 32-byte chunks; at every position the run (the byte
-    repeats its predecessor) and the previous record (the same bytes `dist` earlier) are tried, the longer one wins
-    with >= 3 (run) / >= 4 (previous record) bytes inside the chunk, else a literal.
-    -> (symbol, kind 0 literal / 1 run / 2 previous record, extra bits of the length code, their value)"""
-    out = []
-    for at in range(0, len(data), 32):
-        chunk = data[at:at + 32]
-        has_src = bool(dist) and at >= dist
-        i = 0
-        while i < len(chunk):
-            c = chunk[i]
-            r1 = rd = 0
-            while i + r1 < len(chunk) and at + i + r1 > 0 and data[at + i + r1] == data[at + i + r1 - 1]:
-                r1 += 1
-            while has_src and i + rd < len(chunk) and chunk[i + rd] == data[at + i + rd - dist]:
-                rd += 1
-            if r1 >= 3 and r1 >= rd:
-                out.append((*_length_code(r1)[:1], 1, *_length_code(r1)[1:]))
-                i += r1
-            elif rd >= 4:
-                out.append((*_length_code(rd)[:1], 2, *_length_code(rd)[1:]))
-                i += rd
-            else:
-                out.append((c, 0, 0, 0))
-                i += 1
-    return out
-
-
-def _deflate_block(native, data, hist=None, dist=0):
-    """One DEFLATE block of `data` built on the CPU with the code tables of iss_deflate_code_build (what the device
-    kernels pack): header bits, the tokens' codes, end of block, then an empty stored block and a final empty block."""
-    import ctypes as C
-
-    toks = _tokens(data, dist)
-    if hist is None:
-        hist = np.bincount(np.array([t[0] for t in toks] + [256], dtype=np.int64), minlength=273).astype(np.uint32)
-    hist = np.ascontiguousarray(hist, dtype=np.uint32)
-    assert hist.size == 273
-    entry = np.zeros(273, dtype=np.uint32)
-    hdr = np.zeros(64, dtype=np.uint32)
-    dcode = np.zeros(3, dtype=np.uint32)
-    nbits = C.c_uint32(0)
-    assert native.lib().iss_deflate_code_build(hist.ctypes.data, dist, entry.ctypes.data, C.byref(nbits), hdr.ctypes.data,
-                                               dcode.ctypes.data) == 0
-    lens = (entry >> 16).astype(np.int64)
-    assert lens.min() >= 1 and lens.max() <= 15
-    assert sum(2.0 ** -int(x) for x in lens) == 1.0  # complete code (inflate rejects anything else)
-    acc = 0
-    for w in range((nbits.value + 31) // 32):
-        acc |= int(hdr[w]) << (32 * w)
-    acc &= (1 << nbits.value) - 1
-    n = nbits.value
-    for sym, kind, xbits, xval in toks:
-        acc |= (int(entry[sym]) & 0xffff) << n
-        n += int(lens[sym])
-        acc |= xval << n           # extra bits of the length code
-        n += xbits
-        if kind == 1:              # distance 1: the bit 0
-            n += 1
-        elif kind == 2:            # the record distance: the bit 1, then its extra bits
-            acc |= (1 | (int(dcode[2]) << 1)) << n
-            n += 1 + int(dcode[1])
-    acc |= (int(entry[256]) & 0xffff) << n
-    n += int(lens[256])
-    n += 3                      # empty stored block: BFINAL 0, BTYPE 00
-    n = (n + 7) // 8 * 8
-    acc |= 0xffff0000 << n      # LEN 0, NLEN 0xffff
-    n += 32
-    return acc.to_bytes(n // 8, "little") + b"\x03\x00", lens
 
 
 def test_deflate_code_builder_makes_valid_streams(native):
