@@ -295,6 +295,28 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
  */
 int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t encoding, uint8_t *truth, int32_t *events,
                          int64_t capacity, int64_t *n_events);
+/*
+ * Integer tallies of rows [first_pair, first_pair + n_pairs), built ON THE DEVICE and ADDED to d_tally: device memory of
+ * iss_tally_words(ctx) uint64 words that the caller owns and zeroes, so that a run accumulates over its batches -- what a run
+ * produced (per-position quality profile, base composition, GC distribution, insert sizes) without writing a byte of FASTQ
+ * (additive in ABI 8).  For read length L, Q = ISS_TALLY_PHREDS, I = ISS_TALLY_INSERT_BINS, the fields in
+ * this order, no padding:
+ *   pairs  [1]          pairs tallied
+ *   qual   [2][L][Q]    (mate, position, phred byte of the row); a byte above Q - 1 counts in bin Q - 1
+ *   base   [2][L][5]    (mate, position, ISS_EXPORT_CODES code of the base: A, C, G, T -> 0..3 in either case, every other letter 4)
+ *   gc     [2][L + 1]   reads of the mate by their number of G, C, g, c letters
+ *   meanq  [2][Q]       reads of the mate by floor(sum of the read's phred bytes / L) (Q - 1 at most)
+ *   insert [I]          pairs by insert_size (the fourth coordinate of iss_output_download_coords), clamped to [0, I - 1]
+ * Every count is an exact integer sum: the words depend neither on the launch geometry nor on the order of arrival.
+ * Stream and ownership as for iss_output_export: asynchronous on the context's current stream behind the generation it reads, no
+ * wait on the host, no device allocation; the rows may be generated anew as soon as the call returns.  Rows of iss_generate,
+ * iss_generate_batch and iss_generate_mt alike.  ISS_E_INVALID, nothing launched: no model, rows outside the reserved range,
+ * d_tally NULL with n_pairs > 0.  n_pairs == 0: 0, nothing launched.  iss_tally_words: -1 without a model.
+ */
+#define ISS_TALLY_PHREDS 94
+#define ISS_TALLY_INSERT_BINS 2048
+int64_t iss_tally_words(const iss_ctx *ctx); /* 1 + 2*L*94 + 2*L*5 + 2*(L+1) + 2*94 + 2048 */
+int iss_output_tally(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint64_t *d_tally);
 /* iss_ctx_set_stream without the wait on the host (additive in ABI 8): everything queued on the context's streams so far is
  * ordered in front of what the context queues on `hip_stream` from now on, by events.  NULL: back to the context's own stream. */
 int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream);

@@ -29,6 +29,7 @@ EXPORTS = (
     "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
     "iss_bam_tally_download", "iss_bam_kde",
     "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export",
+    "iss_tally_words", "iss_output_tally",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -144,6 +145,10 @@ def lib():
     # (additive to ABI 8 again: the mutation rows as dense device arrays; without it ReadEngine.export_mutations raises)
     if hasattr(L, "iss_mutations_export"):
         L.iss_mutations_export.argtypes = [vp, i64, i64, i32, vp, vp, i64, vp]
+    # (additive to ABI 8 once more: tallies of the rows built on the device; without them ReadEngine.tally raises)
+    if hasattr(L, "iss_output_tally"):
+        L.iss_tally_words.argtypes = [vp]
+        L.iss_output_tally.argtypes = [vp, i64, i64, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -167,10 +172,13 @@ def lib():
     L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
     for name in EXPORTS:
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
-                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export") and not hasattr(L, name):
+                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
+                    "iss_output_tally") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "iss_tally_words"):
+        L.iss_tally_words.restype = i64
     _lib = L
     return L
 

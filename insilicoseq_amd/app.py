@@ -184,10 +184,15 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, records=None):
+            fragment, compress=False, mode=None, report=False, records=None):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
-    pickles them; same content) unless the caller runs in this process and hands its own over."""
+    pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
+    its reads on the device into ``<prefix>.tally.npy`` (worker_iterator)."""
     logging.basicConfig(level=logging.WARNING)
+    if report:
+        from .tensors import _torch
+
+        _torch()  # (the tally words are a torch tensor: torch's HIP runtime has to be the process's first)
     # (records are identified by their ordinal in the concatenated FASTA, not by id: draft assemblies repeat ids)
     records = list(records if records is not None else parse_fasta(genome_file))
     if mode is None:  # (callers that name no mode: a model file is kde, none is basic)
@@ -199,7 +204,7 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
     else:
         model = KDErrorModel(npz, fragment[0], fragment[1], store_mutations)
     work = [(records[idx], n, "default") for idx, n in work_spec]
-    worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress)
+    worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report)
 
 
 def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
@@ -219,6 +224,23 @@ def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
     except WorkerSetNotSetUp as e:  # (seeding, the row pool of --store_mutations, or the first call's stream buffers: nothing ran yet)
         logger.warning("%d workers side by side do not fit the device (%s): one process per worker instead" % (workers, e))
         return None
+
+
+def _write_report(output, n_workers, read_length):
+    """--report: the workers' tallies (``<temp prefix>.tally.npy``) summed into ``<output>_tally.npy`` -- the raw uint64 words,
+    tally.tally_layout -- and ``<output>_report.json`` (tally.report_dict); the workers' files are removed."""
+    import json
+
+    from .tally import merge_tallies, report_dict
+
+    paths = ["%s.tally.npy" % temp_prefix(output, rank) for rank in range(n_workers)]
+    words = merge_tallies([np.load(path) for path in paths])
+    np.save(output + "_tally.npy", words)
+    with open(output + "_report.json", "w") as fh:
+        json.dump(report_dict(words, read_length), fh)
+        fh.write("\n")
+    for path in paths:
+        os.remove(path)
 
 
 def load_readcount_or_abundance(args, records, error_model):
@@ -279,6 +301,7 @@ def generate_reads(args):
         sys.exit(1)
     readcount_dic, abundance_dic, n_reads = load_readcount_or_abundance(args, records, error_model)
     workers = args.gpus
+    report = bool(getattr(args, "report", False))
     # --compress: the workers' FASTQ files already hold gzip members built on the device (one per batch); concatenated
     # they are the .gz files util.compress would have made from the text (iss/util.py:255-268), which never exists
     device_gzip = bool(args.compress) and os.environ.get("ISS_HOST_FASTQ", "") != "1"
@@ -292,14 +315,14 @@ def generate_reads(args):
         spec = [(ordinal_of[id(rec)], n) for rec, n, _ in chunk]
         jobs.append((rank, rank % max(args.devices, 1), genome_file, spec, error_model.npz_path, args.seed,
                      temp_prefix(args.output, rank), args.sequence_type, args.gc_bias, args.rng, args.store_mutations,
-                     (args.fragment_length, args.fragment_length_sd), device_gzip, args.mode))
+                     (args.fragment_length, args.fragment_length_sd), device_gzip, args.mode, report))
     t_gen = time.perf_counter()
     in_place = None
     if workers == 1:
         for j in jobs:
             _worker(*j, records=records)
     elif args.rng == "mt" and args.devices == 1 and args.seed is not None and workers <= 1024 \
-            and os.environ.get("ISS_HOST_FASTQ", "") != "1":
+            and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report:  # (--report: the set has no tally of its own -- the pool)
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
@@ -316,6 +339,8 @@ def generate_reads(args):
     else:
         concatenate_rank_files(args.output, workers, out_suffixes=gz)  # raises if a worker had no chunk (util.py:233)
     logger.info("Workers %.2f s, concatenation of their files %.2f s" % (t_cat - t_gen, time.perf_counter() - t_cat))
+    if report:
+        _write_report(args.output, len(jobs), error_model.read_length)
     os.remove(genome_file)
     if args.compress:  # util.compress (iss/util.py:255-268): <file>.gz next to the file, original removed
         for suffix in (() if device_gzip else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
@@ -371,6 +396,11 @@ def main(argv=None):
     g.add_argument("--rng", default="philox", choices=["philox", "mt"],
                    help="philox: parallel counter-based streams (default); mt: the reference's Mersenne-Twister "
                         "streams consumed sequentially on the GPU -- output identical to `iss generate` for the same --seed")
+    g.add_argument("--report", action="store_true",
+                   help="tally the reads on the GPU as they are generated and write <output>_report.json (per-position quality "
+                        "profile, base composition, GC, mean-quality and insert-size histograms) and <output>_tally.npy (the raw "
+                        "counters) next to the FASTQ files; with --rng mt --devices 1 the workers then run as one process each "
+                        "instead of side by side in one context (same files, byte for byte)")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

@@ -500,6 +500,26 @@ class ReadEngine(object):
         self._check(self._lib.iss_mutations_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding],
                                                    ptrs[0], ptrs[1], int(capacity), ptrs[2]))
 
+    def tally_words(self):
+        """uint64 words of a tally of this engine's model (include/iss_mi355x.h: iss_tally_words; tally.tally_layout)."""
+        self._need_tally_entries()
+        n = self._lib.iss_tally_words(self._ctx)
+        if n < 0:
+            raise EngineError(_native.E_INVALID, "tally_words: upload a model first")
+        return int(n)
+
+    def tally(self, first_pair, n_pairs, tally_ptr):
+        """Add the tallies of rows [first_pair, +n_pairs) -- per-position phreds and bases, GC and mean-quality histograms of the
+        reads, insert sizes, pairs -- to the tally_words() uint64 words at ``tally_ptr`` (a raw device address; the caller's
+        memory, zeroed by the caller).  Asynchronous on the engine's current stream, behind the generation; nothing waits on the
+        host (include/iss_mi355x.h: iss_output_tally; tally.split_tally names the fields)."""
+        self._need_tally_entries()
+        self._check(self._lib.iss_output_tally(self._ctx, int(first_pair), int(n_pairs), C.c_void_p(int(tally_ptr)) if tally_ptr else None))
+
+    def _need_tally_entries(self):
+        if not hasattr(self._lib, "iss_output_tally"):  # (no fall-back, like _need_export_entries)
+            raise _native.NativeLibraryError("%s does not export iss_tally_words / iss_output_tally: rebuild it" % _native.LIB_PATH)
+
     def _need_export_entries(self):
         if not hasattr(self._lib, "iss_output_export"):  # (no fall-back, like _need_vcf_entries)
             raise _native.NativeLibraryError("%s does not export iss_output_export / iss_ctx_set_stream_ordered: rebuild it"

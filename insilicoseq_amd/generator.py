@@ -327,6 +327,7 @@ class Worker(object):
         self.has_fragment = (getattr(error_model, "fragment_length", None) is not None and
                              getattr(error_model, "fragment_sd", None) is not None)
         self.ordinal = 0
+        self.tally = None  # --report: the device words every generate call's rows are tallied into (enable_tally)
         self.genomes = GenomeStore(
             self.engine, self,
             budget_divisor=1,     # the whole GENOME_BUDGET: beside the genomes a worker holds one batch of rows and its text
@@ -339,7 +340,28 @@ class Worker(object):
         self.genomes.plan(records)
 
     def close(self):
+        self.tally = None
         self.engine.close()
+
+    def enable_tally(self):
+        """--report: one zeroed tensor of ReadEngine.tally_words() words on the engine's device; tally_rows() adds to it."""
+        from .tensors import _torch
+
+        torch = _torch()
+        with torch.cuda.device(self.engine.device):
+            self.tally = torch.zeros(self.engine.tally_words(), dtype=torch.int64, device=torch.device("cuda", self.engine.device))
+            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
+
+    def tally_rows(self, first_pair, n_pairs):
+        """Tally rows [first_pair, +n_pairs) of the generate call just made -- once its rows are final (behind a repeated call
+        of _retry_on_row_overflow) and before they are generated anew.  Asynchronous, like the text jobs."""
+        if self.tally is not None:
+            self.engine.tally(first_pair, n_pairs, self.tally.data_ptr())
+
+    def tally_words_host(self):
+        """The tally so far as uint64 words on the host (waits for the engine)."""
+        self.engine.synchronize()
+        return self.tally.cpu().numpy().view(np.uint64).copy()
 
     def needs_room_for(self, record):
         """Would uploading this record drop the resident genomes (GENOME_BUDGET)?"""
@@ -385,6 +407,7 @@ class Worker(object):
                                  gc_bias=gc_bias, out_first_pair=0)
             gen()
             _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
+            self.tally_rows(0, n)
             if self.device_fastq:
                 # text built on the device, copied and written behind the next batch's generation
                 # (one pwrite stream per file: tmpfs gets slower with concurrent writers to one file)
@@ -505,6 +528,8 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                 gen1()
                 _take_mutations(route, eng, gen1, mutations_handle, [item], w.cpu_number, "philox")
                 ordinal += n
+        if getattr(w, "tally", None) is not None:  # --report (every call of the batch has settled: a repeated one is not counted twice)
+            w.tally_rows(0, row)
         eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
         w.ordinal += row
         if timings is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
@@ -563,14 +588,16 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
-                    rng="philox", compress=False, timings=None):
+                    rng="philox", compress=False, timings=None, report=False):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
     (same names) hold gzip members built on the device instead of text -- `--compress` without the text ever leaving
     the GPU; gunzipped they are the files ``compress=False`` writes.  ``timings``: a dict that receives ``t_start``, ``t_ready``
     (engine created, model uploaded), ``batches`` [(time a batch was queued for the files, its pairs)] and ``t_end`` (files
-    complete) -- bench.py's end-to-end legs report the steady state apart from the start-up."""
+    complete) -- bench.py's end-to-end legs report the steady state apart from the start-up.  ``report=True`` (`--report`): the rows
+    of every generate call are tallied on the device (ReadEngine.tally) and the worker's tally -- tally.tally_layout, uint64
+    words -- is written to ``{prefix}.tally.npy`` at the end; without it no engine call is added."""
     logger = logging.getLogger(__name__)
     if timings is not None:
         timings["t_start"] = time.perf_counter()
@@ -586,6 +613,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
         sys.exit(1)
     w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
     w.plan(record for record, _n, _mode in work)
+    if report:
+        w.enable_tally()
     if timings is not None:
         timings["t_ready"] = time.perf_counter()
     if store_mutations:
@@ -610,6 +639,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
             w.engine.fastq_flush()
             if store_mutations and w.device_vcf:
                 w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
+            if report:
+                np.save("%s.tally.npy" % worker_prefix, w.tally_words_host())
             if timings is not None:
                 timings["t_end"] = time.perf_counter()
     finally:

@@ -329,10 +329,17 @@ class ReadTensorStream(object):
     copy; the word of a batch is looked at when the NEXT batch is asked for (by then the event has normally passed; if not,
     that one event is waited for), the last batch's when the iteration ends.  On -1 the stream raises EngineError(E_NOMEM)
     naming the batch and ``mutation_slots`` -- so the batch in question has already been handed out when the error comes:
-    do not keep results of an iteration that raised."""
+    do not keep results of an iteration that raised.
+
+    ``tally=True``: the stream owns ``stream.tally``, one zeroed torch.int64 tensor of ReadEngine.tally_words() words on the
+    device (zeroed on the current stream of the constructor), and adds every batch's tallies to it (ReadEngine.tally: quality
+    profile, base composition, GC, mean quality, insert sizes; tally.split_tally names the fields) behind the batch's generation,
+    on the same stream, with no wait on the host -- it is complete when the stream has passed the last batch, and does not
+    depend on ``batch_pairs``.  The batches are unchanged.  ``tally=False`` (the default): ``stream.tally`` is None, no launch is
+    added."""
 
     def __init__(self, records, error_model, work, batch_pairs, seed=0, device=0, encoding="codes", sequence_type="metagenomics",
-                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None):
+                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False):
         from .engine import ReadEngine
 
         if encoding not in EXPORT_ENCODINGS:
@@ -370,6 +377,7 @@ class ReadTensorStream(object):
             dev = torch.device("cuda", self.engine.device)
             # the record of every work item, on the device once: a batch's labels are a gather from its slice
             self._work_record = torch.tensor([k for k, _ in self.work], dtype=torch.int32, device=dev)
+            self.tally = torch.zeros(self.engine.tally_words(), dtype=torch.int64, device=dev) if tally else None
             if self.truth:
                 if mutation_slots is None:
                     mutation_slots = default_mutation_slots(error_model, min(self.batch_pairs, max(self.n_pairs, 1)),
@@ -415,6 +423,8 @@ class ReadTensorStream(object):
                                        sequence_type=self.sequence_type, gc_bias=self.gc_bias, out_first_pair=0)
                     on.join_inputs()
                     _export_into(eng, 0, n, self.encoding, out)
+                    if self.tally is not None:
+                        eng.tally(0, n, self.tally.data_ptr())
                     count = out.n_events
                     if self.truth and count is None:
                         # no events wanted: the overflow word alone, from an empty window (one small kernel, no row is ordered)
