@@ -317,6 +317,60 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
 #define ISS_TALLY_INSERT_BINS 2048
 int64_t iss_tally_words(const iss_ctx *ctx); /* 1 + 2*L*94 + 2*L*5 + 2*(L+1) + 2*94 + 2048 */
 int iss_output_tally(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint64_t *d_tally);
+/*
+ * Per-base coverage depth of the generated reads, built ON THE DEVICE (additive in ABI 8): where on the
+ * records the reads fell, without a byte of FASTQ, an aligner or a depth tool.
+ *
+ * Definition.  For a pair let (fs, rs, re, isz) be what iss_output_download_coords returns, RL the read length and len the length
+ * of the pair's record.  The pair covers the half-open intervals [fs, fs + RL) (forward) and [rs, re) (reverse) of record
+ * coordinates, each CLAMPED to the record: [min(max(s, 0), len), min(max(e, 0), len)), empty when that leaves s >= e.  It is a
+ * clamp, not Python's negative-index wrap, and it only bites with custom fragment lengths (negative inserts, templates cut by
+ * the record's end).  The depth of a base is the number of such intervals over it.  It is the NOMINAL depth: the template
+ * intervals the reads were cut from (iss/generator.py:146-147, 165-177).  A third quirk beside the two of iss_mutations_export:
+ *   3. indels make a read consume a few bases more or fewer than its interval (adjust_seq_length); the depth ignores that.
+ *
+ * Accumulator.  The caller owns it and its layout.  A record table is int64 [n][2] of (offset, length) in device memory; record
+ * k owns the length + 1 int32 words [offset, offset + length] of a difference array, the last one being the record's sink.  An
+ * interval adds +1 at offset + s and -1 at offset + e (e <= length: in the sink at the latest).  So every record's words sum
+ * to zero, a plain inclusive prefix sum over the whole array is the depth of every base of every record at once, and the array
+ * is additive over calls, batches, record groups, workers and GPUs.  The caller zeroes it.
+ *
+ * iss_depth_mark adds the intervals of rows [first_pair, first_pair + n_pairs) to d_diff.  d_table[item] is the record of the
+ * pair's item: its item in the last iss_generate_batch call (as iss_output_export's d_item says), 0 for every other row (those of
+ * iss_generate, iss_generate_mt).  A row of the table with offset < 0: the pair is skipped.  One lane per pair, up to four int32
+ * global atomic adds without return; an empty interval adds nothing.  The table's rows must lie inside the caller's array: the
+ * entry has no way to check that.  Stream and ownership as for iss_output_tally: asynchronous on the context's current stream
+ * behind the generation, no wait on the host, no device allocation; the rows may be generated anew as soon as the call returns.
+ * It needs no mutation reservation and serves Philox and iss_generate_mt rows alike (not the rows of iss_generate_mt_workers).
+ * ISS_E_INVALID, nothing launched: no model, rows outside the reserved range, d_table or d_diff NULL with n_pairs > 0, n_table
+ * smaller than the item count of the last batch call when the window touches its rows (or < 1).  n_pairs == 0: 0, nothing launched.
+ * BOUND: the depth of a base must stay below 2^31.  The device does not check it.  A pair adds at most 2 to a base, so a caller
+ * that marks no more than 2^30 pairs into one accumulator is safe (the Python callers keep that count on the host and refuse
+ * more); a C caller keeps the rule itself.
+ *
+ * iss_depth_finish turns a difference array of n_words words into
+ *   d_depth uint32 [n_words]    its inclusive prefix sum: the depth of every base (a sink holds the depth behind the record's
+ *                               last base: 0).  It may be d_diff itself (in place; no other overlap), or NULL
+ *   d_stats uint64 [n_table][4] per record over its `length` bases, the sink left out: sum of depth, sum of depth squared (mod
+ *                               2^64), bases with depth > 0, maximum depth.  Overwritten, not added to.  NULL: not wanted
+ *   d_bins  uint64 [sum over the table's rows of ceil(length / bin)]  with bin > 0: the sum of depth over every bin-base window
+ *                               of every record, the records in table order, a record's last window short.  Overwritten.  NULL
+ *                               (or bin == 0): not wanted
+ * The rows of d_table used here must not overlap, must lie within n_words and must ascend by offset in table order; a row with
+ * offset < 0 is skipped wherever it stands (its statistics and windows are zero; it still owns its windows in d_bins).  Words
+ * that belong to no record (gaps) are scanned like the rest and counted nowhere.  The scan is a reduce-then-scan over tiles of
+ * ISS_DEPTH_TILE_WORDS words with 16-byte loads and stores when d_diff and d_depth are 16-byte aligned (4-byte accesses
+ * otherwise).  All results are exact integers and depend neither on the launch geometry nor on the order of arrival.
+ * It works on a context with no model and no genome.  Same stream rule as above, with one exception: the first call allocates a
+ * work array (tile sums, the table's rows in use) on the device, and a call that needs a larger one waits for the stream, frees
+ * it and allocates anew.  ISS_E_INVALID, nothing launched: negative n_words, n_table or bin, d_diff NULL with n_words > 0, d_table
+ * NULL with statistics or windows wanted.  Nothing wanted: 0, nothing launched.
+ * ISS_DEPTH_WGS (environment, read per call like ISS_TALLY_WGS): the workgroups k_depth_mark and the scan's passes aim at.
+ */
+#define ISS_DEPTH_TILE_WORDS 4096
+int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int64_t *d_table, int32_t n_table, int32_t *d_diff);
+int iss_depth_finish(iss_ctx *ctx, const int32_t *d_diff, int64_t n_words, uint32_t *d_depth, const int64_t *d_table, int32_t n_table,
+                     int32_t bin, uint64_t *d_stats, uint64_t *d_bins);
 /* iss_ctx_set_stream without the wait on the host (additive in ABI 8): everything queued on the context's streams so far is
  * ordered in front of what the context queues on `hip_stream` from now on, by events.  NULL: back to the context's own stream. */
 int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream);

@@ -30,6 +30,7 @@ EXPORTS = (
     "iss_bam_tally_download", "iss_bam_kde",
     "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export",
     "iss_tally_words", "iss_output_tally",
+    "iss_depth_mark", "iss_depth_finish",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -149,6 +150,10 @@ def lib():
     if hasattr(L, "iss_output_tally"):
         L.iss_tally_words.argtypes = [vp]
         L.iss_output_tally.argtypes = [vp, i64, i64, vp]
+    # (and again: per-base coverage depth built on the device; without them ReadEngine.depth_mark / depth_finish raise)
+    if hasattr(L, "iss_depth_mark"):
+        L.iss_depth_mark.argtypes = [vp, i64, i64, vp, i32, vp]
+        L.iss_depth_finish.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -173,7 +178,7 @@ def lib():
     for name in EXPORTS:
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
                     "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
-                    "iss_output_tally") and not hasattr(L, name):
+                    "iss_output_tally", "iss_depth_mark", "iss_depth_finish") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

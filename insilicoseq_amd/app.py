@@ -184,15 +184,16 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, report=False, records=None):
+            fragment, compress=False, mode=None, report=False, depth=False, records=None):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
-    its reads on the device into ``<prefix>.tally.npy`` (worker_iterator)."""
+    its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
+    (worker_iterator)."""
     logging.basicConfig(level=logging.WARNING)
-    if report:
+    if report or depth:
         from .tensors import _torch
 
-        _torch()  # (the tally words are a torch tensor: torch's HIP runtime has to be the process's first)
+        _torch()  # (the tally words / the depth accumulator are torch tensors: torch's HIP runtime has to be the process's first)
     # (records are identified by their ordinal in the concatenated FASTA, not by id: draft assemblies repeat ids)
     records = list(records if records is not None else parse_fasta(genome_file))
     if mode is None:  # (callers that name no mode: a model file is kde, none is basic)
@@ -204,7 +205,8 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
     else:
         model = KDErrorModel(npz, fragment[0], fragment[1], store_mutations)
     work = [(records[idx], n, "default") for idx, n in work_spec]
-    worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report)
+    more = {"depth": True, "ordinals": [idx for idx, _n in work_spec]} if depth else {}  # (without the flag: the call as it was)
+    worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report, **more)
 
 
 def _run_worker_set(jobs, records, error_model, args, device_gzip, workers):
@@ -239,6 +241,41 @@ def _write_report(output, n_workers, read_length):
     with open(output + "_report.json", "w") as fh:
         json.dump(report_dict(words, read_length), fh)
         fh.write("\n")
+    for path in paths:
+        os.remove(path)
+
+
+def _write_depth(output, n_workers, records, bin):
+    """--depth: the workers' accumulators (``<temp prefix>.depth.npz``) merged into one difference array over all records in FASTA
+    order (depth.merge_into: a record split across two workers' chunks is summed), finished ONCE on device 0 through a bare engine
+    context (ReadEngine.depth_finish), then ``<output>_depth.txt`` and, with ``bin`` > 0, ``<output>_depth.bedgraph``; the
+    workers' files are removed."""
+    from . import depth as D
+    from .engine import ReadEngine
+    from .tensors import _torch
+
+    torch = _torch()
+    table, n_words = D.depth_table([len(r.seq) for r in records])
+    diff = np.zeros(n_words, dtype=np.int32)
+    paths = ["%s.depth.npz" % temp_prefix(output, rank) for rank in range(n_workers)]
+    for path in paths:
+        with np.load(path) as z:
+            D.merge_into(diff, table, z["diff"], z["table"], z["ordinals"])
+    n_bins = int(D.n_windows(table, bin).sum())
+    with ReadEngine(0) as eng, torch.cuda.device(0):
+        dev = torch.device("cuda", 0)
+        d_diff, d_table = torch.from_numpy(diff).to(dev), torch.from_numpy(table).to(dev)
+        d_stats = torch.empty((len(records), 4), dtype=torch.int64, device=dev)
+        d_bins = torch.empty(max(n_bins, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()  # (uploaded on torch's stream; the engine works on its own)
+        eng.depth_finish(d_diff.data_ptr(), n_words, None, d_table.data_ptr(), len(records), bin, d_stats.data_ptr(),
+                         d_bins.data_ptr() if n_bins else None)
+        eng.synchronize()
+        stats, bins = d_stats.cpu().numpy().view(np.uint64), d_bins.cpu().numpy().view(np.uint64)[:n_bins]
+    ids = [r.id for r in records]
+    D.write_depth_table(output + "_depth.txt", D.depth_rows(stats, table, ids))
+    if bin > 0:
+        D.write_bedgraph(output + "_depth.bedgraph", bins, table, ids, bin)
     for path in paths:
         os.remove(path)
 
@@ -302,6 +339,11 @@ def generate_reads(args):
     readcount_dic, abundance_dic, n_reads = load_readcount_or_abundance(args, records, error_model)
     workers = args.gpus
     report = bool(getattr(args, "report", False))
+    depth_bin = int(getattr(args, "depth_bin", None) or 0)
+    if depth_bin < 0:
+        logger.error("--depth_bin must be positive")
+        sys.exit(1)
+    depth = bool(getattr(args, "depth", False)) or depth_bin > 0  # (--depth_bin implies --depth)
     # --compress: the workers' FASTQ files already hold gzip members built on the device (one per batch); concatenated
     # they are the .gz files util.compress would have made from the text (iss/util.py:255-268), which never exists
     device_gzip = bool(args.compress) and os.environ.get("ISS_HOST_FASTQ", "") != "1"
@@ -315,14 +357,14 @@ def generate_reads(args):
         spec = [(ordinal_of[id(rec)], n) for rec, n, _ in chunk]
         jobs.append((rank, rank % max(args.devices, 1), genome_file, spec, error_model.npz_path, args.seed,
                      temp_prefix(args.output, rank), args.sequence_type, args.gc_bias, args.rng, args.store_mutations,
-                     (args.fragment_length, args.fragment_length_sd), device_gzip, args.mode, report))
+                     (args.fragment_length, args.fragment_length_sd), device_gzip, args.mode, report, depth))
     t_gen = time.perf_counter()
     in_place = None
     if workers == 1:
         for j in jobs:
             _worker(*j, records=records)
     elif args.rng == "mt" and args.devices == 1 and args.seed is not None and workers <= 1024 \
-            and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report:  # (--report: the set has no tally of its own -- the pool)
+            and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth:  # (--report, --depth: the set has no tally or depth of its own -- the pool)
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
@@ -341,6 +383,8 @@ def generate_reads(args):
     logger.info("Workers %.2f s, concatenation of their files %.2f s" % (t_cat - t_gen, time.perf_counter() - t_cat))
     if report:
         _write_report(args.output, len(jobs), error_model.read_length)
+    if depth:
+        _write_depth(args.output, len(jobs), records, depth_bin)
     os.remove(genome_file)
     if args.compress:  # util.compress (iss/util.py:255-268): <file>.gz next to the file, original removed
         for suffix in (() if device_gzip else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
@@ -401,6 +445,13 @@ def main(argv=None):
                         "profile, base composition, GC, mean-quality and insert-size histograms) and <output>_tally.npy (the raw "
                         "counters) next to the FASTQ files; with --rng mt --devices 1 the workers then run as one process each "
                         "instead of side by side in one context (same files, byte for byte)")
+    g.add_argument("--depth", action="store_true",
+                   help="mark where the reads fall on the GPU as they are generated and write <output>_depth.txt: per record, in "
+                        "FASTA order, id, length, mean_depth, depth_variance, covered_fraction, max_depth of the nominal per-base "
+                        "depth (the template intervals the reads were cut from); like --report it makes --rng mt --devices 1 run "
+                        "one process per worker (same files, byte for byte)")
+    g.add_argument("--depth_bin", type=int, default=None, metavar="N",
+                   help="with --depth (implied): also <output>_depth.bedgraph, the mean depth of every N-base window of every record")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

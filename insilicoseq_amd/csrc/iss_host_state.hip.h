@@ -298,6 +298,12 @@ struct iss_ctx {
         uint64_t *d_seg = nullptr, *d_tiles = nullptr;
         size_t slots_cap = 0, pairs_cap = 0, tiles_cap = 0;
     } tw;
+    // iss_depth_finish's work array (tile sums of the scan, the table's rows in use and first windows: iss::DepthPlan), grown on
+    // demand.  Only kernels of the context's stream touch it, in order.
+    struct DepthWork {
+        uint8_t *d = nullptr;
+        size_t cap = 0;
+    } dw;
     int64_t last_row0 = 0, last_n = 0;  // rows of the last iss_generate call (their flags tell which rows are stale)
     std::vector<int64_t> last_first;     // the last call was a batch: its item_first (rows last_row0 + ...), else empty
     std::vector<int64_t> last_off;       // ... and the arena offsets its descriptors carry

@@ -5,7 +5,7 @@
 // Device side: iss_kernels.hip.h (the Philox path), iss_perfect.hip.h (its perfect-model kernel), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
 // iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h;
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
-// iss_tally.hip.h (integer tallies of the rows: what a run produced).
+// iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -38,6 +38,7 @@
 #include "iss_export.hip.h"     // k_rows_export: the rows as dense arrays in the caller's device memory (behind every other kernel, for the same reason)
 #include "iss_truth.hip.h"      // k_truth_scatter, k_truth_events: the mutation rows as dense device arrays (behind those again)
 #include "iss_tally.hip.h"      // k_tally_lines, k_tally_reads: quality, base, GC and insert-size tallies of the rows (last, likewise)
+#include "iss_depth.hip.h"      // k_depth_*: per-base coverage depth of the reads (behind every other kernel, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
@@ -54,3 +55,4 @@
 #include "iss_api_bam.hip.h"
 #include "iss_api_export.hip.h"
 #include "iss_api_tally.hip.h"
+#include "iss_api_depth.hip.h"

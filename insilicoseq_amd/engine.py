@@ -520,6 +520,31 @@ class ReadEngine(object):
         if not hasattr(self._lib, "iss_output_tally"):  # (no fall-back, like _need_export_entries)
             raise _native.NativeLibraryError("%s does not export iss_tally_words / iss_output_tally: rebuild it" % _native.LIB_PATH)
 
+    def depth_mark(self, first_pair, n_pairs, table_ptr, n_table, diff_ptr):
+        """Add the template intervals of rows [first_pair, +n_pairs) to the int32 difference array at ``diff_ptr``: +1 at the
+        start, -1 at the end of each pair's forward and reverse interval, clamped to the record (depth.py has the definition).
+        ``table_ptr``: int64 [n_table, 2] of (offset, length) on the device, row ``item`` the record of the pair's item in the
+        last generate_batch() (row 0 for other rows); offset < 0: the pair is skipped.  Raw device addresses, the caller's memory.
+        Asynchronous on the engine's current stream, behind the generation; nothing waits on the host.  The caller marks no more
+        than 2^30 pairs into one accumulator (depth.count_marked) (include/iss_mi355x.h: iss_depth_mark)."""
+        self._need_depth_entries()
+        self._check(self._lib.iss_depth_mark(self._ctx, int(first_pair), int(n_pairs), C.c_void_p(int(table_ptr)) if table_ptr else None,
+                                             int(n_table), C.c_void_p(int(diff_ptr)) if diff_ptr else None))
+
+    def depth_finish(self, diff_ptr, n_words, depth_ptr, table_ptr, n_table, bin=0, stats_ptr=None, bins_ptr=None):
+        """The difference array of ``n_words`` int32 words at ``diff_ptr`` -> its inclusive prefix sum, the depth of every base
+        (uint32 [n_words] at ``depth_ptr``; it may be ``diff_ptr`` itself), per-record statistics (uint64 [n_table, 4] at
+        ``stats_ptr``: sum, sum of squares, covered bases, maximum) and, with ``bin`` > 0, the sums over ``bin``-base windows
+        (uint64 [depth.n_windows(table, bin).sum()] at ``bins_ptr``); None: not wanted.  Works on an engine with no model.
+        Asynchronous on the engine's current stream (include/iss_mi355x.h: iss_depth_finish; depth.finish_host is its twin)."""
+        self._need_depth_entries()
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (diff_ptr, depth_ptr, table_ptr, stats_ptr, bins_ptr)]
+        self._check(self._lib.iss_depth_finish(self._ctx, ptrs[0], int(n_words), ptrs[1], ptrs[2], int(n_table), int(bin), ptrs[3], ptrs[4]))
+
+    def _need_depth_entries(self):
+        if not hasattr(self._lib, "iss_depth_mark"):  # (no fall-back, like _need_tally_entries)
+            raise _native.NativeLibraryError("%s does not export iss_depth_mark / iss_depth_finish: rebuild it" % _native.LIB_PATH)
+
     def _need_export_entries(self):
         if not hasattr(self._lib, "iss_output_export"):  # (no fall-back, like _need_vcf_entries)
             raise _native.NativeLibraryError("%s does not export iss_output_export / iss_ctx_set_stream_ordered: rebuild it"

@@ -328,6 +328,7 @@ class Worker(object):
                              getattr(error_model, "fragment_sd", None) is not None)
         self.ordinal = 0
         self.tally = None  # --report: the device words every generate call's rows are tallied into (enable_tally)
+        self.depth_diff = None  # --depth: the device's difference array over the distinct records of the work list (enable_depth)
         self.genomes = GenomeStore(
             self.engine, self,
             budget_divisor=1,     # the whole GENOME_BUDGET: beside the genomes a worker holds one batch of rows and its text
@@ -341,6 +342,8 @@ class Worker(object):
 
     def close(self):
         self.tally = None
+        self.depth_diff = None
+        self._depth_tables = []
         self.engine.close()
 
     def enable_tally(self):
@@ -362,6 +365,53 @@ class Worker(object):
         """The tally so far as uint64 words on the host (waits for the engine)."""
         self.engine.synchronize()
         return self.tally.cpu().numpy().view(np.uint64).copy()
+
+    def enable_depth(self, records, ordinals):
+        """--depth: one zeroed int32 difference array on the engine's device over the distinct records of the work list (in
+        order of first appearance; ``ordinals``: their ordinals in the FASTA), whatever GenomeStore groups and arena offsets
+        they come to stand in; depth_rows() adds every generate call's template intervals to it (depth.py)."""
+        from .depth import depth_table
+        from .tensors import _torch
+
+        torch = _torch()
+        self._depth_row, self.depth_ordinals, lengths = {}, [], []
+        for record, ordinal in zip(records, ordinals):
+            if id(record) not in self._depth_row:
+                self._depth_row[id(record)] = len(lengths)
+                self.depth_ordinals.append(int(ordinal))
+                lengths.append(len(record.seq))
+        self.depth_table, n_words = depth_table(lengths)
+        self._depth_tables, self._depth_marked = [], 0
+        with torch.cuda.device(self.engine.device):
+            self.depth_diff = torch.zeros(n_words, dtype=torch.int32, device=torch.device("cuda", self.engine.device))
+            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
+
+    def depth_rows(self, first_pair, n_pairs, records):
+        """Mark rows [first_pair, +n_pairs) of the generate call just made -- ``records``: the record of each of the call's items
+        (one for generate / generate_mt) -- where tally_rows stands: once the rows are final, before they are generated anew.
+        The call's table (item -> the record's words) is uploaded for it; asynchronous otherwise."""
+        if self.depth_diff is None or not n_pairs:
+            return
+        from .depth import count_marked
+        from .tensors import _torch
+
+        torch = _torch()
+        self._depth_marked = count_marked(self._depth_marked, n_pairs)
+        table = self.depth_table[[self._depth_row[id(r)] for r in records]]
+        if len(self._depth_tables) >= 8:  # (the marks that read the tables kept so far have run once the engine has been waited for)
+            self.engine.synchronize()
+            self._depth_tables = []
+        with torch.cuda.device(self.engine.device):
+            dev_table = torch.from_numpy(np.ascontiguousarray(table)).to(torch.device("cuda", self.engine.device))
+            torch.cuda.current_stream().synchronize()  # (uploaded on torch's stream; the engine reads it on its own)
+        self._depth_tables.append(dev_table)
+        self.engine.depth_mark(first_pair, n_pairs, dev_table.data_ptr(), len(records), self.depth_diff.data_ptr())
+
+    def depth_save(self, path):
+        """The worker's accumulator for the parent's merge: diff, table and the records' FASTA ordinals (waits for the engine)."""
+        self.engine.synchronize()
+        with open(path, "wb") as fh:  # (a handle: numpy adds no suffix to the name)
+            np.savez(fh, diff=self.depth_diff.cpu().numpy(), table=self.depth_table, ordinals=np.asarray(self.depth_ordinals, dtype=np.int64))
 
     def needs_room_for(self, record):
         """Would uploading this record drop the resident genomes (GENOME_BUDGET)?"""
@@ -408,6 +458,7 @@ class Worker(object):
             gen()
             _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
             self.tally_rows(0, n)
+            self.depth_rows(0, n, [record])
             if self.device_fastq:
                 # text built on the device, copied and written behind the next batch's generation
                 # (one pwrite stream per file: tmpfs gets slower with concurrent writers to one file)
@@ -500,11 +551,13 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
     eng = w.engine
     route = _mutation_route(w)
     pending, cur = [], 0  # (record id, genome id, pairs, id of the item's first pair in this piece)
+    pending_records = []  # --depth: the record of every pending piece
 
     def run():
-        nonlocal pending, cur
+        nonlocal pending, cur, pending_records
         if not pending:
             return
+        marked = False
         row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
         for rid, _gid, n, first_i in pending:
             emit.append((rid, first_i, row, n))
@@ -521,20 +574,25 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
             # records too long to stand side by side in one arena: the same rows, the same call, one item at a time
             eng.reserve(row)
             ordinal = w.ordinal
-            for (_rid, gid, n, _first_i), item in zip(pending, emit):
+            for (_rid, gid, n, _first_i), item, record in zip(pending, emit, pending_records):
                 def gen1():
                     eng.generate(gid, n, first_ordinal=ordinal, seed=w.seed, sequence_type=sequence_type, gc_bias=gc_bias,
                                  out_first_pair=item[2])
                 gen1()
                 _take_mutations(route, eng, gen1, mutations_handle, [item], w.cpu_number, "philox")
+                if getattr(w, "depth_diff", None) is not None:  # --depth: the item is a call of its own (item 0 of its rows)
+                    w.depth_rows(item[2], n, [record])
+                    marked = True
                 ordinal += n
         if getattr(w, "tally", None) is not None:  # --report (every call of the batch has settled: a repeated one is not counted twice)
             w.tally_rows(0, row)
+        if getattr(w, "depth_diff", None) is not None and not marked:  # --depth, likewise: the batch call's items through its table
+            w.depth_rows(0, row, pending_records)
         eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
         w.ordinal += row
         if timings is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
             timings.setdefault("batches", []).append((time.perf_counter(), row))
-        pending, cur = [], 0
+        pending, cur, pending_records = [], 0, []
 
     for fh in (forward_handle, reverse_handle):
         fh.flush()
@@ -549,6 +607,7 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         while done < n_pairs:
             take = min(n_pairs - done, w.BATCH_PAIRS - cur)
             pending.append((record.id, gid, take, done))
+            pending_records.append(record)
             cur += take
             done += take
             if cur >= w.BATCH_PAIRS:
@@ -588,7 +647,7 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
-                    rng="philox", compress=False, timings=None, report=False):
+                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
@@ -597,7 +656,10 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     (engine created, model uploaded), ``batches`` [(time a batch was queued for the files, its pairs)] and ``t_end`` (files
     complete) -- bench.py's end-to-end legs report the steady state apart from the start-up.  ``report=True`` (`--report`): the rows
     of every generate call are tallied on the device (ReadEngine.tally) and the worker's tally -- tally.tally_layout, uint64
-    words -- is written to ``{prefix}.tally.npy`` at the end; without it no engine call is added."""
+    words -- is written to ``{prefix}.tally.npy`` at the end; without it no engine call is added.  ``depth=True`` (`--depth`): the
+    template intervals of every generate call are marked on the device (ReadEngine.depth_mark) into one difference array over the
+    distinct records of ``work`` and written to ``{prefix}.depth.npz`` (diff, table, ``ordinals``: the FASTA ordinal of each work
+    item's record, default its position in ``work``) at the end; without it no engine call is added."""
     logger = logging.getLogger(__name__)
     if timings is not None:
         timings["t_start"] = time.perf_counter()
@@ -615,6 +677,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     w.plan(record for record, _n, _mode in work)
     if report:
         w.enable_tally()
+    if depth:
+        w.enable_depth([record for record, _n, _mode in work], ordinals if ordinals is not None else range(len(work)))
     if timings is not None:
         timings["t_ready"] = time.perf_counter()
     if store_mutations:
@@ -641,6 +705,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                 w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
             if report:
                 np.save("%s.tally.npy" % worker_prefix, w.tally_words_host())
+            if depth:
+                w.depth_save("%s.depth.npz" % worker_prefix)
             if timings is not None:
                 timings["t_end"] = time.perf_counter()
     finally:

@@ -336,10 +336,21 @@ class ReadTensorStream(object):
     profile, base composition, GC, mean quality, insert sizes; tally.split_tally names the fields) behind the batch's generation,
     on the same stream, with no wait on the host -- it is complete when the stream has passed the last batch, and does not
     depend on ``batch_pairs``.  The batches are unchanged.  ``tally=False`` (the default): ``stream.tally`` is None, no launch is
-    added."""
+    added.
+
+    ``depth=True``: per-base coverage depth (depth.py has the definition).  The stream owns
+    ``stream.depth_diff``, one zeroed torch.int32 difference array over the records its work list names, and
+    ``stream.depth_table``, torch.int64 [len(records), 2] of (offset, length) on the device, uploaded once -- row k is record k of
+    the list the stream was given, offset -1 for a record the work list does not name (or that is too short).  Every batch's
+    template intervals are added (ReadEngine.depth_mark) behind the batch's generation, on the same stream, with no wait on the
+    host.  The contract extends to it: the array after the last batch does not depend on ``batch_pairs``.  ``stream.depth(bin=0)``
+    -> (depth torch.uint32 [words], stats torch.uint64 [len(records), 4][, bins torch.uint64 with ``bin`` > 0]) computed on the
+    device on torch's current stream (ReadEngine.depth_finish), not in place: iteration can go on, and a later call sees more.
+    A stream refuses to mark more than 2^30 pairs (EngineError(E_INVALID)): a depth stays below 2^31.  ``depth=False`` (the
+    default): both attributes are None, no launch is added."""
 
     def __init__(self, records, error_model, work, batch_pairs, seed=0, device=0, encoding="codes", sequence_type="metagenomics",
-                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False):
+                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False, depth=False):
         from .engine import ReadEngine
 
         if encoding not in EXPORT_ENCODINGS:
@@ -378,6 +389,20 @@ class ReadTensorStream(object):
             # the record of every work item, on the device once: a batch's labels are a gather from its slice
             self._work_record = torch.tensor([k for k, _ in self.work], dtype=torch.int32, device=dev)
             self.tally = torch.zeros(self.engine.tally_words(), dtype=torch.int64, device=dev) if tally else None
+            self.depth_diff = self.depth_table = self._work_table = None
+            self._marked = 0
+            if depth:
+                from .depth import depth_table
+
+                named = sorted(set(k for k, _ in self.work))
+                table = np.full((len(records), 2), -1, dtype=np.int64)
+                table[:, 1] = [len(r) for r in records]
+                packed, n_words = depth_table([len(records[k]) for k in named])
+                table[named, 0] = packed[:, 0]
+                self.depth_table = torch.from_numpy(table).to(dev)
+                self.depth_diff = torch.zeros(n_words, dtype=torch.int32, device=dev)
+                # the table row of every work item: a batch's items are a slice of it
+                self._work_table = torch.index_select(self.depth_table, 0, self._work_record.long()).contiguous()
             if self.truth:
                 if mutation_slots is None:
                     mutation_slots = default_mutation_slots(error_model, min(self.batch_pairs, max(self.n_pairs, 1)),
@@ -398,6 +423,36 @@ class ReadTensorStream(object):
 
     def __exit__(self, *exc):
         self.close()
+
+    def depth(self, bin=0):
+        """(depth, stats[, bins]) of what has been marked so far -- see the class -- on the device, behind the marks, on
+        torch's current stream; the accumulator is left as it is."""
+        if self.depth_diff is None:
+            raise EngineError(E_INVALID, "ReadTensorStream.depth: the stream was made without depth=True")
+        from .depth import n_windows
+
+        torch = _torch()
+        eng = self.engine
+        bin = int(bin)
+        if bin < 0:
+            raise EngineError(E_INVALID, "ReadTensorStream.depth: bin must not be negative")
+        with torch.cuda.device(eng.device):
+            dev = self.depth_diff.device
+            n_words, n_table = int(self.depth_diff.shape[0]), int(self.depth_table.shape[0])
+            depth = torch.empty(n_words, dtype=torch.int32, device=dev)
+            stats = torch.empty((n_table, 4), dtype=torch.int64, device=dev)
+            bins = torch.empty(int(n_windows(self._depth_lengths(), bin).sum()), dtype=torch.int64, device=dev) if bin else None
+            with _EngineOnCurrentStream(eng, restore=True) as on:
+                on.join_inputs()
+                eng.depth_finish(self.depth_diff.data_ptr(), n_words, depth.data_ptr(), self.depth_table.data_ptr(), n_table, bin,
+                                 stats.data_ptr(), bins.data_ptr() if bins is not None and bins.numel() else None)
+        out = (depth.view(torch.uint32), stats.view(torch.uint64))
+        return out + (bins.view(torch.uint64),) if bin else out
+
+    def _depth_lengths(self):
+        if getattr(self, "_depth_table_host", None) is None:
+            self._depth_table_host = self.depth_table.cpu().numpy()
+        return self._depth_table_host
 
     def _check_overflow(self, pending):
         """The pinned word of a batch handed out before: -1 says its generate call overflowed the reserved row slots."""
@@ -425,6 +480,11 @@ class ReadTensorStream(object):
                     _export_into(eng, 0, n, self.encoding, out)
                     if self.tally is not None:
                         eng.tally(0, n, self.tally.data_ptr())
+                    if self.depth_diff is not None:
+                        from .depth import count_marked
+
+                        self._marked = count_marked(self._marked, n)
+                        eng.depth_mark(0, n, self._work_table[first_item:].data_ptr(), len(counts), self.depth_diff.data_ptr())
                     count = out.n_events
                     if self.truth and count is None:
                         # no events wanted: the overflow word alone, from an empty window (one small kernel, no row is ordered)
