@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive) iss_mt_workers_mutations_reserve / iss_mt_workers_mutations_download / iss_vcf_emit_workers: --store_mutations for
+/* 8: (additive) iss_ubam_emit_batch / iss_ubam_flush / iss_ubam_host_records: the rows as unaligned BAM, records and BGZF
+ *    blocks built on the device.
+ *    (additive) iss_mt_workers_mutations_reserve / iss_mt_workers_mutations_download / iss_vcf_emit_workers: --store_mutations for
  *    the W workers of a set (rows per worker, placed on the device; one text job per call).
  *    (additive, like the three entries before them) iss_vcf_emit / iss_vcf_flush: the --store_mutations text built on the device.
  *    iss_main_kernel (which instantiation of the hot kernel the last Philox-mode call launched: k_main or k_main_g -- the
@@ -534,6 +536,32 @@ int iss_deflate_code_build(const uint32_t *hist, uint32_t record_distance, uint3
 int iss_fastq_write(int fd_r1, int fd_r2, const char *record_id, int64_t first_i, int32_t cpu_number,
                     int64_t n_pairs, int32_t read_length, int32_t pitch, const uint8_t *r1_base,
                     const uint8_t *r1_qual, const uint8_t *r2_base, const uint8_t *r2_qual, int32_t n_threads);
+
+/*
+ * Unaligned BAM built ON THE DEVICE (additive in ABI 8): the FASTQ's content in the other container that
+ * pipelines take directly (the uBAM convention of GATK / Picard).  The item table is iss_fastq_emit_batch's.  Rows
+ * [first_pair[k], +n_pairs[k]) become alignment records (SAM/BAM specification 4.2) in ONE stream, R1 then R2 of every pair:
+ * refID / pos / next_refID / next_pos -1, mapq 0, bin 4680, no CIGAR, flag 77 (R1) / 141 (R2), tlen 0, read name
+ * "{id}_{i}_{cpu_number}" (no /1, /2: the flags carry the mate), the bases as 4-bit codes of "=ACMGRSVTWYHKDBN" (lower-case
+ * letters count as their capitals -- BAM has no case -- and any other byte is N), the raw phreds, no tags.  The call's record
+ * bytes are cut into blocks of 32 768 bytes, each written as one complete BGZF member (specification 4.1: a gzip member with the
+ * `BC` field, its own CRC-32 and ISIZE) that inflates on its own, and the members are appended to fd at its current position.  A
+ * call writes record blocks only: the BAM header in front and the 28-byte EOF block behind are the caller's.  Asynchronous like
+ * iss_fastq_emit_batch -- kernels on the context's stream behind the generation, the size on a copy stream, the bytes fetched and
+ * appended (pwrite) by a writer thread, two slots; iss_ubam_flush waits until every queued byte is in the file and leaves the
+ * descriptor at its end.  A member never exceeds BGZF's 65 536 bytes (32 768 literals at the 15-bit code limit stay under it); the
+ * writer walks the BSIZE chain of what it fetched before it writes, and a chain that does not hold is ISS_E_INVALID at the next
+ * emit or flush, never a wrapped BSIZE in the file.  A read name of more than 254 characters does not fit l_read_name: ISS_E_INVALID naming the record id,
+ * before anything is launched or written.
+ *
+ * iss_ubam_host_records (host only, no GPU; single-threaded): the same record bytes, uncompressed, from host rows
+ * ([pairs][pitch] arrays as iss_output_download returns them), appended to fd -- the counterpart of iss_fastq_write.
+ */
+int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
+                        const int64_t *first_pair, const int64_t *n_pairs, int32_t cpu_number);
+int iss_ubam_flush(iss_ctx *ctx);
+int iss_ubam_host_records(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,
+                          int32_t pitch, const uint8_t *r1_base, const uint8_t *r1_qual, const uint8_t *r2_base, const uint8_t *r2_qual);
 
 /*
  * `model`: the reference's `iss model` (iss/app.py:147-169 -> iss/bam.py:103-227, iss/modeller.py) from a BAM file.  Additive to

@@ -31,6 +31,7 @@ EXPORTS = (
     "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export",
     "iss_tally_words", "iss_output_tally",
     "iss_depth_mark", "iss_depth_finish",
+    "iss_ubam_emit_batch", "iss_ubam_flush", "iss_ubam_host_records",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -154,6 +155,11 @@ def lib():
     if hasattr(L, "iss_depth_mark"):
         L.iss_depth_mark.argtypes = [vp, i64, i64, vp, i32, vp]
         L.iss_depth_finish.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp]
+    # (and once more: unaligned BAM built on the device; without them ReadEngine.ubam_emit_batch / ubam_flush raise)
+    if hasattr(L, "iss_ubam_emit_batch"):
+        L.iss_ubam_emit_batch.argtypes = [vp, C.c_int, i32, vp, vp, vp, vp, i32]
+        L.iss_ubam_flush.argtypes = [vp]
+        L.iss_ubam_host_records.argtypes = [C.c_int, C.c_char_p, i64, i32, i64, i32, i32, vp, vp, vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -178,7 +184,8 @@ def lib():
     for name in EXPORTS:
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
                     "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
-                    "iss_output_tally", "iss_depth_mark", "iss_depth_finish") and not hasattr(L, name):
+                    "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
+                    "iss_ubam_host_records") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

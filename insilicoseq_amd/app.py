@@ -184,11 +184,11 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, report=False, depth=False, records=None):
+            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
-    (worker_iterator)."""
+    (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files."""
     logging.basicConfig(level=logging.WARNING)
     if report or depth:
         from .tensors import _torch
@@ -206,6 +206,8 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
         model = KDErrorModel(npz, fragment[0], fragment[1], store_mutations)
     work = [(records[idx], n, "default") for idx, n in work_spec]
     more = {"depth": True, "ordinals": [idx for idx, _n in work_spec]} if depth else {}  # (without the flag: the call as it was)
+    if ubam:
+        more["ubam"] = True
     worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report, **more)
 
 
@@ -327,7 +329,38 @@ def load_readcount_or_abundance(args, records, error_model):
     return readcount_dic, abundance_dic, n_reads
 
 
+def _worker_set_wanted(args, report, depth):
+    """Do the workers of this command run side by side in one context (worker_set_iterator) rather than one process each?"""
+    return args.gpus > 1 and args.rng == "mt" and args.devices == 1 and args.seed is not None and args.gpus <= 1024 \
+        and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth  # (--report, --depth: the set has no tally or depth of its own -- the pool)
+
+
+def _remove_ubam_files(output, workers):
+    for path in [output + ".bam"] + ["%s.bam" % temp_prefix(output, rank) for rank in range(workers)]:
+        if os.path.exists(path):
+            os.remove(path)
+
+
 def generate_reads(args):
+    logger = logging.getLogger(__name__)
+    ubam = bool(getattr(args, "ubam", False))
+    if ubam and _worker_set_wanted(args, bool(getattr(args, "report", False)),
+                                   bool(getattr(args, "depth", False)) or int(getattr(args, "depth_bin", None) or 0) > 0):
+        logger.error("--ubam is not supported with --rng mt --cpus %d --devices 1 (workers side by side in one context): "
+                     "use one device per worker, or --cpus 1" % args.gpus)
+        sys.exit(1)
+    if ubam and os.environ.get("ISS_HOST_FASTQ", "") == "1":
+        logger.error("--ubam builds its records on the device: unset ISS_HOST_FASTQ")
+        sys.exit(1)
+    try:
+        _generate_reads(args, ubam)
+    except BaseException:
+        if ubam:  # (no half-written final file, and no blocks without their frame)
+            _remove_ubam_files(args.output, args.gpus)
+        raise
+
+
+def _generate_reads(args, ubam):
     logger = logging.getLogger(__name__)
     error_model = load_error_model(args.mode, args.seed, args.model, args.fragment_length, args.fragment_length_sd,
                                    args.store_mutations, args.rng)
@@ -346,7 +379,8 @@ def generate_reads(args):
     depth = bool(getattr(args, "depth", False)) or depth_bin > 0  # (--depth_bin implies --depth)
     # --compress: the workers' FASTQ files already hold gzip members built on the device (one per batch); concatenated
     # they are the .gz files util.compress would have made from the text (iss/util.py:255-268), which never exists
-    device_gzip = bool(args.compress) and os.environ.get("ISS_HOST_FASTQ", "") != "1"
+    # --ubam: the workers write BGZF record blocks (one .bam stream instead of the two FASTQ files); --compress then applies to the .vcf only
+    device_gzip = bool(args.compress) and not ubam and os.environ.get("ISS_HOST_FASTQ", "") != "1"
     gz = {"_R1.fastq": "_R1.fastq.gz", "_R2.fastq": "_R2.fastq.gz"} if device_gzip else None
     chunk_size = -((n_reads // 2) // -workers)  # ceildiv, app.py:82
     chunks = list(generate_work_divider(records, readcount_dic, abundance_dic, n_reads, args.coverage, args.coverage_file,
@@ -362,17 +396,24 @@ def generate_reads(args):
     in_place = None
     if workers == 1:
         for j in jobs:
-            _worker(*j, records=records)
-    elif args.rng == "mt" and args.devices == 1 and args.seed is not None and workers <= 1024 \
-            and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth:  # (--report, --depth: the set has no tally or depth of its own -- the pool)
+            _worker(*j, records=records, ubam=ubam)
+    elif _worker_set_wanted(args, report, depth):
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            pool.starmap(_worker, jobs)
+            pool.starmap(_worker, [j + (None, True) for j in jobs] if ubam else jobs)
     t_cat = time.perf_counter()
-    if in_place:
+    if ubam:  # header, the workers' record blocks in worker order, the EOF block; a worker without a chunk is an error as below
+        from .ubam import assemble
+
+        assemble(args.output + ".bam", ["%s.bam" % temp_prefix(args.output, rank) for rank in range(workers)])
+        if args.store_mutations:
+            concatenate_rank_files(args.output, workers, suffixes=(".vcf",), headers={".vcf": VCF_HEADER})
+        else:
+            concatenate_rank_files(args.output, workers, suffixes=())  # (removes the workers' empty .vcf files)
+    elif in_place:
         if args.store_mutations:  # the FASTQ files are final; a VCF's size is not arithmetic: the workers' .vcf behind the header
             concatenate_rank_files(args.output, workers, suffixes=(".vcf",), headers={".vcf": VCF_HEADER})
     elif args.store_mutations:  # app.py:128-133
@@ -387,7 +428,7 @@ def generate_reads(args):
         _write_depth(args.output, len(jobs), records, depth_bin)
     os.remove(genome_file)
     if args.compress:  # util.compress (iss/util.py:255-268): <file>.gz next to the file, original removed
-        for suffix in (() if device_gzip else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
+        for suffix in (() if device_gzip or ubam else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
             compress_file(args.output + suffix)
     logger.info("Read generation complete")
 
@@ -412,7 +453,7 @@ def model_from_bam(args):
     return 0
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(prog="insilicoseq_amd", description="iss generate on MI355X")
     sub = p.add_subparsers(dest="cmd")
     g = sub.add_parser("generate")
@@ -452,6 +493,10 @@ def main(argv=None):
                         "one process per worker (same files, byte for byte)")
     g.add_argument("--depth_bin", type=int, default=None, metavar="N",
                    help="with --depth (implied): also <output>_depth.bedgraph, the mean depth of every N-base window of every record")
+    g.add_argument("--ubam", action="store_true",
+                   help="write <output>.bam instead of the two FASTQ files: unaligned BAM (flags 77 / 141, R1 then R2 of every pair, "
+                        "names without /1 and /2, lower-case bases as their capitals), records and BGZF blocks built on the GPU; "
+                        "--compress then applies to the .vcf only; not with the side-by-side workers of --rng mt --cpus W --devices 1")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")
@@ -462,6 +507,11 @@ def main(argv=None):
     m.add_argument("--seed", type=int, default=0, help="Philox key of the subsample (more than 1 000 000 mapped records)")
     m.add_argument("--device", type=int, default=0, help="GPU ordinal")
     m.add_argument("--dense", action="store_true", help="also write <prefix>.dense.npz (this project's pickle-free form)")
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     args = p.parse_args(argv)
     if args.cmd == "model":
         return model_from_bam(args)

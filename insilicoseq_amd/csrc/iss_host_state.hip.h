@@ -1,4 +1,4 @@
-// iss_host_state.hip.h -- host-side state of the engine: the FASTQ pipeline's job / pipe records, timed launches, and struct iss_ctx
+// iss_host_state.hip.h -- host-side state of the engine: the FASTQ, VCF and unaligned-BAM pipelines' job / pipe records, timed launches, and struct iss_ctx
 // (one per GPU: streams, uploaded model and genomes, output rows, MT-mode chains and worker sets).  Included by iss_mi355x.hip.
 #pragma once
 
@@ -172,6 +172,44 @@ struct VcfPipe {
     bool busy[2] = {false, false};
     bool stop = false;
     std::string error;
+};
+
+// Unaligned BAM (--ubam) on its way to ONE file: the records (k_ubam_format) and their BGZF members (iss_ubam.hip.h) are built on the
+// context's stream behind the generation; the members' total size comes back on a copy stream, the writer thread fetches exactly
+// those bytes and appends them.  Two slots, like the FASTQ pipeline's.
+struct UbamJob {
+    int slot;
+    int fd;
+    uint32_t n_blocks;
+};
+struct UbamPipe {
+    bool ready = false;
+    hipStream_t copy_stream = nullptr, data_stream = nullptr;
+    hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    uint8_t *d_text[2] = {nullptr, nullptr};   // the record bytes (never leave the device)
+    uint8_t *d_comp[2] = {nullptr, nullptr};   // the BGZF members, back to back
+    uint8_t *h_comp[2] = {nullptr, nullptr};   // pinned
+    size_t cap = 0, comp_cap = 0;
+    uint32_t blocks_cap = 0;
+    uint32_t *d_hist[2] = {nullptr, nullptr};
+    iss::DeflateCode *d_code[2] = {nullptr, nullptr};
+    uint32_t *d_bbytes[2] = {nullptr, nullptr}, *d_bcrc[2] = {nullptr, nullptr};
+    uint64_t *d_boff[2] = {nullptr, nullptr};
+    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value
+    iss::FastqItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
+    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
+    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    int next = 0;
+    int fd = -1;
+    int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
+    std::thread writer;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<UbamJob> jobs;
+    bool busy[2] = {false, false};
+    bool stop = false;
+    std::string error;
+    int error_code = 0;  // of `error`: ISS_E_IO, or ISS_E_INVALID for members that do not have the layout BGZF asks for
 };
 
 // MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's
@@ -371,6 +409,7 @@ struct iss_ctx {
     } mts;
     FastqPipe fq;
     VcfPipe vq;
+    UbamPipe uq;
     // timing
     bool timing = false, timing_main_only = false;
     std::vector<TimedLaunch> timed;

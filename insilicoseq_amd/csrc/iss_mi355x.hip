@@ -5,7 +5,8 @@
 // Device side: iss_kernels.hip.h (the Philox path), iss_perfect.hip.h (its perfect-model kernel), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
 // iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h;
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
-// iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads).
+// iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads),
+// iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -39,6 +40,7 @@
 #include "iss_truth.hip.h"      // k_truth_scatter, k_truth_events: the mutation rows as dense device arrays (behind those again)
 #include "iss_tally.hip.h"      // k_tally_lines, k_tally_reads: quality, base, GC and insert-size tallies of the rows (last, likewise)
 #include "iss_depth.hip.h"      // k_depth_*: per-base coverage depth of the reads (behind every other kernel, likewise)
+#include "iss_ubam.hip.h"       // k_ubam_format, k_bgzf_*: unaligned BAM records and their BGZF members (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
@@ -46,6 +48,7 @@
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
 #include "iss_host_fastq_pipe.hip.h"  // writer thread, flush
 #include "iss_host_vcf_pipe.hip.h"    // the VCF text's writer thread, flush
+#include "iss_host_ubam_pipe.hip.h"   // the BGZF members' writer thread, flush
 #include "iss_api_context.hip.h"
 #include "iss_api_model.hip.h"
 #include "iss_api_generate.hip.h"
@@ -56,3 +59,4 @@
 #include "iss_api_export.hip.h"
 #include "iss_api_tally.hip.h"
 #include "iss_api_depth.hip.h"
+#include "iss_api_ubam.hip.h"

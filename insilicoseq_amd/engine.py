@@ -434,6 +434,28 @@ class ReadEngine(object):
     def fastq_flush(self):
         self._check(self._lib.iss_fastq_flush(self._ctx))
 
+    def ubam_emit_batch(self, fd, items, cpu_number):
+        """The rows of the items of fastq_emit_batch -- (record id, first pair id, first output row, pairs) -- as unaligned BAM
+        records (R1 then R2 of every pair: flags 77 / 141, names "{id}_{i}_{cpu}", lower-case bases as their capitals) in BGZF
+        blocks built on the device, appended to ``fd`` (asynchronous; ``ubam_flush`` before the file is used).  Record blocks
+        only: the BAM header and the EOF block are the caller's (ubam.py).  Ids may be str or bytes."""
+        self._need_ubam_entries()
+        n = len(items)
+        ids = (C.c_char_p * n)(*[it[0] if isinstance(it[0], bytes) else str(it[0]).encode() for it in items])
+        first_i = np.array([it[1] for it in items], dtype=np.int64)
+        first_pair = np.array([it[2] for it in items], dtype=np.int64)
+        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
+        self._check(self._lib.iss_ubam_emit_batch(self._ctx, int(fd), n, ids, first_i.ctypes.data, first_pair.ctypes.data,
+                                                  n_pairs.ctypes.data, int(cpu_number)))
+
+    def ubam_flush(self):
+        self._need_ubam_entries()
+        self._check(self._lib.iss_ubam_flush(self._ctx))
+
+    def _need_ubam_entries(self):
+        if not hasattr(self._lib, "iss_ubam_emit_batch"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_ubam_emit_batch / iss_ubam_flush: rebuild it" % _native.LIB_PATH)
+
     def mt_path_counts(self):
         """(pairs resolved in parallel, pairs walked sequentially) by generate_mt so far."""
         a, b = C.c_int64(0), C.c_int64(0)

@@ -310,6 +310,7 @@ class Worker(object):
         self.device_fastq = os.environ.get("ISS_HOST_FASTQ", "") != "1"  # ISS_HOST_FASTQ=1: host formatter (iss_fastq_write)
         # the --store_mutations text is built on the device too (ReadEngine.vcf_emit); ISS_HOST_VCF=1: rows to the host, write_mutations
         self.device_vcf = self.device_fastq and os.environ.get("ISS_HOST_VCF", "") != "1"
+        self.ubam = False  # --ubam (worker_iterator): the rows leave as unaligned BAM records in BGZF blocks instead of FASTQ text
         self.compress = bool(compress)
         if self.compress:
             if not self.device_fastq:
@@ -459,7 +460,9 @@ class Worker(object):
             _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
             self.tally_rows(0, n)
             self.depth_rows(0, n, [record])
-            if self.device_fastq:
+            if self.ubam:  # (one stream: both handles are the .bam)
+                eng.ubam_emit_batch(forward_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number)
+            elif self.device_fastq:
                 # text built on the device, copied and written behind the next batch's generation
                 # (one pwrite stream per file: tmpfs gets slower with concurrent writers to one file)
                 eng.fastq_emit(forward_handle.fileno(), reverse_handle.fileno(), record.id, done, self.cpu_number, 0, n,
@@ -472,6 +475,8 @@ class Worker(object):
             self.ordinal += n
             done += n
         if self.device_fastq and flush:
+            if self.ubam:
+                eng.ubam_flush()
             eng.fastq_flush()  # the handles are the caller's again
             if route == "device":
                 eng.vcf_flush()
@@ -588,7 +593,10 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
             w.tally_rows(0, row)
         if getattr(w, "depth_diff", None) is not None and not marked:  # --depth, likewise: the batch call's items through its table
             w.depth_rows(0, row, pending_records)
-        eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
+        if getattr(w, "ubam", False):
+            eng.ubam_emit_batch(forward_handle.fileno(), emit, w.cpu_number)  # one job of record blocks
+        else:
+            eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
         w.ordinal += row
         if timings is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
             timings.setdefault("batches", []).append((time.perf_counter(), row))
@@ -647,7 +655,7 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
-                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None):
+                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
@@ -659,21 +667,30 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     words -- is written to ``{prefix}.tally.npy`` at the end; without it no engine call is added.  ``depth=True`` (`--depth`): the
     template intervals of every generate call are marked on the device (ReadEngine.depth_mark) into one difference array over the
     distinct records of ``work`` and written to ``{prefix}.depth.npz`` (diff, table, ``ordinals``: the FASTA ordinal of each work
-    item's record, default its position in ``work``) at the end; without it no engine call is added."""
+    item's record, default its position in ``work``) at the end; without it no engine call is added.  ``ubam=True`` (`--ubam`):
+    instead of the two FASTQ files the worker writes ``{prefix}.bam``, the BGZF record blocks of its reads (R1 then R2 of every
+    pair) built on the device (ReadEngine.ubam_emit_batch) -- no BAM header, no EOF block: the parent frames the workers' blocks
+    (ubam.assemble)."""
     logger = logging.getLogger(__name__)
+    if ubam and (compress or os.environ.get("ISS_HOST_FASTQ", "") == "1"):
+        raise ValueError("ubam=True needs the device path (unset ISS_HOST_FASTQ) and takes no compress=True: BGZF blocks are compressed")
     if timings is not None:
         timings["t_start"] = time.perf_counter()
     store_mutations = bool(getattr(error_model, "store_mutations", False))
     if sequence_type not in _native.SEQ_TYPES:
         raise RuntimeError("sequence type '%s' is not supported" % sequence_type)  # generator.py:139
     try:
-        forward_handle = open("%s_R1.fastq" % worker_prefix, "w")
-        reverse_handle = open("%s_R2.fastq" % worker_prefix, "w")
+        if ubam:
+            forward_handle = reverse_handle = open("%s.bam" % worker_prefix, "wb")  # (one stream for both mates)
+        else:
+            forward_handle = open("%s_R1.fastq" % worker_prefix, "w")
+            reverse_handle = open("%s_R2.fastq" % worker_prefix, "w")
         mutation_handle = open("%s.vcf" % worker_prefix, "w")
     except PermissionError as e:
         logger.error("Failed to write temporary output file(s): %s" % e)
         sys.exit(1)
     w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
+    w.ubam = bool(ubam)
     w.plan(record for record, _n, _mode in work)
     if report:
         w.enable_tally()
@@ -700,6 +717,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                 for record, n_pairs, _mode in work:
                     w.simulate_reads(record, n_pairs, forward_handle, reverse_handle, mutation_handle, sequence_type,
                                      gc_bias, flush=False)  # keep the text pipeline running across work items
+            if ubam:
+                w.engine.ubam_flush()
             w.engine.fastq_flush()
             if store_mutations and w.device_vcf:
                 w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
