@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive) iss_ubam_emit_batch / iss_ubam_flush / iss_ubam_host_records: the rows as unaligned BAM, records and BGZF
+/* 8: (additive) iss_origins_emit_batch / iss_origins_flush / iss_origins_host_text: every pair's source intervals as BEDPE text built
+ *    on the device.
+ *    (additive) iss_ubam_emit_batch / iss_ubam_flush / iss_ubam_host_records: the rows as unaligned BAM, records and BGZF
  *    blocks built on the device.
  *    (additive) iss_mt_workers_mutations_reserve / iss_mt_workers_mutations_download / iss_vcf_emit_workers: --store_mutations for
  *    the W workers of a set (rows per worker, placed on the device; one text job per call).
@@ -562,6 +564,34 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
 int iss_ubam_flush(iss_ctx *ctx);
 int iss_ubam_host_records(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,
                           int32_t pitch, const uint8_t *r1_base, const uint8_t *r1_qual, const uint8_t *r2_base, const uint8_t *r2_qual);
+
+/*
+ * Origins built ON THE DEVICE (additive in ABI 8): where every pair came from, as BEDPE text, one line per
+ * pair, tab separated, no header:
+ *     {id} s1 e1 {id} s2 e2 {id}_{i}_{cpu_number} . + - isz \n
+ * With (fs, rs, re, isz) what iss_output_download_coords returns for the row, RL the read length and len = record_len[k]:
+ * [s1, e1) = [fs, fs + RL) is the template interval read 1 was cut from (iss/generator.py:135-147), [s2, e2) = [rs, re) that of
+ * read 2 (generator.py:165-177), each clamped like the depth's intervals: s' = min(max(s, 0), len), e' = max(min(max(e, 0), len), s')
+ * -- an interval that is empty after the clamp reads "s' s'"; the clamp bites only with custom fragment lengths.  Read 1 is always
+ * '+' and read 2 always '-' (generator.py:149, 180), the score is '.', the name is the FASTQ read name without /1, /2 and isz the
+ * insert size as drawn, signed.  Plain decimals, no padding.  Nothing is read from the mutation rows.
+ *
+ * The item table is iss_fastq_emit_batch's plus the record lengths; items stand in ascending row order and do not overlap.
+ * Asynchronous like iss_ubam_emit_batch -- line lengths, a scan and the format kernel on the context's stream behind the
+ * generation (rows may be generated anew right behind the call), the text's size on a copy stream, the bytes fetched and appended
+ * (pwrite) at fd's current position by a writer thread, two slots; iss_origins_flush waits until every queued byte is in the file
+ * and leaves the descriptor at its end.  ISS_E_INVALID with nothing launched or written: rows outside the reserved range, a
+ * record_len below 1, items out of order or overlapping.  No pairs at all: nothing is appended.  ISS_ORIGINS_TILE (read per call):
+ * pairs per workgroup of the format kernel; the text does not depend on it.
+ *
+ * iss_origins_host_text (host only, no GPU; single-threaded): the same lines for one item from coords[n_pairs][4] as
+ * iss_output_download_coords returns them, appended to fd.
+ */
+int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const *record_ids, const int64_t *first_i,
+                           const int64_t *first_pair, const int64_t *n_pairs, const int64_t *record_len, int32_t cpu_number);
+int iss_origins_flush(iss_ctx *ctx);
+int iss_origins_host_text(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,
+                          int64_t record_len, const int64_t *coords);
 
 /*
  * `model`: the reference's `iss model` (iss/app.py:147-169 -> iss/bam.py:103-227, iss/modeller.py) from a BAM file.  Additive to

@@ -25,6 +25,7 @@ from . import drafts
 from .distributed import VCF_HEADER, concatenate_rank_files, temp_prefix
 from .generator import WorkerSetNotSetUp, generate_work_divider, parse_fasta, worker_iterator, worker_set_iterator
 from .model import BasicErrorModel, KDErrorModel, PerfectErrorModel
+from .origins import SUFFIX as ORIGINS_SUFFIX
 
 PROFILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
 # names of iss/generator.py:377-387 -> dense files converted from the reference's profiles
@@ -184,11 +185,12 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False):
+            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
-    (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files."""
+    (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files; ``origins``: it also
+    writes ``<prefix>_origins.bedpe``, every pair's source intervals."""
     logging.basicConfig(level=logging.WARNING)
     if report or depth:
         from .tensors import _torch
@@ -208,6 +210,8 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
     more = {"depth": True, "ordinals": [idx for idx, _n in work_spec]} if depth else {}  # (without the flag: the call as it was)
     if ubam:
         more["ubam"] = True
+    if origins:
+        more["origins"] = True
     worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report, **more)
 
 
@@ -332,7 +336,8 @@ def load_readcount_or_abundance(args, records, error_model):
 def _worker_set_wanted(args, report, depth):
     """Do the workers of this command run side by side in one context (worker_set_iterator) rather than one process each?"""
     return args.gpus > 1 and args.rng == "mt" and args.devices == 1 and args.seed is not None and args.gpus <= 1024 \
-        and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth  # (--report, --depth: the set has no tally or depth of its own -- the pool)
+        and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth \
+        and not getattr(args, "origins", False)  # (--report, --depth, --origins: the set has no tally, depth or origins writer of its own -- the pool)
 
 
 def _remove_ubam_files(output, workers):
@@ -351,6 +356,9 @@ def generate_reads(args):
         sys.exit(1)
     if ubam and os.environ.get("ISS_HOST_FASTQ", "") == "1":
         logger.error("--ubam builds its records on the device: unset ISS_HOST_FASTQ")
+        sys.exit(1)
+    if getattr(args, "origins", False) and os.environ.get("ISS_HOST_FASTQ", "") == "1":
+        logger.error("--origins builds its text on the device: unset ISS_HOST_FASTQ")
         sys.exit(1)
     try:
         _generate_reads(args, ubam)
@@ -372,6 +380,7 @@ def _generate_reads(args, ubam):
     readcount_dic, abundance_dic, n_reads = load_readcount_or_abundance(args, records, error_model)
     workers = args.gpus
     report = bool(getattr(args, "report", False))
+    origins = bool(getattr(args, "origins", False))
     depth_bin = int(getattr(args, "depth_bin", None) or 0)
     if depth_bin < 0:
         logger.error("--depth_bin must be positive")
@@ -396,14 +405,14 @@ def _generate_reads(args, ubam):
     in_place = None
     if workers == 1:
         for j in jobs:
-            _worker(*j, records=records, ubam=ubam)
+            _worker(*j, records=records, ubam=ubam, origins=origins)
     elif _worker_set_wanted(args, report, depth):
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            pool.starmap(_worker, [j + (None, True) for j in jobs] if ubam else jobs)
+            pool.starmap(_worker, [j + (None, ubam, origins) for j in jobs] if ubam or origins else jobs)
     t_cat = time.perf_counter()
     if ubam:  # header, the workers' record blocks in worker order, the EOF block; a worker without a chunk is an error as below
         from .ubam import assemble
@@ -421,6 +430,8 @@ def _generate_reads(args, ubam):
                                headers={".vcf": VCF_HEADER}, out_suffixes=gz)
     else:
         concatenate_rank_files(args.output, workers, out_suffixes=gz)  # raises if a worker had no chunk (util.py:233)
+    if origins:  # the workers' lines in worker order, like their FASTQ files
+        concatenate_rank_files(args.output, workers, suffixes=(ORIGINS_SUFFIX,))
     logger.info("Workers %.2f s, concatenation of their files %.2f s" % (t_cat - t_gen, time.perf_counter() - t_cat))
     if report:
         _write_report(args.output, len(jobs), error_model.read_length)
@@ -430,6 +441,8 @@ def _generate_reads(args, ubam):
     if args.compress:  # util.compress (iss/util.py:255-268): <file>.gz next to the file, original removed
         for suffix in (() if device_gzip or ubam else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
             compress_file(args.output + suffix)
+        if origins:
+            compress_file(args.output + ORIGINS_SUFFIX)
     logger.info("Read generation complete")
 
 
@@ -497,6 +510,11 @@ def build_parser():
                    help="write <output>.bam instead of the two FASTQ files: unaligned BAM (flags 77 / 141, R1 then R2 of every pair, "
                         "names without /1 and /2, lower-case bases as their capitals), records and BGZF blocks built on the GPU; "
                         "--compress then applies to the .vcf only; not with the side-by-side workers of --rng mt --cpus W --devices 1")
+    g.add_argument("--origins", action="store_true",
+                   help="also write <output>_origins.bedpe: one BEDPE line per pair, in FASTQ order, with the record and the two nominal "
+                        "template intervals its reads were cut from (read 1 '+', read 2 '-', the name without /1 and /2, the insert "
+                        "size as the eleventh column), text built on the GPU; --compress gzips it; like --report it makes --rng mt "
+                        "--devices 1 run one process per worker (same FASTQ and VCF files, byte for byte)")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

@@ -88,6 +88,7 @@ void iss_ctx_destroy(iss_ctx *ctx) {
     fastq_shutdown(ctx);
     vcf_shutdown(ctx);
     ubam_shutdown(ctx);
+    origins_shutdown(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->indel_stream) (void)hipStreamSynchronize(ctx->indel_stream);
     if (ctx->fill_stream) (void)hipStreamSynchronize(ctx->fill_stream);

@@ -1,4 +1,4 @@
-// iss_host_state.hip.h -- host-side state of the engine: the FASTQ, VCF and unaligned-BAM pipelines' job / pipe records, timed launches, and struct iss_ctx
+// iss_host_state.hip.h -- host-side state of the engine: the FASTQ, VCF, unaligned-BAM and origins pipelines' job / pipe records, timed launches, and struct iss_ctx
 // (one per GPU: streams, uploaded model and genomes, output rows, MT-mode chains and worker sets).  Included by iss_mi355x.hip.
 #pragma once
 
@@ -212,6 +212,41 @@ struct UbamPipe {
     int error_code = 0;  // of `error`: ISS_E_IO, or ISS_E_INVALID for members that do not have the layout BGZF asks for
 };
 
+// The origins text (--origins, iss_origins.hip.h) on its way to ONE file: lengths, scan and format run on the context's stream behind
+// the generation; the text's size comes back on a copy stream, the writer thread fetches exactly those bytes and appends them.  Two
+// slots of (device text, pinned host text, item table, total); the work arrays (len, off, tile sums) are one set: only kernels of
+// the context's stream touch them, in order.
+struct OriginsJob {
+    int slot;
+    int fd;
+};
+struct OriginsPipe {
+    bool ready = false;
+    hipStream_t copy_stream = nullptr, data_stream = nullptr;
+    hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    uint8_t *d_text[2] = {nullptr, nullptr};
+    uint8_t *h_text[2] = {nullptr, nullptr};    // pinned
+    size_t cap = 0;                             // bytes of each of the four
+    uint64_t *d_total[2] = {nullptr, nullptr};  // bytes of the slot's text (the scan's grand total)
+    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value
+    iss::OriginsItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
+    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
+    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    uint32_t *d_len = nullptr;                  // [pairs_cap]
+    uint64_t *d_off = nullptr, *d_tiles = nullptr;  // [pairs_cap], [tiles_cap]
+    size_t pairs_cap = 0, tiles_cap = 0;
+    int next = 0;
+    int fd = -1;
+    int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
+    std::thread writer;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<OriginsJob> jobs;
+    bool busy[2] = {false, false};
+    bool stop = false;
+    std::string error;
+};
+
 // MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's
 // own worker (iss_mt_seed / iss_generate_mt) owns its allocations; a worker of a set (iss_mt_workers_seed) holds slices of the
 // set's.  Only the owner allocates or frees them: the single-worker path (mt_chain_generate) works on whichever chain it is given.
@@ -410,6 +445,7 @@ struct iss_ctx {
     FastqPipe fq;
     VcfPipe vq;
     UbamPipe uq;
+    OriginsPipe oq;
     // timing
     bool timing = false, timing_main_only = false;
     std::vector<TimedLaunch> timed;

@@ -6,7 +6,7 @@
 // iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h;
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
 // iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads),
-// iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members).
+// iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -41,6 +41,7 @@
 #include "iss_tally.hip.h"      // k_tally_lines, k_tally_reads: quality, base, GC and insert-size tallies of the rows (last, likewise)
 #include "iss_depth.hip.h"      // k_depth_*: per-base coverage depth of the reads (behind every other kernel, likewise)
 #include "iss_ubam.hip.h"       // k_ubam_format, k_bgzf_*: unaligned BAM records and their BGZF members (last, likewise)
+#include "iss_origins.hip.h"    // k_origins_len, k_origins_format: the pairs' source intervals as BEDPE text (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
@@ -49,6 +50,7 @@
 #include "iss_host_fastq_pipe.hip.h"  // writer thread, flush
 #include "iss_host_vcf_pipe.hip.h"    // the VCF text's writer thread, flush
 #include "iss_host_ubam_pipe.hip.h"   // the BGZF members' writer thread, flush
+#include "iss_host_origins_pipe.hip.h"  // the origins text's writer thread, flush
 #include "iss_api_context.hip.h"
 #include "iss_api_model.hip.h"
 #include "iss_api_generate.hip.h"
@@ -60,3 +62,4 @@
 #include "iss_api_tally.hip.h"
 #include "iss_api_depth.hip.h"
 #include "iss_api_ubam.hip.h"
+#include "iss_api_origins.hip.h"

@@ -456,6 +456,31 @@ class ReadEngine(object):
         if not hasattr(self._lib, "iss_ubam_emit_batch"):  # (no fall-back, like _need_vcf_entries)
             raise _native.NativeLibraryError("%s does not export iss_ubam_emit_batch / iss_ubam_flush: rebuild it" % _native.LIB_PATH)
 
+    def origins_emit_batch(self, fd, items, record_lengths, cpu_number):
+        """Where the pairs of the items of fastq_emit_batch -- (record id, first pair id, first output row, pairs), in ascending
+        row order -- came from, as BEDPE text built on the device and appended to ``fd`` (asynchronous; ``origins_flush`` before
+        the file is used): one line "{id} s1 e1 {id} s2 e2 {id}_{i}_{cpu} . + - isz" per pair, the two template intervals clamped
+        against ``record_lengths[k]``, the length of item k's record (origins.py).  Ids may be str or bytes."""
+        self._need_origins_entries()
+        n = len(items)
+        if len(record_lengths) != n:
+            raise ValueError("one record length per item")
+        ids = (C.c_char_p * n)(*[it[0] if isinstance(it[0], bytes) else str(it[0]).encode() for it in items])
+        first_i = np.array([it[1] for it in items], dtype=np.int64)
+        first_pair = np.array([it[2] for it in items], dtype=np.int64)
+        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
+        lengths = np.array([int(x) for x in record_lengths], dtype=np.int64)
+        self._check(self._lib.iss_origins_emit_batch(self._ctx, int(fd), n, ids, first_i.ctypes.data, first_pair.ctypes.data,
+                                                     n_pairs.ctypes.data, lengths.ctypes.data, int(cpu_number)))
+
+    def origins_flush(self):
+        self._need_origins_entries()
+        self._check(self._lib.iss_origins_flush(self._ctx))
+
+    def _need_origins_entries(self):
+        if not hasattr(self._lib, "iss_origins_emit_batch"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_origins_emit_batch / iss_origins_flush: rebuild it" % _native.LIB_PATH)
+
     def mt_path_counts(self):
         """(pairs resolved in parallel, pairs walked sequentially) by generate_mt so far."""
         a, b = C.c_int64(0), C.c_int64(0)

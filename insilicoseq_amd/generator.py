@@ -17,6 +17,7 @@ One worker == one GPU (``cpu_number`` == rank).  The uniforms come from Philox a
 (seed, cpu_number, work list) -- independent of launch geometry.  It is bit-identical to the
 CPU oracle in Philox mode, which in MT mode is bit-identical to the reference.
 """
+import contextlib
 import logging
 import os
 import sys
@@ -311,6 +312,7 @@ class Worker(object):
         # the --store_mutations text is built on the device too (ReadEngine.vcf_emit); ISS_HOST_VCF=1: rows to the host, write_mutations
         self.device_vcf = self.device_fastq and os.environ.get("ISS_HOST_VCF", "") != "1"
         self.ubam = False  # --ubam (worker_iterator): the rows leave as unaligned BAM records in BGZF blocks instead of FASTQ text
+        self.origins_handle = None  # --origins (worker_iterator): the file every call's source intervals are appended to (origins.py)
         self.compress = bool(compress)
         if self.compress:
             if not self.device_fastq:
@@ -408,6 +410,12 @@ class Worker(object):
         self._depth_tables.append(dev_table)
         self.engine.depth_mark(first_pair, n_pairs, dev_table.data_ptr(), len(records), self.depth_diff.data_ptr())
 
+    def origins_rows(self, items, records):
+        """--origins: the source intervals of ``items`` -- the tuples of the text job, ``records`` their records -- appended to the
+        worker's BEDPE file as text built on the device; where the text job is handed over (the rows are final).  Asynchronous."""
+        if self.origins_handle is not None:
+            self.engine.origins_emit_batch(self.origins_handle.fileno(), items, [len(r.seq) for r in records], self.cpu_number)
+
     def depth_save(self, path):
         """The worker's accumulator for the parent's merge: diff, table and the records' FASTA ordinals (waits for the engine)."""
         self.engine.synchronize()
@@ -460,6 +468,7 @@ class Worker(object):
             _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
             self.tally_rows(0, n)
             self.depth_rows(0, n, [record])
+            self.origins_rows([(record.id, done, 0, n)], [record])
             if self.ubam:  # (one stream: both handles are the .bam)
                 eng.ubam_emit_batch(forward_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number)
             elif self.device_fastq:
@@ -477,6 +486,8 @@ class Worker(object):
         if self.device_fastq and flush:
             if self.ubam:
                 eng.ubam_flush()
+            if self.origins_handle is not None:
+                eng.origins_flush()
             eng.fastq_flush()  # the handles are the caller's again
             if route == "device":
                 eng.vcf_flush()
@@ -562,7 +573,7 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         nonlocal pending, cur, pending_records
         if not pending:
             return
-        marked = False
+        marked = origins_done = False
         row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
         for rid, _gid, n, first_i in pending:
             emit.append((rid, first_i, row, n))
@@ -588,11 +599,16 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                 if getattr(w, "depth_diff", None) is not None:  # --depth: the item is a call of its own (item 0 of its rows)
                     w.depth_rows(item[2], n, [record])
                     marked = True
+                if getattr(w, "origins_handle", None) is not None:  # --origins, likewise: the next call moves on to the other set of descriptors
+                    w.origins_rows([item], [record])
+                    origins_done = True
                 ordinal += n
         if getattr(w, "tally", None) is not None:  # --report (every call of the batch has settled: a repeated one is not counted twice)
             w.tally_rows(0, row)
         if getattr(w, "depth_diff", None) is not None and not marked:  # --depth, likewise: the batch call's items through its table
             w.depth_rows(0, row, pending_records)
+        if getattr(w, "origins_handle", None) is not None and not origins_done:  # --origins: one text job beside the reads'
+            w.origins_rows(emit, pending_records)
         if getattr(w, "ubam", False):
             eng.ubam_emit_batch(forward_handle.fileno(), emit, w.cpu_number)  # one job of record blocks
         else:
@@ -655,7 +671,7 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
-                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False):
+                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False, origins=False):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
@@ -670,8 +686,12 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     item's record, default its position in ``work``) at the end; without it no engine call is added.  ``ubam=True`` (`--ubam`):
     instead of the two FASTQ files the worker writes ``{prefix}.bam``, the BGZF record blocks of its reads (R1 then R2 of every
     pair) built on the device (ReadEngine.ubam_emit_batch) -- no BAM header, no EOF block: the parent frames the workers' blocks
-    (ubam.assemble)."""
+    (ubam.assemble).  ``origins=True`` (`--origins`): the worker also writes ``{prefix}_origins.bedpe``, one line per pair with the
+    record and the two template intervals its reads were cut from (origins.py), built on the device
+    (ReadEngine.origins_emit_batch) where the text job is handed over; without it no engine call is added."""
     logger = logging.getLogger(__name__)
+    if origins and os.environ.get("ISS_HOST_FASTQ", "") == "1":
+        raise ValueError("origins=True needs the device path (unset ISS_HOST_FASTQ)")
     if ubam and (compress or os.environ.get("ISS_HOST_FASTQ", "") == "1"):
         raise ValueError("ubam=True needs the device path (unset ISS_HOST_FASTQ) and takes no compress=True: BGZF blocks are compressed")
     if timings is not None:
@@ -686,11 +706,14 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
             forward_handle = open("%s_R1.fastq" % worker_prefix, "w")
             reverse_handle = open("%s_R2.fastq" % worker_prefix, "w")
         mutation_handle = open("%s.vcf" % worker_prefix, "w")
+        origins_handle = open("%s_origins.bedpe" % worker_prefix, "wb") if origins else contextlib.nullcontext()
     except PermissionError as e:
         logger.error("Failed to write temporary output file(s): %s" % e)
         sys.exit(1)
     w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
     w.ubam = bool(ubam)
+    if origins:
+        w.origins_handle = origins_handle
     w.plan(record for record, _n, _mode in work)
     if report:
         w.enable_tally()
@@ -708,7 +731,7 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
         else:
             w.engine.mutations_reserve(int(Worker.BATCH_PAIRS * per_pair) + (1 << 21))
     try:
-        with forward_handle, reverse_handle, mutation_handle:
+        with forward_handle, reverse_handle, mutation_handle, origins_handle:
             if store_mutations and w.device_vcf:
                 mutation_handle.flush()  # the device's text goes to the descriptor, behind what the handle holds (nothing)
             if rng == "philox" and w.device_fastq and os.environ.get("ISS_ITEMWISE", "") != "1":
@@ -719,6 +742,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                                      gc_bias, flush=False)  # keep the text pipeline running across work items
             if ubam:
                 w.engine.ubam_flush()
+            if origins:
+                w.engine.origins_flush()  # (before the handle closes: the text is appended to its descriptor)
             w.engine.fastq_flush()
             if store_mutations and w.device_vcf:
                 w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
