@@ -1,6 +1,8 @@
 """Shared helpers for the parity tests."""
+import collections
 import json
 import os
+import re
 
 import numpy as np
 
@@ -174,6 +176,69 @@ def export_tile_alignments(RL, n_pairs, shift):
     """Addresses mod 16 at which the tiles of one export of n_pairs pairs start in an output array that begins at ``shift``."""
     tile = export_tile_pairs(RL)
     return [(shift + t0 * 2 * RL) % 16 for t0 in range(0, n_pairs, tile)]
+
+
+# ------------------------------------------------------------------ the position-tile geometries of k_main / k_main_g
+# What the two kernels execute is fixed at model upload by the position tiling (iss_api_model.hip.h, fits()): TS superitems (of 8
+# positions) per tile, n_tiles, ni = ceil(TS / 4) iterations per pass, how short the last tile is -- and from ni the width of the
+# iteration field of a deferred entry's tag (it_bits), the script rows per tile and read (sc_gpt = ceil(ni / 8)) and the
+# k_main_g<NI, NP> instantiation.  The shipped profiles reach ni 1, 2, 4 and 5 only; these rows reach the rest.  Guide bits are
+# pinned to 6 (TILE_GEOMETRY_ENV), so the width of a table row -- and with it the tiling -- follows from n_q alone.
+# test_tile_geometry_host.py derives (n_tiles, TS, last, ni) of every row from its (RL, n_q, slots, ISS_TILES); the GPU sweep
+# asserts what the library reports (model_geometry) against the row before it compares a single read.
+TileGeometry = collections.namedtuple("TileGeometry", "id RL n_q nonempty tiles n_tiles TS last ni what")
+SLOTS_DEFAULT = ((1, 1, 1, 1), (1, 0, 1, 1))  # synthetic_model's own: 4 / 3 mean-quality bins with histograms
+SLOTS_TWO = ((1, 0, 1, 0), (0, 1, 0, 1))
+SLOTS_ONE = ((1, 0, 0, 0), (0, 0, 1, 0))
+TILE_GEOMETRIES = (
+    TileGeometry("A", 65, 9, SLOTS_DEFAULT, 0, 1, 9, 9, 3, "k_main_g<3, 1>; third iteration: one lane of work, one valid position in the last superitem"),
+    TileGeometry("B", 96, 9, SLOTS_DEFAULT, 0, 1, 12, 12, 3, "ni == 3 exact, row without padding"),
+    TileGeometry("C", 151, 9, SLOTS_DEFAULT, 2, 2, 12, 7, 3, "NI == 3 with a last tile of two iterations"),
+    TileGeometry("D", 185, 9, SLOTS_DEFAULT, 2, 2, 12, 12, 3, "two full tiles, RL % 8 == 1"),
+    TileGeometry("E", 33, 9, SLOTS_DEFAULT, 2, 2, 4, 1, 1, "last tile: one superitem with one position; k_main_g<1, 2>"),
+    TileGeometry("F", 301, 4, SLOTS_TWO, 0, 1, 38, 38, 10, "sc_gpt == 2, it_bits == 4"),
+    TileGeometry("G", 260, 4, SLOTS_TWO, 0, 1, 33, 33, 9, "ninth iteration: lane 0 only; group 1 of the script rows holds one iteration"),
+    TileGeometry("H", 384, 3, SLOTS_ONE, 0, 1, 48, 48, 12, "pitch == AP_MAX_PITCH, the last scripted length"),
+    TileGeometry("I", 392, 3, SLOTS_ONE, 0, 1, 49, 49, 13, "first pitch above it: all listed reads to k_indel_fixup, idle scripts of two groups"),
+    TileGeometry("J", 520, 2, SLOTS_ONE, 0, 1, 65, 65, 17, "it_bits == 5, sc_gpt == 3"),
+    TileGeometry("K", 640, 3, SLOTS_ONE, 0, 1, 80, 80, 20, "largest one-tile model: about 153 KB of the 158 KB LDS budget"),
+)
+TILE_GEOMETRY_ENV = {"ISS_GUIDE_BITS": "6", "ISS_DEBUG_MODEL": "1"}
+# the grouped route of the sweep: geometry -> (ISS_MAIN_GROUP, the kernel that must have run).  F has no instantiation (ni == 10):
+# the host keeps k_main.  test_tile_geometry_host.py holds ISS_MAIN_G_LIST to these and test_gpu_grouped.FORCED.
+TILE_GROUPED = {"A": (1, "k_main_g<3, 1>"), "B": (1, "k_main_g<3, 1>"), "C": (1, "k_main_g<3, 1>"), "D": (1, "k_main_g<3, 1>"),
+                "E": (2, "k_main_g<1, 2>"), "F": (1, "k_main<false, true, false>")}
+TILE_INDEL = (1e-3, 2e-3)
+ModelGeometry = collections.namedtuple("ModelGeometry", "RL NB GB TG TS n_tiles ni")
+
+
+def tile_geometry(gid):
+    return next(g for g in TILE_GEOMETRIES if g.id == gid)
+
+
+def tile_geometry_model(geo, indel=False):
+    """The dense model of a row of TILE_GEOMETRIES: random tables, without indels or with TILE_INDEL's rates."""
+    return synthetic_model(geo.RL, geo.n_q, 7, seed=7000 + geo.RL, indel=TILE_INDEL if indel else (0.0, 0.0), nonempty=geo.nonempty)
+
+
+def tile_geometry_genome_length(geo):
+    return max(8 * geo.RL + 7, 64) + 1000
+
+
+def model_geometry(stderr_text):
+    """The layout iss_model_upload reports under ISS_DEBUG_MODEL=1 -- its line
+    `[model] RL .. G .. NB .. GB .. stride_w .. GS .. TG .. n_tiles ..` (the last one of the text) -- as (RL, NB, GB, TG,
+    TS = TG / 2, n_tiles, ni = ceil(TS / 4))."""
+    found = re.findall(r"\[model\] RL (\d+) G \d+ NB (\d+) GB (\d+) stride_w \d+ GS \d+ TG (\d+) n_tiles (\d+)", stderr_text)
+    assert found, "no [model] layout line in: %r" % stderr_text[-400:]
+    RL, NB, GB, TG, n_tiles = (int(x) for x in found[-1])
+    assert TG % 2 == 0
+    return ModelGeometry(RL, NB, GB, TG, TG // 2, n_tiles, (TG // 2 + 3) // 4)
+
+
+def tag_iteration_bits(ni):
+    """Bits of the iteration field of a deferred entry's tag (k_main: it_bits), of the 13 that hold (pass, iteration)."""
+    return (ni - 1).bit_length()
 
 
 GUARD = 64

@@ -402,10 +402,14 @@ def test_device_genome_packing_roundtrip(engine):
 
 @pytest.mark.parametrize("indel", [None, (0.001, 0.003)])
 def test_chunked_launches_compose(engine, indel):
-    """One call larger than the library's per-launch chunk (row byte offsets are 32 bits wide) == two smaller calls with
-    consecutive ordinals; spot-checked around the chunk boundary and at both ends.  (The indel-heavy variant: event
-    lists, read lists and their counters are per chunk.)"""
-    dense = dense_model("hiseq", indel)  # rows of 512 bytes -> chunk = (2^32 - 1) / 512 = 8,388,607 pairs
+    """One large call == two smaller calls with consecutive ordinals; spot-checked at both ends and around row 8,388,607, where
+    a launch had to end while row byte offsets were 32 bits wide ((2^32 - 1) / 512-byte rows).  Since round 5 they are 64 bits
+    wide: generate_core cuts a call at MAIN_CHUNK_PAIRS (12,582,912 pairs; ISS_CHUNK_PAIRS overrides) or, sooner, at the pass
+    limit of the deferred entries' tag, max_passes * 256 * (workgroups of the smallest tile) pairs -- neither is reached here, so
+    the call is one launch whose rows cross 2^32 bytes, and the two calls meet in the middle of it.  Calls of many chunks:
+    test_calls_of_many_chunks_reuse_the_counter_rings; the pass limit: test_gpu_tile_geometry.py.  (The indel-heavy variant:
+    event lists, read lists and their counters are per chunk.)"""
+    dense = dense_model("hiseq", indel)  # rows of 512 bytes: row 8,388,607 ends at byte 2^32 - 512
     chunk = ((1 << 32) - 1) // 512
     n = chunk + 300_000
     genome = random_genome(123, 2_000_000)
