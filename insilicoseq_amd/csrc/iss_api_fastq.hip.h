@@ -119,37 +119,10 @@ static int fastq_emit_core(iss_ctx *ctx, int fd_r1, int fd_r2, int32_t n_items, 
             }
     }
     const int slot = q.next;
-    {
-        std::unique_lock<std::mutex> lk(q.mu);
-        q.cv.wait(lk, [&] { return !q.busy[slot]; });
-        if (!q.error.empty()) { const std::string e = q.error; q.error.clear(); return fail(ctx, ISS_E_IO, e); }
-    }
-    if (items.size() > q.items_cap[slot] || ids.size() + 1 > q.ids_cap[slot]) {  // (the slot is free: nothing reads its tables)
-        if (q.h_items[slot]) (void)hipHostFree(q.h_items[slot]);
-        if (q.d_items[slot]) (void)hipFree(q.d_items[slot]);
-        if (q.h_ids[slot]) (void)hipHostFree(q.h_ids[slot]);
-        if (q.d_ids[slot]) (void)hipFree(q.d_ids[slot]);
-        q.h_items[slot] = q.d_items[slot] = nullptr;
-        q.h_ids[slot] = q.d_ids[slot] = nullptr;
-        const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
-        void *v = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(iss::FastqItem), hipHostMallocDefault));
-        q.h_items[slot] = static_cast<iss::FastqItem *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(iss::FastqItem)));
-        q.d_items[slot] = static_cast<iss::FastqItem *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault));
-        q.h_ids[slot] = static_cast<char *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, dc));
-        q.d_ids[slot] = static_cast<char *>(v);
-        q.items_cap[slot] = ic;
-        q.ids_cap[slot] = dc;
-    }
-    memcpy(q.h_items[slot], items.data(), items.size() * sizeof(iss::FastqItem));
-    memcpy(q.h_ids[slot], ids.data(), ids.size());
-    HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::FastqItem), hipMemcpyHostToDevice, ctx->stream));
-    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, ctx->stream));
-    A.items = q.d_items[slot];
-    A.ids = q.d_ids[slot];
+    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
+    { int rc_ = q.tab.stage(ctx, slot, items, ids, ctx->stream); if (rc_) return rc_; }
+    A.items = q.tab.d_items[slot];
+    A.ids = q.tab.d_ids[slot];
     for (int m = 0; m < 2; ++m) {
         A.base[m] = ctx->out[2 * m];
         A.qual[m] = ctx->out[2 * m + 1];

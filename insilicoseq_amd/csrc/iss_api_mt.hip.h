@@ -1031,7 +1031,7 @@ int iss_mt_workers_mutations_reserve(iss_ctx *ctx, int64_t rows_per_worker) {
     if (!ctx || rows_per_worker < 0 || rows_per_worker > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_mutations_reserve: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }  // (a queued text's kernels read the pool)
+    { int rc_ = append_flush(ctx, ctx->vq); if (rc_) return rc_; }  // (a queued text's kernels read the pool)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     free_mt_set_rows(ctx);
     ctx->mts.mut_rows = rows_per_worker;

@@ -57,30 +57,12 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     OriginsPipe &q = ctx->oq;
     if (!q.ready) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.copy_stream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
-        for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : q.ev_copy) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (int sl = 0; sl < 2; ++sl) {
-            void *v = nullptr;
-            HIP_TRY(ctx, hipMalloc(&v, 64));
-            q.d_total[sl] = static_cast<uint64_t *>(v);
-            HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault));
-            q.h_total[sl] = static_cast<uint64_t *>(v);
-        }
-        q.stop = false;
-        q.writer = std::thread(origins_writer_loop, ctx);
-        q.ready = true;
+        for (auto &p : q.d_total) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 64)); p = static_cast<uint64_t *>(v); }
+        { int rc_ = append_start(ctx, q, true, origins_write, "origins text"); if (rc_) return rc_; }
     }
-    if (q.fd != fd) {
-        { int rc_ = origins_flush(ctx); if (rc_) return rc_; }
-        const off_t at = lseek(fd, 0, SEEK_CUR);
-        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
-        q.fd = fd;
-        q.off = at;
-    }
+    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
     if (bytes > q.cap) {
-        { int rc_ = origins_flush(ctx, true); if (rc_) return rc_; }
+        { int rc_ = append_flush(ctx, q, true); if (rc_) return rc_; }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the kernels of the last call write the buffers)
         origins_free_text(ctx);
         const size_t cap = bytes + bytes / 8 + (1u << 16);
@@ -104,44 +86,16 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
         q.tiles_cap = tc;
     }
     const int slot = q.next;
-    {
-        std::unique_lock<std::mutex> lk(q.mu);
-        q.cv.wait(lk, [&] { return !q.busy[slot]; });
-        if (!q.error.empty()) { const std::string e = q.error; q.error.clear(); return fail(ctx, ISS_E_IO, e); }
-    }
-    if (items.size() > q.items_cap[slot] || ids.size() + 1 > q.ids_cap[slot]) {  // (the slot is free: nothing reads its tables)
-        if (q.h_items[slot]) (void)hipHostFree(q.h_items[slot]);
-        if (q.d_items[slot]) (void)hipFree(q.d_items[slot]);
-        if (q.h_ids[slot]) (void)hipHostFree(q.h_ids[slot]);
-        if (q.d_ids[slot]) (void)hipFree(q.d_ids[slot]);
-        q.h_items[slot] = q.d_items[slot] = nullptr;
-        q.h_ids[slot] = q.d_ids[slot] = nullptr;
-        q.items_cap[slot] = q.ids_cap[slot] = 0;
-        const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
-        void *v = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(iss::OriginsItem), hipHostMallocDefault));
-        q.h_items[slot] = static_cast<iss::OriginsItem *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(iss::OriginsItem)));
-        q.d_items[slot] = static_cast<iss::OriginsItem *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault));
-        q.h_ids[slot] = static_cast<char *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, dc));
-        q.d_ids[slot] = static_cast<char *>(v);
-        q.items_cap[slot] = ic;
-        q.ids_cap[slot] = dc;
-    }
+    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
     hipStream_t st = ctx->stream;
-    memcpy(q.h_items[slot], items.data(), items.size() * sizeof(iss::OriginsItem));
-    memcpy(q.h_ids[slot], ids.data(), ids.size());
-    HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::OriginsItem), hipMemcpyHostToDevice, st));
-    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, st));
+    { int rc_ = q.tab.stage(ctx, slot, items, ids, st); if (rc_) return rc_; }
     iss::OriginsArgs A{};
     A.desc = ctx->desc;
     A.n_pairs = pairs;
     A.RL = M.RL;
     A.n_items = (int32_t)items.size();
-    A.items = q.d_items[slot];
-    A.ids = q.d_ids[slot];
+    A.items = q.tab.d_items[slot];
+    A.ids = q.tab.d_ids[slot];
     A.len = q.d_len;
     A.off = q.d_off;
     A.total = q.d_total[slot];
@@ -171,23 +125,12 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     //  next rewrites the descriptors' set once this one has: these launches are the last readers now)
     if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], st));
     if (ctx->call_seq) HIP_TRY(ctx, hipEventRecord(ctx->ev_call_done[(int)((ctx->call_seq - 1) & 1u)], st));
-    HIP_TRY(ctx, hipEventRecord(q.ev_fmt[slot], st));
-    HIP_TRY(ctx, hipStreamWaitEvent(q.copy_stream, q.ev_fmt[slot], 0));
-    HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot], q.d_total[slot], 8, hipMemcpyDeviceToHost, q.copy_stream));
-    HIP_TRY(ctx, hipEventRecord(q.ev_copy[slot], q.copy_stream));
-    {
-        std::lock_guard<std::mutex> lk(q.mu);
-        q.jobs.push_back(OriginsJob{slot, q.fd});
-        q.busy[slot] = true;
-    }
-    q.cv.notify_all();
-    q.next ^= 1;
-    return 0;
+    return append_enqueue(ctx, q, slot, q.fd, q.d_total[slot]);
 }
 
 int iss_origins_flush(iss_ctx *ctx) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    return origins_flush(ctx);
+    return append_flush(ctx, ctx->oq);
 }
 
 int iss_origins_host_text(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,

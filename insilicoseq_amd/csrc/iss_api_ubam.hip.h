@@ -55,10 +55,6 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     UbamPipe &q = ctx->uq;
     if (!q.ready) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.copy_stream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
-        for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : q.ev_copy) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         iss::DeflateCode init{};
         for (int k = 0; k < 8; ++k) iss::crc_shift_operator((uint64_t)128 << k, init.crc_shift[k]);
         for (int sl = 0; sl < 2; ++sl) {
@@ -68,26 +64,16 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
             HIP_TRY(ctx, hipMalloc(&v, sizeof(iss::DeflateCode)));
             q.d_code[sl] = static_cast<iss::DeflateCode *>(v);
             HIP_TRY(ctx, hipMemcpy(v, &init, sizeof init, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault));
-            q.h_total[sl] = static_cast<uint64_t *>(v);
         }
-        q.stop = false;
-        q.writer = std::thread(ubam_writer_loop, ctx);
-        q.ready = true;
+        { int rc_ = append_start(ctx, q, true, ubam_write, "unaligned BAM"); if (rc_) return rc_; }
     }
-    if (q.fd != fd) {
-        { int rc_ = ubam_flush(ctx); if (rc_) return rc_; }
-        const off_t at = lseek(fd, 0, SEEK_CUR);
-        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
-        q.fd = fd;
-        q.off = at;
-    }
+    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
     const uint32_t n_blocks = (uint32_t)((bytes + iss::DEFLATE_BLOCK - 1) / iss::DEFLATE_BLOCK);
     // members of a call: its own Huffman code never needs more than 8 bits per byte plus rounding; the smoothing of the counts,
     // the block headers and the members' frames are covered by the margin (a call that needs more fails, it is never cut)
     auto comp_bytes = [](size_t text, size_t blocks) { return text + text / 8 + blocks * (320 + iss::BGZF_FRAME) + 64; };
     if (bytes > q.cap || comp_bytes(bytes, n_blocks) > q.comp_cap || n_blocks > q.blocks_cap) {
-        { int rc_ = ubam_flush(ctx, true); if (rc_) return rc_; }
+        { int rc_ = append_flush(ctx, q, true); if (rc_) return rc_; }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the kernels of the last call read the buffers)
         ubam_free_buffers(ctx);
         const size_t cap = bytes + bytes / 8 + (1u << 20);
@@ -107,43 +93,15 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
         q.blocks_cap = (uint32_t)cap_blocks;
     }
     const int slot = q.next;
-    {
-        std::unique_lock<std::mutex> lk(q.mu);
-        q.cv.wait(lk, [&] { return !q.busy[slot]; });
-        if (!q.error.empty()) { const std::string e = q.error; q.error.clear(); return fail(ctx, q.error_code, e); }
-    }
-    if (items.size() > q.items_cap[slot] || ids.size() + 1 > q.ids_cap[slot]) {  // (the slot is free: nothing reads its tables)
-        if (q.h_items[slot]) (void)hipHostFree(q.h_items[slot]);
-        if (q.d_items[slot]) (void)hipFree(q.d_items[slot]);
-        if (q.h_ids[slot]) (void)hipHostFree(q.h_ids[slot]);
-        if (q.d_ids[slot]) (void)hipFree(q.d_ids[slot]);
-        q.h_items[slot] = q.d_items[slot] = nullptr;
-        q.h_ids[slot] = q.d_ids[slot] = nullptr;
-        q.items_cap[slot] = q.ids_cap[slot] = 0;
-        const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
-        void *v = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(iss::FastqItem), hipHostMallocDefault));
-        q.h_items[slot] = static_cast<iss::FastqItem *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(iss::FastqItem)));
-        q.d_items[slot] = static_cast<iss::FastqItem *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault));
-        q.h_ids[slot] = static_cast<char *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, dc));
-        q.d_ids[slot] = static_cast<char *>(v);
-        q.items_cap[slot] = ic;
-        q.ids_cap[slot] = dc;
-    }
-    memcpy(q.h_items[slot], items.data(), items.size() * sizeof(iss::FastqItem));
-    memcpy(q.h_ids[slot], ids.data(), ids.size());
-    HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::FastqItem), hipMemcpyHostToDevice, ctx->stream));
-    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, ctx->stream));
+    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
+    { int rc_ = q.tab.stage(ctx, slot, items, ids, ctx->stream); if (rc_) return rc_; }
     iss::UbamArgs A{};
     A.row = M.row;
     A.RL = M.RL;
     A.n_items = (int32_t)items.size();
     A.n_pairs = pairs;
-    A.items = q.d_items[slot];
-    A.ids = q.d_ids[slot];
+    A.items = q.tab.d_items[slot];
+    A.ids = q.tab.d_ids[slot];
     A.text = q.d_text[slot];
     for (int m = 0; m < 2; ++m) {
         A.base[m] = ctx->out[2 * m];
@@ -176,23 +134,13 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
     hipLaunchKernelGGL(iss::k_deflate_scan, dim3(1), dim3(1024), 0, ctx->stream, D);
     hipLaunchKernelGGL(iss::k_bgzf_encode, dim3(n_blocks), dim3(iss::DEFLATE_THREADS), 0, ctx->stream, D);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(q.ev_fmt[slot], ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(q.copy_stream, q.ev_fmt[slot], 0));
-    HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot], q.d_boff[slot] + n_blocks, 8, hipMemcpyDeviceToHost, q.copy_stream));
-    HIP_TRY(ctx, hipEventRecord(q.ev_copy[slot], q.copy_stream));
-    {
-        std::lock_guard<std::mutex> lk(q.mu);
-        q.jobs.push_back(UbamJob{slot, q.fd, n_blocks});
-        q.busy[slot] = true;
-    }
-    q.cv.notify_all();
-    q.next ^= 1;
-    return 0;
+    q.job_blocks[slot] = n_blocks;
+    return append_enqueue(ctx, q, slot, q.fd, q.d_boff[slot] + n_blocks);
 }
 
 int iss_ubam_flush(iss_ctx *ctx) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    return ubam_flush(ctx);
+    return append_flush(ctx, ctx->uq);
 }
 
 int iss_ubam_host_records(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,

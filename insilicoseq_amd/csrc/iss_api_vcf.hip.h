@@ -20,15 +20,9 @@ struct VcfJob {
 int vcf_pipe_init(iss_ctx *ctx) {
     VcfPipe &q = ctx->vq;
     if (q.ready) return 0;
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
-    for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &p : q.h_total) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); p = static_cast<uint64_t *>(v); }
     { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); q.h_count = static_cast<uint32_t *>(v); }
     { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 2 * sizeof(uint32_t))); q.d_stats = static_cast<uint32_t *>(v); }
-    q.stop = false;
-    q.writer = std::thread(vcf_writer_loop, ctx);
-    q.ready = true;
-    return 0;
+    return append_start(ctx, q, false, vcf_write, "VCF text");  // (no copy stream: the size rides the context's stream)
 }
 
 // an item of the table: the id's place in `ids`, the worker's number, the longest "{id}_{i}_" so far
@@ -82,11 +76,7 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         q.slots_cap = sc; q.pairs_cap = pc; q.tiles_cap = tc;
     }
     const int slot = q.next;
-    {
-        std::unique_lock<std::mutex> lk(q.mu);
-        q.cv.wait(lk, [&] { return !q.busy[slot]; });
-        if (!q.error.empty()) { const std::string e = q.error; q.error.clear(); return fail(ctx, ISS_E_IO, e); }
-    }
+    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
     // (the slot is free: nothing reads its text or its tables)
     if (bound > q.text_cap[slot]) {
         if (q.d_text[slot]) (void)hipFree(q.d_text[slot]);
@@ -98,28 +88,8 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         q.d_text[slot] = static_cast<uint8_t *>(v);
         q.text_cap[slot] = cap;
     }
-    if (items.size() > q.items_cap[slot] || ids.size() + 1 > q.ids_cap[slot]) {
-        if (q.h_items[slot]) (void)hipHostFree(q.h_items[slot]);
-        if (q.d_items[slot]) (void)hipFree(q.d_items[slot]);
-        if (q.h_ids[slot]) (void)hipHostFree(q.h_ids[slot]);
-        if (q.d_ids[slot]) (void)hipFree(q.d_ids[slot]);
-        q.h_items[slot] = q.d_items[slot] = nullptr;
-        q.h_ids[slot] = q.d_ids[slot] = nullptr;
-        q.items_cap[slot] = q.ids_cap[slot] = 0;
-        const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
-        void *v = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(iss::VcfItem), hipHostMallocDefault)); q.h_items[slot] = static_cast<iss::VcfItem *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(iss::VcfItem))); q.d_items[slot] = static_cast<iss::VcfItem *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault)); q.h_ids[slot] = static_cast<char *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, dc)); q.d_ids[slot] = static_cast<char *>(v);
-        q.items_cap[slot] = ic;
-        q.ids_cap[slot] = dc;
-    }
-    memcpy(q.h_items[slot], items.data(), items.size() * sizeof(iss::VcfItem));
-    memcpy(q.h_ids[slot], ids.data(), ids.size());
     hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(q.d_items[slot], q.h_items[slot], items.size() * sizeof(iss::VcfItem), hipMemcpyHostToDevice, st));
-    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(q.d_ids[slot], q.h_ids[slot], ids.size(), hipMemcpyHostToDevice, st));
+    { int rc_ = q.tab.stage(ctx, slot, items, ids, st); if (rc_) return rc_; }
     A.mut = J.mut;
     A.n_slots = (uint32_t)n_slots;
     A.n_pairs = call_pairs;
@@ -131,8 +101,8 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
     A.off = q.d_off;
     A.text = q.d_text[slot];
     A.text_cap = q.text_cap[slot];
-    A.items = q.d_items[slot];
-    A.ids = q.d_ids[slot];
+    A.items = q.tab.d_items[slot];
+    A.ids = q.tab.d_ids[slot];
     A.n_items = (int32_t)items.size();
     const bool set = !J.wbase.empty();  // a worker set: item k = worker k, its rows from wbase[k] (the table behind the items' copy)
     if (set) {
@@ -195,18 +165,8 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(q.h_wb[slot] + J.wbase.size(), A.wbytes, J.wbase.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(q.h_total[slot], q.d_off + n_slots, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipEventRecord(q.ev_fmt[slot], st));
-    {
-        std::lock_guard<std::mutex> lk(q.mu);
-        q.job_fd[slot] = J.fd;
-        q.job_wfds[slot] = J.wfds;
-        q.jobs.push_back(slot);
-        q.busy[slot] = true;
-    }
-    q.cv.notify_all();
-    q.next ^= 1;
-    return 0;
+    q.job_wfds[slot] = J.wfds;
+    return append_enqueue(ctx, q, slot, J.fd, q.d_off + n_slots);
 }
 
 }  // namespace
@@ -259,13 +219,7 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
     }
     if (J.items.empty() || n_slots == 0) return 0;
     if (n_slots > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: too many rows");
-    if (q.fd != fd) {
-        { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }
-        const off_t at = lseek(fd, 0, SEEK_CUR);
-        if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
-        q.fd = fd;
-        q.off = at;
-    }
+    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
     J.fd = fd;
     J.philox = philox;
     J.mut = philox ? ctx->d_pmut : ctx->mt.d_mut;
@@ -303,7 +257,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
     J.wbase.push_back(rows);
     if (rows == 0) return 0;
     if (rows > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: too many rows");
-    if (q.fd >= 0) { int rc_ = vcf_flush(ctx); if (rc_) return rc_; }  // (a single file's running offset ends here)
+    if (q.fd >= 0) { int rc_ = append_flush(ctx, q); if (rc_) return rc_; }  // (a single file's running offset ends here)
     J.mut = t.d_mut;
     J.wstride = (uint64_t)t.mut_rows;
     J.n_slots = (int64_t)rows;
@@ -312,7 +266,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
 
 int iss_vcf_flush(iss_ctx *ctx) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    return vcf_flush(ctx);
+    return append_flush(ctx, ctx->vq);
 }
 
 }  // extern "C"

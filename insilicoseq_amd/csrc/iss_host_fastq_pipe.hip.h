@@ -4,15 +4,6 @@
 
 namespace {
 
-int pwrite_all(int fd, const uint8_t *p, size_t n, int64_t off) {
-    while (n) {
-        const ssize_t k = pwrite(fd, p, n, (off_t)off);
-        if (k < 0) { if (errno == EINTR) continue; return -1; }
-        p += k; n -= (size_t)k; off += k;
-    }
-    return 0;
-}
-
 void fastq_writer_loop(iss_ctx *ctx) {
     FastqPipe &q = ctx->fq;
     (void)hipSetDevice(ctx->device);
@@ -201,26 +192,13 @@ void fastq_shutdown(iss_ctx *ctx) {
     FastqPipe &q = ctx->fq;
     if (!q.ready) return;
     (void)fastq_flush(ctx);
-    {
-        std::lock_guard<std::mutex> lk(q.mu);
-        q.stop = true;
-    }
-    q.cv.notify_all();
-    if (q.writer.joinable()) q.writer.join();
+    writer_stop(q);
     fastq_free_buffers(ctx);
     for (auto &sl : q.d_hist) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto &sl : q.d_code) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto &sl : q.h_total) for (auto &p : sl) { if (p) (void)hipHostFree(p); p = nullptr; }
     if (q.data_stream) (void)hipStreamDestroy(q.data_stream);
-    for (int sl = 0; sl < 2; ++sl) {
-        if (q.h_items[sl]) (void)hipHostFree(q.h_items[sl]);
-        if (q.d_items[sl]) (void)hipFree(q.d_items[sl]);
-        if (q.h_ids[sl]) (void)hipHostFree(q.h_ids[sl]);
-        if (q.d_ids[sl]) (void)hipFree(q.d_ids[sl]);
-        q.h_items[sl] = q.d_items[sl] = nullptr;
-        q.h_ids[sl] = q.d_ids[sl] = nullptr;
-        q.items_cap[sl] = q.ids_cap[sl] = 0;
-    }
+    q.tab.release();
     for (auto &e : q.ev_fmt) if (e) (void)hipEventDestroy(e);
     for (auto &e : q.ev_copy) if (e) (void)hipEventDestroy(e);
     if (q.copy_stream) (void)hipStreamDestroy(q.copy_stream);

@@ -1,4 +1,5 @@
-// iss_host_state.hip.h -- host-side state of the engine: the FASTQ, VCF, unaligned-BAM and origins pipelines' job / pipe records, timed launches, and struct iss_ctx
+// iss_host_state.hip.h -- host-side state of the engine: the records of the device-built outputs (the slot table, the writer's state and the
+// append pipe they share; the FASTQ, VCF, unaligned-BAM and origins pipes), timed launches, and struct iss_ctx
 // (one per GPU: streams, uploaded model and genomes, output rows, MT-mode chains and worker sets).  Included by iss_mi355x.hip.
 #pragma once
 
@@ -78,6 +79,48 @@ struct TimedLaunch {
 
 constexpr int FIX_SLOTS = FIX_SLOTS_C;  // ring of fix-list / read-list counters (one per chunk in flight)
 
+// What every device-built output shares on the host (the functions: iss_host_pipe.hip.h).
+// The item table and the record ids of an emit call, per slot: a pinned host copy and the device copy the format kernels read.
+template <typename Item>
+struct SlotTable {
+    Item *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
+    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
+    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    int stage(iss_ctx *ctx, int slot, const std::vector<Item> &items, const std::string &ids, hipStream_t st);
+    void release();
+};
+// A pipeline's writer thread and what the caller shares with it: two slots, a pending error.
+struct WriterSync {
+    std::thread writer;
+    std::mutex mu;
+    std::condition_variable cv;
+    bool busy[2] = {false, false};
+    bool stop = false;
+    std::string error;          // the first error of the writer since the caller last took it
+    int error_code = ISS_E_IO;  // of `error`
+};
+// What a format does with a slot's bytes once their count is known: fetch them, check them, write them at `at`.  Returns the error
+// ("": none) with *code (preset: ISS_E_IO); *advance (preset: true) says whether the pipe's `off` moves by `total`.
+typedef std::string (*AppendWriteFn)(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *code, bool *advance);
+// A device-built output appended to ONE file (VCF text, unaligned BAM, origins text): the format kernels run on the context's
+// stream behind the generation, the size of a slot's bytes comes back in h_total, the writer thread fetches exactly those bytes
+// on data_stream and appends them.  A format's per-job payload lies in slot-indexed arrays beside job_fd (a slot is busy from
+// the moment its job is queued until the writer has popped it).
+struct AppendPipe : WriterSync {
+    bool ready = false;
+    hipStream_t data_stream = nullptr;   // the writer thread's copies
+    hipStream_t copy_stream = nullptr;   // the size's way back; nullptr: it rides the context's stream (VCF)
+    hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};  // the writer waits for ev_copy, without a copy stream for ev_fmt
+    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, 64 bytes: bytes of the slot's output first
+    int next = 0;
+    int fd = -1;
+    int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
+    std::deque<int> jobs;  // slots, in call order
+    int job_fd[2] = {-1, -1};
+    AppendWriteFn write = nullptr;
+    const char *noun = nullptr;  // "the {noun}'s kernels failed"
+};
+
 // Device-formatted FASTQ on its way to the files: two slots of (device text, pinned host text) per mate; the
 // format kernel runs on the context's stream, the copy back on a copy stream, the file writes on a writer thread.
 struct FastqJob {
@@ -91,16 +134,13 @@ struct FastqJob {
     std::vector<uint64_t> item_off;  // text offsets of the job's work items (the writer checks the record structure there)
     std::vector<int64_t> item_file_off;  // iss_fastq_emit_scatter: where each item's text goes in BOTH files (empty: the job is one piece at `off`)
 };
-struct FastqPipe {
+struct FastqPipe : WriterSync {
     bool ready = false;
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
     uint8_t *d_text[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [slot][mate]
     uint8_t *h_text[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    // per slot: the item table and the record ids of the emit call (pinned host copy + device copy)
-    iss::FastqItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
-    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
-    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    SlotTable<iss::FastqItem> tab;
     size_t cap = 0;
     int next = 0;
     int fd[2] = {-1, -1};
@@ -111,13 +151,7 @@ struct FastqPipe {
     int64_t off[2] = {0, 0};
     int64_t attached_off[2] = {0, 0};  // offsets when the files were attached ...
     int64_t accounted[2] = {0, 0};     // ... and the bytes queued (text) / written (gzip) since: off == attached_off + accounted
-    std::thread writer;
-    std::mutex mu;
-    std::condition_variable cv;
     std::deque<FastqJob> jobs;
-    bool busy[2] = {false, false};
-    bool stop = false;
-    std::string error;
     // compressed mode (iss_fastq_compress): per slot and mate the device-side state of iss_deflate.hip.h, the
     // compressed bytes land in h_text; the writer thread fetches exactly the bytes a member has
     int gzip = 0;
@@ -135,21 +169,14 @@ struct FastqPipe {
 };
 constexpr size_t FASTQ_ID_MAX = 4096;
 
-// Device-formatted VCF text (--store_mutations) on its way to the file: the kernels of iss_vcf.hip.h run on the context's stream
-// behind the generation, the writer thread fetches the text once it knows its size and appends it.  Two slots of text; the work
-// arrays are one set (only kernels of the context's stream touch them, in order).
-struct VcfPipe {
-    bool ready = false;
-    hipStream_t data_stream = nullptr;   // the writer thread's copies
-    hipEvent_t ev_fmt[2] = {nullptr, nullptr};
+// Device-formatted VCF text (--store_mutations): the kernels of iss_vcf.hip.h.  Its size copy rides the context's stream (no copy
+// stream).  Two slots of text; the work arrays are one set (only kernels of the context's stream touch them, in order).
+struct VcfPipe : AppendPipe {
     uint8_t *d_text[2] = {nullptr, nullptr};
     size_t text_cap[2] = {0, 0};
     uint8_t *h_text[2] = {nullptr, nullptr};  // pinned; grown by the writer thread to the size a text has
     size_t h_cap[2] = {0, 0};
-    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value: bytes of the slot's text
-    iss::VcfItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
-    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
-    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    SlotTable<iss::VcfItem> tab;
     uint32_t *h_count = nullptr;         // pinned: the slots a Philox call reserved
     uint32_t *d_stats = nullptr;         // ISS_VCF_DEBUG: k_vcf_count's two counters (they come back behind h_total)
     bool job_debug[2] = {false, false};
@@ -157,35 +184,15 @@ struct VcfPipe {
     uint32_t *d_key = nullptr, *d_slot = nullptr, *d_order = nullptr, *d_len = nullptr, *d_cnt = nullptr;
     uint64_t *d_off = nullptr, *d_seg = nullptr, *d_tiles = nullptr;
     size_t slots_cap = 0, pairs_cap = 0, tiles_cap = 0;
-    int next = 0;
-    int fd = -1;
-    int64_t off = 0;                     // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
-    std::thread writer;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<int> jobs;                // slots, in call order
-    int job_fd[2] = {-1, -1};
     // iss_vcf_emit_workers: the text of a slot is W byte ranges, range k appended to job_wfds[k] (empty: one file, job_fd)
     std::vector<int> job_wfds[2];
     uint64_t *h_wb[2] = {nullptr, nullptr}, *d_wb[2] = {nullptr, nullptr};  // [2][wb_cap]: the workers' first rows (wbase), then their byte offsets
     size_t wb_cap[2] = {0, 0};
-    bool busy[2] = {false, false};
-    bool stop = false;
-    std::string error;
 };
 
-// Unaligned BAM (--ubam) on its way to ONE file: the records (k_ubam_format) and their BGZF members (iss_ubam.hip.h) are built on the
-// context's stream behind the generation; the members' total size comes back on a copy stream, the writer thread fetches exactly
-// those bytes and appends them.  Two slots, like the FASTQ pipeline's.
-struct UbamJob {
-    int slot;
-    int fd;
-    uint32_t n_blocks;
-};
-struct UbamPipe {
-    bool ready = false;
-    hipStream_t copy_stream = nullptr, data_stream = nullptr;
-    hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+// Unaligned BAM (--ubam): the records (k_ubam_format) and their BGZF members (iss_ubam.hip.h); the members' total size comes back
+// on the copy stream.
+struct UbamPipe : AppendPipe {
     uint8_t *d_text[2] = {nullptr, nullptr};   // the record bytes (never leave the device)
     uint8_t *d_comp[2] = {nullptr, nullptr};   // the BGZF members, back to back
     uint8_t *h_comp[2] = {nullptr, nullptr};   // pinned
@@ -195,56 +202,22 @@ struct UbamPipe {
     iss::DeflateCode *d_code[2] = {nullptr, nullptr};
     uint32_t *d_bbytes[2] = {nullptr, nullptr}, *d_bcrc[2] = {nullptr, nullptr};
     uint64_t *d_boff[2] = {nullptr, nullptr};
-    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value
-    iss::FastqItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
-    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
-    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
-    int next = 0;
-    int fd = -1;
-    int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
-    std::thread writer;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<UbamJob> jobs;
-    bool busy[2] = {false, false};
-    bool stop = false;
-    std::string error;
-    int error_code = 0;  // of `error`: ISS_E_IO, or ISS_E_INVALID for members that do not have the layout BGZF asks for
+    SlotTable<iss::FastqItem> tab;
+    uint32_t job_blocks[2] = {0, 0};           // members of the slot's job
 };
 
-// The origins text (--origins, iss_origins.hip.h) on its way to ONE file: lengths, scan and format run on the context's stream behind
-// the generation; the text's size comes back on a copy stream, the writer thread fetches exactly those bytes and appends them.  Two
+// The origins text (--origins, iss_origins.hip.h): lengths, scan and format; the text's size comes back on the copy stream.  Two
 // slots of (device text, pinned host text, item table, total); the work arrays (len, off, tile sums) are one set: only kernels of
 // the context's stream touch them, in order.
-struct OriginsJob {
-    int slot;
-    int fd;
-};
-struct OriginsPipe {
-    bool ready = false;
-    hipStream_t copy_stream = nullptr, data_stream = nullptr;
-    hipEvent_t ev_fmt[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+struct OriginsPipe : AppendPipe {
     uint8_t *d_text[2] = {nullptr, nullptr};
     uint8_t *h_text[2] = {nullptr, nullptr};    // pinned
     size_t cap = 0;                             // bytes of each of the four
     uint64_t *d_total[2] = {nullptr, nullptr};  // bytes of the slot's text (the scan's grand total)
-    uint64_t *h_total[2] = {nullptr, nullptr};  // pinned, one value
-    iss::OriginsItem *h_items[2] = {nullptr, nullptr}, *d_items[2] = {nullptr, nullptr};
-    char *h_ids[2] = {nullptr, nullptr}, *d_ids[2] = {nullptr, nullptr};
-    size_t items_cap[2] = {0, 0}, ids_cap[2] = {0, 0};
+    SlotTable<iss::OriginsItem> tab;
     uint32_t *d_len = nullptr;                  // [pairs_cap]
     uint64_t *d_off = nullptr, *d_tiles = nullptr;  // [pairs_cap], [tiles_cap]
     size_t pairs_cap = 0, tiles_cap = 0;
-    int next = 0;
-    int fd = -1;
-    int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
-    std::thread writer;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<OriginsJob> jobs;
-    bool busy[2] = {false, false};
-    bool stop = false;
-    std::string error;
 };
 
 // MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's

@@ -1,7 +1,8 @@
 // iss_mi355x.hip -- C-ABI shared library of the MI355X read-generation engine (see include/iss_mi355x.h).
 // Host side: context, HBM uploads (model tables, genomes; small records from an arena), launch sequencing on one HIP
 // stream for one record (iss_generate) or a whole work list (iss_generate_batch: records side by side in one arena),
-// HIP-event timing, downloads, the FASTQ pipeline (text or gzip members built on the device, copy stream, writer thread).
+// HIP-event timing, downloads, the FASTQ pipeline (text or gzip members built on the device, copy stream, writer thread) and the
+// append pipe of the one-file outputs (VCF text, unaligned BAM, origins text: iss_host_pipe.hip.h).
 // Device side: iss_kernels.hip.h (the Philox path), iss_perfect.hip.h (its perfect-model kernel), iss_mt_compat.hip.h (the reference's Mersenne-Twister streams),
 // iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h;
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
@@ -44,13 +45,14 @@
 #include "iss_origins.hip.h"    // k_origins_len, k_origins_format: the pairs' source intervals as BEDPE text (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
-#include "iss_host_state.hip.h"       // FASTQ pipeline records, struct iss_ctx
+#include "iss_host_state.hip.h"       // the output pipes' records, struct iss_ctx
 #include "iss_host_util.hip.h"        // errors, uploads, switches, frees, kernel choice, timing, synchronisation
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
-#include "iss_host_fastq_pipe.hip.h"  // writer thread, flush
-#include "iss_host_vcf_pipe.hip.h"    // the VCF text's writer thread, flush
-#include "iss_host_ubam_pipe.hip.h"   // the BGZF members' writer thread, flush
-#include "iss_host_origins_pipe.hip.h"  // the origins text's writer thread, flush
+#include "iss_host_pipe.hip.h"        // shared by the output pipes: slot table, slot wait, the append pipe and its writer thread
+#include "iss_host_fastq_pipe.hip.h"  // the two FASTQ files' writer thread, flush
+#include "iss_host_vcf_pipe.hip.h"    // append pipe: the VCF text's check and write
+#include "iss_host_ubam_pipe.hip.h"   // append pipe: the BGZF members' check and write
+#include "iss_host_origins_pipe.hip.h"  // append pipe: the origins text's write
 #include "iss_api_context.hip.h"
 #include "iss_api_model.hip.h"
 #include "iss_api_generate.hip.h"

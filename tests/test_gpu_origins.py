@@ -268,6 +268,65 @@ def test_errors_launch_nothing(rows, tmp_path):
     check(r.eng, [([("fine", 0, 0, 5)], [ln])], 0, r.coords, r.RL, tmp_path / "fine.bedpe")  # (the context still works)
 
 
+def _text_bound(call, cpu):
+    """The bytes iss_origins_emit_batch reserves for a call's text: every pair at the longest line its item can have -- three ids,
+    the worker's number, 16 fixed bytes, four coordinates within the record, the item's last pair number, 11 for the insert size."""
+    items, lengths = call
+    return sum(n * (3 * len(rid) + len(str(cpu)) + 16 + 4 * len(str(ln)) + len(str(first_i + n - 1)) + 11)
+               for (rid, first_i, _row, n), ln in zip(items, lengths) if n)
+
+
+def test_text_buffers_grow_mid_run(rows, tmp_path):
+    """One pair, then a call whose bound is past what the first one allocated (bound + bound / 8 + 64 KiB: the id stands three
+    times in a line), then a small one; no flush in between, the file stays attached while the buffers are replaced."""
+    r = rows("miseq", seed=78)  # (an engine no other case has emitted from: its buffers are the first call's)
+    ln = [r.length]
+    calls = [([("one", 0, 0, 1)], ln), ([("L" * 300, 7, 1, 333)], ln), ([("small", 0, 334, 20)], ln)]
+    first = _text_bound(calls[0], 2)
+    allocated = first + first // 8 + (1 << 16)
+    assert _text_bound(calls[1], 2) > allocated > _text_bound(calls[2], 2)
+    got = check(r.eng, calls, 2, r.coords, r.RL, tmp_path / "grow.bedpe")
+    assert len(got) > allocated
+
+
+def test_a_new_descriptor_without_a_flush(rows, tmp_path):
+    """File A, then file B, one flush: the emit to B lands A's text and leaves A's descriptor at A's end; B is appended to where B
+    stood, whatever A's offset was."""
+    r = rows("miseq")
+    ln = [r.length]
+    calls = {"a": ([("to_a", 0, 0, 150)], ln), "b": ([("to_b", 5, 150, 90)], ln)}
+    front = {"a": b"A: in front\n", "b": b"B: other bytes, and more of them, in front\n"}
+    with open(tmp_path / "a.bedpe", "wb") as fa, open(tmp_path / "b.bedpe", "wb") as fb:
+        for k, fh in (("a", fa), ("b", fb)):
+            fh.write(front[k])
+            fh.flush()
+            r.eng.origins_emit_batch(fh.fileno(), calls[k][0], calls[k][1], 2)
+        r.eng.origins_flush()
+        for k, fh in (("a", fa), ("b", fb)):
+            assert os.lseek(fh.fileno(), 0, os.SEEK_CUR) == os.path.getsize(str(tmp_path / (k + ".bedpe"))), k
+    for k in "ab":
+        assert open(tmp_path / (k + ".bedpe"), "rb").read() == front[k] + twin([calls[k]], 2, r.coords, r.RL), k
+
+
+def test_a_write_error_surfaces_once(rows, tmp_path):
+    """A descriptor opened read-only (EBADF on the host, nothing on the device): the next flush raises E_IO "write failed ...",
+    the one after returns, the file is as it was and the next emit appends the twin's bytes."""
+    from insilicoseq_amd._native import E_IO, EngineError
+
+    r = rows("miseq")
+    call = ([("rec", 3, 10, 120)], [r.length])
+    path = tmp_path / "readonly.bedpe"
+    path.write_bytes(b"read only\n")
+    with open(path, "rb") as fh:
+        r.eng.origins_emit_batch(fh.fileno(), call[0], call[1], 0)
+        with pytest.raises(EngineError) as e:
+            r.eng.origins_flush()
+        assert e.value.code == E_IO and e.value.message.startswith("write failed"), e.value.message
+        r.eng.origins_flush()
+    assert path.read_bytes() == b"read only\n"
+    check(r.eng, [call], 0, r.coords, r.RL, tmp_path / "good.bedpe")
+
+
 # ---------------------------------------------------------------------------------------------------- the command line
 _COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
 IDS = ["rec0", "rec1", "rec2"]

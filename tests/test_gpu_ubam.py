@@ -23,10 +23,10 @@ ROWS = 400  # rows generated per read length (the largest case takes 333)
 
 
 class Rows(object):
-    """One engine with ROWS rows of the shipped model at RL over a lower-case / IUPAC genome, and their downloaded arrays (left
+    """One engine with ``rows`` rows of the shipped model at RL over a lower-case / IUPAC genome, and their downloaded arrays (left
     unchanged: every case's reference)."""
 
-    def __init__(self, RL):
+    def __init__(self, RL, rows=ROWS):
         from insilicoseq_amd.engine import ReadEngine
 
         self.RL = RL
@@ -35,9 +35,9 @@ class Rows(object):
             eng.load_model(H.dense_model(MODELS[RL]))
             assert eng.read_length == RL
             self.gid = eng.add_genome(H.mixed_genome(700 + RL, 20000))
-            eng.generate(self.gid, ROWS, first_ordinal=3, seed=77)
+            eng.generate(self.gid, rows, first_ordinal=3, seed=77)
             eng.synchronize()
-            d = eng.download(0, ROWS)
+            d = eng.download(0, rows)
             self.rows = [d[k].copy() for k in ("r1_base", "r1_qual", "r2_base", "r2_qual")]
         except Exception:
             eng.close()
@@ -194,6 +194,57 @@ def test_generation_behind_an_emit(rows, native, tmp_path):
         d = r.eng.download(0, ROWS)
         for have, k in zip(r.rows, ("r1_base", "r1_qual", "r2_base", "r2_qual")):
             assert np.array_equal(have, d[k])
+
+
+def test_buffers_grow_mid_run(native, tmp_path):
+    """One pair, then a call whose record bytes are past what the first one allocated (bytes + bytes / 8 + 1 MiB), then a small
+    one; no flush in between, the file stays attached while the record, member and block buffers are replaced."""
+    r = Rows(301, rows=800)  # (an engine no other case has emitted from: its buffers are the first call's)
+    try:
+        calls = [[("one", 0, 0, 1)], [("L" * 240, 7, 1, 760)], [("small", 0, 761, 20)]]
+        size = [sum(U.record_length(rid, first_i + k, 2, 301) for rid, first_i, _row, n in items for k in range(n)) * 2 for items in calls]
+        allocated = size[0] + size[0] // 8 + (1 << 20)
+        assert size[1] > allocated > size[2]
+        check(r, native, calls, 2, tmp_path / "grow.bam")
+    finally:
+        r.eng.close()
+
+
+def test_a_new_descriptor_without_a_flush(rows, native, tmp_path):
+    """File A, then file B, one flush: the emit to B lands A's members and leaves A's descriptor at A's end; B is appended to where
+    B stood, whatever A's offset was."""
+    r = rows(126)
+    calls = {"a": [("to_a", 0, 0, 150)], "b": [("to_b", 5, 150, 90)]}
+    front = {"a": b"A: in front", "b": b"B: other bytes, and more of them, in front"}
+    with open(tmp_path / "a.bam", "wb") as fa, open(tmp_path / "b.bam", "wb") as fb:
+        for k, fh in (("a", fa), ("b", fb)):
+            fh.write(front[k])
+            fh.flush()
+            r.eng.ubam_emit_batch(fh.fileno(), calls[k], 2)
+        r.eng.ubam_flush()
+        for k, fh in (("a", fa), ("b", fb)):
+            assert os.lseek(fh.fileno(), 0, os.SEEK_CUR) == os.path.getsize(str(tmp_path / (k + ".bam"))), k
+    for k in "ab":
+        want = U.members(native, U.records(calls[k], 2, *r.rows), U.record_distance(calls[k], r.RL, 2))
+        assert open(tmp_path / (k + ".bam"), "rb").read() == front[k] + want, k
+
+
+def test_a_write_error_surfaces_once(rows, native, tmp_path):
+    """A descriptor opened read-only (EBADF on the host, nothing on the device): the next flush raises E_IO "write failed ...",
+    the one after returns, the file is as it was and the next emit appends the twin's bytes."""
+    from insilicoseq_amd._native import E_IO, EngineError
+
+    r = rows(126)
+    path = tmp_path / "readonly.bam"
+    path.write_bytes(b"read only")
+    with open(path, "rb") as fh:
+        r.eng.ubam_emit_batch(fh.fileno(), [("rec", 3, 10, 120)], 0)
+        with pytest.raises(EngineError) as e:
+            r.eng.ubam_flush()
+        assert e.value.code == E_IO and e.value.message.startswith("write failed"), e.value.message
+        r.eng.ubam_flush()
+    assert path.read_bytes() == b"read only"
+    check(r, native, [[("rec", 3, 10, 120)]], 0, tmp_path / "good.bam")
 
 
 def _read(path):

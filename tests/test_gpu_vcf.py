@@ -260,6 +260,33 @@ def test_no_rows_append_nothing(tmp_path):
         assert os.path.getsize(path) == 0
 
 
+def test_a_write_error_surfaces_once(tmp_path):
+    """A descriptor opened read-only (EBADF on the host, nothing on the device): the next flush raises E_IO "write failed ...",
+    the one after returns, the file is as it was and the next emit appends the host route's bytes."""
+    from insilicoseq_amd import _native
+    from insilicoseq_amd.engine import ReadEngine
+
+    n, items = 3000, [("w", 0, 0, 3000)]
+    path, good = str(tmp_path / "readonly.vcf"), str(tmp_path / "good.vcf")
+    with open(path, "wb") as fh:
+        fh.write(b"#read only\n")
+    with ReadEngine(0) as eng:
+        eng.load_model(dense_model("hiseq"))
+        gid = eng.add_genome(random_genome(370, 30000))
+        eng.mutations_reserve(1_000_000)
+        eng.generate(gid, n, first_ordinal=0, seed=1)
+        with open(path, "rb") as fh:
+            eng.vcf_emit(fh.fileno(), items, 0)
+            with pytest.raises(_native.EngineError) as e:
+                eng.vcf_flush()
+            assert e.value.code == _native.E_IO and e.value.message.startswith("write failed"), e.value.message
+            eng.vcf_flush()
+        assert open(path, "rb").read() == b"#read only\n"
+        got = _device_text(eng, good, items, 0)
+        rows = eng.mutations()
+    assert got == _host_text(rows, items, 0) and len(rows) > 100
+
+
 @pytest.mark.parametrize("model", ["novaseq", "basic"])
 def test_mt_mode(model, tmp_path):
     """generate_mt rows (already in the reference's order) through the same length / offset / format kernels: several work items
