@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive) iss_origins_emit_batch / iss_origins_flush / iss_origins_host_text: every pair's source intervals as BEDPE text built
+/* 8: (additive) iss_origins_compress / iss_vcf_compress / iss_bgzf_text_code_build: the origins and VCF text as BGZF members built on the device, copies
+ *    from the line above.
+ *    (additive) iss_origins_emit_batch / iss_origins_flush / iss_origins_host_text: every pair's source intervals as BEDPE text built
  *    on the device.
  *    (additive) iss_ubam_emit_batch / iss_ubam_flush / iss_ubam_host_records: the rows as unaligned BAM, records and BGZF
  *    blocks built on the device.
@@ -592,6 +594,28 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
 int iss_origins_flush(iss_ctx *ctx);
 int iss_origins_host_text(int fd, const char *record_id, int64_t first_i, int32_t cpu_number, int64_t n_pairs, int32_t read_length,
                           int64_t record_len, const int64_t *coords);
+
+/*
+ * `--bgzip` (additive in ABI 8): the two one-file texts as BGZF, compressed ON THE DEVICE, with the
+ * semantics of iss_fastq_compress.  mode 0 (default): iss_origins_emit_batch / iss_vcf_emit append their text.  mode 1: they
+ * append the BGZF members of that call's text instead -- every 32 768 bytes of it one complete member (`BC` field, its own CRC-32
+ * and ISIZE) that inflates on its own, all members of a call under one dynamic Huffman code built from the call's own tokens.
+ * Inside 32-byte chunks a match is a run (distance 1) or a copy from the LINE ABOVE: the distance of a chunk is the byte length of
+ * the line in front of the line that holds the chunk's first byte, taken from the offsets the formatter computed; there is no
+ * such candidate in the text's first line, past 32 768 bytes, or where the source would start before the chunk's own block.  The
+ * concatenated members inflate to exactly the bytes mode 0 writes.  A call without text appends nothing; the file's frame -- a
+ * header member in front, the 28-byte EOF block behind -- is the caller's.  The text never reaches the host: the writer thread
+ * walks the BSIZE chain of the members it fetched before it writes them, and a chain that does not hold is ISS_E_INVALID at the
+ * next emit or flush.  The mode is switched only while nothing is queued (after a flush): otherwise ISS_E_INVALID.
+ * iss_vcf_emit_workers in mode 1: ISS_E_INVALID, nothing written (a worker set's text is split over W descriptors).
+ */
+int iss_origins_compress(iss_ctx *ctx, int32_t mode);
+int iss_vcf_compress(iss_ctx *ctx, int32_t mode);
+/* The code builder of that stage as a host function (tests, tools; no GPU needed): hist[273 + 30] -- the token counts of
+ * iss_deflate_code_build, then the matches per DEFLATE distance code (a run counts under code 0) -> entry[273] and dentry[30]
+ * (bit-reversed code | length << 16; a distance code nobody uses has length 0) and the dynamic-block header, hdr_bits bits, least
+ * significant first, in hdr_words[80]. */
+int iss_bgzf_text_code_build(const uint32_t *hist, uint32_t *entry, uint32_t *dentry, uint32_t *hdr_bits, uint32_t *hdr_words);
 
 /*
  * `model`: the reference's `iss model` (iss/app.py:147-169 -> iss/bam.py:103-227, iss/modeller.py) from a BAM file.  Additive to

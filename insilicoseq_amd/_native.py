@@ -33,6 +33,7 @@ EXPORTS = (
     "iss_depth_mark", "iss_depth_finish",
     "iss_ubam_emit_batch", "iss_ubam_flush", "iss_ubam_host_records",
     "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
+    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -166,6 +167,11 @@ def lib():
         L.iss_origins_emit_batch.argtypes = [vp, C.c_int, i32, vp, vp, vp, vp, vp, i32]
         L.iss_origins_flush.argtypes = [vp]
         L.iss_origins_host_text.argtypes = [C.c_int, C.c_char_p, i64, i32, i64, i32, i64, vp]
+    # (and the BGZF stage of the two text pipes; without them ReadEngine.origins_compress / vcf_compress raise)
+    if hasattr(L, "iss_origins_compress"):
+        L.iss_origins_compress.argtypes = [vp, i32]
+        L.iss_vcf_compress.argtypes = [vp, i32]
+        L.iss_bgzf_text_code_build.argtypes = [vp, vp, vp, vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -191,7 +197,8 @@ def lib():
         if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
                     "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
                     "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
-                    "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text") and not hasattr(L, name):
+                    "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
+                    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int

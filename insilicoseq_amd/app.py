@@ -185,12 +185,13 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False):
+            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False, bgzip=False):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
     (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files; ``origins``: it also
-    writes ``<prefix>_origins.bedpe``, every pair's source intervals."""
+    writes ``<prefix>_origins.bedpe``, every pair's source intervals; ``bgzip``: its ``.vcf`` and ``_origins.bedpe`` hold BGZF members
+    compressed on the device instead of text."""
     logging.basicConfig(level=logging.WARNING)
     if report or depth:
         from .tensors import _torch
@@ -212,6 +213,8 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
         more["ubam"] = True
     if origins:
         more["origins"] = True
+    if bgzip:
+        more["bgzip"] = True
     worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report, **more)
 
 
@@ -360,6 +363,11 @@ def generate_reads(args):
     if getattr(args, "origins", False) and os.environ.get("ISS_HOST_FASTQ", "") == "1":
         logger.error("--origins builds its text on the device: unset ISS_HOST_FASTQ")
         sys.exit(1)
+    if getattr(args, "bgzip", False):
+        for switch in ("ISS_HOST_FASTQ", "ISS_HOST_VCF"):
+            if os.environ.get(switch, "") == "1":
+                logger.error("--bgzip compresses its text on the device: unset %s" % switch)
+                sys.exit(1)
     try:
         _generate_reads(args, ubam)
     except BaseException:
@@ -381,6 +389,11 @@ def _generate_reads(args, ubam):
     workers = args.gpus
     report = bool(getattr(args, "report", False))
     origins = bool(getattr(args, "origins", False))
+    # --bgzip: the .vcf and the origins text leave the GPU as BGZF members; the parent frames the workers' members (bgzf.py)
+    bgzip = bool(getattr(args, "bgzip", False))
+    if bgzip and not (args.store_mutations or origins):
+        logger.warning("--bgzip has no effect without --store_mutations or --origins")
+        bgzip = False
     depth_bin = int(getattr(args, "depth_bin", None) or 0)
     if depth_bin < 0:
         logger.error("--depth_bin must be positive")
@@ -405,33 +418,49 @@ def _generate_reads(args, ubam):
     in_place = None
     if workers == 1:
         for j in jobs:
-            _worker(*j, records=records, ubam=ubam, origins=origins)
+            _worker(*j, records=records, ubam=ubam, origins=origins, bgzip=bgzip)
     elif _worker_set_wanted(args, report, depth):
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            pool.starmap(_worker, [j + (None, ubam, origins) for j in jobs] if ubam or origins else jobs)
+            pool.starmap(_worker, [j + (None, ubam, origins, bgzip) for j in jobs] if ubam or origins or bgzip else jobs)
     t_cat = time.perf_counter()
+    # the side-by-side worker set keeps its text VCF route (one text job split over the workers' files): host BGZF further down
+    bgzip_vcf_device = bgzip and bool(args.store_mutations) and in_place is None
+    if bgzip_vcf_device:  # the header as a member of its own, the workers' members in worker order, the EOF block
+        from . import bgzf
+
+        bgzf.assemble(args.output + ".vcf.gz", ["%s.vcf" % temp_prefix(args.output, rank) for rank in range(workers)],
+                      header=(VCF_HEADER + "\n").encode())
+    cat_vcf = bool(args.store_mutations) and not bgzip_vcf_device
     if ubam:  # header, the workers' record blocks in worker order, the EOF block; a worker without a chunk is an error as below
         from .ubam import assemble
 
         assemble(args.output + ".bam", ["%s.bam" % temp_prefix(args.output, rank) for rank in range(workers)])
-        if args.store_mutations:
+        if cat_vcf:
             concatenate_rank_files(args.output, workers, suffixes=(".vcf",), headers={".vcf": VCF_HEADER})
         else:
             concatenate_rank_files(args.output, workers, suffixes=())  # (removes the workers' empty .vcf files)
     elif in_place:
-        if args.store_mutations:  # the FASTQ files are final; a VCF's size is not arithmetic: the workers' .vcf behind the header
+        if cat_vcf:  # the FASTQ files are final; a VCF's size is not arithmetic: the workers' .vcf behind the header
             concatenate_rank_files(args.output, workers, suffixes=(".vcf",), headers={".vcf": VCF_HEADER})
-    elif args.store_mutations:  # app.py:128-133
+    elif cat_vcf:  # app.py:128-133
         concatenate_rank_files(args.output, workers, suffixes=("_R1.fastq", "_R2.fastq", ".vcf"),
                                headers={".vcf": VCF_HEADER}, out_suffixes=gz)
     else:
         concatenate_rank_files(args.output, workers, out_suffixes=gz)  # raises if a worker had no chunk (util.py:233)
-    if origins:  # the workers' lines in worker order, like their FASTQ files
+    if origins and bgzip:  # the workers' members in worker order, the EOF block (no pairs at all: the EOF block alone)
+        from . import bgzf
+
+        bgzf.assemble(args.output + ORIGINS_SUFFIX + ".gz", [temp_prefix(args.output, rank) + ORIGINS_SUFFIX for rank in range(workers)])
+    elif origins:  # the workers' lines in worker order, like their FASTQ files
         concatenate_rank_files(args.output, workers, suffixes=(ORIGINS_SUFFIX,))
+    if bgzip and cat_vcf:  # (the worker set's text: the same container, compressed on host threads)
+        from . import bgzf
+
+        bgzf.compress_file(args.output + ".vcf")
     logger.info("Workers %.2f s, concatenation of their files %.2f s" % (t_cat - t_gen, time.perf_counter() - t_cat))
     if report:
         _write_report(args.output, len(jobs), error_model.read_length)
@@ -439,9 +468,9 @@ def _generate_reads(args, ubam):
         _write_depth(args.output, len(jobs), records, depth_bin)
     os.remove(genome_file)
     if args.compress:  # util.compress (iss/util.py:255-268): <file>.gz next to the file, original removed
-        for suffix in (() if device_gzip or ubam else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations else ()):
+        for suffix in (() if device_gzip or ubam else ("_R1.fastq", "_R2.fastq")) + ((".vcf",) if args.store_mutations and not bgzip else ()):
             compress_file(args.output + suffix)
-        if origins:
+        if origins and not bgzip:
             compress_file(args.output + ORIGINS_SUFFIX)
     logger.info("Read generation complete")
 
@@ -515,6 +544,12 @@ def build_parser():
                         "template intervals its reads were cut from (read 1 '+', read 2 '-', the name without /1 and /2, the insert "
                         "size as the eleventh column), text built on the GPU; --compress gzips it; like --report it makes --rng mt "
                         "--devices 1 run one process per worker (same FASTQ and VCF files, byte for byte)")
+    g.add_argument("--bgzip", action="store_true",
+                   help="write the --store_mutations VCF as <output>.vcf.gz and the --origins text as <output>_origins.bedpe.gz: BGZF "
+                        "(blocked gzip: gzip.open, zcat and htslib read it), compressed on the GPU with copies from the line above, so "
+                        "the text never reaches the host; the FASTQ files are not affected (--compress and --ubam work beside it, and "
+                        "with both --compress and --bgzip these two files take this route); with the side-by-side workers of --rng mt "
+                        "--cpus W --devices 1 the .vcf is compressed into the same container on host threads")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

@@ -1,5 +1,5 @@
 // iss_api_origins.hip.h -- C ABI: every pair's source intervals as BEDPE text built on the device (iss_origins_emit_batch,
-// iss_origins_flush; the kernels of iss_origins.hip.h) and the host formatter of the same lines (iss_origins_host_text).
+// iss_origins_flush, iss_origins_compress; the kernels of iss_origins.hip.h, iss_bgzf_text.hip.h) and the host formatter of the same lines (iss_origins_host_text).
 //
 // The line (one per pair, tab separated, no header):
 //     {id} s1 e1 {id} s2 e2 {id}_{i}_{cpu} . + - isz \n
@@ -85,6 +85,7 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
         q.pairs_cap = pc;
         q.tiles_cap = tc;
     }
+    if (q.z.mode) { int rc_ = bgzt_reserve(ctx, q, q.z, q.cap); if (rc_) return rc_; }
     const int slot = q.next;
     { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
     hipStream_t st = ctx->stream;
@@ -125,7 +126,28 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     //  next rewrites the descriptors' set once this one has: these launches are the last readers now)
     if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], st));
     if (ctx->call_seq) HIP_TRY(ctx, hipEventRecord(ctx->ev_call_done[(int)((ctx->call_seq - 1) & 1u)], st));
-    return append_enqueue(ctx, q, slot, q.fd, q.d_total[slot]);
+    const uint64_t *d_total = q.d_total[slot];
+    if (q.z.mode) {  // the text stays on the device: its members are what the writer fetches (the line offsets are still resident)
+        int rc_ = bgzt_launch(ctx, q, q.z, slot, q.d_text[slot], bytes, q.d_off, (uint64_t)pairs, q.d_total[slot], st, &d_total);
+        if (rc_) return rc_;
+    }
+    return append_enqueue(ctx, q, slot, q.fd, d_total);
+}
+
+int iss_origins_compress(iss_ctx *ctx, int32_t mode) {
+    if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
+    return bgzt_set_mode(ctx, ctx->oq, ctx->oq.z, mode, "iss_origins_compress");
+}
+
+int iss_bgzf_text_code_build(const uint32_t *hist, uint32_t *entry, uint32_t *dentry, uint32_t *hdr_bits, uint32_t *hdr_words) {
+    if (!hist || !entry || !dentry || !hdr_bits || !hdr_words) return ISS_E_INVALID;
+    static iss::BgzfTextWork ws;  // (large for a stack frame; the function is a test hook, not re-entrant)
+    iss::bgzf_text_build_code(hist, &ws, 0, 1, iss::DeflateNoSync());
+    for (int s = 0; s < iss::DEFLATE_SYMS; ++s) entry[s] = ws.w.entry[s];
+    for (int d = 0; d < iss::BGZT_DSYMS; ++d) dentry[d] = ws.dentry[d];
+    for (int i = 0; i < iss::BGZT_HDR_WORDS; ++i) hdr_words[i] = ws.hdr[i];
+    *hdr_bits = ws.hdr_bits;
+    return 0;
 }
 
 int iss_origins_flush(iss_ctx *ctx) {

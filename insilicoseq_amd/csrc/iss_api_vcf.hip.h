@@ -1,4 +1,4 @@
-// iss_api_vcf.hip.h -- C ABI: the --store_mutations VCF text built on the device (iss_vcf_emit, iss_vcf_flush).
+// iss_api_vcf.hip.h -- C ABI: the --store_mutations VCF text built on the device (iss_vcf_emit, iss_vcf_flush, iss_vcf_compress).
 #pragma once
 
 namespace {
@@ -75,6 +75,7 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         HIP_TRY(ctx, hipMalloc(&v, tc * 8)); q.d_tiles = static_cast<uint64_t *>(v);
         q.slots_cap = sc; q.pairs_cap = pc; q.tiles_cap = tc;
     }
+    if (q.z.mode) { int rc_ = bgzt_reserve(ctx, q, q.z, bound); if (rc_) return rc_; }
     const int slot = q.next;
     { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
     // (the slot is free: nothing reads its text or its tables)
@@ -166,7 +167,12 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         HIP_TRY(ctx, hipMemcpyAsync(q.h_wb[slot] + J.wbase.size(), A.wbytes, J.wbase.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
     q.job_wfds[slot] = J.wfds;
-    return append_enqueue(ctx, q, slot, J.fd, q.d_off + n_slots);
+    const uint64_t *d_total = q.d_off + n_slots;
+    if (q.z.mode) {  // the rows' offsets are the line offsets (a slot without a row: an empty line)
+        int rc_ = bgzt_launch(ctx, q, q.z, slot, q.d_text[slot], bound, q.d_off, (uint64_t)n_slots, q.d_off + n_slots, st, &d_total);
+        if (rc_) return rc_;
+    }
+    return append_enqueue(ctx, q, slot, J.fd, d_total);
 }
 
 }  // namespace
@@ -232,6 +238,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
                          const int64_t *first_pair, const int64_t *n_pairs, const int32_t *cpu_numbers) {
     if (!ctx || !ctx->have_model || n_workers < 1 || !fds || !record_ids || !first_i || !first_pair || !n_pairs || !cpu_numbers)
         return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: bad argument");
+    if (ctx->vq.z.mode) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: the worker set's text is not compressed (iss_vcf_compress is 1)");
     const auto &t = ctx->mts;
     if (n_workers != t.W) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: one entry per worker of the seeded set");
     if (t.poisoned) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: the last iss_generate_mt_workers call failed (its rows are undefined)");
@@ -262,6 +269,11 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
     J.wstride = (uint64_t)t.mut_rows;
     J.n_slots = (int64_t)rows;
     return vcf_queue(ctx, J);
+}
+
+int iss_vcf_compress(iss_ctx *ctx, int32_t mode) {
+    if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
+    return bgzt_set_mode(ctx, ctx->vq, ctx->vq.z, mode, "iss_vcf_compress");
 }
 
 int iss_vcf_flush(iss_ctx *ctx) {

@@ -5,8 +5,9 @@
 namespace {
 
 // AppendWriteFn of the origins text (a call whose text is empty copies and writes nothing)
-std::string origins_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *, bool *) {
+std::string origins_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *code, bool *) {
     OriginsPipe &q = ctx->oq;
+    if (q.z.mode) return bgzt_write(q, q.z, slot, total, at, code, "origins text");  // (iss_origins_compress: the text's BGZF members)
     if (total > q.cap) return "origins text larger than its buffer";
     if (!total) return "";
     if (hipMemcpyAsync(q.h_text[slot], q.d_text[slot], total, hipMemcpyDeviceToHost, q.data_stream) != hipSuccess ||
@@ -40,6 +41,7 @@ void origins_shutdown(iss_ctx *ctx) {
     if (!append_stop(ctx, q)) return;
     origins_free_text(ctx);
     origins_free_work(ctx);
+    bgzt_free(q.z);
     q.tab.release();
     for (auto &p : q.d_total) { if (p) (void)hipFree(p); p = nullptr; }
 }

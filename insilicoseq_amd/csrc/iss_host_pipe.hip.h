@@ -139,6 +139,7 @@ int append_flush(iss_ctx *ctx, AppendPipe &q, bool keep_file = false) {
         code = q.error_code;
         q.error.clear();
     }
+    q.unflushed = false;
     if (q.fd >= 0) (void)lseek(q.fd, (off_t)q.off, SEEK_SET);
     if (!keep_file) q.fd = -1;
     if (!err.empty()) return fail(ctx, code, err);
@@ -177,6 +178,7 @@ int append_enqueue(iss_ctx *ctx, AppendPipe &q, int slot, int fd, const uint64_t
     }
     q.cv.notify_all();
     q.next ^= 1;
+    q.unflushed = true;
     return 0;
 }
 

@@ -117,6 +117,7 @@ struct AppendPipe : WriterSync {
     int64_t off = 0;  // of the file's next byte: moved by the writer thread (under `mu`) by what it wrote
     std::deque<int> jobs;  // slots, in call order
     int job_fd[2] = {-1, -1};
+    bool unflushed = false;  // a job was queued since the last flush (the caller's side only: a text pipe's mode is switched while false)
     AppendWriteFn write = nullptr;
     const char *noun = nullptr;  // "the {noun}'s kernels failed"
 };
@@ -169,6 +170,23 @@ struct FastqPipe : WriterSync {
 };
 constexpr size_t FASTQ_ID_MAX = 4096;
 
+// The BGZF stage of a text pipe (iss_origins_compress / iss_vcf_compress, iss_bgzf_text.hip.h; the functions:
+// iss_host_bgzf_text.hip.h): per slot the members and their offsets (the writer thread and the copy stream read them), one set of
+// work arrays (only kernels of the context's stream touch them, in order).  `cap` is the text size the buffers were made for.
+struct BgzfTextStage {
+    int mode = 0;                              // 0: the pipe appends its text, 1: the text's BGZF members
+    size_t cap = 0, comp_cap = 0;
+    uint32_t blocks_cap = 0;
+    uint8_t *d_comp[2] = {nullptr, nullptr};   // the members, back to back
+    uint8_t *h_comp[2] = {nullptr, nullptr};   // pinned
+    uint64_t *d_boff[2] = {nullptr, nullptr};  // [blocks_cap + 1]
+    uint32_t *d_dist = nullptr;                // [cap / 32 + 1]
+    uint32_t *d_bbytes = nullptr, *d_bcrc = nullptr;  // [blocks_cap]
+    uint32_t *d_hist = nullptr;
+    iss::BgzfTextCode *d_code = nullptr;
+    size_t job_text_cap[2] = {0, 0};           // the bound of the slot's text (the text's size comes back behind h_total: word 2)
+};
+
 // Device-formatted VCF text (--store_mutations): the kernels of iss_vcf.hip.h.  Its size copy rides the context's stream (no copy
 // stream).  Two slots of text; the work arrays are one set (only kernels of the context's stream touch them, in order).
 struct VcfPipe : AppendPipe {
@@ -188,6 +206,7 @@ struct VcfPipe : AppendPipe {
     std::vector<int> job_wfds[2];
     uint64_t *h_wb[2] = {nullptr, nullptr}, *d_wb[2] = {nullptr, nullptr};  // [2][wb_cap]: the workers' first rows (wbase), then their byte offsets
     size_t wb_cap[2] = {0, 0};
+    BgzfTextStage z;                     // iss_vcf_compress
 };
 
 // Unaligned BAM (--ubam): the records (k_ubam_format) and their BGZF members (iss_ubam.hip.h); the members' total size comes back
@@ -218,6 +237,7 @@ struct OriginsPipe : AppendPipe {
     uint32_t *d_len = nullptr;                  // [pairs_cap]
     uint64_t *d_off = nullptr, *d_tiles = nullptr;  // [pairs_cap], [tiles_cap]
     size_t pairs_cap = 0, tiles_cap = 0;
+    BgzfTextStage z;                            // iss_origins_compress
 };
 
 // MT mode: one worker's chain -- its two MT19937 streams (CPython random, numpy), their word buffers and cursors.  A context's

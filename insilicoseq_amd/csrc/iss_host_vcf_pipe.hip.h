@@ -5,7 +5,7 @@
 namespace {
 
 // AppendWriteFn of the VCF text
-std::string vcf_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *, bool *advance) {
+std::string vcf_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *code, bool *advance) {
     VcfPipe &q = ctx->vq;
     const std::vector<int> &wfds = q.job_wfds[slot];
     *advance = wfds.empty();  // (a worker set's descriptors are moved as they are written)
@@ -13,6 +13,9 @@ std::string vcf_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *,
         const uint32_t *st = reinterpret_cast<const uint32_t *>(q.h_total[slot] + 1);
         fprintf(stderr, "[vcf] slot %d: %u slots hold a row, %u rows stay, %llu bytes of text\n", slot, st[0], st[1], (unsigned long long)total);
     }
+    // iss_vcf_compress: the text's BGZF members.  The text-mode check below (the trailing line feed) reads the text on the host,
+    // where it never arrives in this mode; the members' BSIZE chain is walked instead.
+    if (q.z.mode) return bgzt_write(q, q.z, slot, total, at, code, "VCF text");
     if (total > q.text_cap[slot]) return "VCF text larger than its buffer";
     if (total > q.h_cap[slot]) {  // (pinned allocations are slow: leave room)
         if (q.h_text[slot]) (void)hipHostFree(q.h_text[slot]);
@@ -64,6 +67,7 @@ void vcf_shutdown(iss_ctx *ctx) {
     VcfPipe &q = ctx->vq;
     if (!append_stop(ctx, q)) return;
     vcf_free_work(ctx);
+    bgzt_free(q.z);
     q.tab.release();
     for (int sl = 0; sl < 2; ++sl) {
         if (q.d_text[sl]) (void)hipFree(q.d_text[sl]);

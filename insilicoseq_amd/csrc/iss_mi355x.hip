@@ -7,7 +7,8 @@
 // iss_fastq.hip.h, iss_deflate.hip.h, iss_vcf.hip.h (the --store_mutations text); `model` (BAM tallies, KDE): iss_bam.hip.h;
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
 // iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads),
-// iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text).
+// iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text),
+// iss_bgzf_text.hip.h (the VCF and origins text as BGZF members).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -43,6 +44,7 @@
 #include "iss_depth.hip.h"      // k_depth_*: per-base coverage depth of the reads (behind every other kernel, likewise)
 #include "iss_ubam.hip.h"       // k_ubam_format, k_bgzf_*: unaligned BAM records and their BGZF members (last, likewise)
 #include "iss_origins.hip.h"    // k_origins_len, k_origins_format: the pairs' source intervals as BEDPE text (last, likewise)
+#include "iss_bgzf_text.hip.h"  // k_bgzt_*: the VCF and origins text as BGZF members, copies from the line above (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // the output pipes' records, struct iss_ctx
@@ -50,6 +52,7 @@
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
 #include "iss_host_pipe.hip.h"        // shared by the output pipes: slot table, slot wait, the append pipe and its writer thread
 #include "iss_host_fastq_pipe.hip.h"  // the two FASTQ files' writer thread, flush
+#include "iss_host_bgzf_text.hip.h"   // the BGZF stage of the two text pipes: buffers, launches, the members' check and write
 #include "iss_host_vcf_pipe.hip.h"    // append pipe: the VCF text's check and write
 #include "iss_host_ubam_pipe.hip.h"   // append pipe: the BGZF members' check and write
 #include "iss_host_origins_pipe.hip.h"  // append pipe: the origins text's write

@@ -477,6 +477,21 @@ class ReadEngine(object):
         self._need_origins_entries()
         self._check(self._lib.iss_origins_flush(self._ctx))
 
+    def origins_compress(self, on=True):
+        """Mode of ``origins_emit_batch``: False (default) appends the text, True the text's BGZF members built on the device
+        (bgzf.py frames the file).  Switched only while nothing is queued (after ``origins_flush``)."""
+        self._need_bgzip_entries()
+        self._check(self._lib.iss_origins_compress(self._ctx, 1 if on else 0))
+
+    def vcf_compress(self, on=True):
+        """The same for ``vcf_emit``; ``vcf_emit_workers`` raises in this mode."""
+        self._need_bgzip_entries()
+        self._check(self._lib.iss_vcf_compress(self._ctx, 1 if on else 0))
+
+    def _need_bgzip_entries(self):
+        if not hasattr(self._lib, "iss_origins_compress"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_origins_compress / iss_vcf_compress: rebuild it" % _native.LIB_PATH)
+
     def _need_origins_entries(self):
         if not hasattr(self._lib, "iss_origins_emit_batch"):  # (no fall-back, like _need_vcf_entries)
             raise _native.NativeLibraryError("%s does not export iss_origins_emit_batch / iss_origins_flush: rebuild it" % _native.LIB_PATH)

@@ -671,7 +671,8 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
-                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False, origins=False):
+                    rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False, origins=False,
+                    bgzip=False):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
@@ -688,10 +689,15 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     pair) built on the device (ReadEngine.ubam_emit_batch) -- no BAM header, no EOF block: the parent frames the workers' blocks
     (ubam.assemble).  ``origins=True`` (`--origins`): the worker also writes ``{prefix}_origins.bedpe``, one line per pair with the
     record and the two template intervals its reads were cut from (origins.py), built on the device
-    (ReadEngine.origins_emit_batch) where the text job is handed over; without it no engine call is added."""
+    (ReadEngine.origins_emit_batch) where the text job is handed over; without it no engine call is added.  ``bgzip=True``
+    (`--bgzip`): ``{prefix}.vcf`` and ``{prefix}_origins.bedpe`` hold the BGZF members of their text, compressed on the device
+    (ReadEngine.vcf_compress / origins_compress), instead of the text -- no header member, no EOF block: the parent frames the
+    workers' members (bgzf.assemble)."""
     logger = logging.getLogger(__name__)
     if origins and os.environ.get("ISS_HOST_FASTQ", "") == "1":
         raise ValueError("origins=True needs the device path (unset ISS_HOST_FASTQ)")
+    if bgzip and (os.environ.get("ISS_HOST_FASTQ", "") == "1" or os.environ.get("ISS_HOST_VCF", "") == "1"):
+        raise ValueError("bgzip=True needs the device path (unset ISS_HOST_FASTQ and ISS_HOST_VCF)")
     if ubam and (compress or os.environ.get("ISS_HOST_FASTQ", "") == "1"):
         raise ValueError("ubam=True needs the device path (unset ISS_HOST_FASTQ) and takes no compress=True: BGZF blocks are compressed")
     if timings is not None:
@@ -714,6 +720,10 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     w.ubam = bool(ubam)
     if origins:
         w.origins_handle = origins_handle
+        if bgzip:
+            w.engine.origins_compress(True)
+    if bgzip and store_mutations:
+        w.engine.vcf_compress(True)
     w.plan(record for record, _n, _mode in work)
     if report:
         w.enable_tally()
