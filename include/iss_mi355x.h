@@ -377,6 +377,42 @@ int iss_output_tally(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint64_t
 int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int64_t *d_table, int32_t n_table, int32_t *d_diff);
 int iss_depth_finish(iss_ctx *ctx, const int32_t *d_diff, int64_t n_words, uint32_t *d_depth, const int64_t *d_table, int32_t n_table,
                      int32_t bin, uint64_t *d_stats, uint64_t *d_bins);
+/*
+ * Integer tallies of the MUTATION ROWS of the last generate call, built ON THE DEVICE and ADDED to d_tally: device memory of
+ * iss_error_tally_words(ctx) uint64 words that the caller owns and zeroes, so that a run accumulates over its batches -- what
+ * the run did to the reads (substitutions by position, phred and letters, insertions, deletions, events per read) without a
+ * row on the host or a byte of VCF (additive in ABI 8).  For read length L, Q = ISS_ERRTALLY_PHREDS,
+ * K = ISS_ERRTALLY_READ_BINS, the fields in this order, no padding:
+ *   dropped  [1]            calls whose rows could not be trusted (see Overflow); such a call adds here and nowhere else
+ *   pairs    [1]            pairs of the windows tallied
+ *   sub_q    [2][L][Q]      substitution rows by (mate, position, quality); a quality above Q - 1 counts in bin Q - 1
+ *   sub_mat  [2][L][5][5]   substitution rows by (mate, position, code of ref, code of alt): the ISS_EXPORT_CODES code -- A, C, G,
+ *                           T -> 0..3 in either case, every other byte 4
+ *   ins      [2][L][5]      insertion rows by (mate, position, code of alt): the inserted letter
+ *   del      [2][L][5]      deletion rows by (mate, position, code of ref): the letter that stands at `position` after the pop
+ *   per_read [2][3][K]      reads of the mate by their number of rows of the type (0 substitution, 1 insertion, 2 deletion),
+ *                           clamped to K - 1; bin 0 counts the reads with none
+ * 2 + 258 L + 6 K words.  A position outside [0, L - 1] counts in the nearest end bin (a guard: the loops that make the rows keep
+ * every position inside).  The rows that count are exactly those of iss_mutations_download (source 0: the last iss_generate /
+ * iss_generate_batch call, stale rows of rebuilt reads filtered out) or iss_mt_mutations_download (source 1: the last
+ * iss_generate_mt call) whose pair lies in rows [first_pair, first_pair + n_pairs) -- the window of iss_mutations_export, which
+ * may reach over either end of the call.  Both quirks of iss_mutations_export hold: a substitution back to the original letter
+ * is not a row, and indel positions are positions at the time of the event.  The rows of iss_generate_mt_workers are not served.
+ * Every count is an exact integer sum: the words depend neither on the launch geometry nor on the order of arrival.
+ * Stream and ownership as for iss_output_tally: asynchronous on the context's current stream behind the generation, no wait on
+ * the host; the rows may be generated anew as soon as the call returns.  (The first call allocates one work array of the output
+ * rows' size -- 16 bytes a pair; a call after the output rows grew waits for the stream to replace it.)
+ * Overflow: the device decides.  The kernels read the call's slot counter themselves; when it exceeds iss_mutations_reserve's
+ * capacity they add 1 to `dropped` and nothing else.  Source 1 with more rows than iss_mt_mutations_reserve holds: ISS_E_INVALID.
+ * ISS_E_INVALID, nothing launched: no model, no reservation in force or no generate call of that source since it was made, a
+ * window outside the reserved output rows, an unknown source, d_tally NULL with n_pairs > 0.  n_pairs == 0: 0, nothing launched.
+ * iss_error_tally_words: -1 without a model.
+ * ISS_ERRTALLY_WGS (environment, read per call like ISS_TALLY_WGS): the slot chunks k_errtally_rows runs per position tile.
+ */
+#define ISS_ERRTALLY_PHREDS 94 /* = ISS_TALLY_PHREDS */
+#define ISS_ERRTALLY_READ_BINS 64
+int64_t iss_error_tally_words(const iss_ctx *ctx); /* 2 + 258*L + 6*64 */
+int iss_mutations_tally(iss_ctx *ctx, int32_t source, int64_t first_pair, int64_t n_pairs, uint64_t *d_tally);
 /* iss_ctx_set_stream without the wait on the host (additive in ABI 8): everything queued on the context's streams so far is
  * ordered in front of what the context queues on `hip_stream` from now on, by events.  NULL: back to the context's own stream. */
 int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream);

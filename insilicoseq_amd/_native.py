@@ -34,6 +34,7 @@ EXPORTS = (
     "iss_ubam_emit_batch", "iss_ubam_flush", "iss_ubam_host_records",
     "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
     "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build",
+    "iss_error_tally_words", "iss_mutations_tally",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -172,6 +173,10 @@ def lib():
         L.iss_origins_compress.argtypes = [vp, i32]
         L.iss_vcf_compress.argtypes = [vp, i32]
         L.iss_bgzf_text_code_build.argtypes = [vp, vp, vp, vp, vp]
+    # (and tallies of the mutation rows built on the device; without them ReadEngine.error_tally raises)
+    if hasattr(L, "iss_mutations_tally"):
+        L.iss_error_tally_words.argtypes = [vp]
+        L.iss_mutations_tally.argtypes = [vp, i32, i64, i64, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -198,12 +203,15 @@ def lib():
                     "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
                     "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
                     "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
-                    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build") and not hasattr(L, name):
+                    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
+                    "iss_mutations_tally") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64
+    if hasattr(L, "iss_error_tally_words"):
+        L.iss_error_tally_words.restype = i64
     _lib = L
     return L
 

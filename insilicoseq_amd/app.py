@@ -185,15 +185,17 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
-            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False, bgzip=False):
+            fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False, bgzip=False,
+            error_report=False):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
     (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files; ``origins``: it also
     writes ``<prefix>_origins.bedpe``, every pair's source intervals; ``bgzip``: its ``.vcf`` and ``_origins.bedpe`` hold BGZF members
-    compressed on the device instead of text."""
+    compressed on the device instead of text; ``error_report``: it tallies its mutation rows on the device into
+    ``<prefix>.errtally.npy``."""
     logging.basicConfig(level=logging.WARNING)
-    if report or depth:
+    if report or depth or error_report:
         from .tensors import _torch
 
         _torch()  # (the tally words / the depth accumulator are torch tensors: torch's HIP runtime has to be the process's first)
@@ -215,6 +217,8 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
         more["origins"] = True
     if bgzip:
         more["bgzip"] = True
+    if error_report:
+        more["error_report"] = True
     worker_iterator(work, model, rank, prefix, seed, sequence_type, gc_bias, device=device, rng=rng, compress=compress, report=report, **more)
 
 
@@ -252,6 +256,26 @@ def _write_report(output, n_workers, read_length):
         fh.write("\n")
     for path in paths:
         os.remove(path)
+
+
+def _write_errors(output, n_workers, read_length, with_report):
+    """--error_report: the workers' error tallies (``<temp prefix>.errtally.npy``) summed into ``<output>_errtally.npy`` -- the raw
+    uint64 words, errtally.layout -- and ``<output>_errors.json`` (errtally.report_dict; with --report, whose ``<output>_tally.npy``
+    is then read back, also its ``calibration``); the workers' files are removed.  Returns the sum's ``dropped``."""
+    import json
+
+    from .errtally import merge, report_dict, split
+
+    paths = ["%s.errtally.npy" % temp_prefix(output, rank) for rank in range(n_workers)]
+    words = merge([np.load(path) for path in paths])
+    np.save(output + "_errtally.npy", words)
+    tally = np.load(output + "_tally.npy") if with_report else None
+    with open(output + "_errors.json", "w") as fh:
+        json.dump(report_dict(words, read_length, tally), fh)
+        fh.write("\n")
+    for path in paths:
+        os.remove(path)
+    return int(split(words, read_length)["dropped"][0])
 
 
 def _write_depth(output, n_workers, records, bin):
@@ -340,7 +364,8 @@ def _worker_set_wanted(args, report, depth):
     """Do the workers of this command run side by side in one context (worker_set_iterator) rather than one process each?"""
     return args.gpus > 1 and args.rng == "mt" and args.devices == 1 and args.seed is not None and args.gpus <= 1024 \
         and os.environ.get("ISS_HOST_FASTQ", "") != "1" and not report and not depth \
-        and not getattr(args, "origins", False)  # (--report, --depth, --origins: the set has no tally, depth or origins writer of its own -- the pool)
+        and not getattr(args, "origins", False) and not getattr(args, "error_report", False)
+    # (--report, --depth, --origins, --error_report: the set has no tally, depth, origins or error-tally writer of its own -- the pool)
 
 
 def _remove_ubam_files(output, workers):
@@ -351,6 +376,9 @@ def _remove_ubam_files(output, workers):
 
 def generate_reads(args):
     logger = logging.getLogger(__name__)
+    if getattr(args, "error_report", False) and not args.store_mutations:
+        logger.error("--error_report tallies the --store_mutations rows: add --store_mutations")
+        sys.exit(1)
     ubam = bool(getattr(args, "ubam", False))
     if ubam and _worker_set_wanted(args, bool(getattr(args, "report", False)),
                                    bool(getattr(args, "depth", False)) or int(getattr(args, "depth_bin", None) or 0) > 0):
@@ -389,6 +417,7 @@ def _generate_reads(args, ubam):
     workers = args.gpus
     report = bool(getattr(args, "report", False))
     origins = bool(getattr(args, "origins", False))
+    error_report = bool(getattr(args, "error_report", False))
     # --bgzip: the .vcf and the origins text leave the GPU as BGZF members; the parent frames the workers' members (bgzf.py)
     bgzip = bool(getattr(args, "bgzip", False))
     if bgzip and not (args.store_mutations or origins):
@@ -418,14 +447,17 @@ def _generate_reads(args, ubam):
     in_place = None
     if workers == 1:
         for j in jobs:
-            _worker(*j, records=records, ubam=ubam, origins=origins, bgzip=bgzip)
+            _worker(*j, records=records, ubam=ubam, origins=origins, bgzip=bgzip, **({"error_report": True} if error_report else {}))
     elif _worker_set_wanted(args, report, depth):
         in_place = _run_worker_set(jobs, records, error_model, args, device_gzip, workers)
         if in_place is not None:
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            pool.starmap(_worker, [j + (None, ubam, origins, bgzip) for j in jobs] if ubam or origins or bgzip else jobs)
+            if error_report:
+                pool.starmap(_worker, [j + (None, ubam, origins, bgzip, True) for j in jobs])
+            else:
+                pool.starmap(_worker, [j + (None, ubam, origins, bgzip) for j in jobs] if ubam or origins or bgzip else jobs)
     t_cat = time.perf_counter()
     # the side-by-side worker set keeps its text VCF route (one text job split over the workers' files): host BGZF further down
     bgzip_vcf_device = bgzip and bool(args.store_mutations) and in_place is None
@@ -464,6 +496,11 @@ def _generate_reads(args, ubam):
     logger.info("Workers %.2f s, concatenation of their files %.2f s" % (t_cat - t_gen, time.perf_counter() - t_cat))
     if report:
         _write_report(args.output, len(jobs), error_model.read_length)
+    if error_report:
+        dropped = _write_errors(args.output, len(jobs), error_model.read_length, report)
+        if dropped:  # (cannot happen: a call that overflows its row slots is repeated before it is tallied)
+            logger.error("--error_report: %d generate calls overflowed their mutation row slots and were not tallied" % dropped)
+            sys.exit(1)
     if depth:
         _write_depth(args.output, len(jobs), records, depth_bin)
     os.remove(genome_file)
@@ -528,6 +565,11 @@ def build_parser():
                         "profile, base composition, GC, mean-quality and insert-size histograms) and <output>_tally.npy (the raw "
                         "counters) next to the FASTQ files; with --rng mt --devices 1 the workers then run as one process each "
                         "instead of side by side in one context (same files, byte for byte)")
+    g.add_argument("--error_report", action="store_true",
+                   help="with --store_mutations: tally the mutation rows on the GPU as they are made and write <output>_errors.json "
+                        "(substitution, insertion and deletion rates per position, the substitution matrix, substitutions by phred, "
+                        "events per read; with --report also the phred calibration) and <output>_errtally.npy (the raw counters); "
+                        "like --report it makes --rng mt --devices 1 run one process per worker (same files, byte for byte)")
     g.add_argument("--depth", action="store_true",
                    help="mark where the reads fall on the GPU as they are generated and write <output>_depth.txt: per record, in "
                         "FASTA order, id, length, mean_depth, depth_variance, covered_fraction, max_depth of the nominal per-base "

@@ -104,6 +104,7 @@ void iss_ctx_destroy(iss_ctx *ctx) {
     if (ctx->d_pmut) (void)hipFree(ctx->d_pmut);
     truth_free_work(ctx);
     if (ctx->dw.d) (void)hipFree(ctx->dw.d);
+    if (ctx->ew.d) (void)hipFree(ctx->ew.d);
     if (ctx->d_ov_pairs) (void)hipFree(ctx->d_ov_pairs);
     if (ctx->d_ov_frags) (void)hipFree(ctx->d_ov_frags);
     free_mt(ctx);

@@ -410,6 +410,7 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
                                      m.n_resolved, m.n_walked, rows);
     m.mut_n = rows.n;
     m.mut_row0 = rows.row0;
+    m.mut_call = rc == 0 && m.d_mut != nullptr;
     return rc;
 }
 
@@ -1147,6 +1148,7 @@ int iss_mt_mutations_reserve(iss_ctx *ctx, int64_t capacity) {
     if (m.d_mut) (void)hipFree(m.d_mut);
     m.d_mut = nullptr;
     m.mut_cap = m.mut_n = 0;
+    m.mut_call = false;
     if (capacity) {
         void *p = nullptr;
         HIP_TRY(ctx, hipMalloc(&p, (size_t)capacity * sizeof(iss::MutRecord)));

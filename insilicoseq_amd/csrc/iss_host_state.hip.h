@@ -370,6 +370,12 @@ struct iss_ctx {
         uint8_t *d = nullptr;
         size_t cap = 0;
     } dw;
+    // iss_mutations_tally's work array: [pairs][2] u64, a read's rows by type (iss_errtally.hip.h), sized for the output rows on
+    // first use and replaced when they grow.  Only kernels of the context's stream touch it, in order.
+    struct ErrTallyWork {
+        uint64_t *d = nullptr;
+        size_t pairs_cap = 0;
+    } ew;
     int64_t last_row0 = 0, last_n = 0;  // rows of the last iss_generate call (their flags tell which rows are stale)
     std::vector<int64_t> last_first;     // the last call was a batch: its item_first (rows last_row0 + ...), else empty
     std::vector<int64_t> last_off;       // ... and the arena offsets its descriptors carry
@@ -385,6 +391,7 @@ struct iss_ctx {
         iss::MutRecord *d_mut = nullptr;  // --store_mutations rows of the last iss_generate_mt call
         int64_t mut_cap = 0, mut_n = 0;
         int64_t mut_row0 = 0;             // ... whose pair 0 is this output row
+        bool mut_call = false;            // an iss_generate_mt call has recorded rows under the reservation in force (iss_mutations_tally)
         hipEvent_t ev_main = nullptr, ev_fill = nullptr;  // ordering between ctx->stream and the fill stream
         iss::MtPhredAmb *d_amb = nullptr;  // BasicErrorModel: [0, CAP) phreds for the host, [CAP, 2 CAP) its answers
         int32_t *d_mut_cnt = nullptr;     // k_mt_emit, --store_mutations: rows per (pair, mate), then their offsets

@@ -8,7 +8,8 @@
 // iss_export.hip.h (the rows as dense device arrays for a consumer on the GPU), iss_truth.hip.h (their mutation rows likewise),
 // iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads),
 // iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text),
-// iss_bgzf_text.hip.h (the VCF and origins text as BGZF members).
+// iss_bgzf_text.hip.h (the VCF and origins text as BGZF members), iss_errtally.hip.h (integer tallies of the mutation rows: what
+// a run did to the reads).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,7 @@
 #include "iss_ubam.hip.h"       // k_ubam_format, k_bgzf_*: unaligned BAM records and their BGZF members (last, likewise)
 #include "iss_origins.hip.h"    // k_origins_len, k_origins_format: the pairs' source intervals as BEDPE text (last, likewise)
 #include "iss_bgzf_text.hip.h"  // k_bgzt_*: the VCF and origins text as BGZF members, copies from the line above (last, likewise)
+#include "iss_errtally.hip.h"   // k_errtally_rows, k_errtally_reads: tallies of the mutation rows (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_host_state.hip.h"       // the output pipes' records, struct iss_ctx
@@ -68,3 +70,4 @@
 #include "iss_api_depth.hip.h"
 #include "iss_api_ubam.hip.h"
 #include "iss_api_origins.hip.h"
+#include "iss_api_errtally.hip.h"

@@ -582,6 +582,32 @@ class ReadEngine(object):
         if not hasattr(self._lib, "iss_output_tally"):  # (no fall-back, like _need_export_entries)
             raise _native.NativeLibraryError("%s does not export iss_tally_words / iss_output_tally: rebuild it" % _native.LIB_PATH)
 
+    def error_tally_words(self):
+        """uint64 words of an error tally of this engine's model (include/iss_mi355x.h: iss_error_tally_words; errtally.layout)."""
+        self._need_errtally_entries()
+        n = self._lib.iss_error_tally_words(self._ctx)
+        if n < 0:
+            raise EngineError(_native.E_INVALID, "error_tally_words: upload a model first")
+        return int(n)
+
+    def error_tally(self, first_pair, n_pairs, tally_ptr, source="philox"):
+        """Add the tallies of the mutation rows of the last generate() / generate_batch() call (``source="philox"``, after
+        mutations_reserve()) or generate_mt() call (``"mt"``, after mt_mutations_reserve()) whose pair lies in output rows
+        [first_pair, +n_pairs) -- substitutions by position, phred and letters, insertions, deletions, rows per read, pairs --
+        to the error_tally_words() uint64 words at ``tally_ptr`` (a raw device address; the caller's memory, zeroed by the
+        caller).  A Philox call that overflowed its reserved slots adds 1 to ``dropped`` and nothing else.  Asynchronous on
+        the engine's current stream, behind the generation; nothing waits on the host (include/iss_mi355x.h:
+        iss_mutations_tally; errtally.split names the fields)."""
+        if source not in ("philox", "mt"):
+            raise ValueError("source must be 'philox' or 'mt'")
+        self._need_errtally_entries()
+        self._check(self._lib.iss_mutations_tally(self._ctx, 0 if source == "philox" else 1, int(first_pair), int(n_pairs),
+                                                  C.c_void_p(int(tally_ptr)) if tally_ptr else None))
+
+    def _need_errtally_entries(self):
+        if not hasattr(self._lib, "iss_mutations_tally"):  # (no fall-back, like _need_tally_entries)
+            raise _native.NativeLibraryError("%s does not export iss_error_tally_words / iss_mutations_tally: rebuild it" % _native.LIB_PATH)
+
     def depth_mark(self, first_pair, n_pairs, table_ptr, n_table, diff_ptr):
         """Add the template intervals of rows [first_pair, +n_pairs) to the int32 difference array at ``diff_ptr``: +1 at the
         start, -1 at the end of each pair's forward and reverse interval, clamped to the record (depth.py has the definition).

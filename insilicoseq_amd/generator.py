@@ -332,6 +332,7 @@ class Worker(object):
         self.ordinal = 0
         self.tally = None  # --report: the device words every generate call's rows are tallied into (enable_tally)
         self.depth_diff = None  # --depth: the device's difference array over the distinct records of the work list (enable_depth)
+        self.errtally = None  # --error_report: the device words every generate call's mutation rows are tallied into (enable_errtally)
         self.genomes = GenomeStore(
             self.engine, self,
             budget_divisor=1,     # the whole GENOME_BUDGET: beside the genomes a worker holds one batch of rows and its text
@@ -346,6 +347,7 @@ class Worker(object):
     def close(self):
         self.tally = None
         self.depth_diff = None
+        self.errtally = None
         self._depth_tables = []
         self.engine.close()
 
@@ -368,6 +370,28 @@ class Worker(object):
         """The tally so far as uint64 words on the host (waits for the engine)."""
         self.engine.synchronize()
         return self.tally.cpu().numpy().view(np.uint64).copy()
+
+    def enable_errtally(self):
+        """--error_report: one zeroed tensor of ReadEngine.error_tally_words() words on the engine's device; errtally_rows() adds
+        to it."""
+        from .tensors import _torch
+
+        torch = _torch()
+        with torch.cuda.device(self.engine.device):
+            self.errtally = torch.zeros(self.engine.error_tally_words(), dtype=torch.int64, device=torch.device("cuda", self.engine.device))
+            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
+
+    def errtally_rows(self, first_pair, n_pairs):
+        """Tally the mutation rows of the generate call just made whose pair lies in rows [first_pair, +n_pairs) -- where
+        tally_rows stands: once _take_mutations has settled the call (a repeated one is counted once) and before its rows are
+        generated anew.  Asynchronous, like the text jobs."""
+        if self.errtally is not None:
+            self.engine.error_tally(first_pair, n_pairs, self.errtally.data_ptr(), source=self.rng)
+
+    def errtally_words_host(self):
+        """The error tally so far as uint64 words on the host (waits for the engine)."""
+        self.engine.synchronize()
+        return self.errtally.cpu().numpy().view(np.uint64).copy()
 
     def enable_depth(self, records, ordinals):
         """--depth: one zeroed int32 difference array on the engine's device over the distinct records of the work list (in
@@ -467,6 +491,7 @@ class Worker(object):
             gen()
             _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
             self.tally_rows(0, n)
+            self.errtally_rows(0, n)
             self.depth_rows(0, n, [record])
             self.origins_rows([(record.id, done, 0, n)], [record])
             if self.ubam:  # (one stream: both handles are the .bam)
@@ -573,7 +598,7 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         nonlocal pending, cur, pending_records
         if not pending:
             return
-        marked = origins_done = False
+        marked = origins_done = errors_done = False
         row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
         for rid, _gid, n, first_i in pending:
             emit.append((rid, first_i, row, n))
@@ -596,6 +621,9 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                                  out_first_pair=item[2])
                 gen1()
                 _take_mutations(route, eng, gen1, mutations_handle, [item], w.cpu_number, "philox")
+                if getattr(w, "errtally", None) is not None:  # --error_report: the item is a call of its own, the next one clears its rows
+                    w.errtally_rows(item[2], n)
+                    errors_done = True
                 if getattr(w, "depth_diff", None) is not None:  # --depth: the item is a call of its own (item 0 of its rows)
                     w.depth_rows(item[2], n, [record])
                     marked = True
@@ -605,6 +633,8 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
                 ordinal += n
         if getattr(w, "tally", None) is not None:  # --report (every call of the batch has settled: a repeated one is not counted twice)
             w.tally_rows(0, row)
+        if getattr(w, "errtally", None) is not None and not errors_done:  # --error_report, likewise: the batch call's rows
+            w.errtally_rows(0, row)
         if getattr(w, "depth_diff", None) is not None and not marked:  # --depth, likewise: the batch call's items through its table
             w.depth_rows(0, row, pending_records)
         if getattr(w, "origins_handle", None) is not None and not origins_done:  # --origins: one text job beside the reads'
@@ -672,7 +702,7 @@ def simulate_reads(record, error_model, n_pairs, cpu_number, forward_handle, rev
 
 def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence_type, gc_bias, device=None,
                     rng="philox", compress=False, timings=None, report=False, depth=False, ordinals=None, ubam=False, origins=False,
-                    bgzip=False):
+                    bgzip=False, error_report=False):
     """iss/generator.py:223-251 on GPU ``device`` (default: ``cpu_number``).  ``rng="mt"`` consumes the
     reference's two Mersenne-Twister streams on the device: the files then equal the reference's byte for
     byte (sequential, ~1e5 pairs/s); ``rng="philox"`` is the parallel path.  ``compress=True``: the two FASTQ files
@@ -692,8 +722,12 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     (ReadEngine.origins_emit_batch) where the text job is handed over; without it no engine call is added.  ``bgzip=True``
     (`--bgzip`): ``{prefix}.vcf`` and ``{prefix}_origins.bedpe`` hold the BGZF members of their text, compressed on the device
     (ReadEngine.vcf_compress / origins_compress), instead of the text -- no header member, no EOF block: the parent frames the
-    workers' members (bgzf.assemble)."""
+    workers' members (bgzf.assemble).  ``error_report=True`` (`--error_report`; the model must store its mutations): the mutation
+    rows of every generate call are tallied on the device (ReadEngine.error_tally) and the worker's tally -- errtally.layout,
+    uint64 words -- is written to ``{prefix}.errtally.npy`` at the end; without it no engine call is added."""
     logger = logging.getLogger(__name__)
+    if error_report and not bool(getattr(error_model, "store_mutations", False)):
+        raise ValueError("error_report=True needs a model that stores its mutations (--store_mutations)")
     if origins and os.environ.get("ISS_HOST_FASTQ", "") == "1":
         raise ValueError("origins=True needs the device path (unset ISS_HOST_FASTQ)")
     if bgzip and (os.environ.get("ISS_HOST_FASTQ", "") == "1" or os.environ.get("ISS_HOST_VCF", "") == "1"):
@@ -727,6 +761,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     w.plan(record for record, _n, _mode in work)
     if report:
         w.enable_tally()
+    if error_report:
+        w.enable_errtally()
     if depth:
         w.enable_depth([record for record, _n, _mode in work], ordinals if ordinals is not None else range(len(work)))
     if timings is not None:
@@ -759,6 +795,8 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                 w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
             if report:
                 np.save("%s.tally.npy" % worker_prefix, w.tally_words_host())
+            if error_report:
+                np.save("%s.errtally.npy" % worker_prefix, w.errtally_words_host())
             if depth:
                 w.depth_save("%s.depth.npz" % worker_prefix)
             if timings is not None:

@@ -347,15 +347,26 @@ class ReadTensorStream(object):
     -> (depth torch.uint32 [words], stats torch.uint64 [len(records), 4][, bins torch.uint64 with ``bin`` > 0]) computed on the
     device on torch's current stream (ReadEngine.depth_finish), not in place: iteration can go on, and a later call sees more.
     A stream refuses to mark more than 2^30 pairs (EngineError(E_INVALID)): a depth stays below 2^31.  ``depth=False`` (the
-    default): both attributes are None, no launch is added."""
+    default): both attributes are None, no launch is added.
+
+    ``error_tally=True``: what the run did to the reads (errtally.py has the definition).  The stream owns
+    ``stream.error_tally``, one zeroed torch.int64 tensor of ReadEngine.error_tally_words() words on the device, and adds the
+    tallies of every batch's mutation rows to it (ReadEngine.error_tally; errtally.split names the fields) behind the batch's
+    generation, on the same stream, with no wait on the host; it does not depend on ``batch_pairs``.  It needs the mutation rows:
+    with ``truth=True`` it shares that reservation, without it the stream reserves ``mutation_slots`` slots of its own (default:
+    default_mutation_slots()) and the batches stay without ``truth``.  The overflow rule above covers it: a batch that
+    overflowed adds 1 to the tally's ``dropped`` and nothing else, and the stream raises when the next batch is asked for.
+    ``error_tally=False`` (the default): the attribute is None, no launch is added."""
 
     def __init__(self, records, error_model, work, batch_pairs, seed=0, device=0, encoding="codes", sequence_type="metagenomics",
-                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False, depth=False):
+                 gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False, depth=False,
+                 error_tally=False):
         from .engine import ReadEngine
 
         if encoding not in EXPORT_ENCODINGS:
             raise EngineError(E_INVALID, "ReadTensorStream: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
         self.truth, self.events_capacity = bool(truth), int(events_capacity)
+        self._rows = self.truth or bool(error_tally)  # the mutation rows are reserved, every batch's overflow word is looked at
         if self.events_capacity < 0 or (self.events_capacity and not self.truth):
             raise EngineError(E_INVALID, "ReadTensorStream: events_capacity needs truth=True and must not be negative")
         torch = _torch()
@@ -403,7 +414,10 @@ class ReadTensorStream(object):
                 self.depth_diff = torch.zeros(n_words, dtype=torch.int32, device=dev)
                 # the table row of every work item: a batch's items are a slice of it
                 self._work_table = torch.index_select(self.depth_table, 0, self._work_record.long()).contiguous()
-            if self.truth:
+            self.error_tally = None
+            if error_tally:
+                self.error_tally = torch.zeros(self.engine.error_tally_words(), dtype=torch.int64, device=dev)
+            if self._rows:
                 if mutation_slots is None:
                     mutation_slots = default_mutation_slots(error_model, min(self.batch_pairs, max(self.n_pairs, 1)),
                                                             torch.cuda.get_device_properties(self.engine.device).multi_processor_count)
@@ -460,7 +474,8 @@ class ReadTensorStream(object):
         event.synchronize()  # (normally passed long ago)
         if int(word.item()) < 0:
             raise EngineError(E_NOMEM, "ReadTensorStream: batch %d asked for more mutation row slots than mutation_slots=%d holds; "
-                                       "its truth and events are not valid (pass a larger mutation_slots)" % (index, self.mutation_slots))
+                                       "its truth and events are not valid%s (pass a larger mutation_slots)"
+                              % (index, self.mutation_slots, "" if self.error_tally is None else ", the error tally counts it as dropped"))
 
     def __iter__(self):
         torch = _torch()
@@ -485,12 +500,14 @@ class ReadTensorStream(object):
 
                         self._marked = count_marked(self._marked, n)
                         eng.depth_mark(0, n, self._work_table[first_item:].data_ptr(), len(counts), self.depth_diff.data_ptr())
+                    if self.error_tally is not None:
+                        eng.error_tally(0, n, self.error_tally.data_ptr())
                     count = out.n_events
-                    if self.truth and count is None:
+                    if self._rows and count is None:
                         # no events wanted: the overflow word alone, from an empty window (one small kernel, no row is ordered)
                         count = torch.empty((), dtype=torch.int64, device=out.bases.device)
                         eng.export_mutations(0, 0, events_ptr=self._no_events.data_ptr(), capacity=0, n_events_ptr=count.data_ptr())
-                if self.truth:
+                if self._rows:
                     word = self._words[index & 1]
                     word.copy_(count, non_blocking=True)
                     event = torch.cuda.Event()
