@@ -704,6 +704,53 @@ int iss_bam_feed(iss_bam *bam, const uint8_t *data, int64_t n_bytes, const int64
 int iss_bam_tally_download(iss_bam *bam, uint64_t *tally, int64_t *bad_record, int32_t *bad_code);
 int iss_bam_kde(iss_bam *bam, int32_t read_length, int32_t with_isize, double *qcdf, double *isize_cdf);
 
+/*
+ * `report`: the tallies of iss_output_tally over FASTQ TEXT, built ON THE DEVICE (additive in ABI 8): what a
+ * read set from a sequencer, or a file written earlier, looks like -- to put beside the tally of a run.  A context of its own, no
+ * iss_ctx and no model.  max_len (1 .. ISS_FQ_MAX_LEN) is the longest read the context takes; its words are iss_output_tally's
+ * layout at L = max_len and one field behind it, iss_fq_tally_words words in all (-1 for NULL):
+ *   pairs [1] | qual [2][L][Q] | base [2][L][5] | gc [2][L + 1] | meanq [2][Q] | insert [I] | length [2][L + 1]
+ * A feed is one mate: R1's file feeds mate 0, R2's mate 1.  The phred is the quality byte - 33; base codes and the G / C test are
+ * iss_output_tally's.  qual and base count positions 0 .. len - 1 of a read of length len; meanq is floor(sum of phreds / len) of
+ * the read's own length; a read of length 0 counts in length[mate][0] and gc[mate][0] and nowhere else; pairs counts the good
+ * records of mate 0; insert stays zero (a FASTQ file does not say it).  Every count is an exact integer sum: the words depend
+ * neither on the launch geometry nor on how the text was cut into chunks.
+ *
+ * iss_fq_feed: `text` is HOST memory, n_bytes of FASTQ text that holds whole four-line records (@name, bases, +, qualities; a line
+ * ends at '\n', one '\r' directly before it belongs to the terminator; wrapped FASTQ is not taken and shows as ISS_FQ_REC_LENGTHS
+ * or ISS_FQ_REC_NO_AT).  Records are found by line number modulo 4, never by looking for '@'.  The caller may reuse `text` as soon
+ * as the call returns: the bytes go through one of the context's pinned staging buffers, so that the copy of one chunk overlaps the
+ * kernels of the chunk before.  The first feed that needs more room allocates it; a feed waits for the device only to get its
+ * staging buffer back.  A bad record is not tallied, the records after it are; the FIRST bad record per mate (index over all records
+ * fed for the mate) is kept with its ISS_FQ_REC_* code -- the smallest code that applies to it -- and the caller decides what to
+ * do with it.  ISS_E_INVALID, nothing launched: mate outside {0, 1}, n_bytes < 0 or >= 2^31, text NULL with n_bytes > 0.
+ * n_bytes == 0: 0, nothing launched.
+ * iss_fq_download waits for everything fed, then copies the words, the whole records seen per mate (records[2]) and the first bad
+ * record per mate (bad_record[2]: -1 for none; bad_code[2]).  iss_fq_reset zeroes the words and the counts.
+ * iss_fq_kernel_ms waits for everything fed, then gives the time the kernels of all feeds since the last reset took on the device,
+ * from HIP events around each feed's launches (tools/report_bench.py: the kernels apart from the reading and the copies).
+ * ISS_FQTALLY_WGS (environment, read per call like ISS_TALLY_WGS): the workgroups the record kernels aim at (the per-position
+ * kernel: per column of 64 positions).
+ */
+#define ISS_FQ_MAX_LEN 1024
+#define ISS_FQ_REC_NO_AT 1      /* line 0 of the record does not start with '@' */
+#define ISS_FQ_REC_NO_PLUS 2    /* line 2 does not start with '+' */
+#define ISS_FQ_REC_LENGTHS 3    /* the bases and the quality line differ in length */
+#define ISS_FQ_REC_TOO_LONG 4   /* a read longer than the context's max_len */
+#define ISS_FQ_REC_QUAL_RANGE 5 /* a quality byte below 33 or above 126 */
+#define ISS_FQ_REC_TRUNCATED 6  /* the chunk's line count is no multiple of 4, or its last byte is not '\n': the record behind
+                                 * the chunk's last whole one */
+
+typedef struct iss_fq iss_fq;
+int iss_fq_create(int device_ordinal, int32_t max_len, iss_fq **out);
+void iss_fq_destroy(iss_fq *fq);
+const char *iss_fq_last_error(const iss_fq *fq);
+int iss_fq_reset(iss_fq *fq);
+int64_t iss_fq_tally_words(const iss_fq *fq); /* iss_tally_words at L = max_len, + 2 * (max_len + 1) */
+int iss_fq_feed(iss_fq *fq, int32_t mate, const uint8_t *text, int64_t n_bytes);
+int iss_fq_download(iss_fq *fq, uint64_t *tally, int64_t *records, int64_t *bad_record, int32_t *bad_code);
+int iss_fq_kernel_ms(iss_fq *fq, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@ EXPORTS = (
     "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
     "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build",
     "iss_error_tally_words", "iss_mutations_tally",
+    "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words", "iss_fq_feed", "iss_fq_download",
+    "iss_fq_kernel_ms",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -45,6 +47,15 @@ BAM_REC_ERRORS = {
     1: "malformed record", 2: "read longer than 301 bases", 3: "read without qualities", 4: "CIGAR operation other than M/I/D/S/H",
     5: "mapped read without an MD tag", 6: "MD tag does not match the CIGAR", 7: "indel position outside the read",
     8: "quality above 93", 9: "CIGAR length differs from the read length",
+}
+
+
+# `report` (include/iss_mi355x.h: ISS_FQ_*)
+FQ_MAX_LEN = 1024
+FQ_REC_ERRORS = {
+    1: "line 1 of the record does not start with '@'", 2: "line 3 of the record does not start with '+'",
+    3: "the bases and the quality line differ in length", 4: "read longer than --max_length",
+    5: "quality character outside '!' .. '~'", 6: "truncated record (the file ends inside it)",
 }
 
 
@@ -177,6 +188,18 @@ def lib():
     if hasattr(L, "iss_mutations_tally"):
         L.iss_error_tally_words.argtypes = [vp]
         L.iss_mutations_tally.argtypes = [vp, i32, i64, i64, vp]
+    # (and `report`, the tallies over FASTQ text; without them fastq_report.FastqTally raises)
+    if hasattr(L, "iss_fq_feed"):
+        L.iss_fq_create.argtypes = [C.c_int, i32, C.POINTER(vp)]
+        L.iss_fq_destroy.argtypes = [vp]
+        L.iss_fq_destroy.restype = None
+        L.iss_fq_last_error.argtypes = [vp]
+        L.iss_fq_last_error.restype = C.c_char_p
+        L.iss_fq_reset.argtypes = [vp]
+        L.iss_fq_tally_words.argtypes = [vp]
+        L.iss_fq_feed.argtypes = [vp, i32, vp, i64]
+        L.iss_fq_download.argtypes = [vp, vp, vp, vp, vp]
+        L.iss_fq_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -204,14 +227,18 @@ def lib():
                     "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
                     "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
                     "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
-                    "iss_mutations_tally") and not hasattr(L, name):
+                    "iss_mutations_tally", "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words",
+                    "iss_fq_feed", "iss_fq_download", "iss_fq_kernel_ms") and not hasattr(L, name):
             continue
-        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error"):
+        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error", "iss_fq_destroy",
+                        "iss_fq_last_error"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64
     if hasattr(L, "iss_error_tally_words"):
         L.iss_error_tally_words.restype = i64
+    if hasattr(L, "iss_fq_tally_words"):
+        L.iss_fq_tally_words.restype = i64
     _lib = L
     return L
 

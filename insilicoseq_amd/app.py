@@ -532,6 +532,67 @@ def model_from_bam(args):
     return 0
 
 
+def report_from_fastq(args):
+    """`report`: the --report tallies of existing FASTQ files, built on the GPU (fastq_report.py); errors are one line on stderr
+    and exit status 1."""
+    import json
+    import zlib
+
+    import numpy as np
+
+    from . import fastq_report, tally
+    from ._native import FQ_REC_ERRORS, EngineError, NativeLibraryError
+
+    logging.basicConfig(level=logging.ERROR if args.quiet else logging.INFO)
+    logger = logging.getLogger(__name__)
+
+    def fail(message):
+        sys.stderr.write("ERROR: %s\n" % message)
+        return 1
+
+    try:
+        other = None
+        if args.against:  # (before the GPU is opened)
+            try:
+                other = np.load(args.against, allow_pickle=False)
+            except (OSError, ValueError) as e:
+                return fail("%s: %s" % (args.against, str(e).splitlines()[0] if str(e) else type(e).__name__))
+            other_length = fastq_report.read_length_of_words(other.size) if other.ndim == 1 else None
+            if other_length is None:
+                return fail("%s: %s words fit no read length (a tally of read length L has %s words)"
+                            % (args.against, "x".join(str(n) for n in other.shape), "200 L + 2239"))
+        files = [args.read1] + ([args.read2] if args.read2 else [])
+        t0 = time.perf_counter()
+        with fastq_report.FastqTally(args.device, args.max_length) as dev:
+            for mate, path in enumerate(files):
+                logger.info("Tallying %s" % path)
+                dev.feed_file(path, mate)
+            res = dev.result()
+        logger.info("%s records in %.2f s" % (" + ".join(str(n) for n in res["records"][:len(files)]), time.perf_counter() - t0))
+        for mate, path in enumerate(files):
+            if res["bad_record"][mate] >= 0:
+                code = res["bad_code"][mate]
+                return fail("%s: record %d: %s" % (path, res["bad_record"][mate], FQ_REC_ERRORS.get(code, "error %d" % code)))
+        if args.read2 and res["records"][0] != res["records"][1]:
+            return fail("%s holds %d records and %s holds %d: not the two files of one run"
+                        % (args.read1, res["records"][0], args.read2, res["records"][1]))
+        L = res["read_length"]
+        np.save(args.output + "_tally.npy", res["tally"])
+        np.save(args.output + "_lengths.npy", res["lengths"])
+        report = tally.report_dict(res["tally"], L)
+        report["read_length_histogram"] = [tally._trim(res["lengths"][m]) for m in range(2)]
+        with open(args.output + "_report.json", "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+        if other is not None:
+            with open(args.output + "_compare.json", "w") as fh:
+                json.dump(fastq_report.compare_tallies(res["tally"], L, other, other_length), fh, indent=1)
+                fh.write("\n")
+    except (EngineError, NativeLibraryError, OSError, EOFError, ValueError, zlib.error) as e:  # (a broken .gz: the last two)
+        return fail("%s: %s" % (args.read1, str(e).splitlines()[0] if str(e) else type(e).__name__))
+    return 0
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="insilicoseq_amd", description="iss generate on MI355X")
     sub = p.add_subparsers(dest="cmd")
@@ -602,6 +663,18 @@ def build_parser():
     m.add_argument("--seed", type=int, default=0, help="Philox key of the subsample (more than 1 000 000 mapped records)")
     m.add_argument("--device", type=int, default=0, help="GPU ordinal")
     m.add_argument("--dense", action="store_true", help="also write <prefix>.dense.npz (this project's pickle-free form)")
+    r = sub.add_parser("report", help="the --report tallies of existing FASTQ files, built on the GPU; --against compares them "
+                                      "with another tally")
+    r.add_argument("--read1", "-1", required=True, metavar="R1.fastq[.gz]")
+    r.add_argument("--read2", "-2", default=None, metavar="R2.fastq[.gz]", help="the second reads (without it mate 2's fields are zero)")
+    r.add_argument("--output", "-o", required=True,
+                   help="output prefix: writes <prefix>_tally.npy (the counters, in the layout of generate --report at the longest "
+                        "read seen), <prefix>_report.json and <prefix>_lengths.npy (reads per mate and length)")
+    r.add_argument("--against", default=None, metavar="OTHER_tally.npy",
+                   help="also write <prefix>_compare.json: these reads against another tally (of generate --report, or of report)")
+    r.add_argument("--max_length", type=int, default=1024, metavar="N", help="longest read taken (1 .. 1024, default 1024)")
+    r.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    r.add_argument("--quiet", "-q", action="store_true")
     return p
 
 
@@ -610,6 +683,8 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.cmd == "model":
         return model_from_bam(args)
+    if args.cmd == "report":
+        return report_from_fastq(args)
     if args.cmd != "generate":
         p.print_help()
         return 1
