@@ -18,6 +18,7 @@ One worker == one GPU (``cpu_number`` == rank).  The uniforms come from Philox a
 CPU oracle in Philox mode, which in MT mode is bit-identical to the reference.
 """
 import contextlib
+import functools
 import logging
 import os
 import sys
@@ -26,6 +27,7 @@ import time
 import numpy as np
 
 from . import _native
+from .depth import count_marked, depth_table
 from .engine import ReadEngine, fastq_write
 from .model import DenseModel
 
@@ -287,8 +289,145 @@ class GenomeStore(object):
             self.drop()
 
 
+def _device_zeros(engine, n_words, dtype):
+    """``n_words`` zeroed words (``dtype``: "int32" / "int64") as a torch tensor on the engine's device, for the engine to add to.
+    torch zeroes them on its own stream and the engine adds on its own: torch is waited for here."""
+    from .tensors import _torch
+
+    torch = _torch()
+    with torch.cuda.device(engine.device):
+        words = torch.zeros(n_words, dtype=getattr(torch, dtype), device=torch.device("cuda", engine.device))
+        torch.cuda.synchronize()
+    return words
+
+
+class _Consumer(object):
+    """What reads a settled generate call -- _take_mutations has taken its rows and repeated the call if it had to, so a repeated
+    call is read once -- before its rows are generated anew.  Worker.consumers holds those switched on, in
+    the fixed order tally, error tally, depth, origins, reads; the work loops know nothing else about them.
+    take(items, records): ``items`` are the text job's tuples (record id, id of the first pair, first output row, pairs), their
+    rows contiguous from items[0][2], ``records`` the record of each item; asynchronous, like the text jobs.  flush(): drain its
+    pipe before the handles close.  save(prefix): write the worker's temp file."""
+    # False: it reads the OUTPUT ROWS -- once per batch (the arena fall-back's calls lay their rows side by side).
+    # True: it reads what the next generate call overwrites (pair descriptors, mutation rows) -- behind every call.
+    per_call = False
+
+    def flush(self):
+        pass
+
+    def save(self, prefix):
+        pass
+
+
+class Tally(_Consumer):
+    """Zeroed device words that ``add(first output row, rows, address of the words)`` adds the rows of a call to, written to
+    ``{prefix}.{suffix}.npy`` as uint64 -- --report: ReadEngine.tally over the output rows (tally.tally_layout); --error_report:
+    ReadEngine.error_tally over the call's mutation rows (errtally.layout), which the next call overwrites (``per_call``)."""
+
+    def __init__(self, engine, n_words, add, suffix, per_call):
+        self.engine, self.add, self.suffix, self.per_call = engine, add, suffix, per_call
+        self.words = _device_zeros(engine, n_words, "int64")
+
+    def take(self, items, records):
+        self.add(items[0][2], sum(item[3] for item in items), self.words.data_ptr())
+
+    def save(self, prefix):
+        self.engine.synchronize()
+        np.save("%s.%s.npy" % (prefix, self.suffix), self.words.cpu().numpy().view(np.uint64).copy())
+
+
+class Depth(_Consumer):
+    """--depth: the call's template intervals marked (ReadEngine.depth_mark) into one int32 difference array over the distinct
+    ``records`` of the work list (in order of first appearance; ``ordinals``: their ordinals in the FASTA), whatever GenomeStore
+    groups and arena offsets they come to stand in (depth.py) -> ``{prefix}.depth.npz``, for the parent's merge."""
+    per_call = True
+
+    def __init__(self, engine, records, ordinals):
+        self.engine, self.row, self.ordinals, lengths = engine, {}, [], []
+        for record, ordinal in zip(records, ordinals):
+            if id(record) not in self.row:
+                self.row[id(record)] = len(lengths)
+                self.ordinals.append(int(ordinal))
+                lengths.append(len(record.seq))
+        self.table, n_words = depth_table(lengths)
+        self.uploaded, self.pairs = [], 0  # the calls' tables the engine may still read; pairs taken so far
+        self.diff = _device_zeros(engine, n_words, "int32")
+
+    def take(self, items, records):  # (the call's table, item -> the record's words, is uploaded for it; asynchronous otherwise)
+        from .tensors import _torch
+
+        torch = _torch()
+        n_pairs = sum(item[3] for item in items)
+        self.pairs = count_marked(self.pairs, n_pairs)
+        table = self.table[[self.row[id(r)] for r in records]]
+        if len(self.uploaded) >= 8:  # (the marks that read the tables kept so far have run once the engine has been waited for)
+            self.engine.synchronize()
+            self.uploaded = []
+        with torch.cuda.device(self.engine.device):
+            dev_table = torch.from_numpy(np.ascontiguousarray(table)).to(torch.device("cuda", self.engine.device))
+            torch.cuda.current_stream().synchronize()  # (uploaded on torch's stream; the engine reads it on its own)
+        self.uploaded.append(dev_table)
+        self.engine.depth_mark(items[0][2], n_pairs, dev_table.data_ptr(), len(records), self.diff.data_ptr())
+
+    def save(self, prefix):
+        self.engine.synchronize()
+        with open("%s.depth.npz" % prefix, "wb") as fh:  # (a handle: numpy adds no suffix to the name)
+            np.savez(fh, diff=self.diff.cpu().numpy(), table=self.table, ordinals=np.asarray(self.ordinals, dtype=np.int64))
+
+
+class Origins(_Consumer):
+    """--origins: the call's source intervals appended to ``handle``, the worker's BEDPE file, as text built on the device
+    (ReadEngine.origins_emit_batch; origins.py)."""
+    per_call = True
+
+    def __init__(self, engine, handle, cpu_number):
+        self.engine, self.handle, self.cpu_number = engine, handle, cpu_number
+
+    def take(self, items, records):
+        self.engine.origins_emit_batch(self.handle.fileno(), items, [len(r.seq) for r in records], self.cpu_number)
+
+    def flush(self):
+        self.engine.origins_flush()
+
+
+class Reads(_Consumer):
+    """The reads themselves, always the last consumer, in one ``form``: "device" (FASTQ text built on the device, copied and
+    written behind the next batch's generation), "ubam" (unaligned BAM records in BGZF blocks instead, one stream: both handles
+    are the .bam) or "host" (ISS_HOST_FASTQ=1: rows copied back and formatted by iss_fastq_write).  The work loop says where to
+    before its first call: bind()."""
+
+    def __init__(self, engine, cpu_number, form="device"):
+        self.engine, self.cpu_number, self.form = engine, cpu_number, form
+
+    def bind(self, forward_handle, reverse_handle, item_wise=False, writer_threads=4):
+        """``item_wise``: one fastq_emit per item (one pwrite stream per file: tmpfs gets slower with concurrent writers to one
+        file) instead of one text job for all.  The device's text follows what the handles have written: they are flushed."""
+        for fh in (forward_handle, reverse_handle):
+            fh.flush()
+        self.handles, self.item_wise, self.writer_threads = (forward_handle, reverse_handle), item_wise, writer_threads
+
+    def take(self, items, records):
+        eng, fd1, fd2 = self.engine, self.handles[0].fileno(), self.handles[1].fileno()
+        if self.form == "ubam":
+            eng.ubam_emit_batch(fd1, items, self.cpu_number)  # one job of record blocks
+        elif self.form == "device" and not self.item_wise:
+            eng.fastq_emit_batch(fd1, fd2, items, self.cpu_number)  # one text job
+        else:
+            for rid, first_i, row, n in items:
+                if self.form == "device":
+                    eng.fastq_emit(fd1, fd2, rid, first_i, self.cpu_number, row, n, n_threads=1)
+                else:
+                    eng.synchronize()
+                    rows = eng.download(row, n)["_pitched"]
+                    fastq_write(fd1, fd2, rid, first_i, self.cpu_number, n, eng.read_length, eng.pitch, *rows[:4], n_threads=self.writer_threads)
+
+    def flush(self):
+        if self.form == "ubam":
+            self.engine.ubam_flush()
+
+
 class Worker(object):
-    """State of one reference worker on one GPU: engine + uploaded genomes + running ordinal."""
+    """State of one reference worker on one GPU: engine + uploaded genomes + running ordinal + the consumers of its calls."""
 
     # rows generated / formatted / written per step of the streaming loop (ISS_BATCH_PAIRS: tuning aid).  2^18: the
     # kernels still run at their full rate, the (pinned) buffers are allocated in a quarter of the time of 2^20
@@ -298,41 +437,59 @@ class Worker(object):
     # (ReadEngine.add_genomes: one copy, one pack kernel; a batch whose records are of one group needs no arena copies)
     GROUP_BASES = 1 << 29
 
-    def __init__(self, error_model, cpu_number, seed, device=None, rng="philox", compress=False):
+    @staticmethod
+    def routes(compress=False, ubam=False, origins=False, bgzip=False, error_report=False, store_mutations=False):
+        """(device_fastq, device_vcf): is the FASTQ, is the --store_mutations VCF text built on the device?  The one place that reads
+        ISS_HOST_FASTQ=1 (rows to iss_fastq_write and to write_mutations) and ISS_HOST_VCF=1 (the latter alone), and that refuses
+        what a route cannot do -- before anything is made."""
+        device_fastq = os.environ.get("ISS_HOST_FASTQ", "") != "1"
+        device_vcf = device_fastq and os.environ.get("ISS_HOST_VCF", "") != "1"
+        if error_report and not store_mutations:
+            raise ValueError("error_report=True needs a model that stores its mutations (--store_mutations)")
+        if origins and not device_fastq:
+            raise ValueError("origins=True needs the device path (unset ISS_HOST_FASTQ)")
+        if bgzip and not device_vcf:
+            raise ValueError("bgzip=True needs the device path (unset ISS_HOST_FASTQ and ISS_HOST_VCF)")
+        if ubam and (compress or not device_fastq):
+            raise ValueError("ubam=True needs the device path (unset ISS_HOST_FASTQ) and takes no compress=True: BGZF blocks are compressed")
+        if compress and not device_fastq:
+            raise ValueError("compress=True needs the device FASTQ path (unset ISS_HOST_FASTQ)")
+        return device_fastq, device_vcf
+
+    def __init__(self, error_model, cpu_number, seed, device=None, rng="philox", compress=False, store_mutations=False, ubam=False,
+                 origins_handle=None, bgzip=False, report=False, error_report=False, depth=None):
+        """(worker_iterator's switches; ``origins_handle``: the open BEDPE file, ``depth``: (the work list's records, their ordinals))"""
         if rng not in ("philox", "mt"):
             raise ValueError("rng must be 'philox' (parallel, default) or 'mt' (reference-identical, sequential)")
+        self.device_fastq, self.device_vcf = self.routes(compress, ubam, origins_handle is not None, bgzip, error_report, store_mutations)
         self.rng = rng
         self.cpu_number = int(cpu_number)
         self.seed = worker_seed(seed, cpu_number)
         self.engine = ReadEngine(self.cpu_number if device is None else device)
-        self.dense = _dense_of(error_model)
-        self.engine.load_model(self.dense)
-        self.store_mutations = False
-        self.device_fastq = os.environ.get("ISS_HOST_FASTQ", "") != "1"  # ISS_HOST_FASTQ=1: host formatter (iss_fastq_write)
-        # the --store_mutations text is built on the device too (ReadEngine.vcf_emit); ISS_HOST_VCF=1: rows to the host, write_mutations
-        self.device_vcf = self.device_fastq and os.environ.get("ISS_HOST_VCF", "") != "1"
-        self.ubam = False  # --ubam (worker_iterator): the rows leave as unaligned BAM records in BGZF blocks instead of FASTQ text
-        self.origins_handle = None  # --origins (worker_iterator): the file every call's source intervals are appended to (origins.py)
-        self.compress = bool(compress)
-        if self.compress:
-            if not self.device_fastq:
-                raise ValueError("compress=True needs the device FASTQ path (unset ISS_HOST_FASTQ)")
+        self.engine.load_model(_dense_of(error_model))
+        self.store_mutations = bool(store_mutations)
+        if compress:
             self.engine.fastq_compress(True)  # the FASTQ handles receive gzip members instead of text
+        fragment = getattr(error_model, "fragment_length", None), getattr(error_model, "fragment_sd", None)
         if rng == "mt":
             # random.seed(seed + cpu_number); np.random.seed(seed + cpu_number)  (generator.py:234-236);
             # unseeded workers draw an OS-entropy seed (the reference is then not reproducible either)
             self.engine.seed_mt(self.seed & 0xFFFFFFFF if seed is None else self.seed)
-            self.engine.mt_set_fragment(getattr(error_model, "fragment_length", None),
-                                        getattr(error_model, "fragment_sd", None))
+            self.engine.mt_set_fragment(*fragment)
         else:
-            self.engine.set_fragment(getattr(error_model, "fragment_length", None),
-                                     getattr(error_model, "fragment_sd", None))
-        self.has_fragment = (getattr(error_model, "fragment_length", None) is not None and
-                             getattr(error_model, "fragment_sd", None) is not None)
+            self.engine.set_fragment(*fragment)
         self.ordinal = 0
-        self.tally = None  # --report: the device words every generate call's rows are tallied into (enable_tally)
-        self.depth_diff = None  # --depth: the device's difference array over the distinct records of the work list (enable_depth)
-        self.errtally = None  # --error_report: the device words every generate call's mutation rows are tallied into (enable_errtally)
+        if bgzip and origins_handle is not None:
+            self.engine.origins_compress(True)  # --bgzip: the two text files receive BGZF members instead of text
+        if bgzip and self.store_mutations:
+            self.engine.vcf_compress(True)
+        eng = self.engine
+        self.consumers = ([Tally(eng, eng.tally_words(), eng.tally, "tally", per_call=False)] if report else []) + \
+            ([Tally(eng, eng.error_tally_words(), functools.partial(eng.error_tally, source=rng), "errtally", per_call=True)]
+             if error_report else []) + \
+            ([Depth(eng, *depth)] if depth is not None else []) + \
+            ([Origins(eng, origins_handle, self.cpu_number)] if origins_handle is not None else []) + \
+            [Reads(eng, self.cpu_number, "ubam" if ubam else "device" if self.device_fastq else "host")]
         self.genomes = GenomeStore(
             self.engine, self,
             budget_divisor=1,     # the whole GENOME_BUDGET: beside the genomes a worker holds one batch of rows and its text
@@ -345,106 +502,17 @@ class Worker(object):
         self.genomes.plan(records)
 
     def close(self):
-        self.tally = None
-        self.depth_diff = None
-        self.errtally = None
-        self._depth_tables = []
+        self.consumers = []
         self.engine.close()
 
-    def enable_tally(self):
-        """--report: one zeroed tensor of ReadEngine.tally_words() words on the engine's device; tally_rows() adds to it."""
-        from .tensors import _torch
-
-        torch = _torch()
-        with torch.cuda.device(self.engine.device):
-            self.tally = torch.zeros(self.engine.tally_words(), dtype=torch.int64, device=torch.device("cuda", self.engine.device))
-            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
-
-    def tally_rows(self, first_pair, n_pairs):
-        """Tally rows [first_pair, +n_pairs) of the generate call just made -- once its rows are final (behind a repeated call
-        of _retry_on_row_overflow) and before they are generated anew.  Asynchronous, like the text jobs."""
-        if self.tally is not None:
-            self.engine.tally(first_pair, n_pairs, self.tally.data_ptr())
-
-    def tally_words_host(self):
-        """The tally so far as uint64 words on the host (waits for the engine)."""
-        self.engine.synchronize()
-        return self.tally.cpu().numpy().view(np.uint64).copy()
-
-    def enable_errtally(self):
-        """--error_report: one zeroed tensor of ReadEngine.error_tally_words() words on the engine's device; errtally_rows() adds
-        to it."""
-        from .tensors import _torch
-
-        torch = _torch()
-        with torch.cuda.device(self.engine.device):
-            self.errtally = torch.zeros(self.engine.error_tally_words(), dtype=torch.int64, device=torch.device("cuda", self.engine.device))
-            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
-
-    def errtally_rows(self, first_pair, n_pairs):
-        """Tally the mutation rows of the generate call just made whose pair lies in rows [first_pair, +n_pairs) -- where
-        tally_rows stands: once _take_mutations has settled the call (a repeated one is counted once) and before its rows are
-        generated anew.  Asynchronous, like the text jobs."""
-        if self.errtally is not None:
-            self.engine.error_tally(first_pair, n_pairs, self.errtally.data_ptr(), source=self.rng)
-
-    def errtally_words_host(self):
-        """The error tally so far as uint64 words on the host (waits for the engine)."""
-        self.engine.synchronize()
-        return self.errtally.cpu().numpy().view(np.uint64).copy()
-
-    def enable_depth(self, records, ordinals):
-        """--depth: one zeroed int32 difference array on the engine's device over the distinct records of the work list (in
-        order of first appearance; ``ordinals``: their ordinals in the FASTA), whatever GenomeStore groups and arena offsets
-        they come to stand in; depth_rows() adds every generate call's template intervals to it (depth.py)."""
-        from .depth import depth_table
-        from .tensors import _torch
-
-        torch = _torch()
-        self._depth_row, self.depth_ordinals, lengths = {}, [], []
-        for record, ordinal in zip(records, ordinals):
-            if id(record) not in self._depth_row:
-                self._depth_row[id(record)] = len(lengths)
-                self.depth_ordinals.append(int(ordinal))
-                lengths.append(len(record.seq))
-        self.depth_table, n_words = depth_table(lengths)
-        self._depth_tables, self._depth_marked = [], 0
-        with torch.cuda.device(self.engine.device):
-            self.depth_diff = torch.zeros(n_words, dtype=torch.int32, device=torch.device("cuda", self.engine.device))
-            torch.cuda.synchronize()  # (zeroed on torch's stream; the engine adds on its own)
-
-    def depth_rows(self, first_pair, n_pairs, records):
-        """Mark rows [first_pair, +n_pairs) of the generate call just made -- ``records``: the record of each of the call's items
-        (one for generate / generate_mt) -- where tally_rows stands: once the rows are final, before they are generated anew.
-        The call's table (item -> the record's words) is uploaded for it; asynchronous otherwise."""
-        if self.depth_diff is None or not n_pairs:
-            return
-        from .depth import count_marked
-        from .tensors import _torch
-
-        torch = _torch()
-        self._depth_marked = count_marked(self._depth_marked, n_pairs)
-        table = self.depth_table[[self._depth_row[id(r)] for r in records]]
-        if len(self._depth_tables) >= 8:  # (the marks that read the tables kept so far have run once the engine has been waited for)
-            self.engine.synchronize()
-            self._depth_tables = []
-        with torch.cuda.device(self.engine.device):
-            dev_table = torch.from_numpy(np.ascontiguousarray(table)).to(torch.device("cuda", self.engine.device))
-            torch.cuda.current_stream().synchronize()  # (uploaded on torch's stream; the engine reads it on its own)
-        self._depth_tables.append(dev_table)
-        self.engine.depth_mark(first_pair, n_pairs, dev_table.data_ptr(), len(records), self.depth_diff.data_ptr())
-
-    def origins_rows(self, items, records):
-        """--origins: the source intervals of ``items`` -- the tuples of the text job, ``records`` their records -- appended to the
-        worker's BEDPE file as text built on the device; where the text job is handed over (the rows are final).  Asynchronous."""
-        if self.origins_handle is not None:
-            self.engine.origins_emit_batch(self.origins_handle.fileno(), items, [len(r.seq) for r in records], self.cpu_number)
-
-    def depth_save(self, path):
-        """The worker's accumulator for the parent's merge: diff, table and the records' FASTA ordinals (waits for the engine)."""
-        self.engine.synchronize()
-        with open(path, "wb") as fh:  # (a handle: numpy adds no suffix to the name)
-            np.savez(fh, diff=self.depth_diff.cpu().numpy(), table=self.depth_table, ordinals=np.asarray(self.depth_ordinals, dtype=np.int64))
+    def flush(self):
+        """Drain every pipe before the handles close (the text is appended to their descriptors) and are the caller's again:
+        the consumers' last to first (uBAM, origins), then the FASTQ pipe (with uBAM too) and the device-built VCF text's."""
+        for consumer in reversed(self.consumers):
+            consumer.flush()
+        self.engine.fastq_flush()
+        if _mutation_route(self) == "device":
+            self.engine.vcf_flush()
 
     def needs_room_for(self, record):
         """Would uploading this record drop the resident genomes (GENOME_BUDGET)?"""
@@ -473,8 +541,7 @@ class Worker(object):
                         raise
             return 0
         gid = self.genome_id(record)
-        for fh in (forward_handle, reverse_handle):
-            fh.flush()
+        self.consumers[-1].bind(forward_handle, reverse_handle, item_wise=True, writer_threads=writer_threads)
         route = _mutation_route(self)
         if route == "device":
             mutations_handle.flush()  # (the device's text follows what the handle has written)
@@ -489,33 +556,14 @@ class Worker(object):
                     eng.generate(gid, n, first_ordinal=self.ordinal, seed=self.seed, sequence_type=sequence_type,
                                  gc_bias=gc_bias, out_first_pair=0)
             gen()
-            _take_mutations(route, eng, gen, mutations_handle, [(record.id, done, 0, n)], self.cpu_number, self.rng)
-            self.tally_rows(0, n)
-            self.errtally_rows(0, n)
-            self.depth_rows(0, n, [record])
-            self.origins_rows([(record.id, done, 0, n)], [record])
-            if self.ubam:  # (one stream: both handles are the .bam)
-                eng.ubam_emit_batch(forward_handle.fileno(), [(record.id, done, 0, n)], self.cpu_number)
-            elif self.device_fastq:
-                # text built on the device, copied and written behind the next batch's generation
-                # (one pwrite stream per file: tmpfs gets slower with concurrent writers to one file)
-                eng.fastq_emit(forward_handle.fileno(), reverse_handle.fileno(), record.id, done, self.cpu_number, 0, n,
-                               n_threads=1)
-            else:
-                eng.synchronize()
-                rows = eng.download(0, n)["_pitched"]
-                fastq_write(forward_handle.fileno(), reverse_handle.fileno(), record.id, done, self.cpu_number, n,
-                            eng.read_length, eng.pitch, rows[0], rows[1], rows[2], rows[3], n_threads=writer_threads)
+            items = [(record.id, done, 0, n)]
+            _take_mutations(route, eng, gen, mutations_handle, items, self.cpu_number, self.rng)
+            for consumer in self.consumers:
+                consumer.take(items, [record])
             self.ordinal += n
             done += n
         if self.device_fastq and flush:
-            if self.ubam:
-                eng.ubam_flush()
-            if self.origins_handle is not None:
-                eng.origins_flush()
-            eng.fastq_flush()  # the handles are the caller's again
-            if route == "device":
-                eng.vcf_flush()
+            self.flush()
         return done
 
 
@@ -591,18 +639,18 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
     logger = logging.getLogger(__name__)
     eng = w.engine
     route = _mutation_route(w)
-    pending, cur = [], 0  # (record id, genome id, pairs, id of the item's first pair in this piece)
-    pending_records = []  # --depth: the record of every pending piece
+    pending, cur = [], 0  # (record, genome id, pairs, id of the item's first pair in this piece)
 
     def run():
-        nonlocal pending, cur, pending_records
+        nonlocal pending, cur
         if not pending:
             return
-        marked = origins_done = errors_done = False
         row, emit = 0, []  # one item per pending piece: (record id, first pair id, first output row, pairs)
-        for rid, _gid, n, first_i in pending:
-            emit.append((rid, first_i, row, n))
+        for record, _gid, n, first_i in pending:
+            emit.append((record.id, first_i, row, n))
             row += n
+        records = [p[0] for p in pending]
+        rest = w.consumers  # those still to take the batch as a whole
         try:
             def gen():
                 eng.generate_batch([p[1] for p in pending], [p[2] for p in pending], first_ordinal=w.ordinal, seed=w.seed,
@@ -612,44 +660,29 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         except _native.EngineError as e:
             if e.code != _native.E_INVALID or "records of one call must stay below" not in str(e):
                 raise
-            # records too long to stand side by side in one arena: the same rows, the same call, one item at a time
+            # records too long to stand side by side in one arena: the same rows, the same call, one item at a time -- every item
+            # a call of its own, which the per_call consumers take before the next one overwrites what they read
             eng.reserve(row)
             ordinal = w.ordinal
-            for (_rid, gid, n, _first_i), item, record in zip(pending, emit, pending_records):
+            for (record, gid, n, _first_i), item in zip(pending, emit):
                 def gen1():
                     eng.generate(gid, n, first_ordinal=ordinal, seed=w.seed, sequence_type=sequence_type, gc_bias=gc_bias,
                                  out_first_pair=item[2])
                 gen1()
                 _take_mutations(route, eng, gen1, mutations_handle, [item], w.cpu_number, "philox")
-                if getattr(w, "errtally", None) is not None:  # --error_report: the item is a call of its own, the next one clears its rows
-                    w.errtally_rows(item[2], n)
-                    errors_done = True
-                if getattr(w, "depth_diff", None) is not None:  # --depth: the item is a call of its own (item 0 of its rows)
-                    w.depth_rows(item[2], n, [record])
-                    marked = True
-                if getattr(w, "origins_handle", None) is not None:  # --origins, likewise: the next call moves on to the other set of descriptors
-                    w.origins_rows([item], [record])
-                    origins_done = True
+                for consumer in w.consumers:
+                    if consumer.per_call:
+                        consumer.take([item], [record])
                 ordinal += n
-        if getattr(w, "tally", None) is not None:  # --report (every call of the batch has settled: a repeated one is not counted twice)
-            w.tally_rows(0, row)
-        if getattr(w, "errtally", None) is not None and not errors_done:  # --error_report, likewise: the batch call's rows
-            w.errtally_rows(0, row)
-        if getattr(w, "depth_diff", None) is not None and not marked:  # --depth, likewise: the batch call's items through its table
-            w.depth_rows(0, row, pending_records)
-        if getattr(w, "origins_handle", None) is not None and not origins_done:  # --origins: one text job beside the reads'
-            w.origins_rows(emit, pending_records)
-        if getattr(w, "ubam", False):
-            eng.ubam_emit_batch(forward_handle.fileno(), emit, w.cpu_number)  # one job of record blocks
-        else:
-            eng.fastq_emit_batch(forward_handle.fileno(), reverse_handle.fileno(), emit, w.cpu_number)  # one text job
+            rest = [consumer for consumer in w.consumers if not consumer.per_call]
+        for consumer in rest:  # (every call of the batch has settled: a repeated one is not read twice)
+            consumer.take(emit, records)
         w.ordinal += row
         if timings is not None:  # (measurement: when each batch was handed to the FASTQ pipeline, and how many pairs it held)
             timings.setdefault("batches", []).append((time.perf_counter(), row))
-        pending, cur, pending_records = [], 0, []
+        pending, cur = [], 0
 
-    for fh in (forward_handle, reverse_handle):
-        fh.flush()
+    w.consumers[-1].bind(forward_handle, reverse_handle)
     for record, n_pairs, _mode in work:
         logger.debug("Cpu #%s: Generating %s read pairs" % (w.cpu_number, n_pairs))
         if _warn_short_record(eng, record):
@@ -660,8 +693,7 @@ def _simulate_work_batched(w, work, forward_handle, reverse_handle, mutations_ha
         done = 0
         while done < n_pairs:
             take = min(n_pairs - done, w.BATCH_PAIRS - cur)
-            pending.append((record.id, gid, take, done))
-            pending_records.append(record)
+            pending.append((record, gid, take, done))
             cur += take
             done += take
             if cur >= w.BATCH_PAIRS:
@@ -709,34 +741,22 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
     (same names) hold gzip members built on the device instead of text -- `--compress` without the text ever leaving
     the GPU; gunzipped they are the files ``compress=False`` writes.  ``timings``: a dict that receives ``t_start``, ``t_ready``
     (engine created, model uploaded), ``batches`` [(time a batch was queued for the files, its pairs)] and ``t_end`` (files
-    complete) -- bench.py's end-to-end legs report the steady state apart from the start-up.  ``report=True`` (`--report`): the rows
-    of every generate call are tallied on the device (ReadEngine.tally) and the worker's tally -- tally.tally_layout, uint64
-    words -- is written to ``{prefix}.tally.npy`` at the end; without it no engine call is added.  ``depth=True`` (`--depth`): the
-    template intervals of every generate call are marked on the device (ReadEngine.depth_mark) into one difference array over the
-    distinct records of ``work`` and written to ``{prefix}.depth.npz`` (diff, table, ``ordinals``: the FASTA ordinal of each work
-    item's record, default its position in ``work``) at the end; without it no engine call is added.  ``ubam=True`` (`--ubam`):
-    instead of the two FASTQ files the worker writes ``{prefix}.bam``, the BGZF record blocks of its reads (R1 then R2 of every
-    pair) built on the device (ReadEngine.ubam_emit_batch) -- no BAM header, no EOF block: the parent frames the workers' blocks
-    (ubam.assemble).  ``origins=True`` (`--origins`): the worker also writes ``{prefix}_origins.bedpe``, one line per pair with the
-    record and the two template intervals its reads were cut from (origins.py), built on the device
-    (ReadEngine.origins_emit_batch) where the text job is handed over; without it no engine call is added.  ``bgzip=True``
+    complete) -- bench.py's end-to-end legs report the steady state apart from the start-up.
+
+    The other switches add consumers of the worker's generate calls (the classes above: what each reads, and when); without one
+    no engine call is added.  ``report=True`` (`--report`): ``{prefix}.tally.npy``, uint64 words of tally.tally_layout.
+    ``error_report=True`` (`--error_report`; the model must store its mutations): ``{prefix}.errtally.npy``, uint64 words of
+    errtally.layout.  ``depth=True`` (`--depth`): ``{prefix}.depth.npz`` -- diff, table, ``ordinals``: the FASTA ordinal of each work
+    item's record, default its position in ``work``.  ``origins=True`` (`--origins`): ``{prefix}_origins.bedpe``, one line per pair
+    (origins.py).  ``ubam=True`` (`--ubam`): instead of the two FASTQ files ``{prefix}.bam``, the BGZF record blocks of the reads (R1
+    then R2 of every pair) -- no BAM header, no EOF block: the parent frames the workers' blocks (ubam.assemble).  ``bgzip=True``
     (`--bgzip`): ``{prefix}.vcf`` and ``{prefix}_origins.bedpe`` hold the BGZF members of their text, compressed on the device
-    (ReadEngine.vcf_compress / origins_compress), instead of the text -- no header member, no EOF block: the parent frames the
-    workers' members (bgzf.assemble).  ``error_report=True`` (`--error_report`; the model must store its mutations): the mutation
-    rows of every generate call are tallied on the device (ReadEngine.error_tally) and the worker's tally -- errtally.layout,
-    uint64 words -- is written to ``{prefix}.errtally.npy`` at the end; without it no engine call is added."""
+    (ReadEngine.vcf_compress / origins_compress) -- no header member, no EOF block: the parent frames them (bgzf.assemble)."""
     logger = logging.getLogger(__name__)
-    if error_report and not bool(getattr(error_model, "store_mutations", False)):
-        raise ValueError("error_report=True needs a model that stores its mutations (--store_mutations)")
-    if origins and os.environ.get("ISS_HOST_FASTQ", "") == "1":
-        raise ValueError("origins=True needs the device path (unset ISS_HOST_FASTQ)")
-    if bgzip and (os.environ.get("ISS_HOST_FASTQ", "") == "1" or os.environ.get("ISS_HOST_VCF", "") == "1"):
-        raise ValueError("bgzip=True needs the device path (unset ISS_HOST_FASTQ and ISS_HOST_VCF)")
-    if ubam and (compress or os.environ.get("ISS_HOST_FASTQ", "") == "1"):
-        raise ValueError("ubam=True needs the device path (unset ISS_HOST_FASTQ) and takes no compress=True: BGZF blocks are compressed")
+    store_mutations = bool(getattr(error_model, "store_mutations", False))
+    Worker.routes(compress, ubam, origins, bgzip, error_report, store_mutations)  # (what the worker will refuse, before any file is made)
     if timings is not None:
         timings["t_start"] = time.perf_counter()
-    store_mutations = bool(getattr(error_model, "store_mutations", False))
     if sequence_type not in _native.SEQ_TYPES:
         raise RuntimeError("sequence type '%s' is not supported" % sequence_type)  # generator.py:139
     try:
@@ -746,29 +766,18 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
             forward_handle = open("%s_R1.fastq" % worker_prefix, "w")
             reverse_handle = open("%s_R2.fastq" % worker_prefix, "w")
         mutation_handle = open("%s.vcf" % worker_prefix, "w")
-        origins_handle = open("%s_origins.bedpe" % worker_prefix, "wb") if origins else contextlib.nullcontext()
+        origins_handle = open("%s_origins.bedpe" % worker_prefix, "wb") if origins else None
     except PermissionError as e:
         logger.error("Failed to write temporary output file(s): %s" % e)
         sys.exit(1)
-    w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress)
-    w.ubam = bool(ubam)
-    if origins:
-        w.origins_handle = origins_handle
-        if bgzip:
-            w.engine.origins_compress(True)
-    if bgzip and store_mutations:
-        w.engine.vcf_compress(True)
-    w.plan(record for record, _n, _mode in work)
-    if report:
-        w.enable_tally()
-    if error_report:
-        w.enable_errtally()
-    if depth:
-        w.enable_depth([record for record, _n, _mode in work], ordinals if ordinals is not None else range(len(work)))
+    records = [record for record, _n, _mode in work]
+    w = Worker(error_model, cpu_number, seed, device=device, rng=rng, compress=compress, store_mutations=store_mutations, ubam=ubam,
+               origins_handle=origins_handle, bgzip=bgzip, report=report, error_report=error_report,
+               depth=(records, ordinals if ordinals is not None else range(len(work))) if depth else None)
+    w.plan(records)
     if timings is not None:
         timings["t_ready"] = time.perf_counter()
     if store_mutations:
-        w.store_mutations = True
         # row buffers of a batch, from the model's own error rates (twice the expectation + slack; the Philox kernels
         # reserve 256-row chunks per wavefront on top)
         per_pair = 2.0 * _dense_of(error_model).expected_mutation_rows_per_pair() + 4.0
@@ -777,7 +786,7 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
         else:
             w.engine.mutations_reserve(int(Worker.BATCH_PAIRS * per_pair) + (1 << 21))
     try:
-        with forward_handle, reverse_handle, mutation_handle, origins_handle:
+        with forward_handle, reverse_handle, mutation_handle, origins_handle or contextlib.nullcontext():
             if store_mutations and w.device_vcf:
                 mutation_handle.flush()  # the device's text goes to the descriptor, behind what the handle holds (nothing)
             if rng == "philox" and w.device_fastq and os.environ.get("ISS_ITEMWISE", "") != "1":
@@ -786,19 +795,9 @@ def worker_iterator(work, error_model, cpu_number, worker_prefix, seed, sequence
                 for record, n_pairs, _mode in work:
                     w.simulate_reads(record, n_pairs, forward_handle, reverse_handle, mutation_handle, sequence_type,
                                      gc_bias, flush=False)  # keep the text pipeline running across work items
-            if ubam:
-                w.engine.ubam_flush()
-            if origins:
-                w.engine.origins_flush()  # (before the handle closes: the text is appended to its descriptor)
-            w.engine.fastq_flush()
-            if store_mutations and w.device_vcf:
-                w.engine.vcf_flush()  # (before the handle closes: the text is appended to its descriptor)
-            if report:
-                np.save("%s.tally.npy" % worker_prefix, w.tally_words_host())
-            if error_report:
-                np.save("%s.errtally.npy" % worker_prefix, w.errtally_words_host())
-            if depth:
-                w.depth_save("%s.depth.npz" % worker_prefix)
+            w.flush()
+            for consumer in w.consumers:  # (behind the flushes: tally, error tally, depth)
+                consumer.save(worker_prefix)
             if timings is not None:
                 timings["t_end"] = time.perf_counter()
     finally:

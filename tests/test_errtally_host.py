@@ -287,6 +287,12 @@ class _Words(object):
     def data_ptr(self):
         return 4096
 
+    def cpu(self):
+        return self
+
+    def numpy(self):
+        return np.zeros(E.words(125), dtype=np.int64)
+
 
 @pytest.fixture
 def loops(rec):  # noqa: F811
@@ -295,8 +301,8 @@ def loops(rec):  # noqa: F811
 
     rec.setattr(RecordingEngine, "error_tally", error_tally, raising=False)
     rec.setattr(RecordingEngine, "synchronize", lambda self: None, raising=False)
-    rec.setattr(G.Worker, "enable_errtally", lambda self: setattr(self, "errtally", _Words()))
-    rec.setattr(G.Worker, "errtally_words_host", lambda self: np.zeros(E.words(125), dtype=np.uint64))
+    rec.setattr(RecordingEngine, "error_tally_words", lambda self: E.words(125), raising=False)
+    rec.setattr(G, "_device_zeros", lambda engine, n_words, dtype: _Words())
     return rec
 
 

@@ -315,6 +315,7 @@ def test_batched_worker_loop_cuts_batches_across_items(monkeypatch):
         def __init__(self):
             self.engine = FakeEngine()
             self.ordinal, self.seed, self.cpu_number, self.store_mutations = 7, 5, 3, False
+            self.consumers = [G.Reads(self.engine, self.cpu_number)]
             self.ids = {}
 
         def needs_room_for(self, record):
@@ -500,6 +501,7 @@ def test_batched_worker_loop_falls_back_to_single_calls():
         def __init__(self):
             self.engine = FakeEngine()
             self.ordinal, self.seed, self.cpu_number, self.store_mutations = 0, 1, 4, True
+            self.consumers = [G.Reads(self.engine, self.cpu_number)]
 
         def needs_room_for(self, record):
             return False

@@ -55,6 +55,7 @@ class FakeWorker:
     def __init__(self, engine):
         self.engine = engine
         self.ordinal, self.seed, self.cpu_number, self.store_mutations = 0, 1, 4, True
+        self.consumers = [G.Reads(engine, self.cpu_number)]
 
     def needs_room_for(self, record):
         return False
