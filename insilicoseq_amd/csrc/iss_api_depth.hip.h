@@ -8,7 +8,7 @@ extern "C" {
 
 int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int64_t *d_table, int32_t n_table, int32_t *d_diff) {
     if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_depth_mark: upload a model first");
-    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_depth_mark: rows out of range");
     if (!n_pairs) return 0;
     if (!d_table || !d_diff) return fail(ctx, ISS_E_INVALID, "iss_depth_mark: d_table or d_diff is NULL");
@@ -17,8 +17,8 @@ int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int6
     int set = -1;
     if (!ctx->last_first.empty() && ctx->batch_seq > 0 && first_pair < ctx->last_row0 + ctx->last_n && first_pair + n_pairs > ctx->last_row0) {
         set = (int)((ctx->batch_seq - 1) & 1u);
-        A.items = ctx->d_items[set];
-        A.item_first = ctx->d_item_first[set];
+        A.items = ctx->it.d_items[set];
+        A.item_first = ctx->it.d_item_first[set];
         A.n_items = (int32_t)ctx->last_first.size() - 1;
         A.rel0 = first_pair - ctx->last_row0;
         A.call_pairs = ctx->last_n;
@@ -30,7 +30,7 @@ int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int6
     const int64_t target = wgs > 0 ? wgs : iss::DEPTH_TARGET_WGS;
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(target, (n_pairs + iss::DEPTH_THREADS - 1) / iss::DEPTH_THREADS));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    A.desc = ctx->desc + first_pair;
+    A.desc = ctx->os.desc + first_pair;
     A.n_pairs = n_pairs;
     A.RL = ctx->M.RL;
     A.table = d_table;
@@ -39,7 +39,7 @@ int iss_depth_mark(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, const int6
     hipLaunchKernelGGL(iss::k_depth_mark, dim3((unsigned)std::min<int64_t>(grid, 0x7fffffff)), dim3(iss::DEPTH_THREADS), 0, ctx->stream, A);
     HIP_TRY(ctx, hipGetLastError());
     // (iss_generate_batch refills a set of tables once the event of its last reader has passed: this launch is that reader now)
-    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], ctx->stream));
+    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->it.ev_items[set], ctx->stream));
     return 0;
 }
 
@@ -60,11 +60,10 @@ int iss_depth_finish(iss_ctx *ctx, const int32_t *d_diff, int64_t n_words, uint3
     hipStream_t st = ctx->stream;
     auto &w = ctx->dw;
     if (plan.bytes > w.cap) {  // the work array: grown behind a wait for the kernels that may still read the old one
-        if (w.d) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void)hipFree(w.d); w.d = nullptr; w.cap = 0; }
-        void *v = nullptr;
+        if (w.d) HIP_TRY(ctx, hipStreamSynchronize(st));
+        w = {};
         const size_t cap = plan.bytes + plan.bytes / 4 + 4096;
-        HIP_TRY(ctx, hipMalloc(&v, cap));
-        w.d = static_cast<uint8_t *>(v);
+        DEV_ALLOC(ctx, w.d, cap);
         w.cap = cap;
     }
     iss::DepthFinishArgs A{};
@@ -76,7 +75,7 @@ int iss_depth_finish(iss_ctx *ctx, const int32_t *d_diff, int64_t n_words, uint3
     A.bin = bin;
     A.stats = reinterpret_cast<unsigned long long *>(d_stats);
     A.bins = reinterpret_cast<unsigned long long *>(d_bins);
-    A.tiles = reinterpret_cast<uint32_t *>(w.d);
+    A.tiles = reinterpret_cast<uint32_t *>(w.d.get());
     A.n_tiles = n_words > 0 ? plan.n_tiles : 0;
     A.info = reinterpret_cast<int64_t *>(w.d + plan.off_info);
     A.first = reinterpret_cast<int64_t *>(w.d + plan.off_first);

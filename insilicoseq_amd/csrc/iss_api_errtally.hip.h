@@ -15,21 +15,21 @@ int iss_mutations_tally(iss_ctx *ctx, int32_t source, int64_t first_pair, int64_
     if (source != 0 && source != 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: unknown source");
     const bool philox = source == 0;
     if (philox) {
-        if (!ctx->d_pmut || ctx->pmut_cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: no rows are reserved (iss_mutations_reserve)");
+        if (!ctx->pmut.d || ctx->pmut.cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: no rows are reserved (iss_mutations_reserve)");
         if (!ctx->pmut_call || !ctx->d_pmut_count)
             return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: no iss_generate / iss_generate_batch call since the rows were reserved");
     } else {
         if (!ctx->mt.d_mut || ctx->mt.mut_cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: no rows are reserved (iss_mt_mutations_reserve)");
         if (!ctx->mt.mut_call) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: no iss_generate_mt call since the rows were reserved");
     }
-    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: rows out of range");
     if (!n_pairs) return 0;
     if (!d_tally) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: d_tally is NULL");
     if (!philox && ctx->mt.mut_n > ctx->mt.mut_cap)
         return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: more rows than iss_mt_mutations_reserve holds");
     // the slots a workgroup may have to walk: every one of them adds to a u32 LDS counter at most once
-    const int64_t n_slots = philox ? ctx->pmut_cap : ctx->mt.mut_n;
+    const int64_t n_slots = philox ? ctx->pmut.cap : ctx->mt.mut_n;
     if (n_slots > iss::ERRTALLY_MAX_SLOTS) return fail(ctx, ISS_E_INVALID, "iss_mutations_tally: too many rows for one call");
     const iss::DevModel &M = ctx->M;
     const int64_t n_tiles = (M.RL + iss::ERRTALLY_TILE - 1) / iss::ERRTALLY_TILE;
@@ -47,20 +47,16 @@ int iss_mutations_tally(iss_ctx *ctx, int32_t source, int64_t first_pair, int64_
     auto &w = ctx->ew;  // the per-read work array: sized for the output rows (a larger one waits for the kernels that read the old one)
     if ((size_t)n_pairs > w.pairs_cap) {
         if (w.d) HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (w.d) (void)hipFree(w.d);
-        w.d = nullptr;
-        w.pairs_cap = 0;
-        const size_t pc = std::max((size_t)n_pairs, (size_t)ctx->capacity);
-        void *v = nullptr;
-        HIP_TRY(ctx, hipMalloc(&v, pc * 2 * sizeof(uint64_t)));
-        w.d = static_cast<uint64_t *>(v);
+        w = {};
+        const size_t pc = std::max((size_t)n_pairs, (size_t)ctx->os.capacity);
+        DEV_ALLOC(ctx, w.d, pc * 2);
         w.pairs_cap = pc;
     }
     iss::ErrTallyArgs T{};
     if (philox) {
-        T.mut = ctx->d_pmut;
+        T.mut = ctx->pmut.d;
         T.count = ctx->d_pmut_count;
-        T.cap = (uint32_t)ctx->pmut_cap;
+        T.cap = (uint32_t)ctx->pmut.cap;
         T.flags = ctx->flags + ctx->last_row0;
         T.call_pairs = ctx->last_n;
         T.rel0 = first_pair - ctx->last_row0;
@@ -73,7 +69,7 @@ int iss_mutations_tally(iss_ctx *ctx, int32_t source, int64_t first_pair, int64_
     T.n_pairs = n_pairs;
     T.RL = M.RL;
     T.read_per = read_per;
-    T.reads = reinterpret_cast<unsigned long long *>(w.d);
+    T.reads = reinterpret_cast<unsigned long long *>(w.d.get());
     T.tally = reinterpret_cast<unsigned long long *>(d_tally);
     HIP_TRY(ctx, hipMemsetAsync(w.d, 0, (size_t)n_pairs * 2 * sizeof(uint64_t), st));
     hipLaunchKernelGGL(iss::k_errtally_rows, dim3((unsigned)n_tiles, (unsigned)n_chunks), dim3(iss::ERRTALLY_THREADS), 0, st, T);

@@ -9,7 +9,7 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
                       int64_t *d_coords, int32_t *d_item) {
     if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_output_export: upload a model first");
     if (encoding != ISS_EXPORT_ASCII && encoding != ISS_EXPORT_CODES) return fail(ctx, ISS_E_INVALID, "iss_output_export: unknown encoding");
-    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_output_export: rows out of range");
     if (!n_pairs || (!d_bases && !d_qual && !d_coords && !d_item)) return 0;
     const iss::DevModel &M = ctx->M;
@@ -20,7 +20,7 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     iss::ExportArgs E{};
     E.rows = ctx->out[0] + (size_t)first_pair * (size_t)M.row;
-    E.desc = ctx->desc + first_pair;
+    E.desc = ctx->os.desc + first_pair;
     E.n_pairs = n_pairs;
     E.RL = M.RL;
     E.row = M.row;
@@ -35,8 +35,8 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
     int set = -1;
     if (!ctx->last_first.empty() && ctx->batch_seq > 0 && first_pair < ctx->last_row0 + ctx->last_n && first_pair + n_pairs > ctx->last_row0) {
         set = (int)((ctx->batch_seq - 1) & 1u);
-        E.items = ctx->d_items[set];
-        E.item_first = ctx->d_item_first[set];
+        E.items = ctx->it.d_items[set];
+        E.item_first = ctx->it.d_item_first[set];
         E.n_items = (int32_t)ctx->last_first.size() - 1;
         E.rel0 = first_pair - ctx->last_row0;
         E.call_pairs = ctx->last_n;
@@ -44,7 +44,7 @@ int iss_output_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int32_t
     hipLaunchKernelGGL(iss::k_rows_export, dim3((unsigned)n_tiles), dim3(iss::EXPORT_THREADS), 2 * (size_t)E.region, ctx->stream, E);
     HIP_TRY(ctx, hipGetLastError());
     // (iss_generate_batch refills a set of tables once the event of its last reader has passed: this launch is that reader now)
-    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], ctx->stream));
+    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->it.ev_items[set], ctx->stream));
     return 0;
 }
 
@@ -54,10 +54,10 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
     if (encoding != ISS_EXPORT_ASCII && encoding != ISS_EXPORT_CODES) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: unknown encoding");
     if ((events != nullptr) != (n_events != nullptr) || capacity < 0 || capacity > ((int64_t)1 << 40))
         return fail(ctx, ISS_E_INVALID, "iss_mutations_export: events and n_events go together, with a capacity of 0 or more");
-    if (!ctx->d_pmut || ctx->pmut_cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: no rows are reserved (iss_mutations_reserve)");
+    if (!ctx->pmut.d || ctx->pmut.cap < 1) return fail(ctx, ISS_E_INVALID, "iss_mutations_export: no rows are reserved (iss_mutations_reserve)");
     if (!ctx->pmut_call || !ctx->d_pmut_count)
         return fail(ctx, ISS_E_INVALID, "iss_mutations_export: no iss_generate / iss_generate_batch call since the rows were reserved");
-    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_mutations_export: rows out of range");
     const iss::DevModel &M = ctx->M;
     const bool want_truth = truth && n_pairs;
@@ -70,9 +70,9 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t call_pairs = ctx->last_n;
     iss::TruthArgs T{};
-    T.mut = ctx->d_pmut;
+    T.mut = ctx->pmut.d;
     T.count = ctx->d_pmut_count;
-    T.cap = (uint32_t)ctx->pmut_cap;
+    T.cap = (uint32_t)ctx->pmut.cap;
     T.flags = ctx->flags + ctx->last_row0;
     T.call_pairs = call_pairs;
     T.rel0 = first_pair - ctx->last_row0;
@@ -84,30 +84,29 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
     auto grid_for = [](uint64_t n, int threads) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (n + threads - 1) / threads))); };
     if (events && T.w0 < T.w1) {  // the work arrays: sized once per reservation (a larger one waits for the kernels that read the old set)
         auto &w = ctx->tw;
-        const size_t n_slots = (size_t)ctx->pmut_cap;
+        const size_t n_slots = (size_t)ctx->pmut.cap;
         const size_t n_tiles = ((size_t)call_pairs + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE;
         if (n_slots > w.slots_cap || (size_t)call_pairs > w.pairs_cap || n_tiles > w.tiles_cap) {
             if (w.slots_cap || w.pairs_cap) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             const size_t sc = std::max(w.slots_cap, n_slots);
-            const size_t pc = std::max(w.pairs_cap, std::max((size_t)call_pairs, (size_t)ctx->capacity));
+            const size_t pc = std::max(w.pairs_cap, std::max((size_t)call_pairs, (size_t)ctx->os.capacity));
             const size_t tc = (pc + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE + 1;
-            truth_free_work(ctx);
-            void *v = nullptr;
-            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_key = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_slot = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, sc * 4)); w.d_order = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, pc * 4)); w.d_cnt = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, (pc + 1) * 8)); w.d_seg = static_cast<uint64_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, tc * 8)); w.d_tiles = static_cast<uint64_t *>(v);
+            w = {};
+            DEV_ALLOC(ctx, w.d_key, sc);
+            DEV_ALLOC(ctx, w.d_slot, sc);
+            DEV_ALLOC(ctx, w.d_order, sc);
+            DEV_ALLOC(ctx, w.d_cnt, pc);
+            DEV_ALLOC(ctx, w.d_seg, pc + 1);
+            DEV_ALLOC(ctx, w.d_tiles, tc);
             w.slots_cap = sc; w.pairs_cap = pc; w.tiles_cap = tc;
         }
     }
     hipStream_t st = ctx->stream;
     if (want_truth) {
         // the bases a second time, then the substitutions' ref letters over them -- behind the copy, on the same stream
-        { int rc_ = iss_output_export(ctx, first_pair, n_pairs, encoding, truth, nullptr, nullptr, nullptr); if (rc_) return rc_; }
+        ISS_TRY(iss_output_export(ctx, first_pair, n_pairs, encoding, truth, nullptr, nullptr, nullptr));
         T.truth = truth;
-        hipLaunchKernelGGL(iss::k_truth_scatter, grid_for((uint64_t)ctx->pmut_cap, iss::TRUTH_THREADS), dim3(iss::TRUTH_THREADS), 0, st, T);
+        hipLaunchKernelGGL(iss::k_truth_scatter, grid_for((uint64_t)ctx->pmut.cap, iss::TRUTH_THREADS), dim3(iss::TRUTH_THREADS), 0, st, T);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (events) {
@@ -118,8 +117,8 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
         if (T.w0 < T.w1) {  // stages a and b of the VCF text (iss_vcf.hip.h) over every reserved slot: unused ones hold pair -1
             auto &w = ctx->tw;
             iss::VcfArgs A{};
-            A.mut = ctx->d_pmut;
-            A.n_slots = (uint32_t)ctx->pmut_cap;
+            A.mut = ctx->pmut.d;
+            A.n_slots = (uint32_t)ctx->pmut.cap;
             A.n_pairs = call_pairs;
             A.flags = T.flags;
             A.cnt = w.d_cnt;
@@ -129,8 +128,8 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
             A.order = w.d_order;
             A.n_rows = w.d_seg + call_pairs;
             HIP_TRY(ctx, hipMemsetAsync(w.d_cnt, 0, (size_t)call_pairs * 4, st));
-            HIP_TRY(ctx, hipMemsetAsync(w.d_order, 0, (size_t)ctx->pmut_cap * 4, st));
-            const dim3 grid = grid_for((uint64_t)ctx->pmut_cap, iss::VCF_THREADS), block(iss::VCF_THREADS);
+            HIP_TRY(ctx, hipMemsetAsync(w.d_order, 0, (size_t)ctx->pmut.cap * 4, st));
+            const dim3 grid = grid_for((uint64_t)ctx->pmut.cap, iss::VCF_THREADS), block(iss::VCF_THREADS);
             const unsigned tiles = (unsigned)(((uint64_t)call_pairs + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE);
             hipLaunchKernelGGL(iss::k_vcf_count, grid, block, 0, st, A);
             hipLaunchKernelGGL(iss::k_vcf_scan_sums, dim3(tiles), dim3(iss::VSCAN_THREADS), 0, st, (const uint32_t *)w.d_cnt, (uint64_t)call_pairs, w.d_tiles);
@@ -142,7 +141,7 @@ int iss_mutations_export(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int3
             HIP_TRY(ctx, hipGetLastError());
             T.seg = w.d_seg;
             T.order = w.d_order;
-            rows_max = (uint64_t)std::min<int64_t>(ctx->pmut_cap, capacity);
+            rows_max = (uint64_t)std::min<int64_t>(ctx->pmut.cap, capacity);
         }
         hipLaunchKernelGGL(iss::k_truth_events, grid_for(rows_max, iss::TRUTH_THREADS), dim3(iss::TRUTH_THREADS), 0, st, T);
         HIP_TRY(ctx, hipGetLastError());
@@ -160,7 +159,7 @@ int iss_ctx_set_stream_ordered(iss_ctx *ctx, void *hip_stream) {
     hipStream_t queued[5] = {ctx->stream, ctx->setup_stream, ctx->indel_stream, ctx->fill_stream, ctx->emit_stream};
     for (int k = 0; k < 5; ++k) {
         if (!queued[k]) continue;
-        if (!ctx->ev_handover[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_handover[k], hipEventDisableTiming));
+        if (!ctx->ev_handover[k]) ISS_TRY(event_create(ctx, ctx->ev_handover[k], hipEventDisableTiming));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_handover[k], queued[k]));
         HIP_TRY(ctx, hipStreamWaitEvent(next, ctx->ev_handover[k], 0));
     }

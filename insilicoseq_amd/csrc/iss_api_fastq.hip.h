@@ -24,7 +24,7 @@ static int fastq_emit_core(iss_ctx *ctx, int fd_r1, int fd_r2, int32_t n_items, 
     size_t bytes = 0, rec_len = 0;  // rec_len: record length of the item with the most pairs (the distance of its "previous record")
     int64_t n_records = 0, most = 0;
     for (int32_t k = 0; k < n_items; ++k) {
-        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0 || first_pair[k] + n_pairs[k] > ctx->capacity)
+        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0 || first_pair[k] + n_pairs[k] > ctx->os.capacity)
             return fail(ctx, ISS_E_INVALID, "iss_fastq_emit: bad argument");
         const size_t idlen = strlen(record_ids[k]);
         if (idlen > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_fastq_emit: record id longer than 4096 bytes");
@@ -59,15 +59,15 @@ static int fastq_emit_core(iss_ctx *ctx, int fd_r1, int fd_r2, int32_t n_items, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FastqPipe &q = ctx->fq;
     if (!q.ready) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.copy_stream, hipStreamNonBlocking));
-        for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : q.ev_copy) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ISS_TRY(stream_create(ctx, q.copy_stream, hipStreamNonBlocking));
+        for (auto &e : q.ev_fmt) ISS_TRY(event_create(ctx, e, hipEventDisableTiming));
+        for (auto &e : q.ev_copy) ISS_TRY(event_create(ctx, e, hipEventDisableTiming));
         q.stop = false;
         q.writer = std::thread(fastq_writer_loop, ctx);
         q.ready = true;
     }
     if (q.fd[0] != fd_r1 || q.fd[1] != fd_r2) {
-        { int rc_ = fastq_flush(ctx); if (rc_) return rc_; }
+        ISS_TRY(fastq_flush(ctx));
         q.fd[0] = fd_r1; q.fd[1] = fd_r2;
         for (int m = 0; m < 2; ++m) {
             const off_t at = lseek(q.fd[m], 0, SEEK_CUR);
@@ -81,48 +81,44 @@ static int fastq_emit_core(iss_ctx *ctx, int fd_r1, int fd_r2, int32_t n_items, 
     // smoothing of the counts (every symbol keeps a code) and the block headers are covered by the margin
     auto comp_bytes = [](size_t text, size_t blocks) { return text + text / 8 + blocks * 320 + 64; };
     if (bytes > q.cap || (q.gzip && (comp_bytes(bytes, n_blocks) > q.comp_cap || n_blocks > q.blocks_cap))) {
-        { int rc_ = fastq_flush_keep(ctx); if (rc_) return rc_; }
-        fastq_free_buffers(ctx);
+        ISS_TRY(fastq_flush_keep(ctx));
+        reset_part<FastqBuffers>(q);
         // (pinned allocations are slow: leave room for longer ids and pair numbers instead of growing batch by batch)
         const size_t cap = bytes + bytes / 8 + (1u << 20);
         const size_t cap_blocks = (cap + iss::DEFLATE_BLOCK - 1) / iss::DEFLATE_BLOCK;
         const size_t comp_cap = comp_bytes(cap, cap_blocks);
         const size_t host_bytes = q.gzip ? comp_cap : cap;
-        for (auto &sl : q.d_text) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, cap + 16)); p = static_cast<uint8_t *>(v); }
-        for (auto &sl : q.h_text) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, host_bytes, hipHostMallocDefault)); p = static_cast<uint8_t *>(v); }
+        for (auto &sl : q.d_text) for (auto &p : sl) DEV_ALLOC(ctx, p, cap + 16);
+        for (auto &sl : q.h_text) for (auto &p : sl) PIN_ALLOC(ctx, p, host_bytes);
         q.cap = cap;
         if (q.gzip) {
-            for (auto &sl : q.d_comp) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, comp_cap)); p = static_cast<uint8_t *>(v); }
-            for (auto &sl : q.d_bbytes) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, cap_blocks * 4)); p = static_cast<uint32_t *>(v); }
-            for (auto &sl : q.d_bcrc) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, cap_blocks * 4)); p = static_cast<uint32_t *>(v); }
-            for (auto &sl : q.d_boff) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, (cap_blocks + 1) * 8)); p = static_cast<uint64_t *>(v); }
-            for (auto &sl : q.h_bcrc) for (auto &p : sl) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, cap_blocks * 4, hipHostMallocDefault)); p = static_cast<uint32_t *>(v); }
+            for (auto &sl : q.d_comp) for (auto &p : sl) DEV_ALLOC(ctx, p, comp_cap);
+            for (auto &sl : q.d_bbytes) for (auto &p : sl) DEV_ALLOC(ctx, p, cap_blocks);
+            for (auto &sl : q.d_bcrc) for (auto &p : sl) DEV_ALLOC(ctx, p, cap_blocks);
+            for (auto &sl : q.d_boff) for (auto &p : sl) DEV_ALLOC(ctx, p, cap_blocks + 1);
+            for (auto &sl : q.h_bcrc) for (auto &p : sl) PIN_ALLOC(ctx, p, cap_blocks);
             q.comp_cap = comp_cap;
             q.blocks_cap = (uint32_t)cap_blocks;
         }
     }
-    if (q.gzip && !q.d_code[0][0]) {  // fixed-size state of the compressed mode, once
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
+    if (q.gzip && !q.h_total[1][1]) {  // fixed-size state of the compressed mode, once (the marker: the last piece of it)
+        ISS_TRY(stream_create(ctx, q.data_stream, hipStreamNonBlocking));
         iss::crc_shift_operator(iss::DEFLATE_BLOCK, q.op_block);
         iss::DeflateCode init{};
         for (int k = 0; k < 8; ++k) iss::crc_shift_operator((uint64_t)128 << k, init.crc_shift[k]);
         for (int sl = 0; sl < 2; ++sl)
             for (int m = 0; m < 2; ++m) {
-                void *v = nullptr;
-                HIP_TRY(ctx, hipMalloc(&v, (iss::DEFLATE_SYMS + 7) * 4));
-                q.d_hist[sl][m] = static_cast<uint32_t *>(v);
-                HIP_TRY(ctx, hipMalloc(&v, sizeof(iss::DeflateCode)));
-                q.d_code[sl][m] = static_cast<iss::DeflateCode *>(v);
-                HIP_TRY(ctx, hipMemcpy(v, &init, sizeof init, hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault));
-                q.h_total[sl][m] = static_cast<uint64_t *>(v);
+                DEV_ALLOC(ctx, q.d_hist[sl][m], iss::DEFLATE_SYMS + 7);
+                DEV_ALLOC(ctx, q.d_code[sl][m], 1);
+                HIP_TRY(ctx, hipMemcpy(q.d_code[sl][m], &init, sizeof init, hipMemcpyHostToDevice));
+                PIN_ALLOC(ctx, q.h_total[sl][m], 64 / sizeof(uint64_t));
             }
     }
     const int slot = q.next;
-    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
-    { int rc_ = q.tab.stage(ctx, slot, items, ids, ctx->stream); if (rc_) return rc_; }
-    A.items = q.tab.d_items[slot];
-    A.ids = q.tab.d_ids[slot];
+    ISS_TRY(writer_wait_slot(ctx, q, slot));
+    ISS_TRY(q.tab.stage(ctx, slot, items, ids, ctx->stream));
+    A.items = q.tab.slot[slot].d_items;
+    A.ids = q.tab.slot[slot].d_ids;
     for (int m = 0; m < 2; ++m) {
         A.base[m] = ctx->out[2 * m];
         A.qual[m] = ctx->out[2 * m + 1];
@@ -217,9 +213,9 @@ int iss_fastq_compress(iss_ctx *ctx, int32_t mode) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
     if (mode != 0 && mode != 1) return fail(ctx, ISS_E_INVALID, "iss_fastq_compress: mode must be 0 (text) or 1 (gzip members)");
     if (ctx->fq.gzip == mode) return 0;
-    { int rc_ = fastq_flush(ctx); if (rc_) return rc_; }
+    ISS_TRY(fastq_flush(ctx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    fastq_free_buffers(ctx);  // the host buffers have another size in the other mode
+    reset_part<FastqBuffers>(ctx->fq);  // the host buffers have another size in the other mode
     ctx->fq.gzip = mode;
     return 0;
 }

@@ -13,7 +13,7 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
 // timed, and not when k_indel_script appends --store_mutations rows (the call clears the row buffer on the main stream).
 static bool setup_runs_ahead(const iss_ctx *ctx) {
     const bool heavy = ctx->M.n_scan > 0 && !ctx->light;
-    return ctx->setup_ahead && !ctx->has_frag && !ctx->timing_all && !(heavy && ctx->d_pmut);
+    return ctx->setup_ahead && !ctx->has_frag && !ctx->timing_all && !(heavy && ctx->pmut.d);
 }
 
 int iss_generate(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, uint64_t first_ordinal, uint64_t seed,
@@ -22,7 +22,7 @@ int iss_generate(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, uint64_t firs
     if (genome_id < 0 || genome_id >= (int32_t)ctx->genomes.size()) return fail(ctx, ISS_E_INVALID, "unknown genome id");
     if (sequence_type != ISS_SEQ_METAGENOMICS && sequence_type != ISS_SEQ_AMPLICON)
         return fail(ctx, ISS_E_INVALID, "sequence type is not supported");  // generator.py:139, 171
-    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->capacity)
+    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
     const Genome &G = ctx->genomes[genome_id];
     const iss::DevModel &M = ctx->M;
@@ -69,9 +69,9 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
     // dropped the <= 4 GB chunks when the row offsets became 64-bit, and that was the 7 % it lost on this shape; k_main_g:
     // 11.4-11.5 / 10.8 / 10.8 ms.  (k_setup of chunk k + 1 runs beside k_main of chunk k either way.)
     const int64_t chunk_pairs = std::min(max_chunk, ctx->env_chunk_pairs ? ctx->env_chunk_pairs : MAIN_CHUNK_PAIRS);
-    if (ctx->d_pmut) {  // rows of THIS call only
-        ctx->d_pmut_count = reinterpret_cast<uint32_t *>(ctx->fix_count) + 60;  // +240 B of the scratch block
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_pmut, 0xff, (size_t)ctx->pmut_cap * sizeof(iss::MutRecord), ctx->stream));
+    if (ctx->pmut.d) {  // rows of THIS call only
+        ctx->d_pmut_count = ctx->fix_count + 60;  // +240 B of the scratch block
+        HIP_TRY(ctx, hipMemsetAsync(ctx->pmut.d, 0xff, (size_t)ctx->pmut.cap * sizeof(iss::MutRecord), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pmut_count, 0, sizeof(uint32_t), ctx->stream));
         ctx->pmut_call = true;
     }
@@ -82,8 +82,8 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
     // user of the set -- is done (custom fragment lengths: the host reads k_setup's results back: everything on one stream;
     // --store_mutations: the rows are cleared on the main stream above)
     const int par = (int)(ctx->call_seq++ & 1u);
-    ctx->flags = ctx->flags_buf[par];
-    ctx->fix_list = ctx->fixl_buf[par];
+    ctx->flags = ctx->os.flags_buf[par];
+    ctx->fix_list = ctx->os.fixl_buf[par];
     const bool ahead = setup_runs_ahead(ctx);
     hipStream_t s_setup = ahead ? ctx->setup_stream : ctx->stream;
     hipStream_t s_main = ctx->stream;
@@ -103,8 +103,8 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         A.gc_bias = gc_bias ? 1 : 0;
         A.gc_thr = 8106479329266893ull;  // ceil(0.90 * 2^53), 0.90 being the f64 nearest to 0.9
         for (int k = 0; k < 4; ++k) A.out[k] = ctx->out[k] + (size_t)row0 * M.row;
-        iss::PairDesc *desc = ctx->desc_buf[par] + row0;
-        A.desc_out = ctx->desc + row0;
+        iss::PairDesc *desc = ctx->os.desc_buf[par] + row0;
+        A.desc_out = ctx->os.desc + row0;
         uint32_t *flags = ctx->flags + row0;
         uint32_t *fix_list = ctx->fix_list + 2 * row0;
         TimedLaunch tl{};
@@ -112,9 +112,11 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         auto mark = [&](int k, hipStream_t st) -> hipError_t {
             if (!ctx->timing) return hipSuccess;
             if (ctx->timing_main_only && k != 1 && k != 2) return hipSuccess;  // (every event costs a bubble in the stream)
-            hipError_t e = hipEventCreate(&tl.ev[k]);
+            hipEvent_t ev = nullptr;
+            hipError_t e = hipEventCreate(&ev);
             if (e != hipSuccess) return e;
-            return hipEventRecord(tl.ev[k], st);
+            tl.ev[k].reset(ev);
+            return hipEventRecord(ev, st);
         };
         // fix-list / read-list counters of this chunk: rings of FIX_SLOTS counters.  The setup stream runs ahead of the main
         // stream: before a slot's counters are cleared for its next user, the chunk that used it last must be done with them
@@ -124,9 +126,9 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         uint32_t *read_counter = ctx->read_count + (size_t)slot_i * 2 * iss::SCAN_MAX_WGS;  // (two per workgroup of k_indel_scan, all of them written by it)
         if (ahead && ctx->ev_slot_valid[slot_i]) HIP_TRY(ctx, hipStreamWaitEvent(s_setup, ctx->ev_slot_done[slot_i], 0));
         HIP_TRY(ctx, hipMemsetAsync(counter, 0, sizeof(uint32_t), s_setup));
-        A.mut = ctx->d_pmut;
+        A.mut = ctx->pmut.d;
         A.mut_count = ctx->d_pmut_count;
-        A.mut_cap = (uint32_t)ctx->pmut_cap;
+        A.mut_cap = (uint32_t)ctx->pmut.cap;
         A.pair_base = done;
         A.items = items;
         A.item_first = item_first;
@@ -141,28 +143,22 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         A.read_count = read_counter;
         A.scan_wgs = (uint32_t)std::min<uint64_t>(std::min<uint64_t>((uint64_t)ctx->n_cu * 2, iss::SCAN_MAX_WGS), (2 * (uint64_t)n + iss::SCAN_THREADS - 1) / iss::SCAN_THREADS);
         A.light = ctx->light ? (iss::setup_lds_bytes(M.n_isize, M.ev_ns, true) <= (size_t)150 * 1024 ? 1 : 2) : 0;
-        A.script = heavy ? ctx->script[par] + (size_t)2 * (size_t)row0 * (size_t)M.sc_stride : nullptr;
+        A.script = heavy ? ctx->os.script[par] + (size_t)2 * (size_t)row0 * (size_t)M.sc_stride : nullptr;
         A.has_frag = ctx->has_frag ? 1 : 0;
         A.frag_mu = ctx->frag_mu;
         A.frag_sd = ctx->frag_sd;
         A.frag_guard = ctx->mt_guard;
         if (ctx->has_frag) {
-            if (ctx->amb_cap < n) {
-                if (ctx->d_amb) (void)hipFree(ctx->d_amb);
-                if (ctx->d_ov_pairs) (void)hipFree(ctx->d_ov_pairs);
-                if (ctx->d_ov_frags) (void)hipFree(ctx->d_ov_frags);
-                void *p = nullptr;
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)n * sizeof(iss::FragAmb)));
-                ctx->d_amb = static_cast<iss::FragAmb *>(p);
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)n * sizeof(uint32_t)));
-                ctx->d_ov_pairs = static_cast<uint32_t *>(p);
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)n * sizeof(int64_t)));
-                ctx->d_ov_frags = static_cast<int64_t *>(p);
-                ctx->amb_cap = n;
+            if (ctx->fw.cap < n) {
+                ctx->fw = {};
+                DEV_ALLOC(ctx, ctx->fw.d_amb, (size_t)n);
+                DEV_ALLOC(ctx, ctx->fw.d_ov_pairs, (size_t)n);
+                DEV_ALLOC(ctx, ctx->fw.d_ov_frags, (size_t)n);
+                ctx->fw.cap = n;
             }
-            ctx->d_amb_count = reinterpret_cast<uint32_t *>(ctx->fix_count) + 56;  // +224 B of the 256-byte scratch block
+            ctx->d_amb_count = ctx->fix_count + 56;  // +224 B of the 256-byte scratch block
             HIP_TRY(ctx, hipMemsetAsync(ctx->d_amb_count, 0, sizeof(uint32_t), s_main));
-            A.amb_list = ctx->d_amb;
+            A.amb_list = ctx->fw.d_amb;
             A.amb_count = ctx->d_amb_count;
         }
         tl.scan_first = heavy && !ahead;
@@ -180,17 +176,17 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
             HIP_TRY(ctx, hipStreamSynchronize(s_main));
             if (n_amb) {
                 std::vector<iss::FragAmb> amb(n_amb);
-                HIP_TRY(ctx, hipMemcpy(amb.data(), ctx->d_amb, n_amb * sizeof(iss::FragAmb), hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(amb.data(), ctx->fw.d_amb, n_amb * sizeof(iss::FragAmb), hipMemcpyDeviceToHost));
                 std::vector<uint32_t> pairs(n_amb);
                 std::vector<int64_t> frags(n_amb);
                 for (uint32_t k = 0; k < n_amb; ++k) {
                     pairs[k] = amb[k].pair;
                     frags[k] = host_int_normal(amb[k].x1, amb[k].x2, false, ctx->frag_mu, ctx->frag_sd);
                 }
-                HIP_TRY(ctx, hipMemcpy(ctx->d_ov_pairs, pairs.data(), n_amb * sizeof(uint32_t), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMemcpy(ctx->d_ov_frags, frags.data(), n_amb * sizeof(int64_t), hipMemcpyHostToDevice));
-                A.ov_pairs = ctx->d_ov_pairs;
-                A.ov_frags = ctx->d_ov_frags;
+                HIP_TRY(ctx, hipMemcpy(ctx->fw.d_ov_pairs, pairs.data(), n_amb * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIP_TRY(ctx, hipMemcpy(ctx->fw.d_ov_frags, frags.data(), n_amb * sizeof(int64_t), hipMemcpyHostToDevice));
+                A.ov_pairs = ctx->fw.d_ov_pairs;
+                A.ov_frags = ctx->fw.d_ov_frags;
                 A.n_ov = n_amb;
                 hipLaunchKernelGGL(iss::k_setup_override, dim3((n_amb + 63) / 64), dim3(64), 0, s_main, M, dg, A, desc);
             }
@@ -230,7 +226,7 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
             if (!ahead) HIP_TRY(ctx, mark(4, s_setup));
         }
         if (ahead) {  // k_main (and what follows it) waits for this chunk's setup-stream kernels
-            if (ctx->timing && !ctx->timing_main_only) { HIP_TRY(ctx, hipEventCreate(&tl.ev[7])); HIP_TRY(ctx, hipEventRecord(tl.ev[7], s_setup)); }
+            if (ctx->timing && !ctx->timing_main_only) { ISS_TRY(event_create(ctx, tl.ev[7], hipEventDefault)); HIP_TRY(ctx, hipEventRecord(tl.ev[7], s_setup)); }
             HIP_TRY(ctx, hipEventRecord(ctx->ev_setup_done[slot_i], s_setup));
             HIP_TRY(ctx, hipStreamWaitEvent(s_main, ctx->ev_setup_done[slot_i], 0));
         }
@@ -299,7 +295,7 @@ static int generate_core(iss_ctx *ctx, const iss::DevGenome &dg, bool any_except
         HIP_TRY(ctx, hipEventRecord(ctx->ev_slot_done[slot_i], s_main));
         ctx->ev_slot_valid[slot_i] = true;
         HIP_TRY(ctx, hipGetLastError());
-        if (ctx->timing) ctx->timed.push_back(tl);
+        if (ctx->timing) ctx->timed.push_back(std::move(tl));
         done += n;
     }
     ctx->n_launches += 1;
@@ -315,59 +311,31 @@ int iss_synchronize(iss_ctx *ctx) {
 
 int iss_output_download(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint8_t *r1_base, uint8_t *r1_qual,
                         uint8_t *r2_base, uint8_t *r2_qual) {
-    if (!ctx || first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (!ctx || first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_output_download: rows out of range");
     uint8_t *host[4] = {r1_base, r1_qual, r2_base, r2_qual};
     const size_t pitch = (size_t)ctx->M.pitch;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     if (!n_pairs) return 0;
     // the device rows are interleaved (iss::xp): four plain [n_pairs][pitch] arrays are formed on the device, then copied
     const size_t need = 4 * pitch * (size_t)n_pairs;
-    if (ctx->stage_cap < need) {
-        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr; ctx->stage_cap = 0;
-        void *q = nullptr;
-        HIP_TRY(ctx, hipMalloc(&q, need));
-        ctx->d_stage = static_cast<uint8_t *>(q);
-        ctx->stage_cap = need;
+    if (ctx->os.stage.cap < need) {
+        ctx->os.stage = {};
+        DEV_ALLOC(ctx, ctx->os.stage.d, need);
+        ctx->os.stage.cap = need;
     }
     {
         hipLaunchKernelGGL(iss::k_rows_to_arrays, dim3((unsigned)((n_pairs + 3) / 4)), dim3(64, 4), 0, ctx->stream,
-                           ctx->out[0] + (size_t)first_pair * ctx->M.row, ctx->d_stage, n_pairs, ctx->M.S, ctx->M.row);
+                           ctx->out[0] + (size_t)first_pair * ctx->M.row, ctx->os.stage.d, n_pairs, ctx->M.S, ctx->M.row);
         HIP_TRY(ctx, hipGetLastError());
     }
     for (int k = 0; k < 4; ++k)
         if (host[k])
-            HIP_TRY(ctx, hipMemcpyAsync(host[k], ctx->d_stage + (size_t)k * pitch * (size_t)n_pairs, pitch * (size_t)n_pairs,
+            HIP_TRY(ctx, hipMemcpyAsync(host[k], ctx->os.stage.d + (size_t)k * pitch * (size_t)n_pairs, pitch * (size_t)n_pairs,
                                         hipMemcpyDeviceToHost, ctx->stream));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     return 0;
-}
-
-static void free_item_tables(iss_ctx *ctx) {
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->d_items[k]) (void)hipFree(ctx->d_items[k]);
-        if (ctx->d_item_first[k]) (void)hipFree(ctx->d_item_first[k]);
-        if (ctx->h_items[k]) (void)hipHostFree(ctx->h_items[k]);
-        if (ctx->h_item_first[k]) (void)hipHostFree(ctx->h_item_first[k]);
-        if (ctx->ev_items[k]) (void)hipEventDestroy(ctx->ev_items[k]);
-        ctx->d_items[k] = ctx->h_items[k] = nullptr;
-        ctx->d_item_first[k] = ctx->h_item_first[k] = nullptr;
-        ctx->ev_items[k] = nullptr;
-    }
-    ctx->d_items_cap = 0;
-}
-
-static void free_community(iss_ctx *ctx) {
-    if (ctx->comm_packed) (void)hipFree(ctx->comm_packed);
-    if (ctx->comm_mask) (void)hipFree(ctx->comm_mask);
-    if (ctx->comm_ascii) (void)hipFree(ctx->comm_ascii);
-    ctx->comm_packed = ctx->comm_mask = nullptr;
-    ctx->comm_ascii = nullptr;
-    ctx->comm_cap = 0;
-    ctx->comm_ids.clear();
-    ctx->comm_items.clear();
 }
 
 int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids, const int64_t *n_pairs, uint64_t first_ordinal,
@@ -387,7 +355,7 @@ int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids,
         total += n_pairs[k];
         first[(size_t)k + 1] = total;
     }
-    if (out_first_pair < 0 || out_first_pair + total > ctx->capacity)
+    if (out_first_pair < 0 || out_first_pair + total > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
     if (total == 0) return 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -420,7 +388,7 @@ int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids,
     } else if (!single) {
         // ---- the records side by side in one arena (kept until another list of records is asked for; the buffers are
         // kept as long as they are large enough -- refilling them is ordered on the stream behind their last readers)
-        if (ids != ctx->comm_ids) {
+        if (ids != ctx->comm.ids) {
             std::vector<iss::BatchItem> items((size_t)n_items);
             std::vector<int64_t> place(ctx->genomes.size(), -1);  // a record used by several items stands once
             int64_t coord = 64;
@@ -437,72 +405,63 @@ int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids,
             // (arena coordinates are the pair descriptors' 36-bit coordinates and k_main's 32-bit word numbers, like a single
             //  record's: round 5 -- until then the records of a call had to stay below 2^31 bases)
             if (coord >= iss::MAX_RECORD) return fail(ctx, ISS_E_INVALID, "iss_generate_batch: the records of one call must stay below 2^34 - 4096 bases");
-            if (coord > ctx->comm_cap) {
-                { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-                free_community(ctx);
+            if (coord > ctx->comm.cap) {
+                ISS_TRY(sync_all(ctx));
+                ctx->comm = {};
                 const int64_t cap = coord + coord / 4;
-                void *p = nullptr;
-                HIP_TRY(ctx, hipMalloc(&p, ((size_t)cap / 16 + 8) * 4));
-                ctx->comm_packed = static_cast<uint32_t *>(p);
-                HIP_TRY(ctx, hipMalloc(&p, ((size_t)cap / 32 + 8) * 4));
-                ctx->comm_mask = static_cast<uint32_t *>(p);
-                HIP_TRY(ctx, hipMalloc(&p, (size_t)cap + 64));
-                ctx->comm_ascii = static_cast<uint8_t *>(p);
-                ctx->comm_cap = cap;
+                DEV_ALLOC(ctx, ctx->comm.packed, (size_t)cap / 16 + 8);
+                DEV_ALLOC(ctx, ctx->comm.mask, (size_t)cap / 32 + 8);
+                DEV_ALLOC(ctx, ctx->comm.ascii, (size_t)cap + 64);
+                ctx->comm.cap = cap;
             }
-            ctx->comm_ids.clear();  // (not valid while it is being refilled)
-            HIP_TRY(ctx, hipMemsetAsync(ctx->comm_packed, 0, ((size_t)coord / 16 + 8) * 4, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->comm_mask, 0, ((size_t)coord / 32 + 8) * 4, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->comm_ascii, 'A', (size_t)coord + 64, ctx->stream));
+            ctx->comm.ids.clear();  // (not valid while it is being refilled)
+            HIP_TRY(ctx, hipMemsetAsync(ctx->comm.packed, 0, ((size_t)coord / 16 + 8) * 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->comm.mask, 0, ((size_t)coord / 32 + 8) * 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->comm.ascii, 'A', (size_t)coord + 64, ctx->stream));
             for (size_t g = 0; g < place.size(); ++g) {
                 if (place[g] < 0) continue;
                 const Genome &G = ctx->genomes[g];
                 const size_t w_mk = (size_t)(G.L + 31) / 32;
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm_packed + 2 + place[g] / 16, G.packed, 2 * w_mk * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm_mask + 2 + place[g] / 32, G.mask, w_mk * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm_ascii + place[g], G.ascii, (size_t)G.L, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm.packed + 2 + place[g] / 16, G.packed, 2 * w_mk * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm.mask + 2 + place[g] / 32, G.mask, w_mk * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->comm.ascii + place[g], G.ascii, (size_t)G.L, hipMemcpyDeviceToDevice, ctx->stream));
             }
-            ctx->comm_ids = ids;
-            ctx->comm_items = items;
-            ctx->comm_exceptions = exceptions;
+            ctx->comm.ids = ids;
+            ctx->comm.items = items;
+            ctx->comm.exceptions = exceptions;
             HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));  // (k_setup may run on the setup stream: it waits for the arena)
             ctx->inputs_pending = true;
         }
-        call_items = ctx->comm_items;
-        dg = iss::DevGenome{ctx->comm_packed + 2, ctx->comm_mask + 2, ctx->comm_ascii, 0, ctx->comm_exceptions ? 1 : 0};
-        any_exceptions = ctx->comm_exceptions;
+        call_items = ctx->comm.items;
+        dg = iss::DevGenome{ctx->comm.packed + 2, ctx->comm.mask + 2, ctx->comm.ascii, 0, ctx->comm.exceptions ? 1 : 0};
+        any_exceptions = ctx->comm.exceptions;
     }
-    if ((size_t)n_items + 1 > ctx->d_items_cap) {
-        { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-        free_item_tables(ctx);
+    if ((size_t)n_items + 1 > ctx->it.cap) {
+        ISS_TRY(sync_all(ctx));
+        ctx->it = {};
         const size_t cap = (size_t)n_items + 1 + 64;
         for (int k = 0; k < 2; ++k) {
-            void *p = nullptr;
-            HIP_TRY(ctx, hipMalloc(&p, cap * sizeof(iss::BatchItem)));
-            ctx->d_items[k] = static_cast<iss::BatchItem *>(p);
-            HIP_TRY(ctx, hipMalloc(&p, cap * sizeof(int64_t)));
-            ctx->d_item_first[k] = static_cast<int64_t *>(p);
-            HIP_TRY(ctx, hipHostMalloc(&p, cap * sizeof(iss::BatchItem), hipHostMallocDefault));
-            ctx->h_items[k] = static_cast<iss::BatchItem *>(p);
-            HIP_TRY(ctx, hipHostMalloc(&p, cap * sizeof(int64_t), hipHostMallocDefault));
-            ctx->h_item_first[k] = static_cast<int64_t *>(p);
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_items[k], hipEventDisableTiming));
+            DEV_ALLOC(ctx, ctx->it.d_items[k], cap);
+            DEV_ALLOC(ctx, ctx->it.d_item_first[k], cap);
+            PIN_ALLOC(ctx, ctx->it.h_items[k], cap);
+            PIN_ALLOC(ctx, ctx->it.h_item_first[k], cap);
+            ISS_TRY(event_create(ctx, ctx->it.ev_items[k], hipEventDisableTiming));
         }
-        ctx->d_items_cap = cap;
+        ctx->it.cap = cap;
         ctx->batch_seq = 0;
     }
     const int set = (int)(ctx->batch_seq & 1u);
-    if (ctx->batch_seq >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_items[set]));  // the call before last is done with this set
-    memcpy(ctx->h_items[set], call_items.data(), (size_t)n_items * sizeof(iss::BatchItem));
-    memcpy(ctx->h_item_first[set], first.data(), ((size_t)n_items + 1) * sizeof(int64_t));
+    if (ctx->batch_seq >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->it.ev_items[set]));  // the call before last is done with this set
+    memcpy(ctx->it.h_items[set], call_items.data(), (size_t)n_items * sizeof(iss::BatchItem));
+    memcpy(ctx->it.h_item_first[set], first.data(), ((size_t)n_items + 1) * sizeof(int64_t));
     // (on the stream k_setup runs on: beside the previous call's kernels, not behind them)
     hipStream_t s_in = setup_runs_ahead(ctx) ? ctx->setup_stream : ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_items[set], ctx->h_items[set], (size_t)n_items * sizeof(iss::BatchItem), hipMemcpyHostToDevice, s_in));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_item_first[set], ctx->h_item_first[set], ((size_t)n_items + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s_in));
-    const int rc = generate_core(ctx, dg, any_exceptions, ctx->d_items[set], ctx->d_item_first[set], n_items, total, first_ordinal,
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->it.d_items[set], ctx->it.h_items[set], (size_t)n_items * sizeof(iss::BatchItem), hipMemcpyHostToDevice, s_in));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->it.d_item_first[set], ctx->it.h_item_first[set], ((size_t)n_items + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s_in));
+    const int rc = generate_core(ctx, dg, any_exceptions, ctx->it.d_items[set], ctx->it.d_item_first[set], n_items, total, first_ordinal,
                                  seed, sequence_type, gc_bias, out_first_pair);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->it.ev_items[set], ctx->stream));
     ++ctx->batch_seq;
     ctx->last_first.assign(first.begin(), first.end());
     ctx->last_off.resize((size_t)n_items);
@@ -512,10 +471,6 @@ int iss_generate_batch(iss_ctx *ctx, int32_t n_items, const int32_t *genome_ids,
 
 // ---- the inner plugin surface (ErrorModel methods), batched: see iss_units.hip.h and include/iss_mi355x.h
 namespace {
-struct DevBuf {  // a device allocation freed at scope exit
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
 int unit_prologue(iss_ctx *ctx, int32_t orientation, int64_t n, const char *what) {
     if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, std::string(what) + ": upload a model first");
     if (ctx->M.quality_mode != 0) return fail(ctx, ISS_E_INVALID, std::string(what) + ": KDErrorModel tables only");
@@ -531,12 +486,12 @@ int iss_gen_phred_scores(iss_ctx *ctx, int32_t orientation, int64_t n, uint64_t 
     if (!n) return 0;
     if (!quality) return fail(ctx, ISS_E_INVALID, "iss_gen_phred_scores: NULL output");
     const size_t bytes = (size_t)n * ctx->M.RL;
-    DevBuf d;
-    HIP_TRY(ctx, hipMalloc(&d.p, bytes));
+    DevMem<uint8_t> d;
+    DEV_ALLOC(ctx, d, bytes);
     const iss::UnitArgs U{seed, first_ordinal, orientation, (int32_t)n};
-    hipLaunchKernelGGL(iss::k_unit_phred, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, static_cast<uint8_t *>(d.p));
+    hipLaunchKernelGGL(iss::k_unit_phred, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, d);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(quality, d.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(quality, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -549,18 +504,19 @@ int iss_mut_sequence(iss_ctx *ctx, int32_t orientation, int64_t n, uint64_t firs
     const size_t bytes = (size_t)n * ctx->M.RL;
     for (size_t k = 0; k < bytes; ++k)
         if (quality[k] > (uint8_t)ctx->M.n_q) return fail(ctx, ISS_E_INVALID, "iss_mut_sequence: phred score outside the model's table");
-    DevBuf ds, dq, dst;
-    HIP_TRY(ctx, hipMalloc(&ds.p, bytes));
-    HIP_TRY(ctx, hipMalloc(&dq.p, bytes));
-    HIP_TRY(ctx, hipMalloc(&dst.p, (size_t)n * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ds.p, seq, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dq.p, quality, bytes, hipMemcpyHostToDevice, ctx->stream));
+    DevMem<uint8_t> ds, dq;
+    DevMem<int32_t> dst;
+    DEV_ALLOC(ctx, ds, bytes);
+    DEV_ALLOC(ctx, dq, bytes);
+    DEV_ALLOC(ctx, dst, (size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(ds, seq, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dq, quality, bytes, hipMemcpyHostToDevice, ctx->stream));
     const iss::UnitArgs U{seed, first_ordinal, orientation, (int32_t)n};
-    hipLaunchKernelGGL(iss::k_unit_mut, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, static_cast<uint8_t *>(ds.p),
-                       static_cast<const uint8_t *>(dq.p), static_cast<int32_t *>(dst.p));
+    hipLaunchKernelGGL(iss::k_unit_mut, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, ds,
+                       dq, dst);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(seq, ds.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(status, dst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(seq, ds, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(status, dst, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -569,12 +525,12 @@ int iss_random_insert_size(iss_ctx *ctx, int64_t n, uint64_t first_ordinal, uint
     if (int rc = unit_prologue(ctx, 0, n, "iss_random_insert_size")) return rc;
     if (!n) return 0;
     if (!insert_size) return fail(ctx, ISS_E_INVALID, "iss_random_insert_size: NULL output");
-    DevBuf d;
-    HIP_TRY(ctx, hipMalloc(&d.p, (size_t)n * sizeof(int64_t)));
+    DevMem<int64_t> d;
+    DEV_ALLOC(ctx, d, (size_t)n);
     const iss::UnitArgs U{seed, first_ordinal, 0, (int32_t)n};
-    hipLaunchKernelGGL(iss::k_unit_isize, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, static_cast<int64_t *>(d.p));
+    hipLaunchKernelGGL(iss::k_unit_isize, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, d);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(insert_size, d.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(insert_size, d, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -587,23 +543,25 @@ int iss_ev_step(iss_ctx *ctx, int32_t orientation, int64_t n, const int32_t *cur
     for (int64_t i = 0; i < n; ++i)
         if (cur[i] < -1 || cur[i] > ctx->M.ev_ns - 2 || (m53[i] >> 53) || (v53[i] >> 53))
             return fail(ctx, ISS_E_INVALID, "iss_ev_step: state or numerator out of range");
-    DevBuf dc, dm, dv, dn, ds, dk;
-    HIP_TRY(ctx, hipMalloc(&dc.p, (size_t)n * 4));
-    HIP_TRY(ctx, hipMalloc(&dm.p, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc(&dv.p, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc(&dn.p, (size_t)n * 4));
-    HIP_TRY(ctx, hipMalloc(&ds.p, (size_t)n * 4));
-    HIP_TRY(ctx, hipMalloc(&dk.p, (size_t)n));
-    HIP_TRY(ctx, hipMemcpyAsync(dc.p, cur, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dm.p, m53, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dv.p, v53, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    DevMem<int32_t> dc, dn, ds;
+    DevMem<uint64_t> dm, dv;
+    DevMem<uint8_t> dk;
+    DEV_ALLOC(ctx, dc, (size_t)n);
+    DEV_ALLOC(ctx, dm, (size_t)n);
+    DEV_ALLOC(ctx, dv, (size_t)n);
+    DEV_ALLOC(ctx, dn, (size_t)n);
+    DEV_ALLOC(ctx, ds, (size_t)n);
+    DEV_ALLOC(ctx, dk, (size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(dc, cur, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dm, m53, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dv, v53, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(iss::k_unit_ev_step, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, orientation, (int32_t)n,
-                       static_cast<const int32_t *>(dc.p), static_cast<const uint64_t *>(dm.p), static_cast<const uint64_t *>(dv.p),
-                       static_cast<int32_t *>(dn.p), static_cast<int32_t *>(ds.p), static_cast<uint8_t *>(dk.p));
+                       dc, dm, dv,
+                       dn, ds, dk);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(next, dn.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(slot, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(mask, dk.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(next, dn, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(slot, ds, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(mask, dk, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -623,38 +581,40 @@ int iss_introduce_indels(iss_ctx *ctx, int32_t orientation, int64_t n, uint64_t 
             return fail(ctx, ISS_E_INVALID, "iss_introduce_indels: negative read bounds");
     const int32_t cap = 6 * RL + 8;  // letters (<= 5 RL + 8) + the event masks of the steps
     const size_t bytes = (size_t)n * RL;
-    DevBuf ds, dl, dg, db, dw, dout, dst;
-    HIP_TRY(ctx, hipMalloc(&ds.p, bytes));
-    HIP_TRY(ctx, hipMalloc(&dl.p, (size_t)n * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc(&dg.p, (size_t)full_len));
-    HIP_TRY(ctx, hipMalloc(&db.p, (size_t)n * 2 * sizeof(int64_t)));
-    HIP_TRY(ctx, hipMalloc(&dw.p, (size_t)n * cap));
-    HIP_TRY(ctx, hipMalloc(&dout.p, bytes));
-    HIP_TRY(ctx, hipMalloc(&dst.p, (size_t)n * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ds.p, seq, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dl.p, seq_len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dg.p, full_seq, (size_t)full_len, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(db.p, bounds, (size_t)n * 2 * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    DevMem<uint8_t> ds, dg, dw, dout;
+    DevMem<int32_t> dl, dst;
+    DevMem<int64_t> db;
+    DEV_ALLOC(ctx, ds, bytes);
+    DEV_ALLOC(ctx, dl, (size_t)n);
+    DEV_ALLOC(ctx, dg, (size_t)full_len);
+    DEV_ALLOC(ctx, db, (size_t)n * 2);
+    DEV_ALLOC(ctx, dw, (size_t)n * cap);
+    DEV_ALLOC(ctx, dout, bytes);
+    DEV_ALLOC(ctx, dst, (size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(ds, seq, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dl, seq_len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dg, full_seq, (size_t)full_len, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(db, bounds, (size_t)n * 2 * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     const iss::UnitArgs U{seed, first_ordinal, orientation, (int32_t)n};
-    hipLaunchKernelGGL(iss::k_unit_indels, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, static_cast<const uint8_t *>(ds.p),
-                       static_cast<const int32_t *>(dl.p), static_cast<const uint8_t *>(dg.p), full_len, static_cast<const int64_t *>(db.p),
-                       static_cast<uint8_t *>(dw.p), cap, static_cast<uint8_t *>(dout.p), static_cast<int32_t *>(dst.p));
+    hipLaunchKernelGGL(iss::k_unit_indels, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, ctx->M, U, ds,
+                       dl, dg, full_len, db,
+                       dw, cap, dout, dst);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(status, dst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(status, dst, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
 int iss_output_download_coords(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, int64_t *coords) {
-    if (!ctx || !coords || first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (!ctx || !coords || first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_output_download_coords: rows out of range");
     std::vector<iss::PairDesc> tmp((size_t)n_pairs);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n_pairs)
-        HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->desc + first_pair, sizeof(iss::PairDesc) * (size_t)n_pairs,
+        HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->os.desc + first_pair, sizeof(iss::PairDesc) * (size_t)n_pairs,
                                     hipMemcpyDeviceToHost, ctx->stream));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     for (int64_t i = 0; i < n_pairs; ++i) {
         int64_t off = 0;  // rows of a batch call carry arena coordinates: back to the record's own
         const int64_t r = first_pair + i - ctx->last_row0;
@@ -681,7 +641,7 @@ int iss_timing_enable(iss_ctx *ctx, int enable) {
 
 int iss_timing_read(iss_ctx *ctx, double ms[4], int64_t *n_launches) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     int rc = settle_timing(ctx);
     if (rc) return rc;
     for (int k = 0; k < 4; ++k) { if (ms) ms[k] = ctx->ms_acc[k]; ctx->ms_acc[k] = 0; }
@@ -692,7 +652,7 @@ int iss_timing_read(iss_ctx *ctx, double ms[4], int64_t *n_launches) {
 
 int iss_stats_read(iss_ctx *ctx, int64_t *n_fixup_reads, int64_t *n_scripted_reads) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     uint64_t v[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpy(v, ctx->stats, sizeof v, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemset(ctx->stats, 0, sizeof v));

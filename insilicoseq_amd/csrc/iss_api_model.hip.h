@@ -12,7 +12,7 @@ int iss_model_upload(iss_ctx *ctx, const iss_model_tables *t) {
     if (t->n_isize < 1 || t->n_q < 1 || t->n_q > 60)
         return fail(ctx, ISS_E_INVALID, "bad table sizes (per-position quality CDFs must have 1..60 entries)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     free_model(ctx);
     read_switches(ctx);
     const int RL = t->read_length, nq = t->n_q;
@@ -348,9 +348,8 @@ int iss_model_upload(iss_ctx *ctx, const iss_model_tables *t) {
             for (int x = 0; x < 5; ++x) rate += (double)mt_lim[e * 5 + x] / 134217728.0;
         ctx->mt_bounce_rate = rate;
     }
-    int rc = 0;
     auto *tr = &ctx->model_allocs;
-#define UP(field, src, n, T) if ((rc = upload<T>(ctx, src, n, const_cast<T **>(&M.field), tr))) return rc
+#define UP(field, src, n, T) ISS_TRY(upload<T>(ctx, src, n, const_cast<T **>(&M.field), tr))
     UP(isize_thr, t->isize_thr, (size_t)t->n_isize, uint64_t);
     UP(bin_thr, t->bin_thr, 8, uint64_t);
     UP(q_thr, t->q_thr, n_qthr, uint64_t);
@@ -384,7 +383,7 @@ int iss_genome_upload(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int32_
     const size_t n_mk = (size_t)(length + 31) / 32, n_pk = 2 * n_mk;
     Genome G;
     G.L = length;
-    unsigned long long *status = reinterpret_cast<unsigned long long *>(ctx->fix_count) + 24;  // 3 words at +192 B
+    unsigned long long *status = reinterpret_cast<unsigned long long *>(ctx->fix_count.get()) + 24;  // 3 words at +192 B
     if (length <= SMALL_RECORD) {
         // small record: letters checked here (no wait for the device), buffers cut from the arena
         bool exceptions = false;
@@ -404,41 +403,37 @@ int iss_genome_upload(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int32_
         uint8_t *blk = ctx->arena.take((n_pk + PK_PAD) * 4 + 256 + (n_mk + 4) * 4 + 256 + (size_t)length, &he);
         if (!blk) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
         const size_t pk_bytes = ((n_pk + PK_PAD) * 4 + 255) & ~(size_t)255, mk_bytes = ((n_mk + 4) * 4 + 255) & ~(size_t)255;
-        G.packed_alloc = reinterpret_cast<uint32_t *>(blk);
-        G.mask_alloc = reinterpret_cast<uint32_t *>(blk + pk_bytes);
+        G.packed = reinterpret_cast<uint32_t *>(blk) + 1;  // (one leading pad word)
+        G.mask = reinterpret_cast<uint32_t *>(blk + pk_bytes) + 1;
         G.ascii = blk + pk_bytes + mk_bytes;
-        G.in_arena = true;
         // a synchronous copy: the caller's buffer may go away as soon as this call returns, and nothing waits for the
         // stream here any more (the slice is fresh memory, so no earlier launch can be using it)
         he = hipMemcpy(G.ascii, ascii, (size_t)length, hipMemcpyHostToDevice);
         if (he == hipSuccess) he = hipMemsetAsync(blk, 0, pk_bytes + mk_bytes, ctx->stream);
         if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
         hipLaunchKernelGGL(iss::k_pack_genome, dim3((unsigned)((n_mk + 255) / 256)), dim3(256), 0, ctx->stream, G.ascii, length,
-                           G.packed_alloc + 1, G.mask_alloc + 1, status);
+                           G.packed, G.mask, status);
         G.has_exceptions = exceptions;
-    } else {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, (n_pk + PK_PAD) * sizeof(uint32_t)));
-        G.packed_alloc = static_cast<uint32_t *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, (n_mk + 4) * sizeof(uint32_t)));
-        G.mask_alloc = static_cast<uint32_t *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, (size_t)length));
-        G.ascii = static_cast<uint8_t *>(p);
-        auto release = [&]() { (void)hipFree(G.packed_alloc); (void)hipFree(G.mask_alloc); (void)hipFree(G.ascii); };
+    } else {  // (a return below frees what G owns so far)
+        DEV_ALLOC(ctx, G.packed_own, n_pk + PK_PAD);
+        DEV_ALLOC(ctx, G.mask_own, n_mk + 4);
+        DEV_ALLOC(ctx, G.ascii_own, (size_t)length);
+        G.packed = G.packed_own + 1;
+        G.mask = G.mask_own + 1;
+        G.ascii = G.ascii_own;
         const unsigned long long init[3] = {0ull, (unsigned long long)length, 0ull};
         hipError_t he = hipMemcpyAsync(G.ascii, ascii, (size_t)length, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess) he = hipMemsetAsync(G.packed_alloc, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
-        if (he == hipSuccess) he = hipMemsetAsync(G.mask_alloc, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(G.packed_own, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(G.mask_own, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
         if (he == hipSuccess) he = hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, ctx->stream);
-        if (he != hipSuccess) { release(); return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he)); }
+        if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
         hipLaunchKernelGGL(iss::k_pack_genome, dim3((unsigned)((n_mk + 255) / 256)), dim3(256), 0, ctx->stream, G.ascii, length,
-                           G.packed_alloc + 1, G.mask_alloc + 1, status);
+                           G.packed, G.mask, status);
         unsigned long long res[3] = {0, 0, 0};
         he = hipMemcpyAsync(res, status, sizeof res, hipMemcpyDeviceToHost, ctx->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-        if (he != hipSuccess) { release(); return fail(ctx, ISS_E_HIP, std::string("genome pack: ") + hipGetErrorString(he)); }
+        if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome pack: ") + hipGetErrorString(he));
         if (res[0]) {
-            release();
             char buf[200];
             snprintf(buf, sizeof buf, "genome letter 0x%02x at offset %llu is outside the rev_comp alphabet (%llu such letters; "
                      "the reference raises KeyError, iss/util.py:90)", ascii[res[1]], res[1], res[0]);
@@ -446,12 +441,10 @@ int iss_genome_upload(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int32_
         }
         G.has_exceptions = res[2] != 0;
     }
-    G.packed = G.packed_alloc + 1;
-    G.mask = G.mask_alloc + 1;
     // (the packing kernel / copies of this record may still run on the main stream: k_setup, on the setup stream, waits for them)
     HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));
     ctx->inputs_pending = true;
-    ctx->genomes.push_back(G);
+    ctx->genomes.push_back(std::move(G));
     *genome_id = (int32_t)ctx->genomes.size() - 1;
     return 0;
 }
@@ -463,36 +456,32 @@ int iss_genome_upload_packed(iss_ctx *ctx, const uint32_t *codes, int64_t length
     if (length < 1 || length > iss::MAX_RECORD) return fail(ctx, ISS_E_INVALID, "genome length must be in [1, 2^34 - 4096]");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n_mk = (size_t)(length + 31) / 32, n_pk = 2 * n_mk, n_in = (size_t)(length + 15) / 16;
-    Genome G;
+    Genome G;  // (a return below frees what it owns so far)
     G.L = length;
-    auto release = [&]() {  // (whatever was allocated so far: hipFree(nullptr) is a no-op)
-        (void)hipFree(G.packed_alloc); (void)hipFree(G.mask_alloc); (void)hipFree(G.ascii);
-        G.packed_alloc = G.mask_alloc = nullptr; G.ascii = nullptr;
-    };
-    void *p = nullptr;
-    hipError_t he = hipMalloc(&p, (n_pk + PK_PAD) * sizeof(uint32_t));
-    if (he == hipSuccess) { G.packed_alloc = static_cast<uint32_t *>(p); he = hipMalloc(&p, (n_mk + 4) * sizeof(uint32_t)); }
-    if (he == hipSuccess) { G.mask_alloc = static_cast<uint32_t *>(p); he = hipMalloc(&p, (size_t)length); }
-    if (he == hipSuccess) G.ascii = static_cast<uint8_t *>(p);
-    if (he != hipSuccess) { release(); return fail(ctx, he == hipErrorOutOfMemory ? ISS_E_NOMEM : ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he)); }
-    he = hipMemsetAsync(G.packed_alloc, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(G.mask_alloc, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
+    hipError_t he = hipSuccess;
+    int rc = own_alloc_quiet(G.packed_own, (n_pk + PK_PAD) * sizeof(uint32_t), &he);
+    if (!rc) rc = own_alloc_quiet(G.mask_own, (n_mk + 4) * sizeof(uint32_t), &he);
+    if (!rc) rc = own_alloc_quiet(G.ascii_own, (size_t)length, &he);
+    if (rc) return fail(ctx, rc, std::string("genome upload: ") + hipGetErrorString(he));
+    G.packed = G.packed_own + 1;
+    G.mask = G.mask_own + 1;
+    G.ascii = G.ascii_own;
+    he = hipMemsetAsync(G.packed_own, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(G.mask_own, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
     if (he == hipSuccess)
-        he = hipMemcpyAsync(G.packed_alloc + 1, codes, n_in * sizeof(uint32_t), codes_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+        he = hipMemcpyAsync(G.packed, codes, n_in * sizeof(uint32_t), codes_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                             ctx->stream);
-    if (he != hipSuccess) { release(); return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he)); }
+    if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
     // the ASCII copy (exact path, FASTA-free consumers) from the codes; codes past the end are cleared
-    hipLaunchKernelGGL(iss::k_unpack_genome, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, ctx->stream, G.packed_alloc + 1, length,
+    hipLaunchKernelGGL(iss::k_unpack_genome, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, ctx->stream, G.packed, length,
                        G.ascii);
     he = hipStreamSynchronize(ctx->stream);  // the caller's buffer may go away once this call returns
-    if (he != hipSuccess) { release(); return fail(ctx, ISS_E_HIP, std::string("genome unpack: ") + hipGetErrorString(he)); }
+    if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome unpack: ") + hipGetErrorString(he));
     G.has_exceptions = false;
-    G.packed = G.packed_alloc + 1;
-    G.mask = G.mask_alloc + 1;
     // (the packing kernel / copies of this record may still run on the main stream: k_setup, on the setup stream, waits for them)
     HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));
     ctx->inputs_pending = true;
-    ctx->genomes.push_back(G);
+    ctx->genomes.push_back(std::move(G));
     *genome_id = (int32_t)ctx->genomes.size() - 1;
     return 0;
 }
@@ -523,17 +512,13 @@ int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii
     const size_t asc_b = up(C + 64), st_b = up((size_t)m * 8), stat_b = up((size_t)m * 16);
     const size_t pk_b = up((C / 16 + 2 + 16) * 4), mk_b = up((C / 32 + 2 + 8) * 4);
     const size_t total = asc_b + st_b + stat_b + pk_b + mk_b;
-    if (asc_b + st_b + stat_b > ctx->group_stage_cap) {
-        if (ctx->group_stage) (void)hipHostFree(ctx->group_stage);
-        ctx->group_stage = nullptr;
-        ctx->group_stage_cap = 0;
-        void *p = nullptr;
+    if (asc_b + st_b + stat_b > ctx->group_stage.cap) {
+        ctx->group_stage = {};
         const size_t cap = asc_b + st_b + stat_b;
-        HIP_TRY(ctx, hipHostMalloc(&p, cap, hipHostMallocDefault));
-        ctx->group_stage = static_cast<uint8_t *>(p);
-        ctx->group_stage_cap = cap;
+        PIN_ALLOC(ctx, ctx->group_stage.h, cap);
+        ctx->group_stage.cap = cap;
     }
-    uint8_t *h = ctx->group_stage;
+    uint8_t *h = ctx->group_stage.h;
     memset(h, 'A', 64);
     for (int32_t i = 0; i < m; ++i) {
         const int64_t L = lengths[which[(size_t)i]], s = starts[(size_t)i];
@@ -542,15 +527,13 @@ int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii
         memset(h + s + L, 'A', (size_t)(e - s - L));  // padding up to the next record (the last one: to the end of the region)
     }
     memcpy(h + asc_b, starts.data(), (size_t)m * 8);
-    GenomeGroup grp;
+    GenomeGroup grp;  // (a return below frees the block if the group owns it)
     hipError_t he = hipSuccess;
     if (total <= ARENA_SLAB / 4) {
         grp.block = ctx->arena.take(total, &he);
     } else {
-        void *p = nullptr;
-        he = hipMalloc(&p, total);
-        grp.block = static_cast<uint8_t *>(p);
-        grp.own = true;
+        (void)own_alloc_quiet(grp.own, total, &he);
+        grp.block = grp.own;
     }
     if (!grp.block) return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he));
     grp.ascii = grp.block;
@@ -558,10 +541,9 @@ int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii
     unsigned long long *d_status = reinterpret_cast<unsigned long long *>(grp.block + asc_b + st_b);
     grp.packed = reinterpret_cast<uint32_t *>(grp.block + asc_b + st_b + stat_b) + 2;
     grp.mask = reinterpret_cast<uint32_t *>(grp.block + asc_b + st_b + stat_b + pk_b) + 2;
-    auto release = [&]() { if (grp.own) (void)hipFree(grp.block); };
     he = hipMemcpyAsync(grp.block, h, asc_b + st_b, hipMemcpyHostToDevice, ctx->stream);
     if (he == hipSuccess) he = hipMemsetAsync(grp.block + asc_b + st_b, 0, stat_b + pk_b + mk_b, ctx->stream);
-    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); release(); return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he)); }
+    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he)); }
     const int64_t n_words = (int64_t)(C / 32);
     hipLaunchKernelGGL(iss::k_pack_group, dim3((unsigned)((n_words + iss::PACK_GROUP_THREADS - 1) / iss::PACK_GROUP_THREADS)),
                        dim3(iss::PACK_GROUP_THREADS), 0, ctx->stream, grp.ascii, n_words, d_starts, m, grp.packed, grp.mask, d_status);
@@ -569,22 +551,23 @@ int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii
     unsigned long long *res = reinterpret_cast<unsigned long long *>(h + asc_b + st_b);
     if (he == hipSuccess) he = hipMemcpyAsync(res, d_status, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);  // (also: the staging buffer is free again)
-    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); release(); return fail(ctx, ISS_E_HIP, std::string("genome group pack: ") + hipGetErrorString(he)); }
+    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group pack: ") + hipGetErrorString(he)); }
     const int32_t gi = (int32_t)ctx->groups.size();
-    ctx->groups.push_back(grp);
+    uint32_t *const grp_packed = grp.packed, *const grp_mask = grp.mask;
+    uint8_t *const grp_ascii = grp.ascii;
+    ctx->groups.push_back(std::move(grp));
     for (int32_t i = 0; i < m; ++i) {
         if (res[2 * (size_t)i]) continue;  // letters outside the alphabet: id -1
         const int64_t s = starts[(size_t)i];
         Genome G;
         G.L = lengths[which[(size_t)i]];
-        G.packed = grp.packed + s / 16;
-        G.mask = grp.mask + s / 32;
-        G.ascii = grp.ascii + s;
+        G.packed = grp_packed + s / 16;  // (views into the group's block: freed with the group)
+        G.mask = grp_mask + s / 32;
+        G.ascii = grp_ascii + s;
         G.has_exceptions = res[2 * (size_t)i + 1] != 0;
-        G.in_arena = true;  // (freed with the group)
         G.group = gi;
         G.coord = s;
-        ctx->genomes.push_back(G);
+        ctx->genomes.push_back(std::move(G));
         genome_ids[which[(size_t)i]] = (int32_t)ctx->genomes.size() - 1;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));
@@ -592,90 +575,73 @@ int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii
     return 0;
 }
 
-static void free_community(iss_ctx *ctx);
-static void free_item_tables(iss_ctx *ctx);
-
 int iss_genome_clear(iss_ctx *ctx) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
     (void)sync_all(ctx);
-    for (auto &G : ctx->genomes)
-        if (!G.in_arena) { (void)hipFree(G.packed_alloc); (void)hipFree(G.mask_alloc); (void)hipFree(G.ascii); }
     ctx->genomes.clear();
-    for (auto &g : ctx->groups)
-        if (g.own) (void)hipFree(g.block);
     ctx->groups.clear();
-    if (ctx->group_stage) (void)hipHostFree(ctx->group_stage);
-    ctx->group_stage = nullptr;
-    ctx->group_stage_cap = 0;
-    ctx->arena.clear();
-    free_community(ctx);
-    free_item_tables(ctx);
+    ctx->group_stage = {};
+    ctx->arena = {};
+    ctx->comm = {};
+    ctx->it = {};
     return 0;
 }
 
 int iss_output_reserve(iss_ctx *ctx, int64_t capacity_pairs) {
     if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_output_reserve: upload a model first");
     if (capacity_pairs < 1) return fail(ctx, ISS_E_INVALID, "capacity must be >= 1");
-    if (capacity_pairs <= ctx->capacity) return 0;
+    if (capacity_pairs <= ctx->os.capacity) return 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = fastq_flush(ctx); if (rc_) return rc_; }
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(fastq_flush(ctx));
+    ISS_TRY(sync_all(ctx));
     free_outputs(ctx);
-    void *q = nullptr;
     // (every buffer of the reservation through one checked allocation: out of memory frees what the call has allocated so far and
     //  is reported as ISS_E_NOMEM with the reservation's footprint -- the edit scripts of a five-tile heavy model are 1.3 KB per
     //  pair, more than its rows)
     const bool heavy_ = ctx->M.n_scan > 0 && !ctx->light;
     const double per_pair = (double)ctx->M.row + 3.0 * sizeof(iss::PairDesc) + 2.0 * 12.0 +
                             (heavy_ ? 2.0 : 1.0) * (8.0 + 8.0 * iss::EV_K + 32.0 + 16.0) + (heavy_ ? 4.0 * ctx->M.sc_stride : 0.0);
-#define ISS_RES_ALLOC(bytes)                                                                                                        \
+#define ISS_RES_ALLOC(handle, bytes)                                                                                                \
     do {                                                                                                                            \
-        const hipError_t e_ = hipMalloc(&q, (bytes));                                                                               \
-        if (e_ != hipSuccess) {                                                                                                     \
-            (void)hipGetLastError();                                                                                                \
+        hipError_t e_ = hipSuccess;                                                                                                 \
+        if (const int code_ = own_alloc_quiet(handle, (bytes), &e_)) {                                                                \
             free_outputs(ctx);                                                                                                      \
             char msg_[256];                                                                                                         \
             snprintf(msg_, sizeof msg_, "iss_output_reserve: %lld pairs need %.1f GB of HBM (%.0f B per pair%s): %s", (long long)capacity_pairs, \
                      per_pair * (double)capacity_pairs / 1e9, per_pair, heavy_ ? ", edit scripts included" : "", hipGetErrorString(e_));  \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? ISS_E_NOMEM : ISS_E_HIP, msg_);                                           \
+            return fail(ctx, code_, msg_);                                                                                          \
         }                                                                                                                           \
     } while (0)
     // (plain hipMalloc: physically contiguous rows -- hipExtMallocWithFlags(hipDeviceMallocContiguous) -- were measured at 1.82-1.88
     //  instead of 1.25-1.34 ms per step of the default bench, whatever the grid)
     //  instead of 1.25-1.34 ms per step of the default bench, whatever the grid; rows mapped from separately created physical
     //  chunks -- hipMemCreate / hipMemMap, 64 KB to 16 MB, in order or shuffled -- at 1.23-1.9: no layout helped on every box)
-    ISS_RES_ALLOC((size_t)ctx->M.row * (size_t)capacity_pairs);
-    for (int k = 0; k < 4; ++k) ctx->out[k] = static_cast<uint8_t *>(q) + iss::row_array_off(k);
+    // The ORDER of these allocations is part of that placement: keep it.
+    auto &os = ctx->os;
+    ISS_RES_ALLOC(os.rows, (size_t)ctx->M.row * (size_t)capacity_pairs);
+    for (int k = 0; k < 4; ++k) ctx->out[k] = os.rows + iss::row_array_off(k);
     for (int k = 0; k < 2; ++k) {  // (two sets: k_setup of a call runs beside the kernels of the call before)
-        ISS_RES_ALLOC(sizeof(iss::PairDesc) * (size_t)capacity_pairs);
-        ctx->desc_buf[k] = static_cast<iss::PairDesc *>(q);
-        ISS_RES_ALLOC(sizeof(uint32_t) * (size_t)capacity_pairs);
-        ctx->flags_buf[k] = static_cast<uint32_t *>(q);
-        ISS_RES_ALLOC(sizeof(uint32_t) * 2 * (size_t)capacity_pairs);
-        ctx->fixl_buf[k] = static_cast<uint32_t *>(q);
+        ISS_RES_ALLOC(os.desc_buf[k], sizeof(iss::PairDesc) * (size_t)capacity_pairs);
+        ISS_RES_ALLOC(os.flags_buf[k], sizeof(uint32_t) * (size_t)capacity_pairs);
+        ISS_RES_ALLOC(os.fixl_buf[k], sizeof(uint32_t) * 2 * (size_t)capacity_pairs);
     }
-    ISS_RES_ALLOC(sizeof(iss::PairDesc) * (size_t)capacity_pairs);
-    ctx->desc = static_cast<iss::PairDesc *>(q);  // what the host reads (iss_output_download_coords) and the MT kernels write
-    ctx->flags = ctx->flags_buf[0]; ctx->fix_list = ctx->fixl_buf[0];
+    ISS_RES_ALLOC(os.desc, sizeof(iss::PairDesc) * (size_t)capacity_pairs);
+    ctx->flags = os.flags_buf[0]; ctx->fix_list = os.fixl_buf[0];
     const bool heavy = ctx->M.n_scan > 0 && !ctx->light;
     for (int k = 0; k < (heavy ? 2 : 1); ++k) {
-        ISS_RES_ALLOC(sizeof(uint32_t) * 2 * (size_t)capacity_pairs);
-        ctx->ev_count[k] = static_cast<uint32_t *>(q);
-        ISS_RES_ALLOC(sizeof(uint32_t) * 2 * iss::EV_K * (size_t)capacity_pairs);
-        ctx->ev_list[k] = static_cast<uint32_t *>(q);
-        ISS_RES_ALLOC(sizeof(uint4) * 2 * (size_t)capacity_pairs);
-        ctx->read_list[k] = static_cast<uint4 *>(q);
-        ISS_RES_ALLOC(sizeof(uint2) * 2 * (size_t)capacity_pairs);
-        ctx->read_list1[k] = static_cast<uint2 *>(q);
+        ISS_RES_ALLOC(os.ev_count[k], sizeof(uint32_t) * 2 * (size_t)capacity_pairs);
+        ISS_RES_ALLOC(os.ev_list[k], sizeof(uint32_t) * 2 * iss::EV_K * (size_t)capacity_pairs);
+        ISS_RES_ALLOC(os.read_list[k], sizeof(uint4) * 2 * (size_t)capacity_pairs);
+        ISS_RES_ALLOC(os.read_list1[k], sizeof(uint2) * 2 * (size_t)capacity_pairs);
     }
-    if (!heavy) { ctx->ev_count[1] = ctx->ev_count[0]; ctx->ev_list[1] = ctx->ev_list[0]; ctx->read_list[1] = ctx->read_list[0]; ctx->read_list1[1] = ctx->read_list1[0]; }
+    for (int k = 0; k < 2; ++k) {  // the views by call parity: a light model's two parities share set 0
+        const int o = heavy ? k : 0;
+        ctx->ev_count[k] = os.ev_count[o]; ctx->ev_list[k] = os.ev_list[o]; ctx->read_list[k] = os.read_list[o]; ctx->read_list1[k] = os.read_list1[o];
+    }
     if (heavy)  // the edit scripts of the reads with an event (sparse: a read's slot is written only if it has one)
-        for (int k = 0; k < 2; ++k) {
-            ISS_RES_ALLOC((size_t)ctx->M.sc_stride * 2 * (size_t)capacity_pairs);
-            ctx->script[k] = static_cast<uint8_t *>(q);
-        }
+        for (int k = 0; k < 2; ++k) ISS_RES_ALLOC(os.script[k], (size_t)ctx->M.sc_stride * 2 * (size_t)capacity_pairs);
 #undef ISS_RES_ALLOC
-    ctx->capacity = capacity_pairs;
+    ctx->os.capacity = capacity_pairs;
     return 0;
 }
 
@@ -683,7 +649,7 @@ int iss_output_pitch(const iss_ctx *ctx) { return (ctx && ctx->have_model) ? ctx
 int iss_output_row(const iss_ctx *ctx) { return (ctx && ctx->have_model) ? ctx->M.row : ISS_E_INVALID; }
 
 int iss_output_device_ptrs(const iss_ctx *ctx, void **a, void **b, void **c, void **d) {
-    if (!ctx || !ctx->capacity) return ISS_E_INVALID;
+    if (!ctx || !ctx->os.capacity) return ISS_E_INVALID;
     if (a) *a = ctx->out[0];
     if (b) *b = ctx->out[1];
     if (c) *c = ctx->out[2];

@@ -107,15 +107,18 @@ int mt_grow_boost(iss_ctx *ctx, const iss::MtWalkResult &res, size_t py_avail, s
     return 0;
 }
 
-// a context's own chain: buffers of at least cap_py / cap_np words, the unconsumed words carried over
-int mt_reserve(iss_ctx *ctx, MtChain &c, size_t cap_py, size_t cap_np) {
+// the context's own chain: buffers of at least cap_py / cap_np words, the unconsumed words carried over
+int mt_reserve(iss_ctx *ctx, size_t cap_py, size_t cap_np) {
+    MtChain &c = ctx->mt.chain;
+    MtChainMem &own = ctx->mt.own;
     const size_t want[2] = {cap_py, cap_np};
     for (int s = 0; s < 2; ++s) {
         if (c.cap[s] >= want[s]) continue;
         std::vector<uint32_t> keep(c.fill[s] - c.used[s]);  // the unconsumed words
         if (!keep.empty()) HIP_TRY(ctx, hipMemcpy(keep.data(), c.buf[s][c.cur[s]] + c.used[s], keep.size() * 4, hipMemcpyDeviceToHost));
-        for (auto &b : c.buf[s]) { if (b) (void)hipFree(b); b = nullptr; }
-        for (auto &b : c.buf[s]) { void *p = nullptr; HIP_TRY(ctx, hipMalloc(&p, want[s] * 4)); b = static_cast<uint32_t *>(p); }
+        c.cap[s] = 0;
+        for (int b = 0; b < 2; ++b) { own.buf[s][b].reset(); c.buf[s][b] = nullptr; }
+        for (int b = 0; b < 2; ++b) { DEV_ALLOC(ctx, own.buf[s][b], want[s]); c.buf[s][b] = own.buf[s][b]; }
         if (!keep.empty()) HIP_TRY(ctx, hipMemcpy(c.buf[s][0], keep.data(), keep.size() * 4, hipMemcpyHostToDevice));
         c.fill[s] = keep.size();
         c.cur[s] = 0;
@@ -127,7 +130,7 @@ int mt_reserve(iss_ctx *ctx, MtChain &c, size_t cap_py, size_t cap_np) {
 
 int mt_chain_peek(iss_ctx *ctx, MtChain &c, uint32_t *py_words, uint32_t *np_words, int32_t n) {
     const size_t want[2] = {(size_t)n, (size_t)n};
-    { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+    ISS_TRY(mt_ensure(ctx, c, want));
     if (py_words) HIP_TRY(ctx, hipMemcpyAsync(py_words, c.buf[0][c.cur[0]] + c.used[0], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (np_words) HIP_TRY(ctx, hipMemcpyAsync(np_words, c.buf[1][c.cur[1]] + c.used[1], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -162,7 +165,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             } else {
                 for (size_t used = 0;;) {
                     const size_t want[2] = {0, used + 256};
-                    { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+                    ISS_TRY(mt_ensure(ctx, c, want));
                     uint32_t w[256];
                     // (on the context's stream, which mt_ensure has made wait for the refill: the streams are non-blocking, a copy
                     //  on the null stream would not be ordered behind the fill kernel and the leftover copy)
@@ -194,7 +197,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
         }
         if (kde) {  // (Basic / PerfectErrorModel.random_insert_size is a constant: nothing is drawn)
             const size_t want[2] = {0, 2};
-            { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+            ISS_TRY(mt_ensure(ctx, c, want));
             c.used[1] += 2;
         }
         return fail(ctx, ISS_E_SHORT_RECORD, "record shorter than read length for this ErrorModel");
@@ -209,23 +212,15 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
     if (resolve) {
         HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MT_LDS_BUDGET));
         if (!c.d_rec) {  // (the context's own chain; a worker of the set has its records from mt_set_reserve)
-            void *p = nullptr;
-            HIP_TRY(ctx, hipMalloc(&p, (size_t)CH * sizeof(iss::MtPairRec)));
-            c.d_rec = static_cast<iss::MtPairRec *>(p);
+            DEV_ALLOC(ctx, m.own.d_rec, (size_t)CH);
+            c.d_rec = m.own.d_rec;
         }
-        if (!m.d_mut_cnt) {  // (sized for the longest turn: a set worker's chain takes shorter ones)
-            void *p = nullptr;
-            HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int32_t)));
-            m.d_mut_cnt = static_cast<int32_t *>(p);
-            HIP_TRY(ctx, hipMalloc(&p, (size_t)2 * 8192 * sizeof(int64_t)));
-            m.d_mut_off = static_cast<int64_t *>(p);
+        if (!m.d_mut_off) {  // (sized for the longest turn: a set worker's chain takes shorter ones; the marker: the second of the two)
+            DEV_ALLOC(ctx, m.d_mut_cnt, (size_t)2 * 8192);
+            DEV_ALLOC(ctx, m.d_mut_off, (size_t)2 * 8192);
         }
     }
-    if (basic && !m.d_amb) {  // phreds the host has to round, and its answers
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, 2 * iss::MT_AMB_CAP * sizeof(iss::MtPhredAmb)));
-        m.d_amb = static_cast<iss::MtPhredAmb *>(p);
-    }
+    if (basic && !m.d_amb) DEV_ALLOC(ctx, m.d_amb, 2 * iss::MT_AMB_CAP);  // phreds the host has to round, and its answers
     std::vector<iss::MtPhredAmb> ovq;  // answers for the pair that restarts
     int64_t done = 0;
     rows.n = 0;
@@ -237,12 +232,12 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
         const int64_t n = walk_one ? 1 : std::min(CH, n_pairs - done);
         const size_t want[2] = {std::min(c.cap[0] / 624 * 624 - 624, (size_t)(n + 1 + boost) * py_need),
                                 std::min(c.cap[1] / 624 * 624 - 624, (size_t)(n + 1 + boost) * np_need)};
-        { int rc_ = mt_ensure(ctx, c, want); if (rc_) return rc_; }
+        ISS_TRY(mt_ensure(ctx, c, want));
         MtPrefetch pf;
         if (!walk_one && done + n < n_pairs) {  // produce the next chunk's words while this chunk runs
             const int64_t n_next = std::min(CH, n_pairs - done - n);
             const size_t want_next[2] = {(size_t)(n_next + 1) * py_need, (size_t)(n_next + 1) * np_need};
-            { int rc_ = mt_prefetch_begin(ctx, c, want, want_next, &pf); if (rc_) return rc_; }
+            ISS_TRY(mt_prefetch_begin(ctx, c, want, want_next, &pf));
         }
         const int64_t row0 = out_first_pair + done;
         iss::MtWalkResult res{};
@@ -251,14 +246,14 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             R.has_frag = m.has_frag ? 1 : 0;
             R.frag_mu = m.frag_mu;
             R.frag_sd = m.frag_sd;
-            hipLaunchKernelGGL(resolve, dim3(1), dim3(iss::RES_THREADS), pick.lds, ctx->stream, M, dg, R, ctx->desc + row0);
+            hipLaunchKernelGGL(resolve, dim3(1), dim3(iss::RES_THREADS), pick.lds, ctx->stream, M, dg, R, ctx->os.desc + row0);
             HIP_TRY(ctx, hipMemcpyAsync(&res, c.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             HIP_TRY(ctx, hipGetLastError());
             if (res.n_done > 0) {
                 auto emit = [&](const iss::MtEmitMut &E) {
                     hipLaunchKernelGGL(iss::k_mt_emit, dim3((unsigned)((2 * res.n_done + 3) / 4)), dim3(256), 0, ctx->stream, M, dg,
-                                       R.py_base, R.np_base, res.n_done, ctx->desc + row0, c.d_rec,
+                                       R.py_base, R.np_base, res.n_done, ctx->os.desc + row0, c.d_rec,
                                        ctx->out[0] + (size_t)row0 * M.row, ctx->out[1] + (size_t)row0 * M.row,
                                        ctx->out[2] + (size_t)row0 * M.row, ctx->out[3] + (size_t)row0 * M.row, E);
                 };
@@ -289,11 +284,11 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             }
             c.used[0] += res.py_used;
             c.used[1] += res.np_used;
-            { int rc_ = mt_prefetch_commit(ctx, c, pf); if (rc_) return rc_; }
+            ISS_TRY(mt_prefetch_commit(ctx, c, pf));
             done += res.n_done;
             n_resolved += res.n_done;
             if (res.pad) { walk_one = true; continue; }  // the next pair is not plain: one turn of the walker
-            { int rc_ = mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, want, boost); if (rc_) return rc_; }
+            ISS_TRY(mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, want, boost));
             continue;
         }
         iss::MtWalkArgs A = mt_walk_args(ctx, c, n, row0, done, sequence_type, gc_bias, lds.use_rows, guard);
@@ -313,13 +308,13 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             HIP_TRY(ctx, hipMemcpyAsync(m.d_amb + iss::MT_AMB_CAP, ovq.data(), ovq.size() * sizeof(iss::MtPhredAmb),
                                         hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(iss::k_mt_walk, dim3(1), dim3(64), A.use_rows ? lds.fixed + lds.rows : lds.fixed, ctx->stream, M, dg, A,
-                           ctx->desc + row0);
+                           ctx->os.desc + row0);
         HIP_TRY(ctx, hipMemcpyAsync(&res, c.d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipGetLastError());
         c.used[0] += res.py_used;
         c.used[1] += res.np_used;
-        { int rc_ = mt_prefetch_commit(ctx, c, pf); if (rc_) return rc_; }
+        ISS_TRY(mt_prefetch_commit(ctx, c, pf));
         done += res.n_done;
         n_walked += res.n_done;
         rows.n += res.n_mut;
@@ -350,7 +345,7 @@ int mt_chain_generate(iss_ctx *ctx, MtChain &c, int32_t genome_id, int64_t n_pai
             ov_valid = true;
             continue;
         }
-        { int rc_ = mt_grow_boost(ctx, res, A.py_avail, A.np_avail, want, boost); if (rc_) return rc_; }
+        ISS_TRY(mt_grow_boost(ctx, res, A.py_avail, A.np_avail, want, boost));
         if (res.n_done > 0) walk_one = false;
     }
     if (n_done) *n_done = done;
@@ -366,16 +361,16 @@ int iss_mt_seed(iss_ctx *ctx, uint64_t seed) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
     if (seed > 0xffffffffull) return fail(ctx, ISS_E_INVALID, "seed must be < 2^32 (numpy's legacy seeding raises)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     auto &c = ctx->mt.chain;
-    if (!c.d_state) {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, 2 * sizeof(iss::MtState)));
-        c.d_state = static_cast<iss::MtState *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtWalkResult)));
-        c.d_res = static_cast<iss::MtWalkResult *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, sizeof(iss::MtGauss)));
-        c.d_gauss = static_cast<iss::MtGauss *>(p);
+    if (!c.d_gauss) {  // (the marker: the last of the three)
+        auto &own = ctx->mt.own;
+        DEV_ALLOC(ctx, own.d_state, 2);
+        DEV_ALLOC(ctx, own.d_res, 1);
+        DEV_ALLOC(ctx, own.d_gauss, 1);
+        c.d_state = own.d_state;
+        c.d_res = own.d_res;
+        c.d_gauss = own.d_gauss;
     }
     HIP_TRY(ctx, hipMemset(c.d_gauss, 0, sizeof(iss::MtGauss)));  // np.random.seed() drops the cached gaussian
     iss::MtState st[2];
@@ -394,16 +389,16 @@ int iss_generate_mt(iss_ctx *ctx, int32_t genome_id, int64_t n_pairs, int32_t se
     if (genome_id < 0 || genome_id >= (int32_t)ctx->genomes.size()) return fail(ctx, ISS_E_INVALID, "unknown genome id");
     if (sequence_type != ISS_SEQ_METAGENOMICS && sequence_type != ISS_SEQ_AMPLICON)
         return fail(ctx, ISS_E_INVALID, "sequence type is not supported");
-    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->capacity)
+    if (n_pairs < 0 || out_first_pair < 0 || out_first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
     const iss::DevModel &M = ctx->M;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     ctx->last_first.clear();  // (this call's descriptors carry record coordinates: no batch's arena offsets apply to the rows any more)
     ctx->last_off.clear();
     auto &c = ctx->mt.chain;
     const size_t py_need = iss::mt_py_need(M.RL), np_need = iss::mt_np_need(M.RL, M.quality_mode);
-    { int rc_ = mt_reserve(ctx, c, 3 * ((size_t)(c.ch + 1) * py_need + 1248), 3 * ((size_t)(c.ch + 1) * np_need + 1248)); if (rc_) return rc_; }
+    ISS_TRY(mt_reserve(ctx, 3 * ((size_t)(c.ch + 1) * py_need + 1248), 3 * ((size_t)(c.ch + 1) * np_need + 1248)));
     auto &m = ctx->mt;
     MtRowSink rows{m.d_mut, m.mut_cap, m.mut_n, m.mut_row0};
     const int rc = mt_chain_generate(ctx, c, genome_id, n_pairs, sequence_type, gc_bias, out_first_pair, mt_guard_env(), n_done,
@@ -429,22 +424,18 @@ int mt_set_rows_alloc(iss_ctx *ctx) {
     auto &t = ctx->mts;
     if (!t.W || !t.mut_rows || t.d_mut) return 0;
     const size_t W = (size_t)t.W;
-    void *p = nullptr;
-    if (hipMalloc(&p, W * (size_t)t.mut_rows * sizeof(iss::MutRecord)) != hipSuccess) {
-        (void)hipGetLastError();
+    MtSetRows r;  // (all or nothing: a failure below leaves the set without rows, and d_mut -- the marker -- empty)
+    if (own_alloc_quiet(r.d_mut, W * (size_t)t.mut_rows * sizeof(iss::MutRecord)))
         return fail(ctx, ISS_E_NOMEM, "iss_mt_workers_mutations_reserve: no device memory for " + std::to_string(t.W) + " x " + std::to_string(t.mut_rows) + " rows");
-    }
-    t.d_mut = static_cast<iss::MutRecord *>(p);
-    HIP_TRY(ctx, hipMalloc(&p, W * sizeof(int64_t)));
-    t.d_mut_n = static_cast<int64_t *>(p);
-    HIP_TRY(ctx, hipMemset(t.d_mut_n, 0, W * sizeof(int64_t)));
-    HIP_TRY(ctx, hipHostMalloc(&p, W * sizeof(int64_t), hipHostMallocDefault));
-    t.h_mut_n = static_cast<int64_t *>(p);
-    HIP_TRY(ctx, hipEventCreateWithFlags(&t.ev_place, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&t.ev_walk, hipEventDisableTiming));
-    t.mut_n.assign(W, 0);
-    t.mut_row0.assign(W, 0);
-    t.mut_pairs.assign(W, 0);
+    DEV_ALLOC(ctx, r.d_mut_n, W);
+    HIP_TRY(ctx, hipMemset(r.d_mut_n, 0, W * sizeof(int64_t)));
+    PIN_ALLOC(ctx, r.h_mut_n, W);
+    ISS_TRY(event_create(ctx, r.ev_place, hipEventDisableTiming));
+    ISS_TRY(event_create(ctx, r.ev_walk, hipEventDisableTiming));
+    r.mut_n.assign(W, 0);
+    r.mut_row0.assign(W, 0);
+    r.mut_pairs.assign(W, 0);
+    static_cast<MtSetRows &>(t) = std::move(r);
     return 0;
 }
 
@@ -455,20 +446,17 @@ int iss_mt_workers_seed(iss_ctx *ctx, int32_t n_workers, const uint64_t *seeds) 
     for (int32_t w = 0; w < n_workers; ++w)
         if (seeds[w] > 0xffffffffull) return fail(ctx, ISS_E_INVALID, "seed must be < 2^32 (numpy's legacy seeding raises)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    free_mt_set(ctx);
+    ISS_TRY(sync_all(ctx));
     auto &t = ctx->mts;
+    reset_part<MtSetRows>(t);  // the old set: its rows (the request, mut_rows, stays), its pools, its workers
+    reset_part<MtSetPools>(t);
+    reset_part<MtSetWorkers>(t);
     const size_t W = (size_t)n_workers;
-    void *p = nullptr;
-    HIP_TRY(ctx, hipMalloc(&p, 2 * W * sizeof(iss::MtState)));
-    t.d_state = static_cast<iss::MtState *>(p);
-    HIP_TRY(ctx, hipMalloc(&p, W * sizeof(iss::MtWalkResult)));
-    t.d_res = static_cast<iss::MtWalkResult *>(p);
-    HIP_TRY(ctx, hipMalloc(&p, W * sizeof(iss::MtGauss)));
-    t.d_gauss = static_cast<iss::MtGauss *>(p);
+    DEV_ALLOC(ctx, t.d_state, 2 * W);
+    DEV_ALLOC(ctx, t.d_res, W);
+    DEV_ALLOC(ctx, t.d_gauss, W);
     HIP_TRY(ctx, hipMemset(t.d_gauss, 0, W * sizeof(iss::MtGauss)));  // np.random.seed() drops the cached gaussian
-    HIP_TRY(ctx, hipHostMalloc(&p, W * sizeof(iss::MtWalkResult), hipHostMallocDefault));
-    t.h_res = static_cast<iss::MtWalkResult *>(p);
+    PIN_ALLOC(ctx, t.h_res, W);
     std::vector<iss::MtState> st(2 * W);
     for (size_t w = 0; w < W; ++w) mt_seed_streams(&st[2 * w], (uint32_t)seeds[w]);
     HIP_TRY(ctx, hipMemcpy(t.d_state, st.data(), st.size() * sizeof(iss::MtState), hipMemcpyHostToDevice));
@@ -519,44 +507,27 @@ int mt_set_reserve(iss_ctx *ctx) {
     if (t.cap[0] && (t.cap[0] < want[0] || t.cap[1] < want[1]))
         return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: the set's stream buffers were sized for a model with shorter reads (seed the set again)");
     if (!t.cap[0]) {
-        // (all or nothing: a reservation that failed half way leaves nothing behind and can be repeated -- cap[] marks it as made)
-        auto undo = [&]() {
-            for (auto &st : t.buf) for (auto &b : st) { if (b) (void)hipFree(b); b = nullptr; }
-            if (t.d_rec) (void)hipFree(t.d_rec);
-            if (t.h_jobs) (void)hipHostFree(t.h_jobs);
-            if (t.d_jobs) (void)hipFree(t.d_jobs);
-            t.d_rec = nullptr; t.h_jobs = nullptr; t.d_jobs = nullptr;
-            for (auto &e : t.ev_emit) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-            if (t.ev_side) (void)hipEventDestroy(t.ev_side);
-            if (t.ev_turn) (void)hipEventDestroy(t.ev_turn);
-            t.ev_side = t.ev_turn = nullptr;
-            (void)hipGetLastError();
-        };
+        // (all or nothing: a reservation that failed half way leaves nothing behind and can be repeated -- the pools are made
+        //  aside and moved into the set whole; cap[] marks the reservation as made)
+        MtSetPools pools;
         const size_t jobs_bytes = (((4 * 2 * W) * std::max(sizeof(iss::MtFillJob), sizeof(iss::MtMoveJob)) +
                                     W * (sizeof(iss::MtResolveJob) + sizeof(iss::MtWalkJob) + sizeof(iss::MtEmitJob))) + 255) & ~(size_t)255;
         bool ok = true;
         for (int s = 0; s < 2 && ok; ++s)
-            for (int b = 0; b < 2 && ok; ++b) {
-                void *p = nullptr;
-                ok = hipMalloc(&p, W * want[s] * sizeof(uint32_t)) == hipSuccess;
-                t.buf[s][b] = ok ? static_cast<uint32_t *>(p) : nullptr;
-            }
-        void *p = nullptr;
-        if (ok && (ok = hipMalloc(&p, 2 * W * (size_t)t.ch * sizeof(iss::MtPairRec)) == hipSuccess)) t.d_rec = static_cast<iss::MtPairRec *>(p);
-        if (ok && (ok = hipHostMalloc(&p, 2 * jobs_bytes, hipHostMallocDefault) == hipSuccess)) t.h_jobs = static_cast<uint8_t *>(p);
-        if (ok && (ok = hipMalloc(&p, 2 * jobs_bytes) == hipSuccess)) t.d_jobs = static_cast<uint8_t *>(p);
+            for (int b = 0; b < 2 && ok; ++b) ok = own_alloc_quiet(pools.buf[s][b], W * want[s] * sizeof(uint32_t)) == 0;
+        ok = ok && own_alloc_quiet(pools.d_rec, 2 * W * (size_t)t.ch * sizeof(iss::MtPairRec)) == 0;
+        ok = ok && own_alloc_quiet(pools.h_jobs, 2 * jobs_bytes) == 0;
+        ok = ok && own_alloc_quiet(pools.d_jobs, 2 * jobs_bytes) == 0;
         if (!ok) {
-            undo();
             return fail(ctx, ISS_E_NOMEM, "iss_generate_mt_workers: no memory for the workers' stream buffers (W x " + std::to_string((want[0] + want[1]) * 2 * 4) + " bytes)");
         }
-        hipError_t e = hipSuccess;
-        for (auto &ev : t.ev_emit) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ev_side, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ev_turn, hipEventDisableTiming);
-        if (e != hipSuccess) { undo(); HIP_TRY(ctx, e); }
-        t.jobs_bytes = jobs_bytes;
-        t.cap[0] = want[0];
-        t.cap[1] = want[1];
+        for (auto &ev : pools.ev_emit) ISS_TRY(event_create(ctx, ev, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, pools.ev_side, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, pools.ev_turn, hipEventDisableTiming));
+        pools.jobs_bytes = jobs_bytes;
+        pools.cap[0] = want[0];
+        pools.cap[1] = want[1];
+        static_cast<MtSetPools &>(t) = std::move(pools);
         for (size_t w = 0; w < W; ++w) {  // the workers' slices
             MtChain &c = t.chains[w];
             for (int s = 0; s < 2; ++s) {
@@ -606,24 +577,21 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
         if (status) status[w] = 0;
         if (n_pairs[w] == 0) continue;
         if (genome_ids[w] < 0 || genome_ids[w] >= (int32_t)ctx->genomes.size()) return fail(ctx, ISS_E_INVALID, "unknown genome id");
-        if (n_pairs[w] < 0 || out_first_pair[w] < 0 || out_first_pair[w] + n_pairs[w] > ctx->capacity)
+        if (n_pairs[w] < 0 || out_first_pair[w] < 0 || out_first_pair[w] + n_pairs[w] > ctx->os.capacity)
             return fail(ctx, ISS_E_INVALID, "output rows out of the reserved range");
         for (int v = 0; v < w; ++v)  // (the workers' rows must not overlap)
             if (n_pairs[v] > 0 && out_first_pair[w] < out_first_pair[v] + n_pairs[v] && out_first_pair[v] < out_first_pair[w] + n_pairs[w])
                 return fail(ctx, ISS_E_INVALID, "iss_generate_mt_workers: two workers' output rows overlap");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    { int rc_ = mt_set_reserve(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
+    ISS_TRY(mt_set_reserve(ctx));
     // --store_mutations (iss_mt_workers_mutations_reserve): the rows of this call, per worker from 0
     const bool rows_on = t.d_mut != nullptr;
-    if (rows_on && !t.d_mut_cnt) {  // (a worker's counts and places of one turn; the stride keeps them 16-byte aligned)
+    if (rows_on && !t.d_mut_off) {  // (a worker's counts and places of one turn; the stride keeps them 16-byte aligned)
         const size_t stride = ((size_t)2 * (size_t)t.ch + 7) & ~(size_t)7;
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, (size_t)W * stride * sizeof(int32_t)));
-        t.d_mut_cnt = static_cast<int32_t *>(p);
-        HIP_TRY(ctx, hipMalloc(&p, (size_t)W * stride * sizeof(int64_t)));
-        t.d_mut_off = static_cast<int64_t *>(p);
+        DEV_ALLOC(ctx, t.d_mut_cnt, (size_t)W * stride);
+        DEV_ALLOC(ctx, t.d_mut_off, (size_t)W * stride);
         t.mut_stride = stride;
     }
     if (rows_on)
@@ -686,8 +654,8 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
     };
     const MtWalkLds lds = mt_walk_lds(M);
     if (!m.ev_main) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_main, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_fill, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, m.ev_fill, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, m.ev_main, hipEventDisableTiming));  // (the marker of the pair: last)
     }
     const size_t fm_sz = std::max(sizeof(iss::MtFillJob), sizeof(iss::MtMoveJob));
     std::vector<int64_t> n_w((size_t)W);
@@ -832,7 +800,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                 res_buf[2 * w] = c.cur[0];
                 res_buf[2 * w + 1] = c.cur[1];
                 rj.g = dev_genome(ctx->genomes[ws[w].gid]);
-                rj.desc = ctx->desc + row0;
+                rj.desc = ctx->os.desc + row0;
                 any_res = true;
             } else if (walker) {
                 wj.A = mt_walk_args(ctx, c, n_w[w], row0, ws[w].done, sequence_type, gc_bias, lds.use_rows, guard);
@@ -840,7 +808,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                 wj.A.mut_cap = t.mut_rows;
                 wj.A.mut_count = rows_on ? t.d_mut_n + w : nullptr;
                 wj.g = dev_genome(ctx->genomes[ws[w].gid]);
-                wj.desc = ctx->desc + row0;
+                wj.desc = ctx->os.desc + row0;
                 any_walk = true;
                 walk_rows |= wj.A.use_rows != 0;
             }
@@ -869,7 +837,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             ej.py = h_rj[w].A.py_base;
             ej.np = h_rj[w].A.np_base;
             ej.n_pairs = t.h_res[w].n_done;
-            ej.desc = ctx->desc + row0;
+            ej.desc = ctx->os.desc + row0;
             ej.rec = h_rj[w].A.rec;
             for (int k = 0; k < 4; ++k) ej.out[k] = ctx->out[k] + (size_t)row0 * M.row;
             ej.g = h_rj[w].g;
@@ -917,7 +885,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
             if (h_wj[w].A.n_pairs > 0) {  // (the walker's)
                 const iss::MtWalkArgs &A = h_wj[w].A;
                 t.n_walked += res.n_done;
-                { int rc_ = mt_grow_boost(ctx, res, A.py_avail, A.np_avail, &want[2 * w], ws[w].boost); if (rc_) return rc_; }
+                ISS_TRY(mt_grow_boost(ctx, res, A.py_avail, A.np_avail, &want[2 * w], ws[w].boost));
                 if (res.n_done > 0) ws[w].walk_one = false;
             } else {
                 const iss::MtResolveArgs &R = h_rj[w].A;
@@ -927,8 +895,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                     ws[w].walk_one = true;  // (unless the walk behind this turn takes it)
                     any_odd = true;
                 } else {
-                    int rc_ = mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, &want[2 * w], ws[w].boost);
-                    if (rc_) return rc_;
+                    ISS_TRY(mt_grow_boost(ctx, res, R.py_fill - R.py_off, R.np_fill - R.np_off, &want[2 * w], ws[w].boost));
                 }
             }
         }
@@ -949,7 +916,7 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
                 wj.A.mut_cap = t.mut_rows;
                 wj.A.mut_count = rows_on ? t.d_mut_n + w : nullptr;
                 wj.g = dev_genome(ctx->genomes[ws[w].gid]);
-                wj.desc = ctx->desc + row0;
+                wj.desc = ctx->os.desc + row0;
                 ++n_odd;
             }
             if (n_odd) {
@@ -1031,10 +998,10 @@ static int mt_workers_generate(iss_ctx *ctx, int32_t n_workers, const int32_t *g
 int iss_mt_workers_mutations_reserve(iss_ctx *ctx, int64_t rows_per_worker) {
     if (!ctx || rows_per_worker < 0 || rows_per_worker > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_mutations_reserve: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    { int rc_ = append_flush(ctx, ctx->vq); if (rc_) return rc_; }  // (a queued text's kernels read the pool)
+    ISS_TRY(sync_all(ctx));
+    ISS_TRY(append_flush(ctx, ctx->vq));  // (a queued text's kernels read the pool)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_mt_set_rows(ctx);
+    reset_part<MtSetRows>(ctx->mts);
     ctx->mts.mut_rows = rows_per_worker;
     return mt_set_rows_alloc(ctx);  // (a set seeded later gets its rows then)
 }
@@ -1058,8 +1025,8 @@ int iss_mt_workers_peek(iss_ctx *ctx, int32_t worker, uint32_t *py_words, uint32
     if (!ctx || worker < 0 || worker >= ctx->mts.W || n < 0 || n > 624) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_peek: bad argument");
     if (!ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_mt_workers_peek: upload a model first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    { int rc_ = mt_set_reserve(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
+    ISS_TRY(mt_set_reserve(ctx));
     return mt_chain_peek(ctx, ctx->mts.chains[worker], py_words, np_words, n);
 }
 
@@ -1074,16 +1041,12 @@ int iss_set_fragment(iss_ctx *ctx, int32_t enabled, double fragment_length, doub
 int iss_mutations_reserve(iss_ctx *ctx, int64_t capacity) {
     if (!ctx || capacity < 0 || capacity > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_mutations_reserve: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
-    if (ctx->d_pmut) (void)hipFree(ctx->d_pmut);
-    ctx->d_pmut = nullptr;
-    ctx->pmut_cap = 0;
+    ISS_TRY(sync_all(ctx));
+    ctx->pmut = {};
     ctx->pmut_call = false;
     if (capacity) {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, (size_t)capacity * sizeof(iss::MutRecord)));
-        ctx->d_pmut = static_cast<iss::MutRecord *>(p);
-        ctx->pmut_cap = capacity;
+        DEV_ALLOC(ctx, ctx->pmut.d, (size_t)capacity);
+        ctx->pmut.cap = capacity;
     }
     return 0;
 }
@@ -1091,18 +1054,18 @@ int iss_mutations_reserve(iss_ctx *ctx, int64_t capacity) {
 int iss_mutations_download(iss_ctx *ctx, iss_mutation *out, int64_t capacity, int64_t *n_rows) {
     if (n_rows) *n_rows = 0;
     if (!ctx || capacity < 0) return fail(ctx, ISS_E_INVALID, "iss_mutations_download: bad argument");
-    if (!ctx->d_pmut) return 0;
+    if (!ctx->pmut.d) return 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     uint32_t reserved = 0;
     HIP_TRY(ctx, hipMemcpy(&reserved, ctx->d_pmut_count, sizeof reserved, hipMemcpyDeviceToHost));
-    if ((int64_t)reserved > ctx->pmut_cap) {
+    if ((int64_t)reserved > ctx->pmut.cap) {
         if (n_rows) *n_rows = (int64_t)reserved;  // (the slots the call asked for: what a retry has to reserve)
         return fail(ctx, ISS_E_NOMEM, "mutation buffer too small for this call (reserve more with iss_mutations_reserve)");
     }
     std::vector<iss::MutRecord> rows(reserved);
     std::vector<uint32_t> flags((size_t)ctx->last_n);
-    if (reserved) HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->d_pmut, (size_t)reserved * sizeof(iss::MutRecord), hipMemcpyDeviceToHost));
+    if (reserved) HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->pmut.d, (size_t)reserved * sizeof(iss::MutRecord), hipMemcpyDeviceToHost));
     if (ctx->last_n)
         HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->flags + ctx->last_row0, (size_t)ctx->last_n * sizeof(uint32_t),
                                hipMemcpyDeviceToHost));
@@ -1143,16 +1106,13 @@ int iss_mt_set_fragment(iss_ctx *ctx, int32_t enabled, double fragment_length, d
 int iss_mt_mutations_reserve(iss_ctx *ctx, int64_t capacity) {
     if (!ctx || capacity < 0) return fail(ctx, ISS_E_INVALID, "iss_mt_mutations_reserve: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = sync_all(ctx); if (rc_) return rc_; }
+    ISS_TRY(sync_all(ctx));
     auto &m = ctx->mt;
-    if (m.d_mut) (void)hipFree(m.d_mut);
-    m.d_mut = nullptr;
+    m.d_mut.reset();
     m.mut_cap = m.mut_n = 0;
     m.mut_call = false;
     if (capacity) {
-        void *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, (size_t)capacity * sizeof(iss::MutRecord)));
-        m.d_mut = static_cast<iss::MutRecord *>(p);
+        DEV_ALLOC(ctx, m.d_mut, (size_t)capacity);
         m.mut_cap = capacity;
     }
     return 0;
@@ -1178,7 +1138,7 @@ int iss_mt_path_counts(iss_ctx *ctx, int64_t *n_resolved, int64_t *n_walked) {
 int iss_mt_peek(iss_ctx *ctx, uint32_t *py_words, uint32_t *np_words, int32_t n) {
     if (!ctx || !ctx->mt.seeded || n < 0 || n > 624) return fail(ctx, ISS_E_INVALID, "iss_mt_peek: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = mt_reserve(ctx, ctx->mt.chain, 4 * 624, 4 * 624); if (rc_) return rc_; }
+    ISS_TRY(mt_reserve(ctx, 4 * 624, 4 * 624));
     return mt_chain_peek(ctx, ctx->mt.chain, py_words, np_words, n);
 }
 

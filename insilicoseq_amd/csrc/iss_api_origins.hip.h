@@ -26,7 +26,7 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     for (int32_t k = 0; k < n_items; ++k) {
         if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0)
             return fail(ctx, ISS_E_INVALID, "iss_origins_emit_batch: bad argument");
-        if (first_pair[k] + n_pairs[k] > ctx->capacity) return fail(ctx, ISS_E_INVALID, "iss_origins_emit_batch: rows out of range");
+        if (first_pair[k] + n_pairs[k] > ctx->os.capacity) return fail(ctx, ISS_E_INVALID, "iss_origins_emit_batch: rows out of range");
         if (record_len[k] < 1 || record_len[k] > iss::MAX_RECORD) return fail(ctx, ISS_E_INVALID, "iss_origins_emit_batch: record_len out of range");
         const size_t idlen = strlen(record_ids[k]);
         if (idlen > FASTQ_ID_MAX) return fail(ctx, ISS_E_INVALID, "iss_origins_emit_batch: record id longer than 4096 bytes");
@@ -57,46 +57,44 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     OriginsPipe &q = ctx->oq;
     if (!q.ready) {
-        for (auto &p : q.d_total) { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 64)); p = static_cast<uint64_t *>(v); }
-        { int rc_ = append_start(ctx, q, true, origins_write, "origins text"); if (rc_) return rc_; }
+        for (auto &p : q.d_total) DEV_ALLOC(ctx, p, 64 / sizeof(uint64_t));
+        ISS_TRY(append_start(ctx, q, true, origins_write, "origins text"));
     }
-    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
+    ISS_TRY(append_attach(ctx, q, fd));
     if (bytes > q.cap) {
-        { int rc_ = append_flush(ctx, q, true); if (rc_) return rc_; }
+        ISS_TRY(append_flush(ctx, q, true));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the kernels of the last call write the buffers)
-        origins_free_text(ctx);
+        reset_part<OriginsText>(q);
         const size_t cap = bytes + bytes / 8 + (1u << 16);
         for (int sl = 0; sl < 2; ++sl) {
-            void *v = nullptr;
-            HIP_TRY(ctx, hipMalloc(&v, cap + 16)); q.d_text[sl] = static_cast<uint8_t *>(v);
-            HIP_TRY(ctx, hipHostMalloc(&v, cap, hipHostMallocDefault)); q.h_text[sl] = static_cast<uint8_t *>(v);
+            DEV_ALLOC(ctx, q.d_text[sl], cap + 16);
+            PIN_ALLOC(ctx, q.h_text[sl], cap);
         }
         q.cap = cap;
     }
     const size_t scan_tiles = ((size_t)pairs + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE;
     if ((size_t)pairs > q.pairs_cap || scan_tiles > q.tiles_cap) {  // the work arrays: only kernels of the context's stream touch them
         if (q.pairs_cap) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        origins_free_work(ctx);
+        reset_part<OriginsWork>(q);
         const size_t pc = (size_t)pairs + (size_t)pairs / 8 + 4096, tc = (pc + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE + 1;
-        void *v = nullptr;
-        HIP_TRY(ctx, hipMalloc(&v, pc * 4)); q.d_len = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, pc * 8)); q.d_off = static_cast<uint64_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, tc * 8)); q.d_tiles = static_cast<uint64_t *>(v);
+        DEV_ALLOC(ctx, q.d_len, pc);
+        DEV_ALLOC(ctx, q.d_off, pc);
+        DEV_ALLOC(ctx, q.d_tiles, tc);
         q.pairs_cap = pc;
         q.tiles_cap = tc;
     }
-    if (q.z.mode) { int rc_ = bgzt_reserve(ctx, q, q.z, q.cap); if (rc_) return rc_; }
+    if (q.z.mode) ISS_TRY(bgzt_reserve(ctx, q, q.z, q.cap));
     const int slot = q.next;
-    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
+    ISS_TRY(writer_wait_slot(ctx, q, slot));
     hipStream_t st = ctx->stream;
-    { int rc_ = q.tab.stage(ctx, slot, items, ids, st); if (rc_) return rc_; }
+    ISS_TRY(q.tab.stage(ctx, slot, items, ids, st));
     iss::OriginsArgs A{};
-    A.desc = ctx->desc;
+    A.desc = ctx->os.desc;
     A.n_pairs = pairs;
     A.RL = M.RL;
     A.n_items = (int32_t)items.size();
-    A.items = q.tab.d_items[slot];
-    A.ids = q.tab.d_ids[slot];
+    A.items = q.tab.slot[slot].d_items;
+    A.ids = q.tab.slot[slot].d_ids;
     A.len = q.d_len;
     A.off = q.d_off;
     A.total = q.d_total[slot];
@@ -108,8 +106,8 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     int set = -1;
     if (!ctx->last_first.empty() && ctx->batch_seq > 0) {
         set = (int)((ctx->batch_seq - 1) & 1u);
-        A.batch = ctx->d_items[set];
-        A.item_first = ctx->d_item_first[set];
+        A.batch = ctx->it.d_items[set];
+        A.item_first = ctx->it.d_item_first[set];
         A.n_batch = (int32_t)ctx->last_first.size() - 1;
         A.row0 = ctx->last_row0;
         A.call_pairs = ctx->last_n;
@@ -124,12 +122,11 @@ int iss_origins_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *co
     HIP_TRY(ctx, hipGetLastError());
     // (iss_generate_batch refills a set of tables once the event of its last reader has passed, and k_setup of the call after the
     //  next rewrites the descriptors' set once this one has: these launches are the last readers now)
-    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_items[set], st));
+    if (set >= 0) HIP_TRY(ctx, hipEventRecord(ctx->it.ev_items[set], st));
     if (ctx->call_seq) HIP_TRY(ctx, hipEventRecord(ctx->ev_call_done[(int)((ctx->call_seq - 1) & 1u)], st));
     const uint64_t *d_total = q.d_total[slot];
     if (q.z.mode) {  // the text stays on the device: its members are what the writer fetches (the line offsets are still resident)
-        int rc_ = bgzt_launch(ctx, q, q.z, slot, q.d_text[slot], bytes, q.d_off, (uint64_t)pairs, q.d_total[slot], st, &d_total);
-        if (rc_) return rc_;
+        ISS_TRY(bgzt_launch(ctx, q, q.z, slot, q.d_text[slot], bytes, q.d_off, (uint64_t)pairs, q.d_total[slot], st, &d_total));
     }
     return append_enqueue(ctx, q, slot, q.fd, d_total);
 }

@@ -11,7 +11,7 @@ int64_t iss_tally_words(const iss_ctx *ctx) {
 
 int iss_output_tally(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint64_t *d_tally) {
     if (!ctx || !ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_output_tally: upload a model first");
-    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->capacity)
+    if (first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > ctx->os.capacity)
         return fail(ctx, ISS_E_INVALID, "iss_output_tally: rows out of range");
     if (!n_pairs) return 0;
     if (!d_tally) return fail(ctx, ISS_E_INVALID, "iss_output_tally: d_tally is NULL");
@@ -23,7 +23,7 @@ int iss_output_tally(iss_ctx *ctx, int64_t first_pair, int64_t n_pairs, uint64_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     iss::TallyArgs T{};
     T.rows = ctx->out[0] + (size_t)first_pair * (size_t)M.row;
-    T.desc = ctx->desc + first_pair;
+    T.desc = ctx->os.desc + first_pair;
     T.n_pairs = n_pairs;
     T.RL = M.RL;
     T.row = M.row;

@@ -24,7 +24,7 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
     size_t bytes = 0, rec_len = 0;  // rec_len: record length of the item with the most pairs (the distance of its "previous record")
     int64_t pairs = 0, most = 0;
     for (int32_t k = 0; k < n_items; ++k) {
-        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0 || first_pair[k] + n_pairs[k] > ctx->capacity)
+        if (!record_ids[k] || first_i[k] < 0 || first_pair[k] < 0 || n_pairs[k] < 0 || first_pair[k] + n_pairs[k] > ctx->os.capacity)
             return fail(ctx, ISS_E_INVALID, "iss_ubam_emit_batch: bad argument");
         if (n_pairs[k] == 0) continue;
         const size_t idlen = strlen(record_ids[k]);
@@ -57,51 +57,47 @@ int iss_ubam_emit_batch(iss_ctx *ctx, int fd, int32_t n_items, const char *const
     if (!q.ready) {
         iss::DeflateCode init{};
         for (int k = 0; k < 8; ++k) iss::crc_shift_operator((uint64_t)128 << k, init.crc_shift[k]);
-        for (int sl = 0; sl < 2; ++sl) {
-            void *v = nullptr;
-            HIP_TRY(ctx, hipMalloc(&v, (iss::DEFLATE_SYMS + 7) * 4));
-            q.d_hist[sl] = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, sizeof(iss::DeflateCode)));
-            q.d_code[sl] = static_cast<iss::DeflateCode *>(v);
-            HIP_TRY(ctx, hipMemcpy(v, &init, sizeof init, hipMemcpyHostToDevice));
+        for (int sl = 0; sl < 2; ++sl) {  // (a call that fails before the pipe is ready makes them again: the handles release first)
+            DEV_ALLOC(ctx, q.d_hist[sl], iss::DEFLATE_SYMS + 7);
+            DEV_ALLOC(ctx, q.d_code[sl], 1);
+            HIP_TRY(ctx, hipMemcpy(q.d_code[sl], &init, sizeof init, hipMemcpyHostToDevice));
         }
-        { int rc_ = append_start(ctx, q, true, ubam_write, "unaligned BAM"); if (rc_) return rc_; }
+        ISS_TRY(append_start(ctx, q, true, ubam_write, "unaligned BAM"));
     }
-    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
+    ISS_TRY(append_attach(ctx, q, fd));
     const uint32_t n_blocks = (uint32_t)((bytes + iss::DEFLATE_BLOCK - 1) / iss::DEFLATE_BLOCK);
     // members of a call: its own Huffman code never needs more than 8 bits per byte plus rounding; the smoothing of the counts,
     // the block headers and the members' frames are covered by the margin (a call that needs more fails, it is never cut)
     auto comp_bytes = [](size_t text, size_t blocks) { return text + text / 8 + blocks * (320 + iss::BGZF_FRAME) + 64; };
     if (bytes > q.cap || comp_bytes(bytes, n_blocks) > q.comp_cap || n_blocks > q.blocks_cap) {
-        { int rc_ = append_flush(ctx, q, true); if (rc_) return rc_; }
+        ISS_TRY(append_flush(ctx, q, true));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the kernels of the last call read the buffers)
-        ubam_free_buffers(ctx);
+        reset_part<UbamBuffers>(q);
         const size_t cap = bytes + bytes / 8 + (1u << 20);
         const size_t cap_blocks = (cap + iss::DEFLATE_BLOCK - 1) / iss::DEFLATE_BLOCK;
         const size_t comp_cap = comp_bytes(cap, cap_blocks);
         for (int sl = 0; sl < 2; ++sl) {
-            void *v = nullptr;
-            HIP_TRY(ctx, hipMalloc(&v, cap + 16)); q.d_text[sl] = static_cast<uint8_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, comp_cap + 8)); q.d_comp[sl] = static_cast<uint8_t *>(v);
-            HIP_TRY(ctx, hipHostMalloc(&v, comp_cap, hipHostMallocDefault)); q.h_comp[sl] = static_cast<uint8_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, cap_blocks * 4)); q.d_bbytes[sl] = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, cap_blocks * 4)); q.d_bcrc[sl] = static_cast<uint32_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, (cap_blocks + 1) * 8)); q.d_boff[sl] = static_cast<uint64_t *>(v);
+            DEV_ALLOC(ctx, q.d_text[sl], cap + 16);
+            DEV_ALLOC(ctx, q.d_comp[sl], comp_cap + 8);
+            PIN_ALLOC(ctx, q.h_comp[sl], comp_cap);
+            DEV_ALLOC(ctx, q.d_bbytes[sl], cap_blocks);
+            DEV_ALLOC(ctx, q.d_bcrc[sl], cap_blocks);
+            DEV_ALLOC(ctx, q.d_boff[sl], cap_blocks + 1);
         }
         q.cap = cap;
         q.comp_cap = comp_cap;
         q.blocks_cap = (uint32_t)cap_blocks;
     }
     const int slot = q.next;
-    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
-    { int rc_ = q.tab.stage(ctx, slot, items, ids, ctx->stream); if (rc_) return rc_; }
+    ISS_TRY(writer_wait_slot(ctx, q, slot));
+    ISS_TRY(q.tab.stage(ctx, slot, items, ids, ctx->stream));
     iss::UbamArgs A{};
     A.row = M.row;
     A.RL = M.RL;
     A.n_items = (int32_t)items.size();
     A.n_pairs = pairs;
-    A.items = q.tab.d_items[slot];
-    A.ids = q.tab.d_ids[slot];
+    A.items = q.tab.slot[slot].d_items;
+    A.ids = q.tab.slot[slot].d_ids;
     A.text = q.d_text[slot];
     for (int m = 0; m < 2; ++m) {
         A.base[m] = ctx->out[2 * m];

@@ -20,8 +20,8 @@ struct VcfJob {
 int vcf_pipe_init(iss_ctx *ctx) {
     VcfPipe &q = ctx->vq;
     if (q.ready) return 0;
-    { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); q.h_count = static_cast<uint32_t *>(v); }
-    { void *v = nullptr; HIP_TRY(ctx, hipMalloc(&v, 2 * sizeof(uint32_t))); q.d_stats = static_cast<uint32_t *>(v); }
+    PIN_ALLOC(ctx, q.h_count, 64 / sizeof(uint32_t));
+    DEV_ALLOC(ctx, q.d_stats, 2);
     return append_start(ctx, q, false, vcf_write, "VCF text");  // (no copy stream: the size rides the context's stream)
 }
 
@@ -63,34 +63,29 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
         const size_t sc = std::max(q.slots_cap, (size_t)n_slots + (size_t)n_slots / 4 + 4096);
         const size_t pc = std::max(q.pairs_cap, (size_t)call_pairs + (size_t)call_pairs / 4 + 4096);
         const size_t tc = (std::max(sc, pc) + iss::VSCAN_TILE - 1) / iss::VSCAN_TILE + 1;
-        vcf_free_work(ctx);
-        void *v = nullptr;
-        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_key = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_slot = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_order = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, sc * 4)); q.d_len = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, (sc + 1) * 8)); q.d_off = static_cast<uint64_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, pc * 4)); q.d_cnt = static_cast<uint32_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, (pc + 1) * 8)); q.d_seg = static_cast<uint64_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, tc * 8)); q.d_tiles = static_cast<uint64_t *>(v);
+        reset_part<VcfWork>(q);
+        DEV_ALLOC(ctx, q.d_key, sc);
+        DEV_ALLOC(ctx, q.d_slot, sc);
+        DEV_ALLOC(ctx, q.d_order, sc);
+        DEV_ALLOC(ctx, q.d_len, sc);
+        DEV_ALLOC(ctx, q.d_off, sc + 1);
+        DEV_ALLOC(ctx, q.d_cnt, pc);
+        DEV_ALLOC(ctx, q.d_seg, pc + 1);
+        DEV_ALLOC(ctx, q.d_tiles, tc);
         q.slots_cap = sc; q.pairs_cap = pc; q.tiles_cap = tc;
     }
-    if (q.z.mode) { int rc_ = bgzt_reserve(ctx, q, q.z, bound); if (rc_) return rc_; }
+    if (q.z.mode) ISS_TRY(bgzt_reserve(ctx, q, q.z, bound));
     const int slot = q.next;
-    { int rc_ = writer_wait_slot(ctx, q, slot); if (rc_) return rc_; }
+    ISS_TRY(writer_wait_slot(ctx, q, slot));
     // (the slot is free: nothing reads its text or its tables)
-    if (bound > q.text_cap[slot]) {
-        if (q.d_text[slot]) (void)hipFree(q.d_text[slot]);
-        q.d_text[slot] = nullptr;
-        q.text_cap[slot] = 0;
+    if (bound > q.text[slot].cap) {
+        q.text[slot] = {};
         const size_t cap = bound + bound / 8 + (1u << 20);
-        void *v = nullptr;
-        if (hipMalloc(&v, cap) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, ISS_E_NOMEM, "iss_vcf_emit: no device memory for the text"); }
-        q.d_text[slot] = static_cast<uint8_t *>(v);
-        q.text_cap[slot] = cap;
+        if (own_alloc_quiet(q.text[slot].d, cap)) return fail(ctx, ISS_E_NOMEM, "iss_vcf_emit: no device memory for the text");
+        q.text[slot].cap = cap;
     }
     hipStream_t st = ctx->stream;
-    { int rc_ = q.tab.stage(ctx, slot, items, ids, st); if (rc_) return rc_; }
+    ISS_TRY(q.tab.stage(ctx, slot, items, ids, st));
     A.mut = J.mut;
     A.n_slots = (uint32_t)n_slots;
     A.n_pairs = call_pairs;
@@ -100,29 +95,25 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
     A.slot = q.d_slot;
     A.len = q.d_len;
     A.off = q.d_off;
-    A.text = q.d_text[slot];
-    A.text_cap = q.text_cap[slot];
-    A.items = q.tab.d_items[slot];
-    A.ids = q.tab.d_ids[slot];
+    A.text = q.text[slot].d;
+    A.text_cap = q.text[slot].cap;
+    A.items = q.tab.slot[slot].d_items;
+    A.ids = q.tab.slot[slot].d_ids;
     A.n_items = (int32_t)items.size();
     const bool set = !J.wbase.empty();  // a worker set: item k = worker k, its rows from wbase[k] (the table behind the items' copy)
     if (set) {
         const size_t nw = J.wbase.size();  // n_items + 1
-        if (2 * nw > q.wb_cap[slot]) {
-            if (q.h_wb[slot]) (void)hipHostFree(q.h_wb[slot]);
-            if (q.d_wb[slot]) (void)hipFree(q.d_wb[slot]);
-            q.h_wb[slot] = q.d_wb[slot] = nullptr;
-            q.wb_cap[slot] = 0;
-            void *v = nullptr;
-            HIP_TRY(ctx, hipHostMalloc(&v, 4 * nw * sizeof(uint64_t), hipHostMallocDefault)); q.h_wb[slot] = static_cast<uint64_t *>(v);
-            HIP_TRY(ctx, hipMalloc(&v, 4 * nw * sizeof(uint64_t))); q.d_wb[slot] = static_cast<uint64_t *>(v);
-            q.wb_cap[slot] = 4 * nw;
+        if (2 * nw > q.wb[slot].cap) {
+            q.wb[slot] = {};
+            PIN_ALLOC(ctx, q.wb[slot].h, 4 * nw);
+            DEV_ALLOC(ctx, q.wb[slot].d, 4 * nw);
+            q.wb[slot].cap = 4 * nw;
         }
-        memcpy(q.h_wb[slot], J.wbase.data(), nw * sizeof(uint64_t));
-        HIP_TRY(ctx, hipMemcpyAsync(q.d_wb[slot], q.h_wb[slot], nw * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        A.wbase = q.d_wb[slot];
+        memcpy(q.wb[slot].h, J.wbase.data(), nw * sizeof(uint64_t));
+        HIP_TRY(ctx, hipMemcpyAsync(q.wb[slot].d, q.wb[slot].h, nw * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        A.wbase = q.wb[slot].d;
         A.wstride = J.wstride;
-        A.wbytes = q.d_wb[slot] + nw;
+        A.wbytes = q.wb[slot].d + nw;
     }
     auto grid_for = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>(2048, (n + iss::VCF_THREADS - 1) / iss::VCF_THREADS)); };
     auto scan = [&](const uint32_t *in, uint64_t n, uint64_t *out) {
@@ -164,13 +155,12 @@ int vcf_queue(iss_ctx *ctx, const VcfJob &J) {
     if (set) {
         hipLaunchKernelGGL(iss::k_vcf_worker_bytes, dim3((unsigned)(J.wbase.size() + iss::VCF_THREADS - 1) / iss::VCF_THREADS), block, 0, st, A);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(q.h_wb[slot] + J.wbase.size(), A.wbytes, J.wbase.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(q.wb[slot].h + J.wbase.size(), A.wbytes, J.wbase.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
     q.job_wfds[slot] = J.wfds;
     const uint64_t *d_total = q.d_off + n_slots;
     if (q.z.mode) {  // the rows' offsets are the line offsets (a slot without a row: an empty line)
-        int rc_ = bgzt_launch(ctx, q, q.z, slot, q.d_text[slot], bound, q.d_off, (uint64_t)n_slots, q.d_off + n_slots, st, &d_total);
-        if (rc_) return rc_;
+        ISS_TRY(bgzt_launch(ctx, q, q.z, slot, q.text[slot].d, bound, q.d_off, (uint64_t)n_slots, q.d_off + n_slots, st, &d_total));
     }
     return append_enqueue(ctx, q, slot, J.fd, d_total);
 }
@@ -187,17 +177,17 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
         return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     VcfPipe &q = ctx->vq;
-    { int rc_ = vcf_pipe_init(ctx); if (rc_) return rc_; }
+    ISS_TRY(vcf_pipe_init(ctx));
     // the rows: how many slots to look at, and which output row pair 0 of the call is
     const bool philox = source == 0;
     int64_t n_slots = 0, row0 = 0, call_pairs = 0;
     if (philox) {
-        if (!ctx->d_pmut || !ctx->d_pmut_count) return 0;  // (no rows are captured: like iss_mutations_download)
+        if (!ctx->pmut.d || !ctx->d_pmut_count) return 0;  // (no rows are captured: like iss_mutations_download)
         // the one value that comes back per call: the slots it reserved (this waits for the generation, not for the text)
         HIP_TRY(ctx, hipMemcpyAsync(q.h_count, ctx->d_pmut_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         n_slots = (int64_t)*q.h_count;
-        if (n_slots > ctx->pmut_cap) {
+        if (n_slots > ctx->pmut.cap) {
             if (slots_needed) *slots_needed = n_slots;  // (the slots the call asked for: what a retry has to reserve)
             return fail(ctx, ISS_E_NOMEM, "mutation buffer too small for this call (reserve more with iss_mutations_reserve)");
         }
@@ -221,14 +211,14 @@ int iss_vcf_emit(iss_ctx *ctx, int fd, int32_t source, int32_t n_items, const ch
             return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: an item lies outside the rows of the last generate call");
         if (!J.items.empty() && pair0 < J.items.back().pair0 + J.items.back().n_pairs)
             return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: items must stand in ascending row order and not overlap");
-        { int rc_ = vcf_add_item(ctx, J, record_ids[k], first_i[k], pair0, n_pairs[k], cpu_number); if (rc_) return rc_; }
+        ISS_TRY(vcf_add_item(ctx, J, record_ids[k], first_i[k], pair0, n_pairs[k], cpu_number));
     }
     if (J.items.empty() || n_slots == 0) return 0;
     if (n_slots > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit: too many rows");
-    { int rc_ = append_attach(ctx, q, fd); if (rc_) return rc_; }
+    ISS_TRY(append_attach(ctx, q, fd));
     J.fd = fd;
     J.philox = philox;
-    J.mut = philox ? ctx->d_pmut : ctx->mt.d_mut;
+    J.mut = philox ? ctx->pmut.d : ctx->mt.d_mut;
     J.n_slots = n_slots;
     J.call_pairs = call_pairs;
     return vcf_queue(ctx, J);
@@ -244,7 +234,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
     if (t.poisoned) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: the last iss_generate_mt_workers call failed (its rows are undefined)");
     if (!t.d_mut) return 0;  // (no rows are captured: like iss_vcf_emit)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc_ = vcf_pipe_init(ctx); if (rc_) return rc_; }
+    ISS_TRY(vcf_pipe_init(ctx));
     VcfPipe &q = ctx->vq;
     // item k = worker k (a worker that sits the round out, or made no row, has an empty range); the text's rows are the workers' rows
     // one worker after the other
@@ -256,7 +246,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
         if (n_pairs[k] > 0 && (first_pair[k] != t.mut_row0[(size_t)k] || n_pairs[k] > t.mut_pairs[(size_t)k]))
             return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: a worker's item is not its rows of the last iss_generate_mt_workers call");
         if (t.mut_n[(size_t)k] > t.mut_rows) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: more rows than iss_mt_workers_mutations_reserve holds");
-        { int rc_ = vcf_add_item(ctx, J, record_ids[k], first_i[k], 0, n_pairs[k], cpu_numbers[k]); if (rc_) return rc_; }
+        ISS_TRY(vcf_add_item(ctx, J, record_ids[k], first_i[k], 0, n_pairs[k], cpu_numbers[k]));
         J.wbase.push_back(rows);
         J.wfds.push_back(fds[k]);
         if (n_pairs[k] > 0) rows += (uint64_t)t.mut_n[(size_t)k];
@@ -264,7 +254,7 @@ int iss_vcf_emit_workers(iss_ctx *ctx, int32_t n_workers, const int *fds, const 
     J.wbase.push_back(rows);
     if (rows == 0) return 0;
     if (rows > 0x7fffffff) return fail(ctx, ISS_E_INVALID, "iss_vcf_emit_workers: too many rows");
-    if (q.fd >= 0) { int rc_ = append_flush(ctx, q); if (rc_) return rc_; }  // (a single file's running offset ends here)
+    if (q.fd >= 0) ISS_TRY(append_flush(ctx, q));  // (a single file's running offset ends here)
     J.mut = t.d_mut;
     J.wstride = (uint64_t)t.mut_rows;
     J.n_slots = (int64_t)rows;

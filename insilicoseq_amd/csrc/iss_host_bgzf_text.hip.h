@@ -10,41 +10,25 @@ namespace {
 size_t bgzt_comp_bytes(size_t text, size_t blocks) { return text + text / 8 + blocks * (4 * iss::BGZT_HDR_WORDS + 16 + iss::BGZF_FRAME) + 64; }
 uint32_t bgzt_blocks(size_t text) { return (uint32_t)std::max<size_t>(1, (text + iss::DEFLATE_BLOCK - 1) / iss::DEFLATE_BLOCK); }
 
-void bgzt_free(BgzfTextStage &z) {
-    for (int sl = 0; sl < 2; ++sl) {
-        if (z.d_comp[sl]) (void)hipFree(z.d_comp[sl]);
-        if (z.h_comp[sl]) (void)hipHostFree(z.h_comp[sl]);
-        if (z.d_boff[sl]) (void)hipFree(z.d_boff[sl]);
-        z.d_comp[sl] = z.h_comp[sl] = nullptr;
-        z.d_boff[sl] = nullptr;
-    }
-    for (uint32_t **p : {&z.d_dist, &z.d_bbytes, &z.d_bcrc, &z.d_hist}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (z.d_code) (void)hipFree(z.d_code);
-    z.d_code = nullptr;
-    z.cap = z.comp_cap = 0;
-    z.blocks_cap = 0;
-}
-
 // Buffers for the members of a text of up to `text` bytes.  They grow with the pipe flushed (its file stays attached) and the
 // context's stream idle: the kernels of the last call and the writer thread use them.
 int bgzt_reserve(iss_ctx *ctx, AppendPipe &q, BgzfTextStage &z, size_t text) {
     if (z.d_code && text <= z.cap) return 0;
-    { int rc_ = append_flush(ctx, q, true); if (rc_) return rc_; }
+    ISS_TRY(append_flush(ctx, q, true));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    bgzt_free(z);
+    reset_part<BgzfTextBuffers>(z);
     const size_t cap = text + text / 8 + (1u << 16);
     const size_t blocks = bgzt_blocks(cap), comp_cap = bgzt_comp_bytes(cap, blocks);
-    void *v = nullptr;
     for (int sl = 0; sl < 2; ++sl) {
-        HIP_TRY(ctx, hipMalloc(&v, comp_cap + 8)); z.d_comp[sl] = static_cast<uint8_t *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, comp_cap, hipHostMallocDefault)); z.h_comp[sl] = static_cast<uint8_t *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, (blocks + 1) * 8)); z.d_boff[sl] = static_cast<uint64_t *>(v);
+        DEV_ALLOC(ctx, z.d_comp[sl], comp_cap + 8);
+        PIN_ALLOC(ctx, z.h_comp[sl], comp_cap);
+        DEV_ALLOC(ctx, z.d_boff[sl], blocks + 1);
     }
-    HIP_TRY(ctx, hipMalloc(&v, (cap / iss::DEFLATE_CHUNK + 1) * 4)); z.d_dist = static_cast<uint32_t *>(v);
-    HIP_TRY(ctx, hipMalloc(&v, blocks * 4)); z.d_bbytes = static_cast<uint32_t *>(v);
-    HIP_TRY(ctx, hipMalloc(&v, blocks * 4)); z.d_bcrc = static_cast<uint32_t *>(v);
-    HIP_TRY(ctx, hipMalloc(&v, (iss::BGZT_HIST + 5) * 4)); z.d_hist = static_cast<uint32_t *>(v);
-    HIP_TRY(ctx, hipMalloc(&v, sizeof(iss::BgzfTextCode))); z.d_code = static_cast<iss::BgzfTextCode *>(v);
+    DEV_ALLOC(ctx, z.d_dist, cap / iss::DEFLATE_CHUNK + 1);
+    DEV_ALLOC(ctx, z.d_bbytes, blocks);
+    DEV_ALLOC(ctx, z.d_bcrc, blocks);
+    DEV_ALLOC(ctx, z.d_hist, iss::BGZT_HIST + 5);
+    DEV_ALLOC(ctx, z.d_code, 1);
     static iss::BgzfTextCode init;  // (only the CRC operators: the same for every context)
     for (int k = 0; k < 8; ++k) iss::crc_shift_operator((uint64_t)128 << k, init.crc_shift[k]);
     HIP_TRY(ctx, hipMemcpy(z.d_code, &init, sizeof init, hipMemcpyHostToDevice));

@@ -174,34 +174,12 @@ int fastq_flush(iss_ctx *ctx, bool keep_files = false) {
 // the same, but the files stay attached (buffers are about to be reallocated in the middle of a run)
 int fastq_flush_keep(iss_ctx *ctx) { return fastq_flush(ctx, true); }
 
-void fastq_free_buffers(iss_ctx *ctx) {
-    FastqPipe &q = ctx->fq;
-    for (auto &sl : q.d_text) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.h_text) for (auto &p : sl) { if (p) (void)hipHostFree(p); p = nullptr; }
-    for (auto &sl : q.d_comp) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.d_bbytes) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.d_bcrc) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.d_boff) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.h_bcrc) for (auto &p : sl) { if (p) (void)hipHostFree(p); p = nullptr; }
-    q.cap = 0;
-    q.comp_cap = 0;
-    q.blocks_cap = 0;
-}
-
+// before the context goes: everything queued is written, the writer thread has ended (the pipe's members release its buffers)
 void fastq_shutdown(iss_ctx *ctx) {
     FastqPipe &q = ctx->fq;
     if (!q.ready) return;
     (void)fastq_flush(ctx);
     writer_stop(q);
-    fastq_free_buffers(ctx);
-    for (auto &sl : q.d_hist) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.d_code) for (auto &p : sl) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto &sl : q.h_total) for (auto &p : sl) { if (p) (void)hipHostFree(p); p = nullptr; }
-    if (q.data_stream) (void)hipStreamDestroy(q.data_stream);
-    q.tab.release();
-    for (auto &e : q.ev_fmt) if (e) (void)hipEventDestroy(e);
-    for (auto &e : q.ev_copy) if (e) (void)hipEventDestroy(e);
-    if (q.copy_stream) (void)hipStreamDestroy(q.copy_stream);
     q.ready = false;
 }
 

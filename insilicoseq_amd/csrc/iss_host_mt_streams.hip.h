@@ -58,8 +58,8 @@ int mt_fill_async(iss_ctx *ctx, const MtChain &c, uint32_t *const dst[2], const 
     auto &m = ctx->mt;
     if (!blocks[0] && !blocks[1]) return 0;
     if (!m.ev_main) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_main, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&m.ev_fill, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, m.ev_fill, hipEventDisableTiming));
+        ISS_TRY(event_create(ctx, m.ev_main, hipEventDisableTiming));  // (the marker of the pair: last)
     }
     HIP_TRY(ctx, hipEventRecord(m.ev_main, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->fill_stream, m.ev_main, 0));
@@ -96,7 +96,7 @@ int host_basic_phred(double x1v, double x2v, bool cached, double loc, double sca
 int mt_ensure(iss_ctx *ctx, MtChain &c, const size_t want[2]) {
     uint32_t blocks[2] = {0, 0};
     uint32_t *dst[2] = {nullptr, nullptr};
-    { int rc_ = mt_fill_join(ctx); if (rc_) return rc_; }
+    ISS_TRY(mt_fill_join(ctx));
     for (int s = 0; s < 2; ++s) {
         const size_t left = c.fill[s] - c.used[s];
         if (left >= want[s]) continue;
@@ -111,7 +111,7 @@ int mt_ensure(iss_ctx *ctx, MtChain &c, const size_t want[2]) {
         c.used[s] = 0;
         c.fill[s] = left + (size_t)blocks[s] * 624;
     }
-    { int rc_ = mt_fill_async(ctx, c, dst, blocks); if (rc_) return rc_; }
+    ISS_TRY(mt_fill_async(ctx, c, dst, blocks));
     return mt_fill_join(ctx);
 }
 

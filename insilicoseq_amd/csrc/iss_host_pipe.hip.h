@@ -14,43 +14,24 @@ int pwrite_all(int fd, const uint8_t *p, size_t n, int64_t off) {
     return 0;
 }
 
-template <typename Item>
-void SlotTable<Item>::release() {
-    for (int sl = 0; sl < 2; ++sl) {
-        if (h_items[sl]) (void)hipHostFree(h_items[sl]);
-        if (d_items[sl]) (void)hipFree(d_items[sl]);
-        if (h_ids[sl]) (void)hipHostFree(h_ids[sl]);
-        if (d_ids[sl]) (void)hipFree(d_ids[sl]);
-        h_items[sl] = d_items[sl] = nullptr;
-        h_ids[sl] = d_ids[sl] = nullptr;
-        items_cap[sl] = ids_cap[sl] = 0;
-    }
-}
-
 // A call's items and ids into a FREE slot (nothing reads its tables) and on their way to the device on `st`.
 template <typename Item>
-int SlotTable<Item>::stage(iss_ctx *ctx, int slot, const std::vector<Item> &items, const std::string &ids, hipStream_t st) {
-    if (items.size() > items_cap[slot] || ids.size() + 1 > ids_cap[slot]) {
-        if (h_items[slot]) (void)hipHostFree(h_items[slot]);
-        if (d_items[slot]) (void)hipFree(d_items[slot]);
-        if (h_ids[slot]) (void)hipHostFree(h_ids[slot]);
-        if (d_ids[slot]) (void)hipFree(d_ids[slot]);
-        h_items[slot] = d_items[slot] = nullptr;
-        h_ids[slot] = d_ids[slot] = nullptr;
-        items_cap[slot] = ids_cap[slot] = 0;  // (an allocation that fails below leaves an empty table, not a stale capacity)
+int SlotTable<Item>::stage(iss_ctx *ctx, int sl, const std::vector<Item> &items, const std::string &ids, hipStream_t st) {
+    Slot &s = slot[sl];
+    if (items.size() > s.items_cap || ids.size() + 1 > s.ids_cap) {
+        s = {};  // (an allocation that fails below leaves an empty table, not a stale capacity)
         const size_t ic = std::max<size_t>(64, 2 * items.size()), dc = std::max<size_t>(8192, 2 * (ids.size() + 1));
-        void *v = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&v, ic * sizeof(Item), hipHostMallocDefault)); h_items[slot] = static_cast<Item *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, ic * sizeof(Item))); d_items[slot] = static_cast<Item *>(v);
-        HIP_TRY(ctx, hipHostMalloc(&v, dc, hipHostMallocDefault)); h_ids[slot] = static_cast<char *>(v);
-        HIP_TRY(ctx, hipMalloc(&v, dc)); d_ids[slot] = static_cast<char *>(v);
-        items_cap[slot] = ic;
-        ids_cap[slot] = dc;
+        PIN_ALLOC(ctx, s.h_items, ic);
+        DEV_ALLOC(ctx, s.d_items, ic);
+        PIN_ALLOC(ctx, s.h_ids, dc);
+        DEV_ALLOC(ctx, s.d_ids, dc);
+        s.items_cap = ic;
+        s.ids_cap = dc;
     }
-    memcpy(h_items[slot], items.data(), items.size() * sizeof(Item));
-    memcpy(h_ids[slot], ids.data(), ids.size());
-    HIP_TRY(ctx, hipMemcpyAsync(d_items[slot], h_items[slot], items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
-    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_ids[slot], h_ids[slot], ids.size(), hipMemcpyHostToDevice, st));
+    memcpy(s.h_items, items.data(), items.size() * sizeof(Item));
+    memcpy(s.h_ids, ids.data(), ids.size());
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_items, s.h_items, items.size() * sizeof(Item), hipMemcpyHostToDevice, st));
+    if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(s.d_ids, s.h_ids, ids.size(), hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -113,11 +94,11 @@ void append_writer_loop(iss_ctx *ctx, AppendPipe *pipe) {
 // lazy and idempotent: streams (with_copy_stream: the size comes back beside the context's stream), events, pinned totals, writer
 int append_start(iss_ctx *ctx, AppendPipe &q, bool with_copy_stream, AppendWriteFn write, const char *noun) {
     if (q.ready) return 0;
-    if (with_copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&q.copy_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&q.data_stream, hipStreamNonBlocking));
-    for (auto &e : q.ev_fmt) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (with_copy_stream) for (auto &e : q.ev_copy) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &p : q.h_total) { void *v = nullptr; HIP_TRY(ctx, hipHostMalloc(&v, 64, hipHostMallocDefault)); p = static_cast<uint64_t *>(v); }
+    if (with_copy_stream) ISS_TRY(stream_create(ctx, q.copy_stream, hipStreamNonBlocking));
+    ISS_TRY(stream_create(ctx, q.data_stream, hipStreamNonBlocking));
+    for (auto &e : q.ev_fmt) ISS_TRY(event_create(ctx, e, hipEventDisableTiming));
+    if (with_copy_stream) for (auto &e : q.ev_copy) ISS_TRY(event_create(ctx, e, hipEventDisableTiming));
+    for (auto &p : q.h_total) PIN_ALLOC(ctx, p, 64 / sizeof(uint64_t));
     q.write = write;
     q.noun = noun;
     q.stop = false;
@@ -149,7 +130,7 @@ int append_flush(iss_ctx *ctx, AppendPipe &q, bool keep_file = false) {
 // another descriptor than the attached one: what is queued for the old one lands first, the new one is appended to where it stands
 int append_attach(iss_ctx *ctx, AppendPipe &q, int fd) {
     if (q.fd == fd) return 0;
-    { int rc_ = append_flush(ctx, q); if (rc_) return rc_; }
+    ISS_TRY(append_flush(ctx, q));
     const off_t at = lseek(fd, 0, SEEK_CUR);
     if (at < 0) return fail(ctx, ISS_E_IO, std::string("lseek failed: ") + strerror(errno));
     q.fd = fd;
@@ -182,25 +163,14 @@ int append_enqueue(iss_ctx *ctx, AppendPipe &q, int slot, int fd, const uint64_t
     return 0;
 }
 
-// Flush, stop and join the writer, wait for the context's stream (the kernels of the last emit use the format's buffers: the caller
-// frees them next), destroy streams, events and totals.  false: the pipe was never started.
-bool append_stop(iss_ctx *ctx, AppendPipe &q) {
-    if (!q.ready) return false;
+// Before the context goes: flush, stop and join the writer, wait for the context's stream (the kernels of the last emit use the
+// format's buffers, which the pipe's members release with the context).  A pipe that was never started: nothing to wait for.
+void append_stop(iss_ctx *ctx, AppendPipe &q) {
+    if (!q.ready) return;
     (void)append_flush(ctx, q);
     writer_stop(q);
     (void)hipStreamSynchronize(ctx->stream);
-    for (int sl = 0; sl < 2; ++sl) {
-        if (q.h_total[sl]) (void)hipHostFree(q.h_total[sl]);
-        if (q.ev_fmt[sl]) (void)hipEventDestroy(q.ev_fmt[sl]);
-        if (q.ev_copy[sl]) (void)hipEventDestroy(q.ev_copy[sl]);
-        q.h_total[sl] = nullptr;
-        q.ev_fmt[sl] = q.ev_copy[sl] = nullptr;
-    }
-    if (q.copy_stream) (void)hipStreamDestroy(q.copy_stream);
-    if (q.data_stream) (void)hipStreamDestroy(q.data_stream);
-    q.copy_stream = q.data_stream = nullptr;
     q.ready = false;
-    return true;
 }
 
 }  // namespace

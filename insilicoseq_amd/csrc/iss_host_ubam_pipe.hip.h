@@ -1,5 +1,5 @@
 // iss_host_ubam_pipe.hip.h -- what the append pipe (iss_host_pipe.hip.h) does for iss_ubam_emit_batch: a call's BGZF members
-// fetched, their BSIZE chain checked, appended; buffers.
+// fetched, their BSIZE chain checked, appended.
 #pragma once
 
 namespace {
@@ -22,36 +22,6 @@ std::string ubam_write(iss_ctx *ctx, int slot, uint64_t total, int64_t at, int *
     }
     if (!ok || pos != total) { *code = ISS_E_INVALID; return "BGZF members do not have the layout their sizes were computed from"; }
     return pwrite_all(q.job_fd[slot], p, total, at) ? std::string("write failed: ") + strerror(errno) : "";
-}
-
-void ubam_free_buffers(iss_ctx *ctx) {
-    UbamPipe &q = ctx->uq;
-    for (int sl = 0; sl < 2; ++sl) {
-        if (q.d_text[sl]) (void)hipFree(q.d_text[sl]);
-        if (q.d_comp[sl]) (void)hipFree(q.d_comp[sl]);
-        if (q.h_comp[sl]) (void)hipHostFree(q.h_comp[sl]);
-        if (q.d_bbytes[sl]) (void)hipFree(q.d_bbytes[sl]);
-        if (q.d_bcrc[sl]) (void)hipFree(q.d_bcrc[sl]);
-        if (q.d_boff[sl]) (void)hipFree(q.d_boff[sl]);
-        q.d_text[sl] = q.d_comp[sl] = q.h_comp[sl] = nullptr;
-        q.d_bbytes[sl] = q.d_bcrc[sl] = nullptr;
-        q.d_boff[sl] = nullptr;
-    }
-    q.cap = q.comp_cap = 0;
-    q.blocks_cap = 0;
-}
-
-void ubam_shutdown(iss_ctx *ctx) {
-    UbamPipe &q = ctx->uq;
-    if (!append_stop(ctx, q)) return;
-    ubam_free_buffers(ctx);
-    q.tab.release();
-    for (int sl = 0; sl < 2; ++sl) {
-        if (q.d_hist[sl]) (void)hipFree(q.d_hist[sl]);
-        if (q.d_code[sl]) (void)hipFree(q.d_code[sl]);
-        q.d_hist[sl] = nullptr;
-        q.d_code[sl] = nullptr;
-    }
 }
 
 }  // namespace

@@ -1,30 +1,86 @@
-// iss_host_util.hip.h -- helpers every entry point uses: error reporting, checked uploads, the environment switches, what a
-// context frees, the choice of the hot kernel's instantiation (k_main / k_main_g), its LDS size, timing, synchronisation.
+// iss_host_util.hip.h -- helpers every entry point uses: error reporting, checked allocations into owning handles, checked
+// uploads, the environment switches, what a model upload or a new reservation empties, the choice of the hot kernel's
+// instantiation (k_main / k_main_g), its LDS size, timing, synchronisation.
 #pragma once
 
 namespace {
 
+// What takes an error: a context (NULL: only the thread's last error), or the `model` / `report` contexts (iss_api_bam.hip.h,
+// iss_api_fqtally.hip.h).
 int fail(iss_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->last_error = msg;
     g_last_error = msg;
     return code;
 }
+int fail(std::nullptr_t, int code, const std::string &msg) { return fail(static_cast<iss_ctx *>(nullptr), code, msg); }
+int fail(iss_bam *b, int code, const std::string &msg);
+int fail(iss_fq *f, int code, const std::string &msg);
 
-#define HIP_TRY(ctx, expr)                                                                       \
+// `owner`: whatever fail() takes
+#define HIP_TRY(owner, expr)                                                                     \
     do {                                                                                         \
         hipError_t _e = (expr);                                                                  \
         if (_e != hipSuccess)                                                                    \
-            return fail(ctx, ISS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));      \
+            return fail(owner, ISS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
     } while (0)
 
+// a call that returns the library's codes: pass a failure on
+#define ISS_TRY(expr)                                                                            \
+    do {                                                                                         \
+        const int rc_ = (expr);                                                                  \
+        if (rc_) return rc_;                                                                     \
+    } while (0)
+
+// The handle releases what it held, then holds `count` elements of device (pinned: host) memory; on failure it stays empty and
+// the error names `what`.  (own_alloc_quiet, for the callers that format their own message: iss_host_state.hip.h.)
+template <typename Owner, typename T, void (*Free)(void *)>
+int own_alloc(Owner owner, iss_own::Owned<T, Free> &h, size_t count, const char *what) {
+    hipError_t e = hipSuccess;
+    const size_t bytes = count * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+    if (own_alloc_quiet(h, bytes, &e))
+        return fail(owner, ISS_E_HIP, std::string(Free == own_free_pin ? "hipHostMalloc(" : "hipMalloc(") + what + ", " + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    return 0;
+}
+template <typename Owner, typename T>
+int dev_alloc(Owner owner, DevMem<T> &h, size_t count, const char *what) { return own_alloc(owner, h, count, what); }
+template <typename Owner, typename T>
+int pin_alloc(Owner owner, PinMem<T> &h, size_t count, const char *what) { return own_alloc(owner, h, count, what); }
+#define DEV_ALLOC(owner, handle, count) ISS_TRY(dev_alloc(owner, handle, count, #handle))
+#define PIN_ALLOC(owner, handle, count) ISS_TRY(pin_alloc(owner, handle, count, #handle))
+
+template <typename Owner>
+int event_create(Owner owner, Event &ev, unsigned flags) {
+    ev.reset();
+    hipEvent_t e = nullptr;
+    HIP_TRY(owner, hipEventCreateWithFlags(&e, flags));
+    ev.reset(e);
+    return 0;
+}
+template <typename Owner>
+int stream_create(Owner owner, Stream &st, unsigned flags) {
+    st.reset();
+    hipStream_t s = nullptr;
+    HIP_TRY(owner, hipStreamCreateWithFlags(&s, flags));
+    st.reset(s);
+    return 0;
+}
+template <typename Owner>
+int stream_create(Owner owner, Stream &st, unsigned flags, int priority) {
+    st.reset();
+    hipStream_t s = nullptr;
+    HIP_TRY(owner, hipStreamCreateWithPriority(&s, flags, priority));
+    st.reset(s);
+    return 0;
+}
+
 template <typename T>
-int upload(iss_ctx *ctx, const T *host, size_t n, T **dev, std::vector<void *> *track) {
-    void *p = nullptr;
+int upload(iss_ctx *ctx, const T *host, size_t n, T **dev, std::vector<DevMem<void>> *track) {
+    DevMem<void> d;
     const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    HIP_TRY(ctx, hipMalloc(&p, bytes));
-    if (track) track->push_back(p);
-    if (n) HIP_TRY(ctx, hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
-    *dev = static_cast<T *>(p);
+    ISS_TRY(dev_alloc(ctx, d, bytes, "model table"));
+    if (n) HIP_TRY(ctx, hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice));
+    *dev = static_cast<T *>(d.get());  // a view: `track` keeps the allocation
+    track->push_back(std::move(d));
     return 0;
 }
 
@@ -46,95 +102,18 @@ void read_switches(iss_ctx *ctx) {
 }
 
 void free_model(iss_ctx *ctx) {
-    for (void *p : ctx->model_allocs) (void)hipFree(p);
     ctx->model_allocs.clear();
     ctx->have_model = false;
 }
 
+// the output set and the views into it (free_outputs follows a sync_all: nothing of the old buffers is in flight)
 void free_outputs(iss_ctx *ctx) {
-    if (ctx->out[0]) (void)hipFree(ctx->out[0]);
+    ctx->os = {};
     for (auto &p : ctx->out) p = nullptr;
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    ctx->d_stage = nullptr; ctx->stage_cap = 0;
-    if (ctx->desc) (void)hipFree(ctx->desc);
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->desc_buf[k]) (void)hipFree(ctx->desc_buf[k]);
-        if (ctx->flags_buf[k]) (void)hipFree(ctx->flags_buf[k]);
-        if (ctx->fixl_buf[k]) (void)hipFree(ctx->fixl_buf[k]);
-        ctx->desc_buf[k] = nullptr; ctx->flags_buf[k] = nullptr; ctx->fixl_buf[k] = nullptr;
-        ctx->ev_call_valid[k] = false;
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->ev_count[k] && (k == 0 || ctx->ev_count[k] != ctx->ev_count[0])) (void)hipFree(ctx->ev_count[k]);
-        if (ctx->ev_list[k] && (k == 0 || ctx->ev_list[k] != ctx->ev_list[0])) (void)hipFree(ctx->ev_list[k]);
-        if (ctx->read_list[k] && (k == 0 || ctx->read_list[k] != ctx->read_list[0])) (void)hipFree(ctx->read_list[k]);
-        if (ctx->read_list1[k] && (k == 0 || ctx->read_list1[k] != ctx->read_list1[0])) (void)hipFree(ctx->read_list1[k]);
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->script[k]) (void)hipFree(ctx->script[k]);
-        ctx->script[k] = nullptr;
-    }
-    for (auto &v : ctx->ev_slot_valid) v = false;  // (free_outputs follows a sync_all: nothing of the old buffers is in flight)
+    ctx->flags = ctx->fix_list = nullptr;
     for (int k = 0; k < 2; ++k) { ctx->ev_count[k] = ctx->ev_list[k] = nullptr; ctx->read_list[k] = nullptr; ctx->read_list1[k] = nullptr; }
-    ctx->desc = nullptr; ctx->flags = nullptr; ctx->fix_list = nullptr;
-    ctx->capacity = 0;
-}
-
-// the set's --store_mutations storage (the request, MtSet::mut_rows, stays)
-void free_mt_set_rows(iss_ctx *ctx) {
-    auto &t = ctx->mts;
-    if (t.d_mut) (void)hipFree(t.d_mut);
-    if (t.d_mut_n) (void)hipFree(t.d_mut_n);
-    if (t.h_mut_n) (void)hipHostFree(t.h_mut_n);
-    if (t.d_mut_cnt) (void)hipFree(t.d_mut_cnt);
-    if (t.d_mut_off) (void)hipFree(t.d_mut_off);
-    if (t.ev_place) (void)hipEventDestroy(t.ev_place);
-    if (t.ev_walk) (void)hipEventDestroy(t.ev_walk);
-    t.d_mut = nullptr; t.d_mut_n = nullptr; t.h_mut_n = nullptr; t.d_mut_cnt = nullptr; t.d_mut_off = nullptr;
-    t.ev_place = t.ev_walk = nullptr;
-    t.mut_stride = 0;
-    t.mut_n.clear(); t.mut_row0.clear(); t.mut_pairs.clear();
-}
-
-void free_mt_set(iss_ctx *ctx) {
-    auto &t = ctx->mts;
-    free_mt_set_rows(ctx);
-    if (t.d_state) (void)hipFree(t.d_state);
-    if (t.d_res) (void)hipFree(t.d_res);
-    if (t.d_gauss) (void)hipFree(t.d_gauss);
-    if (t.d_rec) (void)hipFree(t.d_rec);
-    for (auto &st : t.buf) for (auto &b : st) { if (b) (void)hipFree(b); b = nullptr; }
-    if (t.h_jobs) (void)hipHostFree(t.h_jobs);
-    if (t.d_jobs) (void)hipFree(t.d_jobs);
-    if (t.h_res) (void)hipHostFree(t.h_res);
-    for (auto &e : t.ev_emit) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    if (t.ev_side) (void)hipEventDestroy(t.ev_side);
-    if (t.ev_turn) (void)hipEventDestroy(t.ev_turn);
-    t.ev_side = t.ev_turn = nullptr;
-    t.d_state = nullptr; t.d_res = nullptr; t.d_gauss = nullptr; t.d_rec = nullptr; t.h_jobs = nullptr; t.d_jobs = nullptr; t.h_res = nullptr;
-    t.W = 0; t.ch = 0; t.buf_turns = 0; t.cap[0] = t.cap[1] = 0; t.jobs_bytes = 0;
-    t.chains.clear(); t.last_read.clear();
-}
-
-void free_mt(iss_ctx *ctx) {
-    free_mt_set(ctx);
-    auto &m = ctx->mt;
-    auto &c = m.chain;
-    if (c.d_state) (void)hipFree(c.d_state);
-    if (c.d_res) (void)hipFree(c.d_res);
-    if (c.d_gauss) (void)hipFree(c.d_gauss);
-    if (c.d_rec) (void)hipFree(c.d_rec);
-    for (auto &st : c.buf) for (auto &b : st) if (b) (void)hipFree(b);
-    c = MtChain{};
-    if (m.d_mut) (void)hipFree(m.d_mut);
-    if (m.d_mut_cnt) (void)hipFree(m.d_mut_cnt);
-    if (m.d_mut_off) (void)hipFree(m.d_mut_off);
-    if (m.d_amb) (void)hipFree(m.d_amb);
-    m.d_mut = nullptr; m.mut_cap = 0; m.d_mut_cnt = nullptr; m.d_mut_off = nullptr; m.d_amb = nullptr;
-    if (m.ev_main) (void)hipEventDestroy(m.ev_main);
-    if (m.ev_fill) (void)hipEventDestroy(m.ev_fill);
-    m.ev_main = m.ev_fill = nullptr;
-    m.seeded = false;
+    for (auto &v : ctx->ev_call_valid) v = false;
+    for (auto &v : ctx->ev_slot_valid) v = false;
 }
 
 // k_main_g: the instantiations (iterations per pass NI, passes per group NP) the library holds -- a group is at most five
@@ -185,9 +164,8 @@ int settle_timing(iss_ctx *ctx) {
             HIP_TRY(ctx, hipEventElapsedTime(&ms, t.ev[first[k]], e_end));
             ctx->ms_acc[k] += ms;
         }
-        for (auto &e : t.ev) if (e) (void)hipEventDestroy(e);
     }
-    ctx->timed.clear();
+    ctx->timed.clear();  // (with their events)
     return 0;
 }
 

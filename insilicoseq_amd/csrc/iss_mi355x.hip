@@ -25,9 +25,11 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "iss_kernels.hip.h"
@@ -50,8 +52,9 @@
 #include "iss_fqtally.hip.h"    // k_fq_*: `report`, the tallies of the rows over FASTQ text (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
+#include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
 #include "iss_host_state.hip.h"       // the output pipes' records, struct iss_ctx
-#include "iss_host_util.hip.h"        // errors, uploads, switches, frees, kernel choice, timing, synchronisation
+#include "iss_host_util.hip.h"        // errors, checked allocations and uploads, switches, kernel choice, timing, synchronisation
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
 #include "iss_host_pipe.hip.h"        // shared by the output pipes: slot table, slot wait, the append pipe and its writer thread
 #include "iss_host_fastq_pipe.hip.h"  // the two FASTQ files' writer thread, flush

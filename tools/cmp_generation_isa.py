@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Are the generation kernels (k_main*, k_setup, k_indel_*, k_perfect, k_mt_*) of two device assembly files the same code?
-A change that adds kernels of its own must leave them alone.  Compared per kernel: every instruction, directive and label, with
+A change that adds kernels of its own must leave them alone; --all compares every kernel of the first file instead (a change of
+the host side alone must leave all of them as they are).  Compared per kernel: every instruction, directive and label, with
 comments dropped and the function number taken out of the basic-block labels (.LBB<function>_<block>: hipcc numbers the
 functions of a translation unit in order, so a kernel added in front of another renumbers labels and nothing else).
 
 Usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -I include -S --cuda-device-only -o new.s insilicoseq_amd/csrc/iss_mi355x.hip
-       (the same on the parent commit -> parent.s);  python tools/cmp_generation_isa.py parent.s new.s"""
+       (the same on the parent commit -> parent.s);  python tools/cmp_generation_isa.py [--all] parent.s new.s"""
 import re
 import sys
 
@@ -30,13 +31,15 @@ def kernels(path):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    names = [k for k in a if GENERATION.search(k)]
+    every = "--all" in sys.argv[1:]
+    paths = [x for x in sys.argv[1:] if x != "--all"]
+    a, b = kernels(paths[0]), kernels(paths[1])
+    names = [k for k in a if every or GENERATION.search(k)]
     bad = [k for k in names if a[k] != b.get(k)]
     for k in bad:
         print("differs: %s" % k)
-    print("%d generation kernels compared, %d differ (%d instructions and labels in all); kernels only in the second file: %d" % (
-        len(names), len(bad), sum(len(a[k]) for k in names), len(set(b) - set(a))))
+    print("%d %skernels compared, %d differ (%d instructions and labels in all); kernels only in the second file: %d" % (
+        len(names), "" if every else "generation ", len(bad), sum(len(a[k]) for k in names), len(set(b) - set(a))))
     return 1 if bad or not names else 0
 
 
