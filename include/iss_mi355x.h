@@ -751,6 +751,60 @@ int iss_fq_feed(iss_fq *fq, int32_t mate, const uint8_t *text, int64_t n_bytes);
 int iss_fq_download(iss_fq *fq, uint64_t *tally, int64_t *records, int64_t *bad_record, int32_t *bad_code);
 int iss_fq_kernel_ms(iss_fq *fq, double *ms);
 
+/*
+ * BGZF inflate ON THE DEVICE (additive in ABI 8): the BAM input of `model` and BGZF-compressed FASTQ in `report`.
+ * A BGZF file (SAM/BAM specification 4.1) is a series of gzip members that each inflate alone, yield at most 64 KiB and carry
+ * their own size (the BC subfield, BSIZE = size - 1), CRC-32 and inflated size (ISIZE).
+ *
+ * iss_bgzf_scan (host only, no GPU): the BSIZE chain of `data` -- up to `capacity` whole members: where each starts, where its
+ * DEFLATE payload starts and how long it is, its CRC-32 and ISIZE; *consumed is the bytes they cover, an incomplete member at the end
+ * is left for the next call.  Any XLEN is taken, with the BC subfield anywhere among the subfields.  ISS_E_INVALID with one line in
+ * iss_inflate_last_error(NULL): no gzip magic with the extra-field flag (1f 8b 08 04), a member without BC, a BSIZE + 1 smaller than
+ * the member's header and footer; the members in front of the bad one are returned all the same.
+ *
+ * The context: iss_inflate_feed takes HOST bytes and the scan's arrays of one group of whole members (the offsets relative to
+ * `data`) and returns as soon as the bytes are in one of the context's two pinned staging buffers; the copy to the device, the kernel
+ * and the copy of the result to pinned host memory follow on three streams, so that group i + 1 copies in while group i inflates and
+ * group i - 1 copies out.  A feed waits for the device only to get its staging buffer back, never for a collect: any number of
+ * groups may be in flight (each holds a result buffer).  iss_inflate_collect waits for the OLDEST group in flight and hands out its
+ * inflated bytes -- member m at the exclusive sum of ISIZE -- and one ISS_BGZF_* status per member; the pointers are the context's
+ * memory, good until the next collect, reset or destroy.  A bad member does not stop the others; its bytes are unspecified.  The
+ * smallest (member index over all feeds << 8) | status is kept on the device: iss_inflate_first_bad waits for every kernel fed and
+ * returns it (member -1: none).  iss_inflate_reset drops what is in flight, the first-bad word, the member count and the kernel time.
+ * iss_inflate_kernel_ms waits for everything fed and gives the kernels' time from HIP events.
+ * ISS_E_INVALID, nothing launched: NULL arguments, negative sizes, a group of 2^31 bytes or more on either side, payloads that are
+ * not ascending inside the buffer, a member with more than 64 KiB on either side; collect with no group in flight.  n_members == 0: 0,
+ * nothing launched, no group queued.
+ * ISS_INFLATE_WGS (environment, read per feed): the workgroups a launch aims at.
+ *
+ * Status of a member, the first that applies while decoding; behind the final block SHORT, then CRC, then TRAILING:
+ */
+#define ISS_BGZF_OK 0
+#define ISS_BGZF_BAD_BTYPE 1     /* block type 3 */
+#define ISS_BGZF_STORED_LEN 2    /* a stored block's LEN and ~LEN disagree */
+#define ISS_BGZF_BAD_CODE 3      /* a code-length set zlib refuses (over-subscribed, incomplete, no end-of-block code, a repeat with
+                                  * nothing to repeat or past HLIT + HDIST, more than 286 / 30 codes), or bits that are no code */
+#define ISS_BGZF_BAD_SYMBOL 4    /* literal/length symbol 286 or 287, distance symbol 30 or 31 */
+#define ISS_BGZF_BAD_DISTANCE 5  /* a distance greater than the bytes produced so far */
+#define ISS_BGZF_IN_OVERRUN 6    /* the stream wants bits behind the payload's end */
+#define ISS_BGZF_OUT_OVERRUN 7   /* more than ISIZE bytes */
+#define ISS_BGZF_SHORT 8         /* fewer than ISIZE bytes */
+#define ISS_BGZF_TRAILING 9      /* whole payload bytes left behind the final block; the bytes are produced and checked all the same */
+#define ISS_BGZF_CRC 10          /* the CRC-32 of the bytes produced is not the footer's */
+
+typedef struct iss_inflate iss_inflate;
+int iss_bgzf_scan(const uint8_t *data, int64_t n_bytes, int64_t *member_off, int64_t *pay_off, uint32_t *pay_len, uint32_t *crc,
+                  uint32_t *isize, int64_t capacity, int64_t *n_members, int64_t *consumed);
+int iss_inflate_create(int device_ordinal, iss_inflate **out);
+void iss_inflate_destroy(iss_inflate *inf);
+const char *iss_inflate_last_error(const iss_inflate *inf);
+int iss_inflate_reset(iss_inflate *inf);
+int iss_inflate_feed(iss_inflate *inf, const uint8_t *data, int64_t n_bytes, const int64_t *pay_off, const uint32_t *pay_len,
+                     const uint32_t *crc, const uint32_t *isize, int64_t n_members);
+int iss_inflate_collect(iss_inflate *inf, const uint8_t **data, int64_t *n_bytes, const uint8_t **status, int64_t *n_members);
+int iss_inflate_first_bad(iss_inflate *inf, int64_t *member, int32_t *code);
+int iss_inflate_kernel_ms(iss_inflate *inf, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ EXPORTS = (
     "iss_error_tally_words", "iss_mutations_tally",
     "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words", "iss_fq_feed", "iss_fq_download",
     "iss_fq_kernel_ms",
+    "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy", "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed",
+    "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -57,6 +59,12 @@ FQ_REC_ERRORS = {
     3: "the bases and the quality line differ in length", 4: "read longer than --max_length",
     5: "quality character outside '!' .. '~'", 6: "truncated record (the file ends inside it)",
 }
+
+
+# the device inflate (include/iss_mi355x.h: ISS_BGZF_*)
+BGZF_STATUS = ("OK", "BAD_BTYPE", "STORED_LEN", "BAD_CODE", "BAD_SYMBOL", "BAD_DISTANCE", "IN_OVERRUN", "OUT_OVERRUN", "SHORT", "TRAILING",
+               "CRC")
+BGZF_OK, BGZF_TRAILING = 0, 9
 
 
 class NativeLibraryError(RuntimeError):
@@ -200,6 +208,19 @@ def lib():
         L.iss_fq_feed.argtypes = [vp, i32, vp, i64]
         L.iss_fq_download.argtypes = [vp, vp, vp, vp, vp]
         L.iss_fq_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    # (and the device inflate; without them inflate.BgzfInflater raises)
+    if hasattr(L, "iss_inflate_feed"):
+        L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.iss_inflate_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.iss_inflate_destroy.argtypes = [vp]
+        L.iss_inflate_destroy.restype = None
+        L.iss_inflate_last_error.argtypes = [vp]
+        L.iss_inflate_last_error.restype = C.c_char_p
+        L.iss_inflate_reset.argtypes = [vp]
+        L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]
+        L.iss_inflate_collect.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64)]
+        L.iss_inflate_first_bad.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
+        L.iss_inflate_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -228,10 +249,12 @@ def lib():
                     "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
                     "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
                     "iss_mutations_tally", "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words",
-                    "iss_fq_feed", "iss_fq_download", "iss_fq_kernel_ms") and not hasattr(L, name):
+                    "iss_fq_feed", "iss_fq_download", "iss_fq_kernel_ms", "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy",
+                    "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed", "iss_inflate_collect", "iss_inflate_first_bad",
+                    "iss_inflate_kernel_ms") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error", "iss_fq_destroy",
-                        "iss_fq_last_error"):
+                        "iss_fq_last_error", "iss_inflate_destroy", "iss_inflate_last_error"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64

@@ -523,7 +523,8 @@ def model_from_bam(args):
     try:
         timings = {}
         logger.info("Starting model: %s" % args.bam)
-        path = to_model(args.bam, args.output, seed=args.seed, device=args.device, dense=args.dense, timings=timings)
+        path = to_model(args.bam, args.output, seed=args.seed, device=args.device, dense=args.dense, timings=timings,
+                        device_inflate=True if args.device_inflate else None)
         logger.debug("seconds: %s" % ", ".join("%s %.3f" % kv for kv in sorted(timings.items())))
         logger.info("Model written to %s" % path)
     except (BamError, EngineError, NativeLibraryError, OSError) as e:
@@ -542,6 +543,7 @@ def report_from_fastq(args):
 
     from . import fastq_report, tally
     from ._native import FQ_REC_ERRORS, EngineError, NativeLibraryError
+    from .inflate import InflateError
 
     logging.basicConfig(level=logging.ERROR if args.quiet else logging.INFO)
     logger = logging.getLogger(__name__)
@@ -588,6 +590,8 @@ def report_from_fastq(args):
             with open(args.output + "_compare.json", "w") as fh:
                 json.dump(fastq_report.compare_tallies(res["tally"], L, other, other_length), fh, indent=1)
                 fh.write("\n")
+    except InflateError as e:  # (a BGZF member that does not inflate on the device: the message names the file)
+        return fail(str(e).splitlines()[0])
     except (EngineError, NativeLibraryError, OSError, EOFError, ValueError, zlib.error) as e:  # (a broken .gz: the last two)
         return fail("%s: %s" % (args.read1, str(e).splitlines()[0] if str(e) else type(e).__name__))
     return 0
@@ -656,7 +660,11 @@ def build_parser():
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")
-    m.add_argument("--bam", "-b", required=True, help="aligned reads (BAM with MD tags); no index needed")
+    m.add_argument("--bam", "-b", required=True,
+                   help="aligned reads (BAM with MD tags); no index needed")
+    m.add_argument("--device_inflate", action="store_true",
+                   help="inflate the BAM's BGZF blocks on the GPU instead of in the pool of host threads (also: ISS_DEVICE_INFLATE=1; "
+                        "the host pool is the default because it is the faster route end to end, DESIGN.md section 27)")
     m.add_argument("--output", "-o", required=True, help="output prefix: writes <prefix>.npz")
     m.add_argument("--quiet", "-q", action="store_true")
     m.add_argument("--debug", "-d", action="store_true")
@@ -665,7 +673,8 @@ def build_parser():
     m.add_argument("--dense", action="store_true", help="also write <prefix>.dense.npz (this project's pickle-free form)")
     r = sub.add_parser("report", help="the --report tallies of existing FASTQ files, built on the GPU; --against compares them "
                                       "with another tally")
-    r.add_argument("--read1", "-1", required=True, metavar="R1.fastq[.gz]")
+    r.add_argument("--read1", "-1", required=True, metavar="R1.fastq[.gz]",
+                   help="the first reads; a .gz written by bgzip (BGZF) is inflated on the GPU, any other gzip on the host")
     r.add_argument("--read2", "-2", default=None, metavar="R2.fastq[.gz]", help="the second reads (without it mate 2's fields are zero)")
     r.add_argument("--output", "-o", required=True,
                    help="output prefix: writes <prefix>_tally.npy (the counters, in the layout of generate --report at the longest "

@@ -1,5 +1,5 @@
-"""BAM input of `model` (the reference's `iss model`, iss/bam.py:14-46): BGZF inflate on the host, record boundaries in the HIP
-library's host code, the subsample.
+"""BAM input of `model` (the reference's `iss model`, iss/bam.py:14-46): BGZF inflate on the host or, given an inflater, on the device
+(inflate.py), record boundaries in the HIP library's host code, the subsample.
 
 A BAM file is a series of BGZF blocks (gzip members carrying a ``BC`` extra field with the block size, SAM/BAM specification
 section 4.1).  ``BamReader`` inflates them with ``zlib`` in a pool of at most 16 threads (``zlib`` releases the GIL), parses the
@@ -122,16 +122,30 @@ def scan(data, base=0, capacity=None):
 class BamReader(object):
     """Header and record chunks of a BAM file.  ``header`` is the SAM text, ``references`` the (name, length) list."""
 
-    def __init__(self, path, chunk_bytes=64 << 20, threads=None):
+    def __init__(self, path, chunk_bytes=64 << 20, threads=None, inflater=None):
+        """``inflater``: an inflate.BgzfInflater -- the BGZF blocks are then inflated on its device; None: in the host pool."""
         self.path = path
         self.chunk_bytes = int(chunk_bytes)
         self.threads = threads
+        self.inflater = inflater
         self.header = None
         self.references = None
         self.timings = collections.Counter()  # seconds: inflate (waiting for the pool), scan
 
+    def _device_pieces(self):
+        from . import inflate as device_inflate
+
+        try:
+            # (a member with bytes behind its final block is taken, as zlib.decompress takes it on the host route)
+            for piece in device_inflate.inflate_file(self.path, inflater=self.inflater, accept_trailing=True):
+                yield memoryview(piece)
+        except device_inflate.InflateError as e:
+            if e.status is not None:
+                raise BamError("corrupt BGZF block: byte %d of the file: %s" % (e.offset, e.status))
+            raise BamError("not a BAM file (%s)" % e)
+
     def _pieces(self):
-        it = inflate(self.path, self.threads)
+        it = inflate(self.path, self.threads) if self.inflater is None else self._device_pieces()
         while True:
             t0 = time.perf_counter()
             try:

@@ -9,7 +9,8 @@
 // iss_tally.hip.h (integer tallies of the rows: what a run produced), iss_depth.hip.h (per-base coverage depth of the reads),
 // iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text),
 // iss_bgzf_text.hip.h (the VCF and origins text as BGZF members), iss_errtally.hip.h (integer tallies of the mutation rows: what
-// a run did to the reads), iss_fqtally.hip.h (`report`: the tallies of iss_tally.hip.h over FASTQ text).
+// a run did to the reads), iss_fqtally.hip.h (`report`: the tallies of iss_tally.hip.h over FASTQ text), iss_inflate.hip.h (BGZF
+// members inflated: the decoder of iss_inflate_core.h on 64 lanes).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@
 #include "iss_bgzf_text.hip.h"  // k_bgzt_*: the VCF and origins text as BGZF members, copies from the line above (last, likewise)
 #include "iss_errtally.hip.h"   // k_errtally_rows, k_errtally_reads: tallies of the mutation rows (last, likewise)
 #include "iss_fqtally.hip.h"    // k_fq_*: `report`, the tallies of the rows over FASTQ text (last, likewise)
+#include "iss_inflate.hip.h"    // k_bgzf_inflate: BGZF members inflated on the device (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
@@ -76,3 +78,4 @@
 #include "iss_api_origins.hip.h"
 #include "iss_api_errtally.hip.h"
 #include "iss_api_fqtally.hip.h"
+#include "iss_api_inflate.hip.h"

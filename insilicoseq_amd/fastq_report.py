@@ -12,6 +12,7 @@ the smallest code that applies) is not tallied, the records after it are, and th
 DESIGN.md section 24."""
 import ctypes as C
 import gzip
+import os
 
 import numpy as np
 
@@ -186,9 +187,18 @@ def split_chunks(fh, chunk_bytes):
         yield bytes(view)
 
 
-def open_fastq(path):
-    """Binary reader of a FASTQ file; ``.gz`` through gzip (many members per file, as `generate --compress` writes, read through)."""
-    return gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")
+def open_fastq(path, device=None):
+    """Binary reader of a FASTQ file.  ``.gz``: a file whose first member carries the BGZF ``BC`` subfield (bgzip's) is inflated on the
+    GPU ``device`` (inflate.BgzfReader; None, or ISS_HOST_INFLATE=1: on the host); any other gzip goes through gzip.open (many members
+    per file, as `generate --compress` writes, read through)."""
+    if not str(path).endswith(".gz"):
+        return open(path, "rb")
+    if device is not None and os.environ.get("ISS_HOST_INFLATE", "") != "1":
+        from . import inflate
+
+        if inflate.is_bgzf(path):
+            return inflate.BgzfReader(path, device)
+    return gzip.open(path, "rb")
 
 
 class FastqTally(object):
@@ -199,6 +209,7 @@ class FastqTally(object):
         if not hasattr(self._lib, "iss_fq_feed"):
             raise _native.NativeLibraryError("%s has no iss_fq_* entries: rebuild it" % _native.LIB_PATH)
         self.max_len = int(max_len)
+        self.device = int(device)
         self._h = C.c_void_p()
         rc = self._lib.iss_fq_create(int(device), self.max_len, C.byref(self._h))
         if rc < 0:
@@ -238,7 +249,7 @@ class FastqTally(object):
         self._check(self._lib.iss_fq_feed(self._h, int(mate), a.ctypes.data if a.size else None, a.size))
 
     def feed_file(self, path, mate, chunk_bytes=64 << 20):
-        with open_fastq(path) as fh:
+        with open_fastq(path, self.device) as fh:
             for view in _split_views(fh, chunk_bytes):
                 self.feed(view, mate)
 

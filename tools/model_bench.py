@@ -4,6 +4,8 @@ tally (host-to-device copy + k_bam_tally + k_bam_qhist) / KDE / write.  Prints o
 
   python tools/model_bench.py --write /tmp/bench.bam --pairs 1000000   # the BAM only (no GPU)
   python tools/model_bench.py --bam /tmp/bench.bam                     # model it, timed
+  python tools/model_bench.py --bam /tmp/bench.bam --compare           # the BGZF blocks inflated on the device against the host pool
+                                                                       # (the default): alternating, three runs after a warm-up
 
 The kernel times come from a separate run of the second form under `rocprofv3 --kernel-trace --stats`.
 The records are built with numpy, all of one layout: 151M, MD with one reference letter at position 75 (a match, a substitution
@@ -94,6 +96,8 @@ def main():
     ap.add_argument("--write", help="write the BAM here and stop")
     ap.add_argument("--bam", help="model this BAM (default: write one to a temp dir first)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--compare", action="store_true", help="time both inflate routes, alternating: a warm-up, then --reps runs each")
+    ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     if args.write:
         t0 = time.perf_counter()
@@ -110,6 +114,20 @@ def main():
     from insilicoseq_amd.modeller import to_model
 
     out = os.path.join(tempfile.mkdtemp(prefix="model_bench_out_"), "m")
+    if args.compare:
+        import statistics
+
+        runs = {"device": [], "host_pool": []}
+        for rep in range(args.reps + 1):
+            for route in runs:
+                timings = {}
+                t0 = time.perf_counter()
+                to_model(bam, out, device=args.device, timings=timings, device_inflate=route == "device")
+                if rep:
+                    runs[route].append(dict(wall_s=round(time.perf_counter() - t0, 3), **{k + "_s": round(v, 3) for k, v in sorted(timings.items())}))
+        print(json.dumps(dict(bam=bam, bam_bytes=os.path.getsize(bam),
+                              **{r + "_wall_s": statistics.median(x["wall_s"] for x in v) for r, v in runs.items()}, runs=runs)))
+        return 0
     timings = {}
     t0 = time.perf_counter()
     to_model(bam, out, device=args.device, timings=timings)
