@@ -805,6 +805,55 @@ int iss_inflate_collect(iss_inflate *inf, const uint8_t **data, int64_t *n_bytes
 int iss_inflate_first_bad(iss_inflate *inf, int64_t *member, int32_t *code);
 int iss_inflate_kernel_ms(iss_inflate *inf, double *ms);
 
+/*
+ * `report --bam`: the tallies of iss_fq_* over BAM RECORDS, built ON THE DEVICE (additive in ABI 8): the reads of an
+ * aligned BAM, or of `generate --ubam`, as the sequencer gave them -- and the insert sizes, which only a BAM holds.  A context of its
+ * own, no iss_ctx and no model.  The words are exactly iss_fq_*'s at L = max_len (1 .. ISS_BR_MAX_LEN, fixed at creation),
+ * iss_br_tally_words words in all (-1 for NULL):
+ *   pairs [1] | qual [2][L][Q] | base [2][L][5] | gc [2][L + 1] | meanq [2][Q] | insert [I] | length [2][L + 1]
+ * A record as read: its bases are "=ACMGRSVTWYHKDBN"[code] of the 4-bit codes of SEQ, its phreds the quality bytes as stored.  With
+ * flag 0x10 the read as sequenced is the reverse complement of SEQ and the reversed QUAL; the complement of a code is the code with
+ * its four bits in reverse order (A 1 <-> T 8, C 2 <-> G 4, N 15 and '=' 0 fixed).  The letters count as FASTQ letters do (A, C, G, T
+ * base codes 0 .. 3, every other letter 4; G and C in gc).  qual, base, gc, meanq (floor of the phred sum over the read's own
+ * length), length, the read of length 0 and pairs (the good records of mate 0) are iss_fq_*'s, word for word.
+ * Which records count: with 0x100 or 0x800 set a record is skipped (skipped[0]); of the rest a record with 0x1 clear is mate 0; with
+ * 0x1 set, 0x40 alone is mate 0 and 0x80 alone mate 1, both or neither is skipped (skipped[1]).  Unmapped records (0x4) count like
+ * any other.
+ * insert: a taken, good record of mate 0 with 0x1 set, 0x4 and 0x8 clear, refID == next_refID >= 0 and tlen != 0 adds one to
+ * insert[clip(|tlen| - 2 * l_seq, 0, 2047)], |tlen| in 64 bits: the gap between the mates as `generate --report` counts it, exact
+ * where the two mates have the same length.
+ * A bad record gets the first ISS_BR_REC_* code that applies, before the skip rules (a malformed secondary record is reported); it
+ * is not tallied, the records after it are, and the smallest (record index over all records fed, skipped ones included) << 8 | code
+ * is kept.
+ * Every count is an exact integer sum: the words depend neither on the launch geometry nor on how the records were cut into chunks.
+ *
+ * iss_br_feed: `data` is HOST memory, n_bytes of inflated BAM bytes that hold whole records, `offsets` the byte offset of every
+ * record's block_size field as iss_bam_scan gives them.  The caller may reuse both as soon as the call returns: they go through the
+ * context's pinned staging buffers, so that the copy of one chunk overlaps the kernels of the chunk before.  ISS_E_INVALID, nothing
+ * launched, the tally as it was: NULL arguments, negative counts, n_bytes >= 2^31, an offset below 0 or with less than 36 bytes
+ * behind it, a block_size below 32 or past the chunk's end, offsets that do not ascend.  n_records == 0: 0, nothing launched.
+ * iss_br_download waits for everything fed, then copies the words, the good records taken per mate (records[2]), the skipped
+ * records (skipped[2]: secondary or supplementary; mate flags) and the first bad record (*bad_record: -1 for none; *bad_code).
+ * iss_br_reset zeroes the words and the counts.  iss_br_kernel_ms: as iss_fq_kernel_ms.
+ * ISS_BR_WGS (environment, read per call like ISS_FQTALLY_WGS): the workgroups the record kernel aims at (the per-position kernel:
+ * per column of 64 positions).
+ */
+#define ISS_BR_MAX_LEN 1024
+#define ISS_BR_REC_SHORT 1      /* l_read_name == 0, l_seq < 0, or 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq > block_size */
+#define ISS_BR_REC_TOO_LONG 2   /* l_seq > max_len */
+#define ISS_BR_REC_NO_QUAL 3    /* l_seq > 0 and the first quality byte is 0xFF */
+#define ISS_BR_REC_QUAL_RANGE 4 /* a quality byte above 93 */
+
+typedef struct iss_br iss_br;
+int iss_br_create(int device_ordinal, int32_t max_len, iss_br **out);
+void iss_br_destroy(iss_br *br);
+const char *iss_br_last_error(const iss_br *br);
+int iss_br_reset(iss_br *br);
+int64_t iss_br_tally_words(const iss_br *br); /* = iss_fq_tally_words at the same max_len */
+int iss_br_feed(iss_br *br, const uint8_t *data, int64_t n_bytes, const int64_t *offsets, int64_t n_records);
+int iss_br_download(iss_br *br, uint64_t *tally, int64_t *records, int64_t *skipped, int64_t *bad_record, int32_t *bad_code);
+int iss_br_kernel_ms(iss_br *br, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

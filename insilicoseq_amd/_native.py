@@ -39,6 +39,8 @@ EXPORTS = (
     "iss_fq_kernel_ms",
     "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy", "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed",
     "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
+    "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
+    "iss_br_kernel_ms",
 )
 
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
@@ -58,6 +60,13 @@ FQ_REC_ERRORS = {
     1: "line 1 of the record does not start with '@'", 2: "line 3 of the record does not start with '+'",
     3: "the bases and the quality line differ in length", 4: "read longer than --max_length",
     5: "quality character outside '!' .. '~'", 6: "truncated record (the file ends inside it)",
+}
+
+# `report --bam` (include/iss_mi355x.h: ISS_BR_*)
+BR_MAX_LEN = 1024
+BR_REC_ERRORS = {
+    1: "malformed record (its fields do not fit its block_size)", 2: "read longer than --max_length", 3: "read without qualities",
+    4: "quality above 93",
 }
 
 
@@ -208,6 +217,18 @@ def lib():
         L.iss_fq_feed.argtypes = [vp, i32, vp, i64]
         L.iss_fq_download.argtypes = [vp, vp, vp, vp, vp]
         L.iss_fq_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    # (and `report --bam`, the same tallies over BAM records; without them bam_report.BamReadTally raises)
+    if hasattr(L, "iss_br_feed"):
+        L.iss_br_create.argtypes = [C.c_int, i32, C.POINTER(vp)]
+        L.iss_br_destroy.argtypes = [vp]
+        L.iss_br_destroy.restype = None
+        L.iss_br_last_error.argtypes = [vp]
+        L.iss_br_last_error.restype = C.c_char_p
+        L.iss_br_reset.argtypes = [vp]
+        L.iss_br_tally_words.argtypes = [vp]
+        L.iss_br_feed.argtypes = [vp, vp, i64, vp, i64]
+        L.iss_br_download.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
+        L.iss_br_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     # (and the device inflate; without them inflate.BgzfInflater raises)
     if hasattr(L, "iss_inflate_feed"):
         L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
@@ -251,10 +272,11 @@ def lib():
                     "iss_mutations_tally", "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words",
                     "iss_fq_feed", "iss_fq_download", "iss_fq_kernel_ms", "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy",
                     "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed", "iss_inflate_collect", "iss_inflate_first_bad",
-                    "iss_inflate_kernel_ms") and not hasattr(L, name):
+                    "iss_inflate_kernel_ms", "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words",
+                    "iss_br_feed", "iss_br_download", "iss_br_kernel_ms") and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error", "iss_fq_destroy",
-                        "iss_fq_last_error", "iss_inflate_destroy", "iss_inflate_last_error"):
+                        "iss_fq_last_error", "iss_inflate_destroy", "iss_inflate_last_error", "iss_br_destroy", "iss_br_last_error"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64
@@ -262,6 +284,8 @@ def lib():
         L.iss_error_tally_words.restype = i64
     if hasattr(L, "iss_fq_tally_words"):
         L.iss_fq_tally_words.restype = i64
+    if hasattr(L, "iss_br_tally_words"):
+        L.iss_br_tally_words.restype = i64
     _lib = L
     return L
 

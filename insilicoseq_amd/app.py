@@ -533,36 +533,78 @@ def model_from_bam(args):
     return 0
 
 
-def report_from_fastq(args):
-    """`report`: the --report tallies of existing FASTQ files, built on the GPU (fastq_report.py); errors are one line on stderr
-    and exit status 1."""
+def _report_fail(message):
+    sys.stderr.write("ERROR: %s\n" % message)
+    return 1
+
+
+def _report_against(args):
+    """--against of `report`: (the other tally's words or None, its read length, an error message or None); read before the GPU
+    is opened."""
+    import numpy as np
+
+    from . import fastq_report
+
+    if not args.against:
+        return None, None, None
+    try:
+        other = np.load(args.against, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        return None, None, "%s: %s" % (args.against, str(e).splitlines()[0] if str(e) else type(e).__name__)
+    other_length = fastq_report.read_length_of_words(other.size) if other.ndim == 1 else None
+    if other_length is None:
+        return None, None, ("%s: %s words fit no read length (a tally of read length L has %s words)"
+                            % (args.against, "x".join(str(n) for n in other.shape), "200 L + 2239"))
+    return other, other_length, None
+
+
+def _report_write(args, res, other, other_length, more=None):
+    """The files of `report` from a result (fastq_report.finish's keys); ``more``: further keys of <prefix>_report.json."""
     import json
-    import zlib
 
     import numpy as np
 
     from . import fastq_report, tally
+
+    L = res["read_length"]
+    np.save(args.output + "_tally.npy", res["tally"])
+    np.save(args.output + "_lengths.npy", res["lengths"])
+    report = tally.report_dict(res["tally"], L)
+    report["read_length_histogram"] = [tally._trim(res["lengths"][m]) for m in range(2)]
+    report.update(more or {})
+    with open(args.output + "_report.json", "w") as fh:
+        json.dump(report, fh, indent=1)
+        fh.write("\n")
+    if other is not None:
+        with open(args.output + "_compare.json", "w") as fh:
+            json.dump(fastq_report.compare_tallies(res["tally"], L, other, other_length), fh, indent=1)
+            fh.write("\n")
+
+
+def report_from_fastq(args):
+    """`report`: the --report tallies of existing FASTQ files, or with --bam of the reads of a BAM file, built on the GPU
+    (fastq_report.py, bam_report.py); errors are one line on stderr and exit status 1."""
+    import zlib
+
+    from . import fastq_report
     from ._native import FQ_REC_ERRORS, EngineError, NativeLibraryError
     from .inflate import InflateError
 
     logging.basicConfig(level=logging.ERROR if args.quiet else logging.INFO)
     logger = logging.getLogger(__name__)
-
-    def fail(message):
-        sys.stderr.write("ERROR: %s\n" % message)
-        return 1
+    fail = _report_fail
+    bam = getattr(args, "bam", None)
+    if bool(args.read1) == bool(bam):
+        return fail("report takes exactly one of -1 R1.fastq and --bam reads.bam")
+    if bam:
+        if args.read2:
+            return fail("report --bam takes no -2: the mates of a BAM file are told apart by their flags")
+        return _report_from_bam(args, logger)
 
     try:
-        other = None
-        if args.against:  # (before the GPU is opened)
-            try:
-                other = np.load(args.against, allow_pickle=False)
-            except (OSError, ValueError) as e:
-                return fail("%s: %s" % (args.against, str(e).splitlines()[0] if str(e) else type(e).__name__))
-            other_length = fastq_report.read_length_of_words(other.size) if other.ndim == 1 else None
-            if other_length is None:
-                return fail("%s: %s words fit no read length (a tally of read length L has %s words)"
-                            % (args.against, "x".join(str(n) for n in other.shape), "200 L + 2239"))
+        other, other_length, message = _report_against(args)  # (before the GPU is opened)
+        if message:
+            return fail(message)
         files = [args.read1] + ([args.read2] if args.read2 else [])
         t0 = time.perf_counter()
         with fastq_report.FastqTally(args.device, args.max_length) as dev:
@@ -578,22 +620,46 @@ def report_from_fastq(args):
         if args.read2 and res["records"][0] != res["records"][1]:
             return fail("%s holds %d records and %s holds %d: not the two files of one run"
                         % (args.read1, res["records"][0], args.read2, res["records"][1]))
-        L = res["read_length"]
-        np.save(args.output + "_tally.npy", res["tally"])
-        np.save(args.output + "_lengths.npy", res["lengths"])
-        report = tally.report_dict(res["tally"], L)
-        report["read_length_histogram"] = [tally._trim(res["lengths"][m]) for m in range(2)]
-        with open(args.output + "_report.json", "w") as fh:
-            json.dump(report, fh, indent=1)
-            fh.write("\n")
-        if other is not None:
-            with open(args.output + "_compare.json", "w") as fh:
-                json.dump(fastq_report.compare_tallies(res["tally"], L, other, other_length), fh, indent=1)
-                fh.write("\n")
+        _report_write(args, res, other, other_length)
     except InflateError as e:  # (a BGZF member that does not inflate on the device: the message names the file)
         return fail(str(e).splitlines()[0])
     except (EngineError, NativeLibraryError, OSError, EOFError, ValueError, zlib.error) as e:  # (a broken .gz: the last two)
         return fail("%s: %s" % (args.read1, str(e).splitlines()[0] if str(e) else type(e).__name__))
+    return 0
+
+
+def _report_from_bam(args, logger):
+    """`report --bam`: the reads of a BAM file, insert sizes included (bam_report.py).  The BGZF blocks are inflated in the host
+    pool unless --device_inflate or ISS_DEVICE_INFLATE=1 asks for the device; ISS_HOST_INFLATE=1 wins over both."""
+    from . import bam_report
+    from ._native import BR_REC_ERRORS, EngineError, NativeLibraryError
+    from .bam import BamError
+    from .inflate import InflateError
+    from .modeller import device_inflater
+
+    fail = _report_fail
+    try:
+        other, other_length, message = _report_against(args)  # (before the GPU is opened)
+        if message:
+            return fail(message)
+        t0 = time.perf_counter()
+        with bam_report.BamReadTally(args.device, args.max_length) as dev, \
+                device_inflater(args.device, True if args.device_inflate else None) as inflater:
+            logger.info("Tallying %s" % args.bam)
+            dev.feed_file(args.bam, inflater)
+            res = dev.result()
+        logger.info("%d + %d records in %.2f s" % (res["records"][0], res["records"][1], time.perf_counter() - t0))
+        if res["bad_record"] >= 0:
+            code = res["bad_code"]
+            return fail("%s: record %d: %s" % (args.bam, res["bad_record"], BR_REC_ERRORS.get(code, "error %d" % code)))
+        if res["records"][1] and res["records"][0] != res["records"][1]:  # (a filtered BAM: normal)
+            logger.warning("%s holds %d first and %d second reads" % (args.bam, res["records"][0], res["records"][1]))
+        _report_write(args, res, other, other_length,
+                      {"records_skipped": {"secondary_or_supplementary": int(res["skipped"][0]), "mate_flags": int(res["skipped"][1])}})
+    except InflateError as e:  # (the message names the file)
+        return fail(str(e).splitlines()[0])
+    except (BamError, EngineError, NativeLibraryError, OSError) as e:
+        return fail("%s: %s" % (args.bam, str(e).splitlines()[0] if str(e) else type(e).__name__))
     return 0
 
 
@@ -671,10 +737,18 @@ def build_parser():
     m.add_argument("--seed", type=int, default=0, help="Philox key of the subsample (more than 1 000 000 mapped records)")
     m.add_argument("--device", type=int, default=0, help="GPU ordinal")
     m.add_argument("--dense", action="store_true", help="also write <prefix>.dense.npz (this project's pickle-free form)")
-    r = sub.add_parser("report", help="the --report tallies of existing FASTQ files, built on the GPU; --against compares them "
-                                      "with another tally")
-    r.add_argument("--read1", "-1", required=True, metavar="R1.fastq[.gz]",
-                   help="the first reads; a .gz written by bgzip (BGZF) is inflated on the GPU, any other gzip on the host")
+    r = sub.add_parser("report", help="the --report tallies of existing FASTQ files, or of the reads of a BAM file, built on the GPU; "
+                                      "--against compares them with another tally")
+    r.add_argument("--read1", "-1", default=None, metavar="R1.fastq[.gz]",
+                   help="the first reads; a .gz written by bgzip (BGZF) is inflated on the GPU, any other gzip on the host "
+                        "(exactly one of -1 and --bam)")
+    r.add_argument("--bam", default=None, metavar="reads.bam",
+                   help="the reads of a BAM file instead of FASTQ files, aligned or not (generate --ubam): each read as sequenced "
+                        "(reverse-strand records turned back), mates by their flags, secondary and supplementary records skipped, "
+                        "and the insert-size histogram from the template lengths of the aligned pairs; no index needed")
+    r.add_argument("--device_inflate", action="store_true",
+                   help="with --bam: inflate the BGZF blocks on the GPU instead of in the pool of host threads (also: "
+                        "ISS_DEVICE_INFLATE=1; ISS_HOST_INFLATE=1 keeps the host pool)")
     r.add_argument("--read2", "-2", default=None, metavar="R2.fastq[.gz]", help="the second reads (without it mate 2's fields are zero)")
     r.add_argument("--output", "-o", required=True,
                    help="output prefix: writes <prefix>_tally.npy (the counters, in the layout of generate --report at the longest "

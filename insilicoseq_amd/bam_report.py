@@ -1,0 +1,246 @@
+"""`report --bam`: the --report tallies of the reads of a BAM file (include/iss_mi355x.h: iss_br_*; k_br_* of
+csrc/iss_bamreads.hip.h), their numpy twin and the FASTQ text the twin stands for.  numpy only, besides the binding.
+
+The words are fastq_report.py's at L = max_len, so that its relayout, longest_read and compare_tallies and tally.report_dict apply:
+
+    pairs [1] | qual [2][L][94] | base [2][L][5] | gc [2][L + 1] | meanq [2][94] | insert [2048] | length [2][L + 1]
+
+A record as read: its bases are "=ACMGRSVTWYHKDBN"[code], its phreds the quality bytes as stored; with flag 0x10 the read as
+sequenced is the reverse complement of SEQ and the reversed QUAL, the complement of a 4-bit code being the code with its bits in
+reverse order.  The letters then count as FASTQ letters do (tally._CODE_TABLE, tally._GC_TABLE), and every field but ``insert`` is
+fastq_report's definition: the tally equals fastq_tally_host of the text bam_to_fastq writes.
+
+Which records count: 0x100 or 0x800 set -- skipped (skipped[0]); else 0x1 clear -- mate 0; 0x1 set -- 0x40 alone mate 0, 0x80 alone
+mate 1, both or neither skipped (skipped[1]).  Unmapped records count like any other.  A taken, good mate-0 record adds one to
+insert[clip(|tlen| - 2 l_seq, 0, 2047)] when 0x1 is set, 0x4 and 0x8 are clear, refID == next_refID >= 0 and tlen != 0 -- the gap
+between the mates, `generate --report`'s meaning of the word, exact where the mates have equal length.  A bad record (REC_*: the
+first code that applies, checked before the skip rules) is not tallied, the records after it are, and the first bad one over all
+records fed is reported.  DESIGN.md section 28."""
+import ctypes as C
+
+import numpy as np
+
+from . import _native
+from .bam import BamReader, Chunk
+from .fastq_report import finish as _finish, fq_words, split_fq_words
+from .tally import INSERT_BINS, PHREDS, _CODE_TABLE, _GC_TABLE
+
+MAX_LEN = _native.BR_MAX_LEN
+REC_SHORT, REC_TOO_LONG, REC_NO_QUAL, REC_QUAL_RANGE = 1, 2, 3, 4
+SEQ_LETTERS = np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)
+_COMPLEMENT = np.array([int("{:04b}".format(c)[::-1], 2) for c in range(16)], dtype=np.uint8)  # the four bits in reverse order
+
+
+def _field(a, at, n_bytes, signed=False):
+    """Little-endian integers of n_bytes at the byte offsets ``at`` of the uint8 array a, as int64."""
+    v = np.zeros(at.shape, dtype=np.int64)
+    for k in range(n_bytes):
+        v |= a[at + k].astype(np.int64) << (8 * k)
+    if signed:
+        v -= (v >> (8 * n_bytes - 1)) << (8 * n_bytes)
+    return v
+
+
+def _classify(chunk, max_len):
+    """Per record of a chunk: a dict of int64 / bool arrays -- ``code`` (0: good), ``mate`` (0, 1; -1: skipped as secondary or
+    supplementary, -2: skipped for its mate flags; meaningful where code == 0), ``len``, ``seq`` and ``qual`` (byte offsets),
+    ``reverse``, ``insert`` (the bin, or -1)."""
+    a = np.frombuffer(chunk.data, dtype=np.uint8)
+    o = np.asarray(chunk.offsets, dtype=np.int64)
+    block_size, ref_id = _field(a, o, 4, True), _field(a, o + 4, 4, True)
+    l_name, n_cigar, flag = _field(a, o + 12, 1), _field(a, o + 16, 2), _field(a, o + 18, 2)
+    l_seq, next_ref, tlen = _field(a, o + 20, 4, True), _field(a, o + 24, 4, True), _field(a, o + 32, 4, True)
+    seq = o + 36 + l_name + 4 * n_cigar
+    code = np.zeros(o.size, dtype=np.int64)
+    short = (l_name == 0) | (l_seq < 0) | (32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq > block_size)
+    code[short] = REC_SHORT
+    code[~short & (l_seq > max_len)] = REC_TOO_LONG
+    length = np.where(code == 0, l_seq, 0)
+    qual = seq + (length + 1) // 2
+    first_q = a[np.minimum(qual, a.size - 1)]
+    code[(code == 0) & (length > 0) & (first_q == 0xFF)] = REC_NO_QUAL
+    length[code != 0] = 0
+    ok = np.flatnonzero(code == 0)
+    rec = np.repeat(ok, length[ok])
+    pos = np.arange(rec.size) - np.repeat(np.cumsum(length[ok]) - length[ok], length[ok])
+    over = np.bincount(rec, weights=a[qual[rec] + pos] > PHREDS - 1, minlength=o.size) > 0
+    code[over] = REC_QUAL_RANGE
+    paired = (flag & 1) != 0
+    first, last = (flag & 0x40) != 0, (flag & 0x80) != 0
+    mate = np.where(paired & last, 1, 0)
+    mate[paired & (first == last)] = -2
+    mate[(flag & 0x900) != 0] = -1
+    gap = np.clip(np.abs(tlen) - 2 * length, 0, INSERT_BINS - 1)  # (int64: |INT32_MIN| does not wrap)
+    has_insert = paired & ((flag & 0xC) == 0) & (ref_id == next_ref) & (ref_id >= 0) & (tlen != 0) & (mate == 0) & (code == 0)
+    return {"code": code, "mate": mate, "len": length, "seq": seq, "qual": qual, "reverse": (flag & 0x10) != 0,
+            "insert": np.where(has_insert, gap, -1)}
+
+
+def _tally_chunk(chunk, max_len, t):
+    """One feed of the twin: adds the chunk's taken records to the views t; (good records taken [2], skipped [2], first bad
+    (index in the chunk, code) or None)."""
+    a = np.frombuffer(chunk.data, dtype=np.uint8)
+    c = _classify(chunk, max_len)
+    good = c["code"] == 0
+    skipped = [int((good & (c["mate"] == -1)).sum()), int((good & (c["mate"] == -2)).sum())]
+    bad = np.flatnonzero(~good)
+    bad = (int(bad[0]), int(c["code"][bad[0]])) if bad.size else None
+    taken = np.flatnonzero(good & (c["mate"] >= 0))
+    length, mate, reverse = c["len"][taken], c["mate"][taken], c["reverse"][taken]
+    rec = np.repeat(np.arange(taken.size), length)                               # every base of the taken records: its record
+    pos = np.arange(rec.size) - np.repeat(np.cumsum(length) - length, length)  # (index into taken) and position as sequenced
+    src = np.where(reverse[rec], length[rec] - 1 - pos, pos)                    # its position in SEQ and QUAL
+    byte = a[c["seq"][taken][rec] + src // 2]
+    nib = np.where(src & 1, byte & 15, byte >> 4)
+    b = SEQ_LETTERS[np.where(reverse[rec], _COMPLEMENT[nib], nib)]
+    q = a[c["qual"][taken][rec] + src].astype(np.int64)
+    L = int(max_len)
+    m_of = mate[rec]
+    gc = np.bincount(rec, weights=_GC_TABLE[b], minlength=taken.size).astype(np.int64)
+    qsum = np.bincount(rec, weights=q, minlength=taken.size).astype(np.int64)  # (float64 sums of small integers: exact)
+    for m in range(2):
+        at, of = m_of == m, mate == m
+        t["qual"][m] += np.bincount(pos[at] * PHREDS + q[at], minlength=L * PHREDS).reshape(L, PHREDS).astype(np.uint64)
+        t["base"][m] += np.bincount(pos[at] * 5 + _CODE_TABLE[b[at]], minlength=L * 5).reshape(L, 5).astype(np.uint64)
+        t["gc"][m] += np.bincount(gc[of], minlength=L + 1).astype(np.uint64)
+        some = of & (length > 0)
+        t["meanq"][m] += np.bincount(np.minimum(qsum[some] // length[some], PHREDS - 1), minlength=PHREDS).astype(np.uint64)
+        t["length"][m] += np.bincount(length[of], minlength=L + 1).astype(np.uint64)
+    t["pairs"][0] += np.uint64((mate == 0).sum())
+    ins = c["insert"][taken]
+    t["insert"] += np.bincount(ins[ins >= 0], minlength=INSERT_BINS).astype(np.uint64)
+    return [int((mate == 0).sum()), int((mate == 1).sum())], skipped, bad
+
+
+def _as_chunks(chunks):
+    return [chunks] if isinstance(chunks, Chunk) else chunks
+
+
+def bam_reads_host(chunks, max_len=MAX_LEN):
+    """The numpy twin of the device path (iss_br_feed / iss_br_download): the same words and the same bad-record rules.  chunks: a
+    bam.Chunk (data: the bytes of whole records, offsets: their block_size fields) or an iterable of them -- the feeds.  Returns a
+    dict: ``tally`` (the flat uint64 device words at max_len), ``records`` (good records taken, [2]), ``skipped`` [2],
+    ``bad_record`` (index over all records fed; -1: none), ``bad_code``."""
+    max_len = int(max_len)
+    if not 1 <= max_len <= MAX_LEN:
+        raise ValueError("max_len outside 1 .. %d" % MAX_LEN)
+    words = np.zeros(fq_words(max_len), dtype=np.uint64)
+    t = split_fq_words(words, max_len)
+    records, skipped, bad_record, bad_code, fed = [0, 0], [0, 0], -1, 0, 0
+    for chunk in _as_chunks(chunks):
+        if not len(chunk.offsets):
+            continue
+        n, s, bad = _tally_chunk(chunk, max_len, t)
+        records = [records[0] + n[0], records[1] + n[1]]
+        skipped = [skipped[0] + s[0], skipped[1] + s[1]]
+        if bad is not None and bad_record < 0:
+            bad_record, bad_code = fed + bad[0], bad[1]
+        fed += len(chunk.offsets)
+    return {"tally": words, "records": records, "skipped": skipped, "bad_record": bad_record, "bad_code": bad_code}
+
+
+def bam_to_fastq(chunks, max_len=MAX_LEN):
+    """(R1 text, R2 text): the taken, good records of the chunks as FASTQ, each read as sequenced -- mate 0 in the first text, mate
+    1 in the second.  fastq_tally_host of the two texts is the twin's tally in every field but ``insert``.  One record at a time, in
+    plain Python: what the words mean, written a second way."""
+    comp = bytes.maketrans(b"=ACMGRSVTWYHKDBN", bytes(SEQ_LETTERS[_COMPLEMENT]))
+    out = ([], [])
+    for chunk in _as_chunks(chunks):
+        if not len(chunk.offsets):
+            continue
+        data = bytes(chunk.data)
+        c = _classify(chunk, int(max_len))
+        for r in np.flatnonzero((c["code"] == 0) & (c["mate"] >= 0)):
+            o, n, seq, qual = int(chunk.offsets[r]), int(c["len"][r]), int(c["seq"][r]), int(c["qual"][r])
+            name = data[o + 36:seq].split(b"\0", 1)[0]
+            letters = "".join("=ACMGRSVTWYHKDBN"[(data[seq + k // 2] >> (0 if k & 1 else 4)) & 15] for k in range(n)).encode()
+            quals = bytes(x + 33 for x in data[qual:qual + n])
+            if c["reverse"][r]:
+                letters, quals = letters.translate(comp)[::-1], quals[::-1]
+            out[int(c["mate"][r])].append(b"@" + name + b"\n" + letters + b"\n+\n" + quals + b"\n")
+    return b"".join(out[0]), b"".join(out[1])
+
+
+def finish(raw, max_len):
+    """A download (or the twin's dict) as BamReadTally.result() returns it: fastq_report.finish's keys and ``skipped``."""
+    res = _finish(dict(raw, records=list(raw["records"]), bad_record=[raw["bad_record"]], bad_code=[raw["bad_code"]]), max_len)
+    res.update(bad_record=int(raw["bad_record"]), bad_code=int(raw["bad_code"]), skipped=list(raw["skipped"]))
+    return res
+
+
+class BamReadTally(object):
+    """Device tallies of the reads of BAM files (iss_br_*): feed chunks or files, download the result."""
+
+    def __init__(self, device=0, max_len=MAX_LEN):
+        self._lib = _native.lib()
+        if not hasattr(self._lib, "iss_br_feed"):
+            raise _native.NativeLibraryError("%s has no iss_br_* entries: rebuild it" % _native.LIB_PATH)
+        self.max_len = int(max_len)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = self._lib.iss_br_create(int(device), self.max_len, C.byref(self._h))
+        if rc < 0:
+            msg = self._lib.iss_br_last_error(self._h if self._h else None)
+            self.close()
+            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.iss_br_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self._lib.iss_br_last_error(self._h)
+            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
+        return rc
+
+    def reset(self):
+        self._check(self._lib.iss_br_reset(self._h))
+
+    def feed(self, chunk):
+        """One bam.Chunk of whole records; its arrays are free again when the call returns."""
+        data = np.ascontiguousarray(np.frombuffer(chunk.data, dtype=np.uint8))
+        offs = np.ascontiguousarray(chunk.offsets, dtype=np.int64)
+        self._check(self._lib.iss_br_feed(self._h, data.ctypes.data if data.size else None, data.size,
+                                          offs.ctypes.data if offs.size else None, offs.size))
+
+    def feed_file(self, path, inflater=None, chunk_bytes=64 << 20, threads=None):
+        """Every record of a BAM file; ``inflater``: an inflate.BgzfInflater for its BGZF blocks (None: the host pool)."""
+        for chunk in BamReader(path, chunk_bytes, threads, inflater).chunks():
+            self.feed(chunk)
+
+    def download(self):
+        """The twin's dict from the device: ``tally`` at max_len, ``records``, ``skipped``, ``bad_record``, ``bad_code``."""
+        words = np.zeros(fq_words(self.max_len), dtype=np.uint64)
+        assert self._lib.iss_br_tally_words(self._h) == words.size
+        rec, skip, bad, code = (C.c_int64 * 2)(), (C.c_int64 * 2)(), C.c_int64(), C.c_int32()
+        self._check(self._lib.iss_br_download(self._h, words.ctypes.data, C.addressof(rec), C.addressof(skip), C.byref(bad), C.byref(code)))
+        return {"tally": words, "records": list(rec), "skipped": list(skip), "bad_record": bad.value, "bad_code": code.value}
+
+    def kernel_ms(self):
+        """Milliseconds the kernels of all feeds since the last reset took on the device (waits for them)."""
+        ms = C.c_double()
+        self._check(self._lib.iss_br_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def result(self):
+        """``tally``: tally.py's flat words re-laid to L = the longest read seen (interchangeable with `generate --report`'s
+        _tally.npy), ``read_length`` L, ``lengths`` [2][L + 1], ``records`` [2], ``skipped`` [2], ``bad_record``, ``bad_code``."""
+        return finish(self.download(), self.max_len)
+
+
+__all__ = ["MAX_LEN", "REC_SHORT", "REC_TOO_LONG", "REC_NO_QUAL", "REC_QUAL_RANGE", "bam_reads_host", "bam_to_fastq", "finish",
+           "BamReadTally"]

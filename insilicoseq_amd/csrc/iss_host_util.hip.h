@@ -6,7 +6,7 @@
 namespace {
 
 // What takes an error: a context (NULL: only the thread's last error), or the `model` / `report` / inflate contexts (iss_api_bam.hip.h,
-// iss_api_fqtally.hip.h, iss_api_inflate.hip.h).
+// iss_api_fqtally.hip.h, iss_api_inflate.hip.h, iss_api_bamreads.hip.h).
 int fail(iss_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->last_error = msg;
     g_last_error = msg;
@@ -16,6 +16,7 @@ int fail(std::nullptr_t, int code, const std::string &msg) { return fail(static_
 int fail(iss_bam *b, int code, const std::string &msg);
 int fail(iss_fq *f, int code, const std::string &msg);
 int fail(iss_inflate *z, int code, const std::string &msg);
+int fail(iss_br *f, int code, const std::string &msg);
 
 // `owner`: whatever fail() takes
 #define HIP_TRY(owner, expr)                                                                     \

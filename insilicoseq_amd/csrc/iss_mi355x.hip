@@ -10,7 +10,7 @@
 // iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text),
 // iss_bgzf_text.hip.h (the VCF and origins text as BGZF members), iss_errtally.hip.h (integer tallies of the mutation rows: what
 // a run did to the reads), iss_fqtally.hip.h (`report`: the tallies of iss_tally.hip.h over FASTQ text), iss_inflate.hip.h (BGZF
-// members inflated: the decoder of iss_inflate_core.h on 64 lanes).
+// members inflated: the decoder of iss_inflate_core.h on 64 lanes), iss_bamreads.hip.h (`report --bam`: the same tallies over BAM records).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -52,6 +52,7 @@
 #include "iss_errtally.hip.h"   // k_errtally_rows, k_errtally_reads: tallies of the mutation rows (last, likewise)
 #include "iss_fqtally.hip.h"    // k_fq_*: `report`, the tallies of the rows over FASTQ text (last, likewise)
 #include "iss_inflate.hip.h"    // k_bgzf_inflate: BGZF members inflated on the device (last, likewise)
+#include "iss_bamreads.hip.h"   // k_br_*: `report --bam`, the tallies of k_fq_* over BAM records (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
@@ -79,3 +80,4 @@
 #include "iss_api_errtally.hip.h"
 #include "iss_api_fqtally.hip.h"
 #include "iss_api_inflate.hip.h"
+#include "iss_api_bamreads.hip.h"
