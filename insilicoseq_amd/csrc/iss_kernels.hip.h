@@ -352,7 +352,8 @@ __device__ __forceinline__ uint32_t mut_alloc(const RunArgs &A, MutChunk &c, uin
     c.used += n;
     return r + n <= A.mut_cap ? r : 0xffffffffu;
 }
-// all active lanes call this; lanes with `have` write their row
+// EVERY lane of the wavefront calls this, never from a branch some lanes skip: the chunk state is wave-uniform only as long as
+// all 64 lanes update it together (a lane left behind places later rows onto used slots); lanes with `have` write their row
 __device__ __forceinline__ void mut_emit(const RunArgs &A, MutChunk &c, bool have, const MutRecord &r) {
     const unsigned long long m = __ballot(have);
     if (!m) return;
@@ -1038,8 +1039,10 @@ __global__ __launch_bounds__(MAIN_THREADS, ISS_MAIN_OCC) void k_main(DevModel M,
             subst = main_slow_base<PLAIN, INDEL, STORE_MUT>(M, g, A, desc, lds, T, e_pair, 4u * e_it + (e_lane & 3u), (15 - bit) >> 3,
                                                              (15 - bit) & 7, (ent_x >> 8) & 15u, ent_y,
                                                              INDEL ? (ent_x >> (((15 - bit) & 7) >> 2)) & 1u : 0u, rec);
-            if (STORE_MUT) mut_emit(A, mchunk, subst == 3, rec);
         }
+        // (outside the branch: every lane of the wavefront keeps the chunk state -- a lane that sat a short round out would
+        //  place the rows of the next round from a stale `used`, onto slots that hold rows already)
+        if (STORE_MUT) mut_emit(A, mchunk, subst == 3, rec);
         q_head += n;
         const unsigned long long again = __ballot(rest_m != 0u);
         if (again) {
@@ -2397,33 +2400,38 @@ __global__ __launch_bounds__(64 * FIX_WAVES, 5) void k_indel_fixup(DevModel M, D
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // ---- phase 3
-        for (int j = lane; j < RL; j += 64) {
-            int tok = map[j];
-            if (tok == FIX_NONE) {  // governed by the last record with n0 <= j
-                int r = n_rec - 1;
-                while (rec_n0[r] > j) --r;
-                tok = rec_k0[r] + (j - rec_n0[r]);
+        for (int j0 = 0; j0 < RL; j0 += 64) {  // (every lane makes every trip: mut_emit's chunk state stays wave-uniform)
+            const int j = j0 + lane;
+            MutRecord sub = {};
+            bool have = false;
+            if (j < RL) {
+                int tok = map[j];
+                if (tok == FIX_NONE) {  // governed by the last record with n0 <= j
+                    int r = n_rec - 1;
+                    while (rec_n0[r] > j) --r;
+                    tok = rec_k0[r] + (j - rec_n0[r]);
+                }
+                int base = tok < 0 ? -tok : (tok < n_pre ? (int)tmpl[tok] : geom_base(gl, o, geo, tok));
+                const uint32_t e8 = dqm[j];
+                const int q = qual[j];
+                const uint32_t t8 = mut8[q];
+                bool err = e8 > t8;
+                const int before = base;
+                if (e8 >= t8) {
+                    const u32x4 sb = draw_block(a, K_SUB, (uint32_t)j, (uint32_t)o);
+                    if (e8 == t8) err = error_test_draw(e8, sb) > M.mut_thr[q];
+                    if (err) base = substitute(M, sb, o, j, base);
+                }
+                out_base[xp(j)] = (uint8_t)base;
+                if (A.mut) {  // only if the new letter differs from the ORIGINAL read at this index (__init__.py:98)
+                    sub.pair = (int32_t)(A.pair_base + pair); sub.mate = (int8_t)o; sub.type = (int8_t)32; sub.position = (int16_t)j;
+                    sub.ref = (uint8_t)before; sub.alt = (uint8_t)base; sub.quality = (int16_t)q;
+                    // (a read position past a template the genome end cut short has no "original" letter: the reference raises
+                    //  IndexError there; the row is kept)
+                    have = err && base_index(before) >= 0 && (j >= geo.t_len || base != (int)tmpl[j]);
+                }
             }
-            int base = tok < 0 ? -tok : (tok < n_pre ? (int)tmpl[tok] : geom_base(gl, o, geo, tok));
-            const uint32_t e8 = dqm[j];
-            const int q = qual[j];
-            const uint32_t t8 = mut8[q];
-            bool err = e8 > t8;
-            const int before = base;
-            if (e8 >= t8) {
-                const u32x4 sb = draw_block(a, K_SUB, (uint32_t)j, (uint32_t)o);
-                if (e8 == t8) err = error_test_draw(e8, sb) > M.mut_thr[q];
-                if (err) base = substitute(M, sb, o, j, base);
-            }
-            out_base[xp(j)] = (uint8_t)base;
-            if (A.mut) {  // only if the new letter differs from the ORIGINAL read at this index (__init__.py:98)
-                MutRecord sub;
-                sub.pair = (int32_t)(A.pair_base + pair); sub.mate = (int8_t)o; sub.type = (int8_t)32; sub.position = (int16_t)j;
-                sub.ref = (uint8_t)before; sub.alt = (uint8_t)base; sub.quality = (int16_t)q;
-                // (a read position past a template the genome end cut short has no "original" letter: the reference raises
-                //  IndexError there; the row is kept)
-                mut_emit(A, mchunk, err && base_index(before) >= 0 && (j >= geo.t_len || base != (int)tmpl[j]), sub);
-            }
+            if (A.mut) mut_emit(A, mchunk, have, sub);
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
