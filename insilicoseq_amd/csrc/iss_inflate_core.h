@@ -317,11 +317,16 @@ ISS_INF_HD int inflate_member(const uint8_t *pay, uint32_t pay_len, uint8_t *out
             if (nl_codes > 286 || nd_codes > 30) return ST_BAD_CODE;
             for (int i = lane; i < 19; i += nl) W.cl_lens[i] = 0;
             sync();
+            uint32_t any = 0;
             for (int i = 0; i < (int)hclen + 4; ++i) {
                 if (!take(b, 3, &v)) return ST_IN_OVERRUN;
+                any |= v;
                 if (lane == 0) W.cl_lens[cl_order(i)] = (uint8_t)v;
             }
             sync();
+            // A code-length code without a code: zlib reads every length as 0 from one bit each and then misses the end-of-block
+            // code -- or runs out of input before it has read them all.
+            if (!any) return (uint64_t)b.bc + 8ull * (b.len - b.ip) >= (uint64_t)(nl_codes + nd_codes) ? ST_BAD_CODE : ST_IN_OVERRUN;
             if (int st = build_code(W.cl_lens, 19, W.cnt_d, W.sym_d, W.fast_d, FAST_C, KIND_CODES, W.offs, lane, nl, sync)) return st;
             const int total = nl_codes + nd_codes;
             int idx = 0;

@@ -193,8 +193,12 @@ def play(tokens, before=b""):
         if t[0] == "lit":
             out.append(t[1])
         elif t[0] == "match":
-            for _ in range(t[1]):
-                out.append(out[-t[2]])
+            n, start = t[1], len(out) - t[2]
+            assert start >= 0, t
+            if t[2] >= n:
+                out += out[start:start + n]
+            else:  # the period t[2] repeats
+                out += (bytes(out[start:]) * (n // t[2] + 1))[:n]
     return bytes(out[len(before):])
 
 
@@ -449,6 +453,14 @@ def _bad():
     stored_block(w, bytes(flipped))
     add("data_bit_flipped", CRC, w.done(), text)
     add("trailing_bytes", TRAILING, dyn + b"\0\0", text)
+
+    # A code-length code without a code (every HCLEN length 0).  zlib reads each of the HLIT + HDIST lengths as 0 from one bit: the
+    # stream misses its end-of-block code if it holds those 258 bits and runs out of input if it does not (found by
+    # tests/inflate_gen.py's damaged streams: the decoder said BAD_CODE for both).
+    w = BitWriter()
+    dynamic_header(w, 257, 1, [], cl_lens=[0] * 19, hclen=4)
+    add("no_code_length_code", BAD_CODE, w.done() + b"\0" * 33)
+    add("no_code_length_code_input_ends", IN_OVERRUN, w.done() + b"\0\0")
     return cases
 
 

@@ -3,59 +3,13 @@ stand-alone program, inflate_core_main.cpp, built with the system compiler under
 run on the case table: every case's payload and output buffers are allocated at their exact sizes, so a read behind the payload or
 a write outside [0, ISIZE) ends the program with the sanitizer's report.  Status, CRC and bytes are compared with the table."""
 import os
-import shutil
-import struct
-import subprocess
 import sys
 import zlib
 
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "insilicoseq_amd", "csrc")
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import inflate_cases as IC  # noqa: E402
-
-
-def _has_gpu():
-    try:
-        import torch
-
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        if _has_gpu():
-            pytest.skip("no g++ on the GPU machine")
-        pytest.fail("g++ not found: the decoder's host test needs the system compiler")
-    exe = str(tmp_path_factory.mktemp("inflate_core") / "inflate_core")
-    build = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                            "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", CSRC, "-o", exe,
-                            os.path.join(HERE, "inflate_core_main.cpp")], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-    return exe
-
-
-def run_cases(exe, cases, tmp_path):
-    """[(status, crc)] per case and the bytes of the cases that ended OK or TRAILING."""
-    path, out = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<I", len(cases)))
-        for c in cases:
-            pay, crc, isize = IC.split_member(c["member"])
-            fh.write(struct.pack("<III", len(pay), isize, crc) + pay)
-    run = subprocess.run([exe, path, out], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-6000:]
-    rows = [line.split() for line in run.stdout.splitlines()]
-    assert [int(r[0]) for r in rows] == list(range(len(cases)))
-    with open(out, "rb") as fh:
-        return [(int(r[1]), int(r[2], 16)) for r in rows], fh.read()
+from inflate_twin import program, run_cases  # noqa: E402,F401  (the recipe, shared with test_inflate_gen_host.py)
 
 
 def test_good_cases_inflate_to_their_bytes(program, tmp_path):
