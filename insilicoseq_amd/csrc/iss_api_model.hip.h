@@ -25,6 +25,10 @@ int iss_model_upload(iss_ctx *ctx, const iss_model_tables *t) {
         return fail(ctx, ISS_E_INVALID, "threshold above 2^53");
     for (int i = 1; i < t->n_isize; ++i)
         if (t->isize_thr[i] < t->isize_thr[i - 1]) return fail(ctx, ISS_E_INVALID, "insert-size thresholds not monotone");
+    // (a bin CDF that ends below 1.0 sends the rest of the draws to bin 3 -- k_setup's clamp, kde.py:77-78 -- which then needs rows)
+    for (int o = 0; o < 2; ++o)
+        if (!t->bin_nonempty[o * 4 + 3] && t->bin_thr[o * 4 + 3] < two53)
+            return fail(ctx, ISS_E_INVALID, "mean-quality bin thresholds end below 2^53 and the last bin has no histograms");
     for (int o = 0; o < 2; ++o)
         for (int b = 0; b < 4; ++b) {
             if (!t->bin_nonempty[o * 4 + b]) {

@@ -155,6 +155,10 @@ class DenseModel(object):
             prob = np.diff(np.concatenate(([0.0], self.bin_cdf[o])))
             if ((prob > 0) & (self.bin_nonempty[o] == 0)).any():
                 raise ModelError("a mean-quality bin with non-zero probability has no histograms")
+            # a bin CDF that ends below 1.0 sends the rest of the draws to bin 3 (the clamp of kde.py:77-78): with bin 3 empty
+            # they would read histograms that do not exist (np.random.choice refuses such probabilities, so does this)
+            if not self.bin_nonempty[o, N_BINS - 1] and not self.bin_cdf[o, N_BINS - 1] >= 1.0:
+                raise ModelError("mean-quality bin CDF ends below 1.0 and the last bin has no histograms")
 
     # ------------------------------------------------- reference schema -> dense
     @classmethod
