@@ -43,6 +43,10 @@ EXPORTS = (
     "iss_br_kernel_ms",
 )
 
+# The stand-alone device contexts (class Session below): entry prefix -> the arguments of its create call between the device ordinal
+# and the handle.  Each has create, destroy, last_error and reset; kernel_ms and tally_words where EXPORTS names them.
+SESSIONS = {"iss_bam": (), "iss_fq": (C.c_int32,), "iss_inflate": (), "iss_br": (C.c_int32,)}
+
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
 BAM_MAX_LEN, BAM_NQ, BAM_NTLEN = 301, 94, 2000
 BAM_OFF_INDEL, BAM_OFF_QHIST, BAM_OFF_TLEN, BAM_OFF_NREAD, BAM_OFF_MINLEN, BAM_OFF_TAKEN, BAM_TALLY_WORDS = (
@@ -205,43 +209,19 @@ def lib():
     if hasattr(L, "iss_mutations_tally"):
         L.iss_error_tally_words.argtypes = [vp]
         L.iss_mutations_tally.argtypes = [vp, i32, i64, i64, vp]
-    # (and `report`, the tallies over FASTQ text; without them fastq_report.FastqTally raises)
+    # (and `report`, `report --bam` and the device inflate: their own entries here, what every session has in the loop over
+    #  SESSIONS below; without them FastqTally, BamReadTally and BgzfInflater raise)
     if hasattr(L, "iss_fq_feed"):
-        L.iss_fq_create.argtypes = [C.c_int, i32, C.POINTER(vp)]
-        L.iss_fq_destroy.argtypes = [vp]
-        L.iss_fq_destroy.restype = None
-        L.iss_fq_last_error.argtypes = [vp]
-        L.iss_fq_last_error.restype = C.c_char_p
-        L.iss_fq_reset.argtypes = [vp]
-        L.iss_fq_tally_words.argtypes = [vp]
         L.iss_fq_feed.argtypes = [vp, i32, vp, i64]
         L.iss_fq_download.argtypes = [vp, vp, vp, vp, vp]
-        L.iss_fq_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
-    # (and `report --bam`, the same tallies over BAM records; without them bam_report.BamReadTally raises)
     if hasattr(L, "iss_br_feed"):
-        L.iss_br_create.argtypes = [C.c_int, i32, C.POINTER(vp)]
-        L.iss_br_destroy.argtypes = [vp]
-        L.iss_br_destroy.restype = None
-        L.iss_br_last_error.argtypes = [vp]
-        L.iss_br_last_error.restype = C.c_char_p
-        L.iss_br_reset.argtypes = [vp]
-        L.iss_br_tally_words.argtypes = [vp]
         L.iss_br_feed.argtypes = [vp, vp, i64, vp, i64]
         L.iss_br_download.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
-        L.iss_br_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
-    # (and the device inflate; without them inflate.BgzfInflater raises)
     if hasattr(L, "iss_inflate_feed"):
         L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-        L.iss_inflate_create.argtypes = [C.c_int, C.POINTER(vp)]
-        L.iss_inflate_destroy.argtypes = [vp]
-        L.iss_inflate_destroy.restype = None
-        L.iss_inflate_last_error.argtypes = [vp]
-        L.iss_inflate_last_error.restype = C.c_char_p
-        L.iss_inflate_reset.argtypes = [vp]
         L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]
         L.iss_inflate_collect.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64)]
         L.iss_inflate_first_bad.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
-        L.iss_inflate_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -254,38 +234,41 @@ def lib():
     L.iss_ev_step.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp]
     L.iss_fastq_write.argtypes = [C.c_int, C.c_int, C.c_char_p, i64, i32, i64, i32, i32, vp, vp, vp, vp, i32]
     L.iss_bam_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.iss_bam_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.iss_bam_destroy.argtypes = [vp]
-    L.iss_bam_destroy.restype = None
-    L.iss_bam_last_error.argtypes = [vp]
-    L.iss_bam_last_error.restype = C.c_char_p
-    L.iss_bam_reset.argtypes = [vp]
     L.iss_bam_feed.argtypes = [vp, vp, i64, vp, vp, i64]
     L.iss_bam_tally_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
     L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
+    session_entries = tuple(prefix + "_" for prefix in SESSIONS)
     for name in EXPORTS:
-        if name in ("iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
-                    "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
-                    "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
-                    "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
-                    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
-                    "iss_mutations_tally", "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words",
-                    "iss_fq_feed", "iss_fq_download", "iss_fq_kernel_ms", "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy",
-                    "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed", "iss_inflate_collect", "iss_inflate_first_bad",
-                    "iss_inflate_kernel_ms", "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words",
-                    "iss_br_feed", "iss_br_download", "iss_br_kernel_ms") and not hasattr(L, name):
+        if (name.startswith(session_entries) or name in (
+                "iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
+                "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
+                "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
+                "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
+                "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
+                "iss_mutations_tally", "iss_bgzf_scan")) and not hasattr(L, name):
             continue
-        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_bam_destroy", "iss_bam_last_error", "iss_fq_destroy",
-                        "iss_fq_last_error", "iss_inflate_destroy", "iss_inflate_last_error", "iss_br_destroy", "iss_br_last_error"):
+        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64
     if hasattr(L, "iss_error_tally_words"):
         L.iss_error_tally_words.restype = i64
-    if hasattr(L, "iss_fq_tally_words"):
-        L.iss_fq_tally_words.restype = i64
-    if hasattr(L, "iss_br_tally_words"):
-        L.iss_br_tally_words.restype = i64
+    # what every session has (a library from before a prefix still loads, and that prefix's Session raises); the entries whose
+    # restype is not int are set here, behind the loop above
+    for prefix, create_args in SESSIONS.items():
+        if not hasattr(L, prefix + "_create"):
+            continue
+        getattr(L, prefix + "_create").argtypes = [C.c_int] + list(create_args) + [C.POINTER(vp)]
+        getattr(L, prefix + "_destroy").argtypes = [vp]
+        getattr(L, prefix + "_destroy").restype = None
+        getattr(L, prefix + "_last_error").argtypes = [vp]
+        getattr(L, prefix + "_last_error").restype = C.c_char_p
+        getattr(L, prefix + "_reset").argtypes = [vp]
+        if prefix + "_kernel_ms" in EXPORTS:
+            getattr(L, prefix + "_kernel_ms").argtypes = [vp, C.POINTER(C.c_double)]
+        if prefix + "_tally_words" in EXPORTS:
+            getattr(L, prefix + "_tally_words").argtypes = [vp]
+            getattr(L, prefix + "_tally_words").restype = i64
     _lib = L
     return L
 
@@ -295,3 +278,57 @@ def check(ctx, rc):
         msg = lib().iss_last_error(ctx)
         raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
     return rc
+
+
+class Session(object):
+    """A stand-alone device context of the library, one of SESSIONS: the handle, its errors and its life.  A subclass names its
+    entry prefix and hands __init__ the arguments of its create call; ``_entry("feed")`` is the library's ``<prefix>_feed``."""
+
+    PREFIX = None
+
+    def __init__(self, device=0, *create_args):
+        self._lib = lib()
+        if not hasattr(self._lib, self.PREFIX + "_create"):
+            raise NativeLibraryError("%s has no %s_* entries: rebuild it" % (LIB_PATH, self.PREFIX))
+        self.device = int(device)
+        self._h = C.c_void_p()
+        try:  # (a create that fails may leave a handle: its error is read from it, then it goes)
+            self._check(self._entry("create")(self.device, *create_args, C.byref(self._h)))
+        except EngineError:
+            self.close()
+            raise
+
+    def _entry(self, name):
+        return getattr(self._lib, "%s_%s" % (self.PREFIX, name))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._entry("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self._entry("last_error")(self._h if self._h else None)
+            raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
+        return rc
+
+    def reset(self):
+        self._check(self._entry("reset")(self._h))
+
+    def kernel_ms(self):
+        """Milliseconds the kernels of all feeds since the last reset took on the device (waits for them)."""
+        ms = C.c_double()
+        self._check(self._entry("kernel_ms")(self._h, C.byref(ms)))
+        return ms.value

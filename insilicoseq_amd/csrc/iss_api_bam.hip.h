@@ -1,35 +1,33 @@
 // iss_api_bam.hip.h -- C ABI of `model` (iss model, iss/bam.py:103-227): record boundaries of inflated BAM bytes (host), the tally
 // context (device tallies over fed chunks, their download) and the kernel density estimates from the tallies.  Device code: iss_bam.hip.h.
+// The context is a session (iss_host_session.hip.h: open and close, grown buffers, the first-bad word); its feed is synchronous, no slots.
 #pragma once
 
-struct iss_bam {
-    int device = 0;
+namespace {
+struct BamRecords {  // per record of a chunk (a group for reserve()); each array is at least 1 MiB, as the chunk's bytes are
+    DevMem<uint32_t> d_offs;
+    DevMem<uint8_t> d_sel;
+    DevMem<uint2> d_meta;
+    size_t cap = 0;
+    int alloc(iss_session *b, size_t n, const char *) {
+        DEV_ALLOC(b, d_offs, std::max(n, ((size_t)1 << 20) / sizeof(uint32_t)));
+        DEV_ALLOC(b, d_sel, std::max(n, (size_t)1 << 20));
+        DEV_ALLOC(b, d_meta, std::max(n, ((size_t)1 << 20) / sizeof(uint2)));
+        return 0;
+    }
+};
+}  // namespace
+
+struct iss_bam : iss_session {
     Stream stream;
-    std::string last_error;
-    struct Data {  // a chunk's bytes
-        DevMem<uint8_t> d;
-        size_t cap = 0;
-    } data;
-    struct Records {  // per record of a chunk
-        DevMem<uint32_t> d_offs;
-        DevMem<uint8_t> d_sel;
-        DevMem<uint2> d_meta;
-        size_t cap = 0;
-    } rec;
+    Grown<DevMem<uint8_t>> data;  // a chunk's bytes
+    BamRecords rec;
     DevMem<unsigned long long> d_tally;  // TALLY_WORDS, then the error word
     DevMem<double> d_qcdf, d_isize;
     int64_t fed = 0;
     int n_cu = 256;
     std::vector<uint32_t> h_offs;
 };
-
-namespace {
-int fail(iss_bam *b, int code, const std::string &msg) {
-    if (b) b->last_error = msg;
-    else g_last_error = msg;
-    return code;
-}
-}  // namespace
 
 static_assert(iss::bam::TALLY_WORDS == ISS_BAM_TALLY_WORDS, "include/iss_mi355x.h: ISS_BAM_TALLY_WORDS");
 static_assert(iss::bam::OFF_QHIST == ISS_BAM_OFF_QHIST && iss::bam::OFF_TLEN == ISS_BAM_OFF_TLEN && iss::bam::OFF_NREAD == ISS_BAM_OFF_NREAD,
@@ -62,14 +60,8 @@ int iss_bam_scan(const uint8_t *data, int64_t n_bytes, int64_t *offsets, int64_t
 int iss_bam_create(int device_ordinal, iss_bam **out) {
     if (!out) return fail(nullptr, ISS_E_INVALID, "iss_bam_create: out is NULL");
     *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) return fail(nullptr, ISS_E_HIP, std::string("no HIP device available: ") + hipGetErrorString(e));
-    if (device_ordinal < 0 || device_ordinal >= n) return fail(nullptr, ISS_E_INVALID, "device ordinal out of range");
-    iss_bam *b = new iss_bam();
-    *out = b;
-    b->device = device_ordinal;
-    HIP_TRY(b, hipSetDevice(device_ordinal));
+    ISS_TRY(session_open(device_ordinal, out));
+    iss_bam *b = *out;
     hipDeviceProp_t prop;
     HIP_TRY(b, hipGetDeviceProperties(&prop, device_ordinal));
     b->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -86,12 +78,11 @@ int iss_bam_create(int device_ordinal, iss_bam **out) {
 
 void iss_bam_destroy(iss_bam *b) {
     if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    delete b;  // (its members release the buffers and the stream)
+    session_close(b, {b->stream});
+    delete b;
 }
 
-const char *iss_bam_last_error(const iss_bam *b) { return b ? b->last_error.c_str() : g_last_error.c_str(); }
+const char *iss_bam_last_error(const iss_bam *b) { return session_last_error(b); }
 
 int iss_bam_reset(iss_bam *b) {
     if (!b) return fail(nullptr, ISS_E_INVALID, "iss_bam_reset: NULL");
@@ -122,35 +113,22 @@ int iss_bam_feed(iss_bam *b, const uint8_t *data, int64_t n_bytes, const int64_t
         if (bs < 32 || o + 4 + (int64_t)bs > n_bytes) return fail(b, ISS_E_INVALID, "iss_bam_feed: record outside the chunk");
         b->h_offs[(size_t)r] = (uint32_t)o;
     }
-    // (each array is at least 1 MiB, as the chunk's bytes are; the stream is idle between feeds, the wait costs nothing)
-    if ((size_t)n_records > b->rec.cap) {
-        const size_t n = std::max((size_t)n_records, (size_t)1 << 16);
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        b->rec = {};
-        DEV_ALLOC(b, b->rec.d_offs, std::max(n, ((size_t)1 << 20) / sizeof(uint32_t)));
-        DEV_ALLOC(b, b->rec.d_sel, std::max(n, (size_t)1 << 20));
-        DEV_ALLOC(b, b->rec.d_meta, std::max(n, ((size_t)1 << 20) / sizeof(uint2)));
-        b->rec.cap = n;
-    }
-    if ((size_t)n_bytes > b->data.cap) {
-        const size_t n = std::max((size_t)n_bytes, (size_t)1 << 20);
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        b->data = {};
-        DEV_ALLOC(b, b->data.d, n);
-        b->data.cap = n;
-    }
-    HIP_TRY(b, hipMemcpyAsync(b->data.d, data, (size_t)n_bytes, hipMemcpyHostToDevice, b->stream));
+    // (the stream is idle between feeds, the wait in front of a replacement costs nothing)
+    if ((size_t)n_records > b->rec.cap || (size_t)n_bytes > b->data.cap) HIP_TRY(b, hipStreamSynchronize(b->stream));
+    ISS_TRY(reserve(b, b->rec, (size_t)n_records, (size_t)1 << 16));
+    ISS_TRY(reserve(b, b->data, (size_t)n_bytes, (size_t)1 << 20, "chunk bytes"));
+    HIP_TRY(b, hipMemcpyAsync(b->data.p, data, (size_t)n_bytes, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(b, hipMemcpyAsync(b->rec.d_offs, b->h_offs.data(), (size_t)n_records * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(b, hipMemcpyAsync(b->rec.d_sel, select, (size_t)n_records, hipMemcpyHostToDevice, b->stream));
     const int64_t per_wg = iss::bam::TALLY_WAVES;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_records + per_wg - 1) / per_wg, 2LL * b->n_cu));
     const int64_t per_iter = (int64_t)grid * per_wg;
-    hipLaunchKernelGGL(iss::bam::k_bam_tally, dim3(grid), dim3(iss::bam::TALLY_THREADS), iss::bam::TALLY_LDS, b->stream, b->data.d, b->rec.d_offs,
+    hipLaunchKernelGGL(iss::bam::k_bam_tally, dim3(grid), dim3(iss::bam::TALLY_THREADS), iss::bam::TALLY_LDS, b->stream, b->data.p, b->rec.d_offs,
                        b->rec.d_sel, n_records, (n_records + per_iter - 1) / per_iter, b->fed, b->rec.d_meta, b->d_tally, b->d_tally + ISS_BAM_TALLY_WORDS);
     HIP_TRY(b, hipGetLastError());
     const unsigned qgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_records + per_wg - 1) / per_wg, (int64_t)b->n_cu / 4));
     hipLaunchKernelGGL(iss::bam::k_bam_qhist, dim3(qgrid, iss::bam::N_SLICE), dim3(iss::bam::TALLY_THREADS), iss::bam::QHIST_LDS, b->stream,
-                       b->data.d, b->rec.d_meta, n_records, b->d_tally);
+                       b->data.p, b->rec.d_meta, n_records, b->d_tally);
     HIP_TRY(b, hipGetLastError());
     // the host buffers may be reused as soon as the call returns
     HIP_TRY(b, hipStreamSynchronize(b->stream));
@@ -165,9 +143,7 @@ int iss_bam_tally_download(iss_bam *b, uint64_t *tally, int64_t *bad_record, int
     HIP_TRY(b, hipMemcpyAsync(h.data(), b->d_tally, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     memcpy(tally, h.data(), ISS_BAM_TALLY_WORDS * sizeof(uint64_t));
-    const unsigned long long e = h[ISS_BAM_TALLY_WORDS];
-    *bad_record = e == ~0ull ? -1 : (int64_t)(e >> 8);
-    *bad_code = e == ~0ull ? 0 : (int32_t)(e & 0xFF);
+    bad_word_split(h[ISS_BAM_TALLY_WORDS], bad_record, bad_code);
     return 0;
 }
 

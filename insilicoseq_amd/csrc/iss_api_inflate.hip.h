@@ -2,36 +2,25 @@
 // context that takes groups of whole BGZF members and hands their inflated bytes back.  A group goes through one of two pinned staging
 // buffers to the device on the copy-in stream, k_bgzf_inflate (iss_inflate.hip.h) follows on the kernel stream, and the bytes and the
 // members' statuses leave for a pinned result buffer on the copy-out stream, each step ordered behind the one before by an event: group
-// i + 1 copies in while group i inflates and group i - 1 copies out.  No model, no iss_ctx.
+// i + 1 copies in while group i inflates and group i - 1 copies out.  No model, no iss_ctx: a session (iss_host_session.hip.h: open
+// and close, the two timed slots -- here with a fourth event, `fetched`, that a feed waits for --, grown buffers, the first-bad word);
+// the pool of result buffers (results / flight / idle / held) is this file's own.
 #pragma once
 
-struct iss_inflate {
-    static constexpr int SLOTS = 2;
-    struct Slot {  // what a group holds on its way through the device
-        PinMem<uint8_t> h_in;
-        DevMem<uint8_t> d_in;
-        size_t in_cap = 0;
-        PinMem<uint32_t> h_meta;  // [5][meta_cap]: payload offset, payload length, output offset, ISIZE, CRC-32
-        DevMem<uint32_t> d_meta;
-        DevMem<uint8_t> d_status;
-        size_t meta_cap = 0;
-        DevMem<uint8_t> d_out;
-        size_t out_cap = 0;
-        Event copied;   // the group's bytes and arrays are on the device
-        Event begin;    // in front of the kernel,
-        Event done;     // and behind it (both timed: iss_inflate_kernel_ms)
+struct iss_inflate : iss_session {
+    struct Slot : TimedSlot {  // what a group holds on its way through the device
+        Staged<uint8_t> in;
+        Staged<uint32_t> meta;  // [5][cap / 5]: payload offset, payload length, output offset, ISIZE, CRC-32
+        Grown<DevMem<uint8_t>> status, out;
         Event fetched;  // the results have left the slot's device buffers
-        bool busy = false;
     };
     struct Result {  // a group's inflated bytes and statuses on the host
-        PinMem<uint8_t> h_out, h_status;
-        size_t out_cap = 0, status_cap = 0;
+        Grown<PinMem<uint8_t>> out, status;
         Event ready;
         int64_t n_bytes = 0, n_members = 0;
     };
-    int device = 0, n_cu = 256;
+    int n_cu = 256;
     Stream copy_in, stream, copy_out;
-    std::string last_error;
     Slot slot[SLOTS];
     std::vector<std::unique_ptr<Result>> results;  // all of them; the three lists below are views
     std::deque<Result *> flight;                   // fed, not collected: the oldest first
@@ -42,25 +31,6 @@ struct iss_inflate {
     int64_t feeds = 0, fed_members = 0;
     double kernel_ms = 0.0;  // of the groups whose slot has been waited for
 };
-
-namespace {
-int fail(iss_inflate *z, int code, const std::string &msg) {
-    if (z) z->last_error = msg;
-    else g_last_error = msg;
-    return code;
-}
-
-// waits until the group that went through the slot has left it and books its kernel's time
-int inflate_settle(iss_inflate *z, iss_inflate::Slot &s) {
-    if (!s.busy) return 0;
-    HIP_TRY(z, hipEventSynchronize(s.fetched));
-    float ms = 0.f;
-    HIP_TRY(z, hipEventElapsedTime(&ms, s.begin, s.done));
-    z->kernel_ms += ms;
-    s.busy = false;
-    return 0;
-}
-}  // namespace
 
 static_assert(iss_inf::ST_OK == ISS_BGZF_OK && iss_inf::ST_BAD_BTYPE == ISS_BGZF_BAD_BTYPE && iss_inf::ST_STORED_LEN == ISS_BGZF_STORED_LEN &&
                   iss_inf::ST_BAD_CODE == ISS_BGZF_BAD_CODE && iss_inf::ST_BAD_SYMBOL == ISS_BGZF_BAD_SYMBOL &&
@@ -116,17 +86,10 @@ int iss_bgzf_scan(const uint8_t *data, int64_t n_bytes, int64_t *member_off, int
 }
 
 int iss_inflate_create(int device_ordinal, iss_inflate **out) {
-    if (!out) return fail(static_cast<iss_inflate *>(nullptr), ISS_E_INVALID, "iss_inflate_create: out is NULL");
+    if (!out) return fail(nullptr, ISS_E_INVALID, "iss_inflate_create: out is NULL");
     *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(static_cast<iss_inflate *>(nullptr), ISS_E_HIP, std::string("no HIP device available: ") + hipGetErrorString(e));
-    if (device_ordinal < 0 || device_ordinal >= n) return fail(static_cast<iss_inflate *>(nullptr), ISS_E_INVALID, "device ordinal out of range");
-    iss_inflate *z = new iss_inflate();
-    *out = z;
-    z->device = device_ordinal;
-    HIP_TRY(z, hipSetDevice(device_ordinal));
+    ISS_TRY(session_open(device_ordinal, out));
+    iss_inflate *z = *out;
     hipDeviceProp_t prop;
     HIP_TRY(z, hipGetDeviceProperties(&prop, device_ordinal));
     z->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -136,9 +99,7 @@ int iss_inflate_create(int device_ordinal, iss_inflate **out) {
     ISS_TRY(stream_create(z, z->stream, hipStreamNonBlocking));
     ISS_TRY(stream_create(z, z->copy_out, hipStreamNonBlocking));
     for (iss_inflate::Slot &s : z->slot) {
-        ISS_TRY(event_create(z, s.copied, hipEventDisableTiming));
-        ISS_TRY(event_create(z, s.begin, hipEventDefault));
-        ISS_TRY(event_create(z, s.done, hipEventDefault));
+        ISS_TRY(slot_create(z, s));
         ISS_TRY(event_create(z, s.fetched, hipEventDisableTiming));
     }
     std::vector<uint32_t> tab(256), ops((size_t)iss_inf::N_OPS * 32);
@@ -151,14 +112,11 @@ int iss_inflate_create(int device_ordinal, iss_inflate **out) {
 
 void iss_inflate_destroy(iss_inflate *z) {
     if (!z) return;
-    (void)hipSetDevice(z->device);
-    if (z->copy_in) (void)hipStreamSynchronize(z->copy_in);
-    if (z->stream) (void)hipStreamSynchronize(z->stream);
-    if (z->copy_out) (void)hipStreamSynchronize(z->copy_out);
-    delete z;  // (its members release the buffers, events and streams)
+    session_close(z, {z->copy_in, z->stream, z->copy_out});
+    delete z;
 }
 
-const char *iss_inflate_last_error(const iss_inflate *z) { return z ? z->last_error.c_str() : g_last_error.c_str(); }
+const char *iss_inflate_last_error(const iss_inflate *z) { return session_last_error(z); }
 
 int iss_inflate_reset(iss_inflate *z) {
     if (!z) return fail(z, ISS_E_INVALID, "iss_inflate_reset: NULL");
@@ -197,35 +155,14 @@ int iss_inflate_feed(iss_inflate *z, const uint8_t *data, int64_t n_bytes, const
         if (total_out >= ((int64_t)1 << 31)) return fail(z, ISS_E_INVALID, "iss_inflate_feed: a group inflates to less than 2^31 bytes");
     }
     HIP_TRY(z, hipSetDevice(z->device));
-    iss_inflate::Slot &s = z->slot[z->feeds % iss_inflate::SLOTS];
-    ISS_TRY(inflate_settle(z, s));  // the one wait of a feed: for the device to have finished with the slot, never for a collect
-    if ((size_t)n_bytes > s.in_cap) {
-        const size_t cap = std::max((size_t)n_bytes, (size_t)1 << 20);
-        s.h_in.reset();
-        s.d_in.reset();
-        s.in_cap = 0;
-        PIN_ALLOC(z, s.h_in, cap);
-        DEV_ALLOC(z, s.d_in, cap);
-        s.in_cap = cap;
-    }
-    if ((size_t)n_members > s.meta_cap) {
-        const size_t cap = std::max((size_t)n_members, (size_t)1 << 12);
-        s.h_meta.reset();
-        s.d_meta.reset();
-        s.d_status.reset();
-        s.meta_cap = 0;
-        PIN_ALLOC(z, s.h_meta, 5 * cap);
-        DEV_ALLOC(z, s.d_meta, 5 * cap);
-        DEV_ALLOC(z, s.d_status, cap);
-        s.meta_cap = cap;
-    }
-    if ((size_t)total_out + 1 > s.out_cap) {
-        const size_t cap = std::max((size_t)total_out + 1, (size_t)1 << 20);
-        s.d_out.reset();
-        s.out_cap = 0;
-        DEV_ALLOC(z, s.d_out, cap);
-        s.out_cap = cap;
-    }
+    iss_inflate::Slot &s = z->slot[z->feeds % SLOTS];
+    // the one wait of a feed: for the group that went through the slot to have left it, never for a collect
+    ISS_TRY(slot_collect(z, s, s.fetched, z->kernel_ms));
+    const size_t nm = (size_t)n_members;
+    ISS_TRY(reserve(z, s.in, (size_t)n_bytes, (size_t)1 << 20, "slot input"));
+    ISS_TRY(reserve(z, s.meta, 5 * nm, (size_t)5 << 12, "slot member arrays"));
+    ISS_TRY(reserve(z, s.status, nm, (size_t)1 << 12, "slot statuses"));
+    ISS_TRY(reserve(z, s.out, (size_t)total_out + 1, (size_t)1 << 20, "slot output"));
     iss_inflate::Result *r = nullptr;
     if (!z->idle.empty()) {
         r = z->idle.back();
@@ -239,23 +176,10 @@ int iss_inflate_feed(iss_inflate *z, const uint8_t *data, int64_t n_bytes, const
         }
     }
     z->idle.push_back(r);  // (until it is queued: a failure below leaves it idle)
-    if ((size_t)total_out + 1 > r->out_cap) {
-        const size_t cap = std::max((size_t)total_out + 1, (size_t)1 << 20);
-        r->h_out.reset();
-        r->out_cap = 0;
-        PIN_ALLOC(z, r->h_out, cap);
-        r->out_cap = cap;
-    }
-    if ((size_t)n_members > r->status_cap) {
-        const size_t cap = std::max((size_t)n_members, (size_t)1 << 12);
-        r->h_status.reset();
-        r->status_cap = 0;
-        PIN_ALLOC(z, r->h_status, cap);
-        r->status_cap = cap;
-    }
-    memcpy(s.h_in, data, (size_t)n_bytes);  // (the caller's memory is free again when the call returns)
-    uint32_t *meta = s.h_meta;
-    const size_t nm = (size_t)n_members;
+    ISS_TRY(reserve(z, r->out, (size_t)total_out + 1, (size_t)1 << 20, "result bytes"));
+    ISS_TRY(reserve(z, r->status, nm, (size_t)1 << 12, "result statuses"));
+    memcpy(s.in.h, data, (size_t)n_bytes);  // (the caller's memory is free again when the call returns)
+    uint32_t *meta = s.meta.h;
     uint32_t off = 0;
     for (size_t m = 0; m < nm; ++m) {
         meta[m] = (uint32_t)pay_off[m];
@@ -265,20 +189,20 @@ int iss_inflate_feed(iss_inflate *z, const uint8_t *data, int64_t n_bytes, const
         meta[4 * nm + m] = crc[m];
         off += isize[m];
     }
-    HIP_TRY(z, hipMemcpyAsync(s.d_in, s.h_in, (size_t)n_bytes, hipMemcpyHostToDevice, z->copy_in));
-    HIP_TRY(z, hipMemcpyAsync(s.d_meta, s.h_meta, 5 * nm * sizeof(uint32_t), hipMemcpyHostToDevice, z->copy_in));
+    HIP_TRY(z, hipMemcpyAsync(s.in.d, s.in.h, (size_t)n_bytes, hipMemcpyHostToDevice, z->copy_in));
+    HIP_TRY(z, hipMemcpyAsync(s.meta.d, s.meta.h, 5 * nm * sizeof(uint32_t), hipMemcpyHostToDevice, z->copy_in));
     HIP_TRY(z, hipEventRecord(s.copied, z->copy_in));
     HIP_TRY(z, hipStreamWaitEvent(z->stream, s.copied, 0));
     HIP_TRY(z, hipEventRecord(s.begin, z->stream));
     iss::inf::InflateArgs A{};
-    A.in = s.d_in;
-    A.out = s.d_out;
-    A.pay_off = s.d_meta;
-    A.pay_len = s.d_meta + nm;
-    A.out_off = s.d_meta + 2 * nm;
-    A.isize = s.d_meta + 3 * nm;
-    A.crc = s.d_meta + 4 * nm;
-    A.status = s.d_status;
+    A.in = s.in.d;
+    A.out = s.out.p;
+    A.pay_off = s.meta.d;
+    A.pay_len = s.meta.d + nm;
+    A.out_off = s.meta.d + 2 * nm;
+    A.isize = s.meta.d + 3 * nm;
+    A.crc = s.meta.d + 4 * nm;
+    A.status = s.status.p;
     A.ops = z->d_ops;
     A.bad = z->d_bad;
     A.n_members = (uint32_t)n_members;
@@ -290,8 +214,8 @@ int iss_inflate_feed(iss_inflate *z, const uint8_t *data, int64_t n_bytes, const
     HIP_TRY(z, hipGetLastError());
     HIP_TRY(z, hipEventRecord(s.done, z->stream));
     HIP_TRY(z, hipStreamWaitEvent(z->copy_out, s.done, 0));
-    if (total_out) HIP_TRY(z, hipMemcpyAsync(r->h_out, s.d_out, (size_t)total_out, hipMemcpyDeviceToHost, z->copy_out));
-    HIP_TRY(z, hipMemcpyAsync(r->h_status, s.d_status, nm, hipMemcpyDeviceToHost, z->copy_out));
+    if (total_out) HIP_TRY(z, hipMemcpyAsync(r->out.p, s.out.p, (size_t)total_out, hipMemcpyDeviceToHost, z->copy_out));
+    HIP_TRY(z, hipMemcpyAsync(r->status.p, s.status.p, nm, hipMemcpyDeviceToHost, z->copy_out));
     HIP_TRY(z, hipEventRecord(r->ready, z->copy_out));
     HIP_TRY(z, hipEventRecord(s.fetched, z->copy_out));
     s.busy = true;
@@ -313,9 +237,9 @@ int iss_inflate_collect(iss_inflate *z, const uint8_t **data, int64_t *n_bytes, 
     z->flight.pop_front();
     if (z->held) z->idle.push_back(z->held);
     z->held = r;
-    *data = r->h_out;
+    *data = r->out.p;
     *n_bytes = r->n_bytes;
-    *status = r->h_status;
+    *status = r->status.p;
     *n_members = r->n_members;
     return 0;
 }
@@ -326,15 +250,14 @@ int iss_inflate_first_bad(iss_inflate *z, int64_t *member, int32_t *code) {
     unsigned long long e = 0;
     HIP_TRY(z, hipMemcpyAsync(&e, z->d_bad, sizeof e, hipMemcpyDeviceToHost, z->stream));  // (behind every kernel fed)
     HIP_TRY(z, hipStreamSynchronize(z->stream));
-    *member = e == ~0ull ? -1 : (int64_t)(e >> 8);
-    *code = e == ~0ull ? 0 : (int32_t)(e & 0xFF);
+    bad_word_split(e, member, code);
     return 0;
 }
 
 int iss_inflate_kernel_ms(iss_inflate *z, double *ms) {
     if (!z || !ms) return fail(z, ISS_E_INVALID, "iss_inflate_kernel_ms: bad arguments");
     HIP_TRY(z, hipSetDevice(z->device));
-    for (iss_inflate::Slot &s : z->slot) ISS_TRY(inflate_settle(z, s));
+    for (iss_inflate::Slot &s : z->slot) ISS_TRY(slot_collect(z, s, s.fetched, z->kernel_ms));
     *ms = z->kernel_ms;
     return 0;
 }

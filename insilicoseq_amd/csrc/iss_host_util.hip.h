@@ -1,22 +1,29 @@
-// iss_host_util.hip.h -- helpers every entry point uses: error reporting, checked allocations into owning handles, checked
-// uploads, the environment switches, what a model upload or a new reservation empties, the choice of the hot kernel's
-// instantiation (k_main / k_main_g), its LDS size, timing, synchronisation.
+// iss_host_util.hip.h -- helpers every entry point uses: error reporting (into a context, or into the session base of the stand-alone
+// device contexts), checked allocations into owning handles, checked uploads, the environment switches, what a model upload or a new
+// reservation empties, the choice of the hot kernel's instantiation (k_main / k_main_g), its LDS size, timing, synchronisation.
 #pragma once
+
+// What the stand-alone device contexts (iss_bam, iss_fq, iss_inflate, iss_br) have in common: each derives from it and stays a C type
+// of its own (include/iss_mi355x.h declares them opaque).  What works on it: iss_host_session.hip.h.
+struct iss_session {
+    int device = 0;
+    std::string last_error;
+};
 
 namespace {
 
-// What takes an error: a context (NULL: only the thread's last error), or the `model` / `report` / inflate contexts (iss_api_bam.hip.h,
-// iss_api_fqtally.hip.h, iss_api_inflate.hip.h, iss_api_bamreads.hip.h).
+// What takes an error: a context (NULL: only the thread's last error), or a session -- its own last error, or the thread's when there
+// is no session.
 int fail(iss_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->last_error = msg;
     g_last_error = msg;
     return code;
 }
 int fail(std::nullptr_t, int code, const std::string &msg) { return fail(static_cast<iss_ctx *>(nullptr), code, msg); }
-int fail(iss_bam *b, int code, const std::string &msg);
-int fail(iss_fq *f, int code, const std::string &msg);
-int fail(iss_inflate *z, int code, const std::string &msg);
-int fail(iss_br *f, int code, const std::string &msg);
+int fail(iss_session *s, int code, const std::string &msg) {
+    (s ? s->last_error : g_last_error) = msg;
+    return code;
+}
 
 // `owner`: whatever fail() takes
 #define HIP_TRY(owner, expr)                                                                     \

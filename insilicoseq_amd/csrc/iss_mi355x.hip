@@ -26,6 +26,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -58,6 +59,7 @@
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
 #include "iss_host_state.hip.h"       // the output pipes' records, struct iss_ctx
 #include "iss_host_util.hip.h"        // errors, checked allocations and uploads, switches, kernel choice, timing, synchronisation
+#include "iss_host_session.hip.h"     // shared by the stand-alone contexts (iss_bam, iss_fq, iss_inflate, iss_br): open and close, slots, grown buffers
 #include "iss_host_mt_streams.hip.h"  // MT19937 seeding and fill launches
 #include "iss_host_pipe.hip.h"        // shared by the output pipes: slot table, slot wait, the append pipe and its writer thread
 #include "iss_host_fastq_pipe.hip.h"  // the two FASTQ files' writer thread, flush

@@ -675,45 +675,12 @@ def fastq_write(fd_r1, fd_r2, record_id, first_i, cpu_number, n_pairs, read_leng
 __all__ = ["ReadEngine", "EngineError", "fastq_write"]
 
 
-class BamTally(object):
+class BamTally(_native.Session):
     """Device tallies of `model` (include/iss_mi355x.h, iss_bam_*): feed record chunks, download the integer tallies, evaluate the
     quality and insert-size KDE CDFs from them.  Replaces the per-read loop of iss/bam.py:125-170 and the scipy KDEs of
     iss/modeller.py:12-38, 99-134."""
 
-    def __init__(self, device=0):
-        self._lib = _native.lib()
-        self._h = C.c_void_p()
-        rc = self._lib.iss_bam_create(int(device), C.byref(self._h))
-        if rc < 0:
-            msg = self._lib.iss_bam_last_error(self._h if self._h else None)
-            self.close()
-            raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.iss_bam_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc):
-        if rc < 0:
-            msg = self._lib.iss_bam_last_error(self._h)
-            raise EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-        return rc
-
-    def reset(self):
-        self._check(self._lib.iss_bam_reset(self._h))
+    PREFIX = "iss_bam"
 
     def feed(self, data, offsets, select):
         """Tally the selected records of one chunk (data: uint8 record bytes, offsets: int64 block_size offsets, select: uint8)."""

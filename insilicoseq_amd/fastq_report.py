@@ -201,47 +201,14 @@ def open_fastq(path, device=None):
     return gzip.open(path, "rb")
 
 
-class FastqTally(object):
+class FastqTally(_native.Session):
     """Device tallies of FASTQ files (iss_fq_*): feed files, download the result."""
 
+    PREFIX = "iss_fq"
+
     def __init__(self, device=0, max_len=MAX_LEN):
-        self._lib = _native.lib()
-        if not hasattr(self._lib, "iss_fq_feed"):
-            raise _native.NativeLibraryError("%s has no iss_fq_* entries: rebuild it" % _native.LIB_PATH)
         self.max_len = int(max_len)
-        self.device = int(device)
-        self._h = C.c_void_p()
-        rc = self._lib.iss_fq_create(int(device), self.max_len, C.byref(self._h))
-        if rc < 0:
-            msg = self._lib.iss_fq_last_error(self._h if self._h else None)
-            self.close()
-            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.iss_fq_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc):
-        if rc < 0:
-            msg = self._lib.iss_fq_last_error(self._h)
-            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-        return rc
-
-    def reset(self):
-        self._check(self._lib.iss_fq_reset(self._h))
+        _native.Session.__init__(self, device, self.max_len)
 
     def feed(self, text, mate):
         """One chunk of whole records (bytes, or any buffer) of mate 0 or 1; the bytes are free again when the call returns."""
@@ -260,12 +227,6 @@ class FastqTally(object):
         rec, bad, code = (C.c_int64 * 2)(), (C.c_int64 * 2)(), (C.c_int32 * 2)()
         self._check(self._lib.iss_fq_download(self._h, words.ctypes.data, C.addressof(rec), C.addressof(bad), C.addressof(code)))
         return {"tally": words, "records": list(rec), "bad_record": list(bad), "bad_code": list(code)}
-
-    def kernel_ms(self):
-        """Milliseconds the kernels of all feeds since the last reset took on the device (waits for them)."""
-        ms = C.c_double()
-        self._check(self._lib.iss_fq_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
 
     def result(self):
         """``tally``: tally.py's flat words re-laid to L = the longest read seen (interchangeable with `generate --report`'s

@@ -63,48 +63,18 @@ def is_bgzf(path):
     return False
 
 
-class BgzfInflater(object):
+class BgzfInflater(_native.Session):
     """The device context (iss_inflate_*): feed groups of whole members, collect their inflated bytes in feed order."""
 
+    PREFIX = "iss_inflate"
+
     def __init__(self, device=0):
-        self._lib = _native.lib()
-        if not hasattr(self._lib, "iss_inflate_feed"):
-            raise _native.NativeLibraryError("%s has no iss_inflate_* entries: rebuild it" % _native.LIB_PATH)
-        self.device = int(device)
         self.in_flight = 0
-        self._h = C.c_void_p()
-        rc = self._lib.iss_inflate_create(self.device, C.byref(self._h))
-        if rc < 0:
-            msg = self._lib.iss_inflate_last_error(self._h if self._h else None)
-            self.close()
-            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.iss_inflate_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc):
-        if rc < 0:
-            msg = self._lib.iss_inflate_last_error(self._h)
-            raise _native.EngineError(rc, msg.decode("utf-8", "replace") if msg else "unknown error")
-        return rc
+        _native.Session.__init__(self, device)
 
     def reset(self):
         """Drops what is in flight, the first-bad word and the kernel time."""
-        self._check(self._lib.iss_inflate_reset(self._h))
+        _native.Session.reset(self)
         self.in_flight = 0
 
     def feed(self, data, members):
@@ -139,12 +109,6 @@ class BgzfInflater(object):
         member, code = C.c_int64(), C.c_int32()
         self._check(self._lib.iss_inflate_first_bad(self._h, C.byref(member), C.byref(code)))
         return member.value, code.value
-
-    def kernel_ms(self):
-        """Milliseconds k_bgzf_inflate took for all feeds since the last reset (waits for them)."""
-        ms = C.c_double()
-        self._check(self._lib.iss_inflate_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
 
 
 def check_status(status, members, base=0, accept_trailing=True):

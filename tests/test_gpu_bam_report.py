@@ -239,6 +239,22 @@ def test_first_bad_record_wins():
     assert (got["bad_record"], got["bad_code"]) == (4, 4) and got["skipped"] == [1, 0]
 
 
+def test_buffers_grow_in_the_middle_of_a_pipeline():
+    """A fresh context, so that nothing has grown before: the second feed passes the 2^16-record floor of its slot's offsets and of
+    the descriptors and the 1 MiB floor of its slot's bytes while the first is still in flight, and the third follows it at once
+    (the module's shared contexts only ever grow on their first feed)."""
+    from insilicoseq_amd.bam_report import BamReadTally, bam_reads_host
+
+    chunks = [BC.chunk_of(BC.mixed(tuple(range(1, 9)), n, 130 + k)) for k, n in enumerate((40, 70000, 40))]
+    assert chunks[1].offsets.size > (1 << 16) and chunks[1].data.size > (1 << 20) and chunks[0].data.size < 4096
+    with BamReadTally(0, 16) as dev:
+        for chunk in chunks:
+            dev.feed(chunk)
+        got = dev.download()
+    _same(got, bam_reads_host(chunks, 16), 16)
+    assert sum(got["records"]) == 70080 and got["bad_record"] == -1
+
+
 # ---------------------------------------------------------------------------------------------------- invalid arguments
 def test_invalid_arguments_launch_nothing():
     from insilicoseq_amd import _native
@@ -279,6 +295,8 @@ def test_invalid_arguments_launch_nothing():
     for max_len in (0, -1, 1025):
         assert lib.iss_br_create(0, max_len, C.byref(h)) == _native.E_INVALID and not h
     assert lib.iss_br_create(99, 64, C.byref(h)) == _native.E_INVALID and not h
+    assert lib.iss_br_create(1 << 20, 64, C.byref(h)) == _native.E_INVALID and not h
+    assert b"device ordinal out of range" in lib.iss_br_last_error(None)
     assert lib.iss_br_create(0, 64, None) == _native.E_INVALID
     assert lib.iss_br_tally_words(None) == -1 and lib.iss_br_tally_words(dev._h) == 1 + 64 * 200 + 2 + 188 + 2048 + 2 * 65
     rec, skip, bad, code = (C.c_int64 * 2)(), (C.c_int64 * 2)(), C.c_int64(), C.c_int32()

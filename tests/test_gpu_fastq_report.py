@@ -135,6 +135,23 @@ def test_chunking_does_not_change_the_words():
         assert np.array_equal(got["tally"], whole["tally"]) and got["records"] == [101, 0]
 
 
+def test_buffers_grow_in_the_middle_of_a_pipeline():
+    """A fresh context, so that nothing has grown before: the second and the fourth feed pass the 1 MiB floor of their slot and of the
+    work arrays while the feed before them is still in flight (the module's shared contexts only ever grow on their first feed)."""
+    from insilicoseq_amd.fastq_report import FastqTally
+
+    feeds = [(k % 2, FC.mixed(n, 120 + k, (151,))) for k, n in enumerate((8, 4000, 8, 8000, 8))]
+    assert len(feeds[0][1]) < 4096 and (1 << 20) < len(feeds[1][1]) < (1 << 21) < len(feeds[3][1])
+    with FastqTally(0, 151) as dev:
+        for mate, chunk in feeds:
+            dev.feed(chunk, mate)
+        got = dev.download()
+    _same(got, _twin(feeds, 151), 151)
+    assert got["records"] == [24, 12000] and got["bad_record"] == [-1, -1]
+    small = _device([(mate, c) for mate, chunk in feeds for c in _chunks_of(chunk, 16)], 151)
+    assert np.array_equal(small["tally"], got["tally"]) and small["records"] == got["records"]
+
+
 def test_two_mates_interleaved():
     from insilicoseq_amd.fastq_report import split_fq_words
 
@@ -238,6 +255,8 @@ def test_invalid_arguments_launch_nothing():
     for max_len in (0, -1, 1025):
         assert lib.iss_fq_create(0, max_len, C.byref(h)) == _native.E_INVALID and not h
     assert lib.iss_fq_create(99, 64, C.byref(h)) == _native.E_INVALID and not h
+    assert lib.iss_fq_create(1 << 20, 64, C.byref(h)) == _native.E_INVALID and not h
+    assert b"device ordinal out of range" in lib.iss_fq_last_error(None)
     assert lib.iss_fq_tally_words(None) == -1 and lib.iss_fq_tally_words(dev._h) == 1 + 64 * 200 + 2 + 188 + 2048 + 2 * 65
     rec, bad, code = (C.c_int64 * 2)(), (C.c_int64 * 2)(), (C.c_int32 * 2)()
     assert lib.iss_fq_download(dev._h, None, C.addressof(rec), C.addressof(bad), C.addressof(code)) == _native.E_INVALID

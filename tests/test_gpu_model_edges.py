@@ -183,6 +183,23 @@ def test_first_error_in_file_order_wins_across_feeds(dev, twin_all):
     assert not mismatch(device_tallies(dev, [TABLE]), twin_all)
 
 
+def test_invalid_arguments_launch_nothing(dev, twin_all):
+    """Argument validation of iss_bam_create: no handle, the thread's error; the context beside it is untouched."""
+    import ctypes as C
+
+    from insilicoseq_amd import _native
+
+    lib = _native.lib()
+    h = C.c_void_p()
+    assert lib.iss_bam_create(1 << 20, C.byref(h)) == _native.E_INVALID and not h
+    assert b"device ordinal out of range" in lib.iss_bam_last_error(None)
+    assert lib.iss_bam_create(-1, C.byref(h)) == _native.E_INVALID and not h
+    assert lib.iss_bam_create(0, None) == _native.E_INVALID
+    assert lib.iss_bam_reset(None) == _native.E_INVALID
+    lib.iss_bam_destroy(None)
+    assert not mismatch(device_tallies(dev, [TABLE]), twin_all)
+
+
 # ---- 3. k_kde_cdf against the definition
 
 def tolerance(e_ref):
