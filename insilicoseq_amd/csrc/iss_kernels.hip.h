@@ -957,6 +957,70 @@ __device__ __forceinline__ uint32_t shift_in(uint32_t r, unsigned long long flag
     return r;
 }
 
+// ---- The hot block of k_main / k_main_g (8 read positions of both mates), in three pieces.  The kernels use HotPhreds and
+// hot_letters in different orders (k_main the phreds first, k_main_g last): the compiler's schedule and register count follow
+// that order, so it stays each kernel's own.
+// Phred scores + substitution test, loop-free (hot_lookup); 16 independent lookups of the rows at rowf / rowr (guides) and
+// rowf_e / rowr_e (entries), off_g: byte offsets of the rows of the 8 positions.  Fills `sel` with the selected entries and
+// returns the base mask: bit 15 - (8 * half + s) <=> base s = mate * 4 + cc of that half needs the exact path
+__device__ __forceinline__ uint32_t hot_lookups16(uint32_t rowf, uint32_t rowf_e, uint32_t rowr, uint32_t rowr_e,
+                                                  const uint32_t (&off_g)[8], const u32x4 &q0, const u32x4 &ee, const u32x4 &q1,
+                                                  uint32_t gsh, uint32_t gb, uint32_t (&sel)[16]) {
+    uint32_t rare0 = 0;
+    unsigned long long fl;
+#define ISS_LOOKUP(K, ROW, C, HI, BYTE, WQ, WE, RARE)                                                                \
+    sel[K] = hot_lookup<HI, BYTE>(ROW, ROW##_e, off_g[C], WQ, WE, gsh, gb, fl);                                        \
+    RARE = shift_in(RARE, fl);
+    // half 0: positions 0-3
+    ISS_LOOKUP(0, rowf, 0, 0, 0, q0.x, ee.x, rare0)
+    ISS_LOOKUP(1, rowf, 1, 1, 1, q0.x, ee.x, rare0)
+    ISS_LOOKUP(2, rowf, 2, 0, 2, q0.y, ee.x, rare0)
+    ISS_LOOKUP(3, rowf, 3, 1, 3, q0.y, ee.x, rare0)
+    ISS_LOOKUP(4, rowr, 0, 0, 0, q0.z, ee.y, rare0)
+    ISS_LOOKUP(5, rowr, 1, 1, 1, q0.z, ee.y, rare0)
+    ISS_LOOKUP(6, rowr, 2, 0, 2, q0.w, ee.y, rare0)
+    ISS_LOOKUP(7, rowr, 3, 1, 3, q0.w, ee.y, rare0)
+    // half 1: positions 4-7
+    ISS_LOOKUP(8, rowf, 4, 0, 0, q1.x, ee.z, rare0)
+    ISS_LOOKUP(9, rowf, 5, 1, 1, q1.x, ee.z, rare0)
+    ISS_LOOKUP(10, rowf, 6, 0, 2, q1.y, ee.z, rare0)
+    ISS_LOOKUP(11, rowf, 7, 1, 3, q1.y, ee.z, rare0)
+    ISS_LOOKUP(12, rowr, 4, 0, 0, q1.z, ee.w, rare0)
+    ISS_LOOKUP(13, rowr, 5, 1, 1, q1.z, ee.w, rare0)
+    ISS_LOOKUP(14, rowr, 6, 0, 2, q1.w, ee.w, rare0)
+    ISS_LOOKUP(15, rowr, 7, 1, 3, q1.w, ee.w, rare0)
+#undef ISS_LOOKUP
+    return rare0;
+}
+
+// phred bytes: byte 1 of each selected entry, four to a word (the two phred words of the forward and of the reverse piece)
+// (a function object with a reference member and a plain member function, as the lambda it replaces was: written as a
+//  __forceinline__ function it is inlined earlier, and the four INDEL instantiations of k_main come out with the operands of the
+//  lookups' address additions in another order -- tools/cmp_generation_isa.py)
+struct HotPhreds {
+    const uint32_t (&sel)[16];
+    __device__ uint32_t operator()(int k) const {
+        return __builtin_amdgcn_perm(sel[k + 1], sel[k], 0x0c0c0501u) | __builtin_amdgcn_perm(sel[k + 3], sel[k + 2], 0x05010c0cu);
+    }
+};
+
+// Template bases of records of plain A/C/G/T: the letters of the forward window g[pf .. pf+7] (gf) and of the reverse one
+// comp(g[pr+7 .. pr]) (gr); pfs_e / prs_e: pf's / pr's base within its word of the packed genome.  INDEL: a piece with ex_f / ex_r
+// set takes its explicit codes code_f / code_r instead.  Returns the lane-item's `windows` (ring entry).
+template <bool INDEL>
+__device__ __forceinline__ uint32_t hot_letters(uint32_t lds0, uint2 gf, uint2 gr, uint32_t pfs_e, uint32_t prs_e, bool ex_f, bool ex_r,
+                                                uint32_t code_f, uint32_t code_r, uint2 &letters_f, uint2 &letters_r) {
+    uint32_t fb = funnel_r(gf.x, gf.y, pfs_e * 2u);
+    uint32_t rbr = funnel_r(gr.x, gr.y, prs_e * 2u);
+    if (INDEL) { fb = ex_f ? code_f : fb; rbr = ex_r ? code_r : rbr; }
+    const uint32_t windows = __builtin_amdgcn_perm(rbr ^ 0x5555u, fb, 0x05040100u);  // fb[15:0] | complemented (code ^ 1) rb[15:0] << 16
+    // (letters from the LDS tables: forward a byte of codes as it stands; reverse mate: read position c <-> genome
+    //  position pr + 7 - c, complemented)
+    letters_f = make_uint2(lut_at<0, 0>(lds0, fb), lut_at<1, 0>(lds0, fb));
+    letters_r = make_uint2(lut_at<1, 1024>(lds0, rbr), lut_at<0, 1024>(lds0, rbr));
+    return windows;
+}
+
 // STORE_MUT: --store_mutations variant (keeps the row bookkeeping out of the common kernel's register budget)
 // PLAIN: the record holds nothing but A/C/G/T and there is no custom fragment length (no irregular pairs) -- the
 // common case runs without the tests, masks and zero-initialisations of the other two.
@@ -1178,68 +1242,48 @@ __global__ __launch_bounds__(MAIN_THREADS, ISS_MAIN_OCC) void k_main(DevModel M,
                 const u32x4 q0 = draw_block(a, K_QM, s_abs, 0);
                 const u32x4 ee = draw_block(a, K_QM, s_abs, 1);
                 const u32x4 q1 = draw_block(a, K_QM, s_abs, 2);
-                // ---- phred scores + substitution test, loop-free (hot_lookup); 16 independent lookups
                 uint32_t sel[16];
-                unsigned long long fl;
-#define ISS_LOOKUP(K, ROW, C, HI, BYTE, WQ, WE, RARE)                                                                \
-                sel[K] = hot_lookup<HI, BYTE>(ROW, ROW##_e, off_g[C], WQ, WE, gsh, gb, fl);                            \
-                RARE = shift_in(RARE, fl);
-                // half 0: positions 0-3; bit 15 - (8 * half + s) of rare0 <=> base s = mate * 4 + cc of that half
-                ISS_LOOKUP(0, rowf, 0, 0, 0, q0.x, ee.x, rare0)
-                ISS_LOOKUP(1, rowf, 1, 1, 1, q0.x, ee.x, rare0)
-                ISS_LOOKUP(2, rowf, 2, 0, 2, q0.y, ee.x, rare0)
-                ISS_LOOKUP(3, rowf, 3, 1, 3, q0.y, ee.x, rare0)
-                ISS_LOOKUP(4, rowr, 0, 0, 0, q0.z, ee.y, rare0)
-                ISS_LOOKUP(5, rowr, 1, 1, 1, q0.z, ee.y, rare0)
-                ISS_LOOKUP(6, rowr, 2, 0, 2, q0.w, ee.y, rare0)
-                ISS_LOOKUP(7, rowr, 3, 1, 3, q0.w, ee.y, rare0)
-                // half 1: positions 4-7
-                ISS_LOOKUP(8, rowf, 4, 0, 0, q1.x, ee.z, rare0)
-                ISS_LOOKUP(9, rowf, 5, 1, 1, q1.x, ee.z, rare0)
-                ISS_LOOKUP(10, rowf, 6, 0, 2, q1.y, ee.z, rare0)
-                ISS_LOOKUP(11, rowf, 7, 1, 3, q1.y, ee.z, rare0)
-                ISS_LOOKUP(12, rowr, 4, 0, 0, q1.z, ee.w, rare0)
-                ISS_LOOKUP(13, rowr, 5, 1, 1, q1.z, ee.w, rare0)
-                ISS_LOOKUP(14, rowr, 6, 0, 2, q1.w, ee.w, rare0)
-                ISS_LOOKUP(15, rowr, 7, 1, 3, q1.w, ee.w, rare0)
-#undef ISS_LOOKUP
-                // phred bytes: byte 1 of each selected entry
-                auto quals = [&](int k) {
-                    return __builtin_amdgcn_perm(sel[k + 1], sel[k], 0x0c0c0501u) | __builtin_amdgcn_perm(sel[k + 3], sel[k + 2], 0x05010c0cu);
-                };
-                uint2 qual_f = {quals(0), quals(8)}, qual_r = {quals(4), quals(12)};
-                // ---- template bases
-                uint32_t fm = 0, rm = 0;
-                uint32_t fb = funnel_r(gf.x, gf.y, pfs_e * 2u);
-                uint32_t rbr = funnel_r(gr.x, gr.y, prs_e * 2u);
-                if (INDEL) { fb = ex_f ? code_f : fb; rbr = ex_r ? code_r : rbr; }
-                windows = __builtin_amdgcn_perm(rbr ^ 0x5555u, fb, 0x05040100u);  // fb[15:0] | complemented (code ^ 1) rb[15:0] << 16
-                if (!PLAIN && regular && (d.meta & 0x30u)) {  // only pairs whose windows hold IUPAC / lower-case letters (k_setup)
-                    // (a scripted mate lies in a record of plain A/C/G/T -- k_indel_script -- so pf_e / pr_e differ from pf / pr
-                    //  only where the mask is clear)
-                    // (genome position = 16 * (word - 1) + base within the word; mask word = position >> 5)
-                    const uint32_t *mw = g.mask + ((int32_t)(pfw_e - 1u) >> 1);
-                    fm = funnel_r(mw[0], mw[1], ((pfw_e - 1u) & 1u) * 16u + pfs_e) & 0xffu;
-                    const uint32_t *nw = g.mask + ((int32_t)(prw_e - 1u) >> 1);
-                    rm = funnel_r(nw[0], nw[1], ((prw_e - 1u) & 1u) * 16u + prs_e) & 0xffu;
-                }
-                // (letters from the LDS tables: forward a byte of codes as it stands; reverse mate: read position c <-> genome
-                //  position pr + 7 - c, complemented)
-                uint2 base_f = {lut_at<0, 0>(lds0, fb), lut_at<1, 0>(lds0, fb)};
-                uint2 base_r = {lut_at<1, 1024>(lds0, rbr), lut_at<0, 1024>(lds0, rbr)};
-                if (!PLAIN && (fm | rm)) {  // IUPAC / lower-case letters: patch from the ASCII copy
-                    for (int c = 0; c < 8; ++c) {
-                        if ((fm >> c) & 1u) {
-                            const uint32_t ch = g.ascii[(int64_t)(int32_t)(pfw_e - 1u) * 16 + pfs_e + c];
-                            uint32_t &w = c < 4 ? base_f.x : base_f.y;
-                            w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
-                        }
-                        if ((rm >> (7 - c)) & 1u) {
-                            const uint32_t ch = (uint32_t)complement_ascii(g.ascii[(int64_t)(int32_t)(prw_e - 1u) * 16 + prs_e + 7 - c]);
-                            uint32_t &w = c < 4 ? base_r.x : base_r.y;
-                            w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
+                rare0 = hot_lookups16(rowf, rowf_e, rowr, rowr_e, off_g, q0, ee, q1, gsh, gb, sel);
+                const HotPhreds quals = {sel};
+                const uint2 qual_f = {quals(0), quals(8)}, qual_r = {quals(4), quals(12)};
+                uint2 base_f, base_r;
+                if constexpr (PLAIN) {
+                    windows = hot_letters<INDEL>(lds0, gf, gr, pfs_e, prs_e, ex_f, ex_r, code_f, code_r, base_f, base_r);
+                } else {  // hot_letters written out, with the letters that are not A/C/G/T between its lines (through a function the
+                          // four PLAIN = false kernels came out 9-17 instructions shorter and, measured, up to 1.5 % slower: DESIGN.md 6)
+                    uint32_t fm = 0, rm = 0;
+                    uint32_t fb = funnel_r(gf.x, gf.y, pfs_e * 2u);
+                    uint32_t rbr = funnel_r(gr.x, gr.y, prs_e * 2u);
+                    if (INDEL) { fb = ex_f ? code_f : fb; rbr = ex_r ? code_r : rbr; }
+                    windows = __builtin_amdgcn_perm(rbr ^ 0x5555u, fb, 0x05040100u);
+                    if (regular && (d.meta & 0x30u)) {  // only pairs whose windows hold IUPAC / lower-case letters (k_setup)
+                        // (a scripted mate lies in a record of plain A/C/G/T -- k_indel_script -- so pf_e / pr_e differ from pf / pr
+                        //  only where the mask is clear)
+                        // (genome position = 16 * (word - 1) + base within the word; mask word = position >> 5)
+                        const uint32_t *mw = g.mask + ((int32_t)(pfw_e - 1u) >> 1);
+                        fm = funnel_r(mw[0], mw[1], ((pfw_e - 1u) & 1u) * 16u + pfs_e) & 0xffu;
+                        const uint32_t *nw = g.mask + ((int32_t)(prw_e - 1u) >> 1);
+                        rm = funnel_r(nw[0], nw[1], ((prw_e - 1u) & 1u) * 16u + prs_e) & 0xffu;
+                    }
+                    // (brace-initialised locals: assigned, or patched in base_f / base_r, the loop below is no longer unrolled)
+                    uint2 let_f = {lut_at<0, 0>(lds0, fb), lut_at<1, 0>(lds0, fb)};
+                    uint2 let_r = {lut_at<1, 1024>(lds0, rbr), lut_at<0, 1024>(lds0, rbr)};
+                    if (fm | rm) {  // IUPAC / lower-case letters: patch from the ASCII copy
+                        for (int c = 0; c < 8; ++c) {
+                            if ((fm >> c) & 1u) {
+                                const uint32_t ch = g.ascii[(int64_t)(int32_t)(pfw_e - 1u) * 16 + pfs_e + c];
+                                uint32_t &w = c < 4 ? let_f.x : let_f.y;
+                                w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
+                            }
+                            if ((rm >> (7 - c)) & 1u) {
+                                const uint32_t ch = (uint32_t)complement_ascii(g.ascii[(int64_t)(int32_t)(prw_e - 1u) * 16 + prs_e + 7 - c]);
+                                uint32_t &w = c < 4 ? let_r.x : let_r.y;
+                                w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
+                            }
                         }
                     }
+                    base_f = let_f;
+                    base_r = let_r;
                 }
                 // (the padding bytes of the last superitem hold the clamped last row's values; nothing reads them)
                 // (Whole 128-byte lines per store instruction -- lanes l / l + 32 exchanging a forward for a reverse piece with
@@ -1283,6 +1327,7 @@ template <bool PLAIN, int NI, int NP>
 __global__ __launch_bounds__(MAIN_THREADS, ISS_MAIN_OCC) void k_main_g(DevModel M, DevGenome g, RunArgs A,
                                                                        const PairDesc *__restrict__ desc, uint32_t min_round) {
     constexpr int G = NI * NP;
+    static_assert(PLAIN, "records with IUPAC / lower-case letters keep k_main: the letter masks and patches are written there alone");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_all[];
     uint32_t *const lds = lds_all + MAIN_LUT_WORDS;
     int tile = 0;
@@ -1426,56 +1471,10 @@ __global__ __launch_bounds__(MAIN_THREADS, ISS_MAIN_OCC) void k_main_g(DevModel 
                 rowr += it * 8u * gs_b;
                 const uint32_t rowf_e = rowf + gbytes, rowr_e = rowr + gbytes;
                 uint32_t sel[16];
-                unsigned long long fl;
-#define ISS_LOOKUP(K, ROW, C, HI, BYTE, WQ, WE, RARE)                                                                \
-                sel[K] = hot_lookup<HI, BYTE>(ROW, ROW##_e, off_g[C], WQ, WE, gsh, gb, fl);                            \
-                RARE = shift_in(RARE, fl);
-                ISS_LOOKUP(0, rowf, 0, 0, 0, q0.x, ee.x, rare0)
-                ISS_LOOKUP(1, rowf, 1, 1, 1, q0.x, ee.x, rare0)
-                ISS_LOOKUP(2, rowf, 2, 0, 2, q0.y, ee.x, rare0)
-                ISS_LOOKUP(3, rowf, 3, 1, 3, q0.y, ee.x, rare0)
-                ISS_LOOKUP(4, rowr, 0, 0, 0, q0.z, ee.y, rare0)
-                ISS_LOOKUP(5, rowr, 1, 1, 1, q0.z, ee.y, rare0)
-                ISS_LOOKUP(6, rowr, 2, 0, 2, q0.w, ee.y, rare0)
-                ISS_LOOKUP(7, rowr, 3, 1, 3, q0.w, ee.y, rare0)
-                ISS_LOOKUP(8, rowf, 4, 0, 0, q1.x, ee.z, rare0)
-                ISS_LOOKUP(9, rowf, 5, 1, 1, q1.x, ee.z, rare0)
-                ISS_LOOKUP(10, rowf, 6, 0, 2, q1.y, ee.z, rare0)
-                ISS_LOOKUP(11, rowf, 7, 1, 3, q1.y, ee.z, rare0)
-                ISS_LOOKUP(12, rowr, 4, 0, 0, q1.z, ee.w, rare0)
-                ISS_LOOKUP(13, rowr, 5, 1, 1, q1.z, ee.w, rare0)
-                ISS_LOOKUP(14, rowr, 6, 0, 2, q1.w, ee.w, rare0)
-                ISS_LOOKUP(15, rowr, 7, 1, 3, q1.w, ee.w, rare0)
-#undef ISS_LOOKUP
-                auto quals = [&](int k) {
-                    return __builtin_amdgcn_perm(sel[k + 1], sel[k], 0x0c0c0501u) | __builtin_amdgcn_perm(sel[k + 3], sel[k + 2], 0x05010c0cu);
-                };
-                uint32_t fm = 0, rm = 0;
-                const uint32_t fb = funnel_r(gf.x, gf.y, S.pfs * 2u);
-                const uint32_t rbr = funnel_r(gr.x, gr.y, S.prs * 2u);
-                windows = __builtin_amdgcn_perm(rbr ^ 0x5555u, fb, 0x05040100u);
-                if (!PLAIN && S.regular && (S.meta & 0x30u)) {
-                    const uint32_t *mw = g.mask + ((int32_t)(pfw_e - 1u) >> 1);
-                    fm = funnel_r(mw[0], mw[1], ((pfw_e - 1u) & 1u) * 16u + S.pfs) & 0xffu;
-                    const uint32_t *nw = g.mask + ((int32_t)(prw_e - 1u) >> 1);
-                    rm = funnel_r(nw[0], nw[1], ((prw_e - 1u) & 1u) * 16u + S.prs) & 0xffu;
-                }
-                uint2 base_f = {lut_at<0, 0>(lds0, fb), lut_at<1, 0>(lds0, fb)};
-                uint2 base_r = {lut_at<1, 1024>(lds0, rbr), lut_at<0, 1024>(lds0, rbr)};
-                if (!PLAIN && (fm | rm)) {
-                    for (int c = 0; c < 8; ++c) {
-                        if ((fm >> c) & 1u) {
-                            const uint32_t ch = g.ascii[(int64_t)(int32_t)(pfw_e - 1u) * 16 + S.pfs + c];
-                            uint32_t &w = c < 4 ? base_f.x : base_f.y;
-                            w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
-                        }
-                        if ((rm >> (7 - c)) & 1u) {
-                            const uint32_t ch = (uint32_t)complement_ascii(g.ascii[(int64_t)(int32_t)(prw_e - 1u) * 16 + S.prs + 7 - c]);
-                            uint32_t &w = c < 4 ? base_r.x : base_r.y;
-                            w = (w & ~(0xffu << (8 * (c & 3)))) | (ch << (8 * (c & 3)));
-                        }
-                    }
-                }
+                rare0 = hot_lookups16(rowf, rowf_e, rowr, rowr_e, off_g, q0, ee, q1, gsh, gb, sel);
+                uint2 base_f, base_r;
+                windows = hot_letters<false>(lds0, gf, gr, S.pfs, S.prs, false, false, 0u, 0u, base_f, base_r);
+                const HotPhreds quals = {sel};
                 rows[j][0] = base_f.x; rows[j][1] = base_f.y; rows[j][2] = quals(0); rows[j][3] = quals(8);
                 rows[j][4] = base_r.x; rows[j][5] = base_r.y; rows[j][6] = quals(4); rows[j][7] = quals(12);
             }
