@@ -453,6 +453,10 @@ int iss_mt_peek(iss_ctx *ctx, uint32_t *py_words, uint32_t *np_words, int32_t n)
  * (plain pairs) and the sequential walker (pairs with an indel candidate, letters outside ACGT or a template cut by
  * a genome end; indel-heavy models, the BasicErrorModel; everything when ISS_MT_PATH=walk is set in the environment). */
 int iss_mt_path_counts(iss_ctx *ctx, int64_t *n_resolved, int64_t *n_walked);
+/* The resolver instantiation iss_generate_mt / iss_generate_mt_workers take for the loaded model and the current ISS_MT_PATH:
+ * out = (python ring half in K words, numpy ring half in K words, 1 if the digit rows are staged in LDS), or (0, 0, 0) when
+ * every pair goes to the walker.  Launches nothing and changes no state. */
+int iss_mt_resolver_pick(iss_ctx *ctx, int32_t out[3]);
 /*
  * W reference workers side by side in ONE context (ABI 7).  The reference's own parallelism is N workers, each a sequential
  * chain over its two MT19937 streams seeded `seed + cpu_number` (pool.starmap over worker_iterator: iss/app.py:99-106,

@@ -41,6 +41,7 @@ EXPORTS = (
     "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
     "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
     "iss_br_kernel_ms",
+    "iss_mt_resolver_pick",
 )
 
 # The stand-alone device contexts (class Session below): entry prefix -> the arguments of its create call between the device ordinal
@@ -222,6 +223,9 @@ def lib():
         L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]
         L.iss_inflate_collect.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64)]
         L.iss_inflate_first_bad.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
+    # (and which resolver instantiation MT mode takes; without it ReadEngine.mt_resolver raises)
+    if hasattr(L, "iss_mt_resolver_pick"):
+        L.iss_mt_resolver_pick.argtypes = [vp, C.POINTER(i32 * 3)]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -245,7 +249,7 @@ def lib():
                 "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
                 "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
                 "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
-                "iss_mutations_tally", "iss_bgzf_scan")) and not hasattr(L, name):
+                "iss_mutations_tally", "iss_bgzf_scan", "iss_mt_resolver_pick")) and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id"):
             getattr(L, name).restype = C.c_int

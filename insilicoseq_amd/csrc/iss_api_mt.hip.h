@@ -16,8 +16,10 @@ double mt_guard_env() {
 // The resolver (k_mt_resolve / k_mt_resolve_w + k_mt_emit) for plain runs; the sequential walker for indel-heavy models, the
 // BasicErrorModel and perfect mode (walker only -- the resolver knows the KDE draws), and for the single pairs the resolver
 // hands back.  The candidates (py ring, numpy ring in KB, digit rows in LDS) in order of preference: digit rows in LDS first,
-// then the smallest rings that show a whole pair; each path maps the pick to its instantiation through this one list.
-#define ISS_MT_RESOLVERS(X) X(8, 2, true) X(4, 2, true) X(8, 4, true) X(4, 4, true) X(8, 2, false) X(4, 2, false) X(8, 4, false) X(4, 4, false)
+// then the smallest rings that show a whole pair; each path maps the pick to its instantiation through this one list.  The 4 K python
+// ring only ever wins where it makes room for the rows -- (4, 4, .) would need more than 246 positions for the numpy ring and at
+// most 160 for the python ring, and (8, 2, no rows) fits wherever (4, 2, no rows) does -- so these five are all a model can reach.
+#define ISS_MT_RESOLVERS(X) X(8, 2, true) X(4, 2, true) X(8, 4, true) X(8, 2, false) X(8, 4, false)
 #define ISS_MT_RESOLVE_ONE(P_, N_, R_) iss::k_mt_resolve<P_, N_, R_>,
 #define ISS_MT_RESOLVE_SET(P_, N_, R_) iss::k_mt_resolve_w<P_, N_, R_>,
 constexpr size_t MT_LDS_BUDGET = 160 * 1024 - 256;
@@ -1132,6 +1134,19 @@ int iss_mt_path_counts(iss_ctx *ctx, int64_t *n_resolved, int64_t *n_walked) {
     if (!ctx) return fail(nullptr, ISS_E_INVALID, "ctx is NULL");
     if (n_resolved) *n_resolved = ctx->mt.n_resolved + ctx->mts.n_resolved;  // (single-worker calls + the worker set)
     if (n_walked) *n_walked = ctx->mt.n_walked + ctx->mts.n_walked;
+    return 0;
+}
+
+int iss_mt_resolver_pick(iss_ctx *ctx, int32_t out[3]) {
+    if (!ctx || !out) return fail(ctx, ISS_E_INVALID, "iss_mt_resolver_pick: bad argument");
+    if (!ctx->have_model) return fail(ctx, ISS_E_INVALID, "iss_mt_resolver_pick: upload a model first");
+    struct Cand { int32_t pyv, npv, rows; };
+#define ISS_MT_CAND(P_, N_, R_) Cand{P_, N_, R_ ? 1 : 0},
+    static const Cand cands[] = {ISS_MT_RESOLVERS(ISS_MT_CAND)};
+#undef ISS_MT_CAND
+    const MtResolverPick pick = mt_pick_resolver(ctx);
+    out[0] = out[1] = out[2] = 0;
+    if (pick.idx >= 0) { out[0] = cands[pick.idx].pyv; out[1] = cands[pick.idx].npv; out[2] = cands[pick.idx].rows; }
     return 0;
 }
 

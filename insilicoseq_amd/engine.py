@@ -502,6 +502,15 @@ class ReadEngine(object):
         self._check(self._lib.iss_mt_path_counts(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def mt_resolver(self):
+        """The resolver instantiation generate_mt / generate_mt_workers take for the loaded model and the current ISS_MT_PATH:
+        (python ring half in K words, numpy ring half in K words, digit rows in LDS), or None when every pair is walked."""
+        if not hasattr(self._lib, "iss_mt_resolver_pick"):  # (no fall-back)
+            raise _native.NativeLibraryError("%s does not export iss_mt_resolver_pick: rebuild it" % _native.LIB_PATH)
+        out = (C.c_int32 * 3)()
+        self._check(self._lib.iss_mt_resolver_pick(self._ctx, C.byref(out)))
+        return (out[0], out[1], bool(out[2])) if out[0] else None
+
     def synchronize(self):
         self._check(self._lib.iss_synchronize(self._ctx))
 
