@@ -858,6 +858,38 @@ int iss_br_feed(iss_br *br, const uint8_t *data, int64_t n_bytes, const int64_t 
 int iss_br_download(iss_br *br, uint64_t *tally, int64_t *records, int64_t *skipped, int64_t *bad_record, int32_t *bad_code);
 int iss_br_kernel_ms(iss_br *br, double *ms);
 
+/*
+ * `report --bam --errors`: the errors of an aligned BAM's reads, as CIGAR and MD tell them, tallied ON THE DEVICE by a third stage of
+ * the context above (additive in ABI 8).  The words are iss_mutations_tally's at L = max_len, followed by the
+ * aligned bases, 2 + 446 L + 384 in all:
+ *   dropped [1] | pairs [1] | sub_q [2][L][Q] | sub_mat [2][L][5][5] | ins [2][L][5] | del [2][L][5] | per_read [2][3][K]
+ *   | bases [2][L][Q]
+ * A record the read tally took (good, mate 0 or 1) is ALIGNED when 0x4 is clear, n_cigar_op > 0 and l_seq > 0; one that is not adds
+ * 1 to counts[2].  An aligned record is validated, the first ISS_BR_ALN_* code that applies deciding; a walk of the optional fields
+ * that ends cleanly without an MD:Z adds 1 to counts[3], and the record is neither bad nor tallied.  A bad record adds 1 to
+ * `dropped` and nothing else -- it is validated completely before any of its counts is added -- and the smallest (record index over
+ * all records fed) << 8 | code is kept.  It stays in the read tally, whose words do not depend on this stage.
+ * A valid record of mate m and length len counts at the positions and with the letters of the read as sequenced: SEQ index q at q,
+ * with 0x10 at len - 1 - q and every letter complemented (letters by code: A, C, G, T in either case 0 .. 3, every other byte 4;
+ * the complement 0 <-> 3, 1 <-> 2, 4 fixed).  bases[m][pos][phred] takes every column of an M, = or X operation; every MD letter at
+ * SEQ index q one substitution row, sub_q[m][pos][QUAL[q]] and sub_mat[m][pos][ref][alt] (ref the MD letter, alt the SEQ letter,
+ * counted also where the codes are equal); every base of an I one insertion row, ins[m][pos][alt]; every letter of a '^' group one
+ * deletion row del[m][pos][ref], with q query bases in front of the D at min(q, len - 1), with 0x10 at min(len - q, len - 1): the
+ * base behind the gap in sequencing order.  per_read[m][type][min(rows, K - 1)] takes the read once per type, pairs the records of
+ * mate 0, counts[0 .. 1] the records per mate.  N and P consume nothing, S and H add nothing.
+ * Enabling is allowed only while nothing has been fed since the context was created or reset (ISS_E_INVALID afterwards, nothing
+ * changed); from then on every feed runs the stage, and the feeds' kernel time includes it.  A reset zeroes these words too and
+ * leaves the stage enabled.  The word count is -1 for NULL or while the stage is off; the download returns ISS_E_INVALID for NULL
+ * arguments or while the stage is off, else counts[4] (tallied per mate [2], not aligned, without MD) and the first bad alignment
+ * (*bad_record: -1 for none).
+ */
+#define ISS_BR_ALN_CIGAR 1 /* an op code above 8, or the lengths of M, I, S, =, X do not add up to l_seq (in 64 bits) */
+#define ISS_BR_ALN_TAGS 2  /* unknown type byte, value past block_size, Z / H without NUL, B with unknown subtype or negative count */
+#define ISS_BR_ALN_MD 3    /* the MD string does not fit the CIGAR */
+int iss_br_errors_enable(iss_br *br);
+int64_t iss_br_error_words(const iss_br *br);
+int iss_br_errors_download(iss_br *br, uint64_t *words, int64_t *counts /* [4] */, int64_t *bad_record, int32_t *bad_code);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ EXPORTS = (
     "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy", "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed",
     "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
     "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
-    "iss_br_kernel_ms",
+    "iss_br_kernel_ms", "iss_br_errors_enable", "iss_br_error_words", "iss_br_errors_download",
     "iss_mt_resolver_pick",
 )
 
@@ -72,6 +72,10 @@ BR_MAX_LEN = 1024
 BR_REC_ERRORS = {
     1: "malformed record (its fields do not fit its block_size)", 2: "read longer than --max_length", 3: "read without qualities",
     4: "quality above 93",
+}
+BR_ALN_ERRORS = {
+    1: "CIGAR with an unknown operation, or one that does not add up to the read's length",
+    2: "malformed optional fields", 3: "MD tag does not fit the CIGAR",
 }
 
 
@@ -218,6 +222,11 @@ def lib():
     if hasattr(L, "iss_br_feed"):
         L.iss_br_feed.argtypes = [vp, vp, i64, vp, i64]
         L.iss_br_download.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
+    # (and the alignments' errors behind `report --bam`; without them BamReadTally(errors=True) raises)
+    if hasattr(L, "iss_br_errors_enable"):
+        L.iss_br_errors_enable.argtypes = [vp]
+        L.iss_br_error_words.argtypes = [vp]
+        L.iss_br_errors_download.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     if hasattr(L, "iss_inflate_feed"):
         L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
         L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]
@@ -257,6 +266,8 @@ def lib():
         L.iss_tally_words.restype = i64
     if hasattr(L, "iss_error_tally_words"):
         L.iss_error_tally_words.restype = i64
+    if hasattr(L, "iss_br_error_words"):
+        L.iss_br_error_words.restype = i64
     # what every session has (a library from before a prefix still loads, and that prefix's Session raises); the entries whose
     # restype is not int are set here, behind the loop above
     for prefix, create_args in SESSIONS.items():

@@ -596,6 +596,10 @@ def report_from_fastq(args):
     bam = getattr(args, "bam", None)
     if bool(args.read1) == bool(bam):
         return fail("report takes exactly one of -1 R1.fastq and --bam reads.bam")
+    if getattr(args, "errors", False) and not bam:
+        return fail("report --errors reads the alignments of a BAM file: it goes with --bam")
+    if getattr(args, "against_errors", None) and not getattr(args, "errors", False):
+        return fail("report --against_errors compares the --errors tally: add --errors")
     if bam:
         if args.read2:
             return fail("report --bam takes no -2: the mates of a BAM file are told apart by their flags")
@@ -628,11 +632,69 @@ def report_from_fastq(args):
     return 0
 
 
+def _report_against_errors(args, other, other_length):
+    """--against_errors of `report --bam --errors`: (the other error tally's words, its read length, its bases [2][L][94] or None,
+    an error message or None); read before the GPU is opened.  The bases: the ``qual`` field of the --against tally when that is
+    given (it has to be of the error tally's read length), else OTHER_errbases.npy beside the file when it exists, else None (``pairs`` then)."""
+    import numpy as np
+
+    from . import errtally, tally
+
+    path = args.against_errors
+    try:
+        words = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        return None, None, None, "%s: %s" % (path, str(e).splitlines()[0] if str(e) else type(e).__name__)
+    L, rest = divmod(int(words.size) - 386, 258) if words.ndim == 1 else (0, 1)
+    if rest or L < 1 or errtally.words(L) != words.size:
+        return None, None, None, ("%s: %s words fit no read length (an error tally of read length L has 258 L + 386 words)"
+                                  % (path, "x".join(str(n) for n in words.shape)))
+    bases = None
+    if other is not None:
+        if other_length != L:
+            return None, None, None, "%s is of read length %d and %s of read length %d: not one run's" % (args.against, other_length, path, L)
+        bases = np.array(tally.split_tally(np.asarray(other, dtype=np.uint64), L)["qual"])
+    else:
+        beside = path[:-len("_errtally.npy")] + "_errbases.npy" if path.endswith("_errtally.npy") else None
+        if beside and os.path.exists(beside):
+            try:
+                bases = np.load(beside, allow_pickle=False)
+            except (OSError, ValueError) as e:
+                return None, None, None, "%s: %s" % (beside, str(e).splitlines()[0] if str(e) else type(e).__name__)
+            if bases.shape != (2, L, errtally.PHREDS):
+                return None, None, None, "%s: shape %r does not go with read length %d" % (beside, tuple(bases.shape), L)
+    return words, L, bases, None
+
+
+def _report_write_errors(args, res, against):
+    """The files of --errors from a result with errors (BamReadTally.result()); ``against``: _report_against_errors' first three."""
+    import json
+
+    import numpy as np
+
+    from . import bam_errors
+
+    L = res["read_length"]
+    err, bases = bam_errors.errors_and_bases(res["errors"], L)
+    np.save(args.output + "_errtally.npy", err)
+    np.save(args.output + "_errbases.npy", bases)
+    report = bam_errors.report_dict(res["errors"], L, res["error_counts"])
+    report["bad_alignment"] = {"record": int(res["bad_alignment"]), "code": int(res["bad_alignment_code"])}
+    with open(args.output + "_errors.json", "w") as fh:
+        json.dump(report, fh, indent=1)
+        fh.write("\n")
+    if against[0] is not None:
+        with open(args.output + "_errors_compare.json", "w") as fh:
+            json.dump(bam_errors.compare_errors(err, bases, L, against[0], against[2], against[1]), fh, indent=1)
+            fh.write("\n")
+
+
 def _report_from_bam(args, logger):
     """`report --bam`: the reads of a BAM file, insert sizes included (bam_report.py).  The BGZF blocks are inflated in the host
-    pool unless --device_inflate or ISS_DEVICE_INFLATE=1 asks for the device; ISS_HOST_INFLATE=1 wins over both."""
+    pool unless --device_inflate or ISS_DEVICE_INFLATE=1 asks for the device; ISS_HOST_INFLATE=1 wins over both.  With --errors
+    also the alignments' errors (bam_errors.py)."""
     from . import bam_report
-    from ._native import BR_REC_ERRORS, EngineError, NativeLibraryError
+    from ._native import BR_ALN_ERRORS, BR_REC_ERRORS, EngineError, NativeLibraryError
     from .bam import BamError
     from .inflate import InflateError
     from .modeller import device_inflater
@@ -642,8 +704,14 @@ def _report_from_bam(args, logger):
         other, other_length, message = _report_against(args)  # (before the GPU is opened)
         if message:
             return fail(message)
+        errors = bool(getattr(args, "errors", False))
+        against = (None, None, None)
+        if errors and args.against_errors:
+            *against, message = _report_against_errors(args, other, other_length)
+            if message:
+                return fail(message)
         t0 = time.perf_counter()
-        with bam_report.BamReadTally(args.device, args.max_length) as dev, \
+        with bam_report.BamReadTally(args.device, args.max_length, **({"errors": True} if errors else {})) as dev, \
                 device_inflater(args.device, True if args.device_inflate else None) as inflater:
             logger.info("Tallying %s" % args.bam)
             dev.feed_file(args.bam, inflater)
@@ -656,6 +724,15 @@ def _report_from_bam(args, logger):
             logger.warning("%s holds %d first and %d second reads" % (args.bam, res["records"][0], res["records"][1]))
         _report_write(args, res, other, other_length,
                       {"records_skipped": {"secondary_or_supplementary": int(res["skipped"][0]), "mate_flags": int(res["skipped"][1])}})
+        if errors:
+            if res["bad_alignment"] >= 0:  # (one odd record must not cost the user the report: the counts are in the json)
+                code = res["bad_alignment_code"]
+                logger.warning("%s: record %d: %s (%d such records are not in the error tally)"
+                               % (args.bam, res["bad_alignment"], BR_ALN_ERRORS.get(code, "error %d" % code),
+                                  int(res["errors"][0])))
+            if not sum(res["error_counts"][:2]) and res["error_counts"][3]:
+                return fail("%s: its aligned records have no MD tags; add them with `samtools calmd -b reads.bam ref.fasta`" % args.bam)
+            _report_write_errors(args, res, against)
     except InflateError as e:  # (the message names the file)
         return fail(str(e).splitlines()[0])
     except (BamError, EngineError, NativeLibraryError, OSError) as e:
@@ -755,6 +832,15 @@ def build_parser():
                         "read seen), <prefix>_report.json and <prefix>_lengths.npy (reads per mate and length)")
     r.add_argument("--against", default=None, metavar="OTHER_tally.npy",
                    help="also write <prefix>_compare.json: these reads against another tally (of generate --report, or of report)")
+    r.add_argument("--errors", action="store_true",
+                   help="with --bam: also tally the alignments' errors as CIGAR and MD tell them, on the GPU -- <prefix>_errtally.npy "
+                        "(the counters, in the layout of generate --error_report), <prefix>_errbases.npy (aligned bases per mate, "
+                        "position and phred: the denominators) and <prefix>_errors.json (rates per aligned base, substitution matrix, "
+                        "indels, errors per read, phred calibration); the BAM needs MD tags (samtools calmd)")
+    r.add_argument("--against_errors", default=None, metavar="OTHER_errtally.npy",
+                   help="with --errors: also write <prefix>_errors_compare.json, these errors against another error tally (of generate "
+                        "--error_report, or of report --bam --errors); the other side's denominators come from --against "
+                        "OTHER_tally.npy when given, else from OTHER_errbases.npy beside the file, else its pairs")
     r.add_argument("--max_length", type=int, default=1024, metavar="N", help="longest read taken (1 .. 1024, default 1024)")
     r.add_argument("--device", type=int, default=0, help="GPU ordinal")
     r.add_argument("--quiet", "-q", action="store_true")

@@ -173,9 +173,21 @@ class BamReadTally(_native.Session):
 
     PREFIX = "iss_br"
 
-    def __init__(self, device=0, max_len=MAX_LEN):
+    def __init__(self, device=0, max_len=MAX_LEN, errors=False):
+        """``errors``: also tally the alignments' errors (bam_errors.py; iss_br_errors_enable) -- download() and result() then
+        hold ``errors``, ``error_counts``, ``bad_alignment`` and ``bad_alignment_code`` as well."""
         self.max_len = int(max_len)
+        self.errors = bool(errors)
         _native.Session.__init__(self, device, self.max_len)
+        if self.errors:
+            if not hasattr(self._lib, "iss_br_errors_enable"):
+                self.close()
+                raise _native.NativeLibraryError("%s has no iss_br_errors_* entries: rebuild it" % _native.LIB_PATH)
+            try:
+                self._check(self._lib.iss_br_errors_enable(self._h))
+            except _native.EngineError:
+                self.close()
+                raise
 
     def feed(self, chunk):
         """One bam.Chunk of whole records; its arrays are free again when the call returns."""
@@ -195,12 +207,30 @@ class BamReadTally(_native.Session):
         assert self._lib.iss_br_tally_words(self._h) == words.size
         rec, skip, bad, code = (C.c_int64 * 2)(), (C.c_int64 * 2)(), C.c_int64(), C.c_int32()
         self._check(self._lib.iss_br_download(self._h, words.ctypes.data, C.addressof(rec), C.addressof(skip), C.byref(bad), C.byref(code)))
-        return {"tally": words, "records": list(rec), "skipped": list(skip), "bad_record": bad.value, "bad_code": code.value}
+        out = {"tally": words, "records": list(rec), "skipped": list(skip), "bad_record": bad.value, "bad_code": code.value}
+        if self.errors:
+            from .bam_errors import words as error_words
+
+            err = np.zeros(error_words(self.max_len), dtype=np.uint64)
+            assert self._lib.iss_br_error_words(self._h) == err.size
+            counts = (C.c_int64 * 4)()
+            self._check(self._lib.iss_br_errors_download(self._h, err.ctypes.data, C.addressof(counts), C.byref(bad), C.byref(code)))
+            out.update(errors=err, error_counts=list(counts), bad_alignment=bad.value, bad_alignment_code=code.value)
+        return out
 
     def result(self):
         """``tally``: tally.py's flat words re-laid to L = the longest read seen (interchangeable with `generate --report`'s
-        _tally.npy), ``read_length`` L, ``lengths`` [2][L + 1], ``records`` [2], ``skipped`` [2], ``bad_record``, ``bad_code``."""
-        return finish(self.download(), self.max_len)
+        _tally.npy), ``read_length`` L, ``lengths`` [2][L + 1], ``records`` [2], ``skipped`` [2], ``bad_record``, ``bad_code``;
+        with errors enabled also ``errors`` (bam_errors.layout's words re-laid to L), ``error_counts`` [4], ``bad_alignment`` and
+        ``bad_alignment_code``."""
+        raw = self.download()
+        res = finish(raw, self.max_len)
+        if self.errors:
+            from .bam_errors import relayout
+
+            res.update(errors=relayout(raw["errors"], self.max_len, res["read_length"]), error_counts=list(raw["error_counts"]),
+                       bad_alignment=int(raw["bad_alignment"]), bad_alignment_code=int(raw["bad_alignment_code"]))
+        return res
 
 
 __all__ = ["MAX_LEN", "REC_SHORT", "REC_TOO_LONG", "REC_NO_QUAL", "REC_QUAL_RANGE", "bam_reads_host", "bam_to_fastq", "finish",

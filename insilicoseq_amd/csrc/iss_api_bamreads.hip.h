@@ -2,6 +2,7 @@
 // whole records and iss_bam_scan's offsets; each goes through pinned staging buffers to device buffers of its slot on the copy
 // stream, and the kernels of iss_bamreads.hip.h follow on the kernel stream: the copy of chunk i + 1 overlaps the kernels of chunk i.
 // No model, no iss_ctx: a session (iss_host_session.hip.h: open and close, the two timed slots, grown buffers, the first-bad word).
+// With iss_br_errors_enable a third stage follows in every feed: the alignments' errors (iss_bamerrors.hip.h), words of their own.
 #pragma once
 
 struct iss_br : iss_session {
@@ -18,6 +19,9 @@ struct iss_br : iss_session {
     Grown<DevMem<uint4>> desc;  // per record of the feed in flight, sized by the largest chunk
     DevMem<iss::br::BrHead> d_head;
     DevMem<unsigned long long> d_tally;  // fq_layout(max_len).words, then BrState
+    bool errors = false;                 // iss_br_errors_enable: every feed also runs k_be_records and k_be_bases
+    DevMem<unsigned long long> d_err;    // be_words(max_len), then BeState
+    Grown<DevMem<unsigned long long>> marks;  // [records][ceil(max_len / 64)] of the feed in flight: k_be_records' aligned columns
 };
 
 static_assert(iss::br::BR_MAX_LEN == ISS_BR_MAX_LEN && ISS_BR_MAX_LEN == ISS_FQ_MAX_LEN, "include/iss_mi355x.h: ISS_BR_MAX_LEN");
@@ -25,6 +29,9 @@ static_assert(iss::br::BR_REC_SHORT == ISS_BR_REC_SHORT && iss::br::BR_REC_TOO_L
                   iss::br::BR_REC_NO_QUAL == ISS_BR_REC_NO_QUAL && iss::br::BR_REC_QUAL_RANGE == ISS_BR_REC_QUAL_RANGE,
               "include/iss_mi355x.h: ISS_BR_REC_*");
 static_assert(iss::br::BR_MAX_LEN <= (int)iss::br::BR_D_LEN, "a descriptor holds the read length in 11 bits");
+static_assert(iss::be::BE_ALN_CIGAR == ISS_BR_ALN_CIGAR && iss::be::BE_ALN_TAGS == ISS_BR_ALN_TAGS && iss::be::BE_ALN_MD == ISS_BR_ALN_MD,
+              "include/iss_mi355x.h: ISS_BR_ALN_*");
+static_assert(sizeof(iss::be::BeState) % sizeof(unsigned long long) == 0, "BeState stands behind the error words");
 
 // room for a chunk of n_bytes and n_records in slot s and in the array of the feed in flight; waits for the device only when it has to free
 static int br_reserve(iss_br *f, iss_br::Slot &s, size_t n_bytes, size_t n_records) {
@@ -32,7 +39,20 @@ static int br_reserve(iss_br *f, iss_br::Slot &s, size_t n_bytes, size_t n_recor
     ISS_TRY(reserve(f, s.bytes, n_bytes + iss::br::BR_PAD, (size_t)1 << 20, "slot bytes"));
     ISS_TRY(reserve(f, s.offs, n_records, (size_t)1 << 16, "slot offsets"));
     if (n_records > f->desc.cap) HIP_TRY(f, hipStreamSynchronize(f->stream));  // (the kernels of the chunk before use this array)
-    return reserve(f, f->desc, n_records, (size_t)1 << 16, "descriptors");
+    ISS_TRY(reserve(f, f->desc, n_records, (size_t)1 << 16, "descriptors"));
+    if (!f->errors) return 0;
+    const size_t marks = n_records * (size_t)((f->max_len + 63) / 64);
+    if (marks > f->marks.cap) HIP_TRY(f, hipStreamSynchronize(f->stream));  // (likewise)
+    return reserve(f, f->marks, marks, (size_t)1 << 16, "aligned-column marks");
+}
+
+// the error words and their state zeroed, the first-bad word all ones (on the kernel stream; the caller waits)
+static int br_errors_clear(iss_br *f) {
+    const size_t words = (size_t)iss::be::be_words(f->max_len);
+    HIP_TRY(f, hipMemsetAsync(f->d_err, 0, sizeof(unsigned long long) * words + sizeof(iss::be::BeState), f->stream));
+    HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_err + words) + offsetof(iss::be::BeState, bad), 0xFF,
+                             sizeof(unsigned long long), f->stream));
+    return 0;
 }
 
 extern "C" {
@@ -71,6 +91,7 @@ int iss_br_reset(iss_br *f) {
     HIP_TRY(f, hipMemsetAsync(f->d_tally, 0, sizeof(unsigned long long) * words + sizeof(iss::br::BrState), f->stream));
     HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_tally + words) + offsetof(iss::br::BrState, bad), 0xFF,
                              sizeof(unsigned long long), f->stream));
+    if (f->errors) ISS_TRY(br_errors_clear(f));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (iss_br::Slot &s : f->slot) s.busy = false;
     f->fed = 0;
@@ -126,6 +147,20 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
     HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(iss::br::k_br_positions, dim3(plan.pos_tiles, plan.pos_chunks), threads, 0, f->stream, A);
     HIP_TRY(f, hipGetLastError());
+    if (f->errors) {
+        iss::be::BeArgs E{};
+        E.R = A;
+        E.err = f->d_err;
+        E.state = reinterpret_cast<iss::be::BeState *>(f->d_err + iss::be::be_words(f->max_len));
+        E.mask = f->marks.p;
+        E.tiles = plan.pos_tiles;
+        const uint32_t record_wgs = iss::be::be_record_wgs(n_records, wgs);
+        E.rounds = iss::be::be_record_rounds(n_records, record_wgs);
+        hipLaunchKernelGGL(iss::be::k_be_records, dim3(record_wgs), dim3(iss::be::BE_THREADS), 0, f->stream, E);
+        HIP_TRY(f, hipGetLastError());
+        hipLaunchKernelGGL(iss::be::k_be_bases, dim3(plan.pos_tiles, plan.pos_chunks), dim3(iss::be::BE_THREADS), 0, f->stream, E);
+        HIP_TRY(f, hipGetLastError());
+    }
     HIP_TRY(f, hipEventRecord(s.done, f->stream));
     s.busy = true;
     ++f->feeds;
@@ -145,6 +180,34 @@ int iss_br_download(iss_br *f, uint64_t *tally, int64_t *records, int64_t *skipp
         records[m] = (int64_t)st.records[m];
         skipped[m] = (int64_t)st.skipped[m];
     }
+    bad_word_split(st.bad, bad_record, bad_code);
+    return 0;
+}
+
+int iss_br_errors_enable(iss_br *f) {
+    if (!f) return fail(nullptr, ISS_E_INVALID, "iss_br_errors_enable: NULL");
+    if (f->fed) return fail(f, ISS_E_INVALID, "iss_br_errors_enable: records have been fed since the last reset");
+    if (f->errors) return 0;
+    HIP_TRY(f, hipSetDevice(f->device));
+    DEV_ALLOC(f, f->d_err, (size_t)iss::be::be_words(f->max_len) + sizeof(iss::be::BeState) / sizeof(unsigned long long));
+    ISS_TRY(br_errors_clear(f));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    f->errors = true;
+    return 0;
+}
+
+int64_t iss_br_error_words(const iss_br *f) { return f && f->errors ? iss::be::be_words(f->max_len) : -1; }
+
+int iss_br_errors_download(iss_br *f, uint64_t *words, int64_t *counts, int64_t *bad_record, int32_t *bad_code) {
+    if (!f || !words || !counts || !bad_record || !bad_code) return fail(f, ISS_E_INVALID, "iss_br_errors_download: bad arguments");
+    if (!f->errors) return fail(f, ISS_E_INVALID, "iss_br_errors_download: errors are not enabled");
+    HIP_TRY(f, hipSetDevice(f->device));
+    const size_t n = (size_t)iss::be::be_words(f->max_len);
+    iss::be::BeState st;
+    HIP_TRY(f, hipMemcpyAsync(words, f->d_err, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, f->stream));  // (behind every kernel fed)
+    HIP_TRY(f, hipMemcpyAsync(&st, f->d_err + n, sizeof(st), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    for (int k = 0; k < 4; ++k) counts[k] = (int64_t)st.counts[k];
     bad_word_split(st.bad, bad_record, bad_code);
     return 0;
 }

@@ -54,6 +54,7 @@
 #include "iss_fqtally.hip.h"    // k_fq_*: `report`, the tallies of the rows over FASTQ text (last, likewise)
 #include "iss_inflate.hip.h"    // k_bgzf_inflate: BGZF members inflated on the device (last, likewise)
 #include "iss_bamreads.hip.h"   // k_br_*: `report --bam`, the tallies of k_fq_* over BAM records (last, likewise)
+#include "iss_bamerrors.hip.h"  // k_be_*: `report --bam --errors`, the errors CIGAR and MD tell of (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
