@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive) iss_origins_compress / iss_vcf_compress / iss_bgzf_text_code_build: the origins and VCF text as BGZF members built on the device, copies
+/* 8: (additive) iss_genome_upload_variants / iss_genome_download / iss_variants_lift / iss_variants_apply_tile / iss_variants_host_apply /
+ *    iss_variants_host_lift: a VCF's alleles spliced into a record on the device, coordinates lifted back.
+ *    (additive) iss_origins_compress / iss_vcf_compress / iss_bgzf_text_code_build: the origins and VCF text as BGZF members built on the device, copies
  *    from the line above.
  *    (additive) iss_origins_emit_batch / iss_origins_flush / iss_origins_host_text: every pair's source intervals as BEDPE text built
  *    on the device.
@@ -889,6 +891,44 @@ int iss_br_kernel_ms(iss_br *br, double *ms);
 int iss_br_errors_enable(iss_br *br);
 int64_t iss_br_error_words(const iss_br *br);
 int iss_br_errors_download(iss_br *br, uint64_t *words, int64_t *counts /* [4] */, int64_t *bad_record, int32_t *bad_code);
+
+/*
+ * `generate --variants`: a record with a VCF's alleles spliced in ON THE DEVICE, in front of the pack kernel (additive in ABI 8;
+ * DESIGN.md section 30).  The tables of a record of `length` letters with n variants, sorted and disjoint (pos0[i + 1] >= pos0[i] +
+ * ref_len[i]; no two pure insertions at one pos0; none empty; none past the record's end):
+ *   pos0 [n] int64: the first replaced letter, 0-based; ref_len / alt_len [n] int32: letters replaced / put in; alt_off / ref_off [n]
+ *   int64: where the variant's ALT / REF letters start in the blobs alt [n_alt] / ref [n_ref]; out_pos [n + 1] int64: pos0[i] plus the
+ *   sum of alt_len[j] - ref_len[j] over j < i, out_pos[n] the haplotype's length L'.
+ * Output offset o, with i the last variant whose out_pos[i] <= o and k = o - out_pos[i]: alt[alt_off[i] + k] while k < alt_len[i],
+ * else ascii[pos0[i] + ref_len[i] + k - alt_len[i]]; in front of the first variant ascii[o].
+ * iss_genome_upload_variants stages the letters and tables in HBM, compares every variant's REF letters with the record (case
+ * ignored; a mismatch: ISS_E_INVALID, one line with the POS and both spellings), builds the haplotype into the new genome's ASCII
+ * copy and packs it like iss_genome_upload does a large record: letters outside the alphabet -- ALT letters too -- are found there.
+ * 1 <= L' <= 2^34 - 4096.  Tables that break a rule above: ISS_E_INVALID, nothing launched.  The call returns when the genome is
+ * resident (the caller's buffers are free); it holds length + L' letters on the device while it runs.  The lift tables stay with the
+ * genome until iss_genome_clear.
+ * iss_genome_download: the resident ASCII copy of any genome (capacity >= its length; ascii NULL: *length alone).  Waits for the stream.
+ * iss_variants_lift: d_out[t] = the record coordinate of haplotype coordinate d_in[t] (device arrays of n int64) of genome d_gid[t]
+ * (device int32 [n]; NULL: `gid` for all).  With i the last variant whose out_pos[i] <= h and k = h - out_pos[i]: pos0[i] +
+ * min(k, ref_len[i]) inside the ALT run (k < alt_len[i]), pos0[i] + ref_len[i] + k - alt_len[i] behind it, h in front of the first
+ * variant.  Non-decreasing, L' -> length: valid for half-open interval ends.  A genome without tables, or an id that names none:
+ * the identity.  Asynchronous on the context's stream, like iss_output_export (the first call after an upload waits for it once).
+ * iss_variants_apply_tile: output bytes per workgroup of the splice kernel (tests straddle it).
+ * iss_variants_host_apply / iss_variants_host_lift (host only, no GPU): the same mapping, compiled from the same source, on the
+ * caller's tables; out takes out_pos[n] <= capacity letters.  The apply checks its tables like the upload; the lift reads only
+ * entries [0, n) of them.
+ */
+int iss_genome_upload_variants(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int64_t n, const int64_t *pos0,
+                               const int32_t *ref_len, const int32_t *alt_len, const int64_t *alt_off, const uint8_t *alt, int64_t n_alt,
+                               const int64_t *ref_off, const uint8_t *ref, int64_t n_ref, const int64_t *out_pos, int32_t *genome_id);
+int iss_genome_download(iss_ctx *ctx, int32_t genome_id, uint8_t *ascii, int64_t capacity, int64_t *length);
+int iss_variants_lift(iss_ctx *ctx, const int32_t *d_gid, int32_t gid, const int64_t *d_in, int64_t n, int64_t *d_out);
+int iss_variants_apply_tile(void);
+int iss_variants_host_apply(const uint8_t *ascii, int64_t length, int64_t n, const int64_t *pos0, const int32_t *ref_len,
+                            const int32_t *alt_len, const int64_t *alt_off, const uint8_t *alt, int64_t n_alt, const int64_t *out_pos,
+                            uint8_t *out, int64_t capacity);
+int iss_variants_host_lift(int64_t n, const int64_t *pos0, const int32_t *ref_len, const int32_t *alt_len, const int64_t *out_pos,
+                           const int64_t *in, int64_t n_coords, int64_t *out);
 
 #ifdef __cplusplus
 }

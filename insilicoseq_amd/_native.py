@@ -42,6 +42,8 @@ EXPORTS = (
     "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
     "iss_br_kernel_ms", "iss_br_errors_enable", "iss_br_error_words", "iss_br_errors_download",
     "iss_mt_resolver_pick",
+    "iss_genome_upload_variants", "iss_genome_download", "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply",
+    "iss_variants_host_lift",
 )
 
 # The stand-alone device contexts (class Session below): entry prefix -> the arguments of its create call between the device ordinal
@@ -235,6 +237,14 @@ def lib():
     # (and which resolver instantiation MT mode takes; without it ReadEngine.mt_resolver raises)
     if hasattr(L, "iss_mt_resolver_pick"):
         L.iss_mt_resolver_pick.argtypes = [vp, C.POINTER(i32 * 3)]
+    # (and `generate --variants`: a record's haplotype spliced on the device; without them ReadEngine.add_genome_variants raises)
+    if hasattr(L, "iss_genome_upload_variants"):
+        L.iss_genome_upload_variants.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, C.POINTER(i32)]
+        L.iss_genome_download.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+        L.iss_variants_lift.argtypes = [vp, vp, i32, vp, i64, vp]
+        L.iss_variants_apply_tile.argtypes = []
+        L.iss_variants_host_apply.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]
+        L.iss_variants_host_lift.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -258,7 +268,8 @@ def lib():
                 "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
                 "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
                 "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
-                "iss_mutations_tally", "iss_bgzf_scan", "iss_mt_resolver_pick")) and not hasattr(L, name):
+                "iss_mutations_tally", "iss_bgzf_scan", "iss_mt_resolver_pick", "iss_genome_upload_variants", "iss_genome_download",
+                "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply", "iss_variants_host_lift")) and not hasattr(L, name):
             continue
         if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id"):
             getattr(L, name).restype = C.c_int

@@ -186,21 +186,27 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
             fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False, bgzip=False,
-            error_report=False):
+            error_report=False, variants=None):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
     (worker_iterator); ``ubam``: it writes ``<prefix>.bam``, BGZF record blocks, instead of the two FASTQ files; ``origins``: it also
     writes ``<prefix>_origins.bedpe``, every pair's source intervals; ``bgzip``: its ``.vcf`` and ``_origins.bedpe`` hold BGZF members
     compressed on the device instead of text; ``error_report``: it tallies its mutation rows on the device into
-    ``<prefix>.errtally.npy``."""
+    ``<prefix>.errtally.npy``; ``variants``: (VCF path, haplotype or None) -- records re-read here get their variants again
+    (variants.load), records handed over carry them already."""
     logging.basicConfig(level=logging.WARNING)
     if report or depth or error_report:
         from .tensors import _torch
 
         _torch()  # (the tally words / the depth accumulator are torch tensors: torch's HIP runtime has to be the process's first)
     # (records are identified by their ordinal in the concatenated FASTA, not by id: draft assemblies repeat ids)
+    reread = records is None
     records = list(records if records is not None else parse_fasta(genome_file))
+    if variants is not None and reread:
+        from . import variants as V
+
+        records = V.load(variants[0], records, variants[1])[0]
     if mode is None:  # (callers that name no mode: a model file is kde, none is basic)
         mode = "kde" if npz is not None else "basic"
     if mode == "basic":
@@ -313,6 +319,55 @@ def _write_depth(output, n_workers, records, bin):
         os.remove(path)
 
 
+def _load_variants(args, records):
+    """--variants: the records with their haplotypes in place of their letters (variants.HaplotypeSeq: every length from here on
+    is the haplotype's), after ``<output>_variants.json`` (per record L, the haplotype's length and the variants by class; what was
+    skipped, by reason) and ``<output>_haplotype.chain`` (haplotype -> record, one chain per record) are written; with
+    --write_haplotype also ``<output>_haplotype.fasta``, every record as the reads will see it, the spliced ones downloaded from
+    the device that built them."""
+    import json
+
+    from . import variants as V
+    from ._native import EngineError, NativeLibraryError
+
+    logger = logging.getLogger(__name__)
+    try:
+        spliced, tables, skipped = V.load(args.variants, records, args.variants_haplotype)
+        if getattr(args, "write_haplotype", False):
+            from .engine import ReadEngine
+
+            if any(getattr(args, flag, None) for flag in ("report", "depth", "depth_bin", "error_report")):
+                from .tensors import _torch
+
+                _torch()  # (those flags work on torch tensors later in this process: torch's HIP runtime has to be its first)
+            with ReadEngine(0) as eng, open(args.output + "_haplotype.fasta", "wb") as fh:
+                for old, new in zip(records, spliced):
+                    if new is old:
+                        letters = old.seq.encode("ascii") if isinstance(old.seq, str) else bytes(old.seq)
+                    else:
+                        letters = eng.genome_letters(eng.add_genome_variants(old.seq, new.seq.table, record_id=old.id)).tobytes()
+                        eng.clear_genomes()
+                    fh.write(b">" + (getattr(old, "description", "") or old.id).encode() + b"\n")
+                    fh.write(b"\n".join(letters[at:at + 80] for at in range(0, len(letters), 80)) + b"\n")
+    except (V.VcfError, EngineError, NativeLibraryError, OSError) as e:
+        logger.error("--variants: %s" % (str(e).splitlines()[0] if str(e) else type(e).__name__))
+        sys.exit(1)
+    summary = {"vcf": args.variants, "haplotype": args.variants_haplotype, "skipped": skipped, "records": {}}
+    with open(args.output + "_haplotype.chain", "w") as fh:
+        for old, new in zip(records, spliced):
+            table = tables.get(old.id) if new is not old else None
+            entry = {"L": len(old.seq), "L_haplotype": len(new.seq)}
+            entry.update(table.counts() if table is not None else V.VariantTable([], [], [], [], [], len(old.seq)).counts())
+            summary["records"][old.id] = entry
+            if table is not None:
+                V.write_chain(fh, old.id, len(old.seq), table)
+    with open(args.output + "_variants.json", "w") as fh:
+        json.dump(summary, fh, indent=1)
+        fh.write("\n")
+    logger.info("--variants: %d records with variants, %d lines skipped" % (len(tables), sum(skipped.values())))
+    return spliced
+
+
 def load_readcount_or_abundance(args, records, error_model):
     """load_readcount_or_abundance (iss/generator.py:497-594), in the reference's order of precedence, with --draft:
     returns (readcount_dic, abundance_dic, n_reads) and writes _abundance.txt / _coverage.txt like the reference."""
@@ -413,6 +468,10 @@ def _generate_reads(args, ubam):
     if not records:
         logger.error("Genome(s) file seems empty: %s" % genome_file)
         sys.exit(1)
+    variants_spec = None
+    if getattr(args, "variants", None):  # the genome the reads are cut from changes here: every length below is a haplotype's
+        records = _load_variants(args, records)
+        variants_spec = (args.variants, args.variants_haplotype)
     readcount_dic, abundance_dic, n_reads = load_readcount_or_abundance(args, records, error_model)
     workers = args.gpus
     report = bool(getattr(args, "report", False))
@@ -454,7 +513,9 @@ def _generate_reads(args, ubam):
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            if error_report:
+            if variants_spec is not None:  # (the workers read the records again: the VCF too)
+                pool.starmap(_worker, [j + (None, ubam, origins, bgzip, error_report, variants_spec) for j in jobs])
+            elif error_report:
                 pool.starmap(_worker, [j + (None, ubam, origins, bgzip, True) for j in jobs])
             else:
                 pool.starmap(_worker, [j + (None, ubam, origins, bgzip) for j in jobs] if ubam or origins or bgzip else jobs)
@@ -800,6 +861,17 @@ def build_parser():
                         "the text never reaches the host; the FASTQ files are not affected (--compress and --ubam work beside it, and "
                         "with both --compress and --bgzip these two files take this route); with the side-by-side workers of --rng mt "
                         "--cpus W --devices 1 the .vcf is compressed into the same container on host threads")
+    g.add_argument("--variants", default=None, metavar="v.vcf[.gz]",
+                   help="splice the alleles of a VCF into the records on the GPU before any read is cut: SNVs, substitutions, insertions "
+                        "and deletions (symbolic alleles, '*', breakends and lines of other records are skipped and counted); the run "
+                        "writes exactly what it would write for the haplotype given as FASTA, every coordinate in haplotype "
+                        "coordinates, plus <output>_variants.json (lengths and counts per record) and <output>_haplotype.chain "
+                        "(haplotype -> record); the first ALT of every line unless --variants_haplotype is given")
+    g.add_argument("--variants_haplotype", type=int, default=None, choices=[1, 2],
+                   help="with --variants: apply the allele the first sample's GT names for this haplotype (0 and '.': the line is "
+                        "skipped; an unphased heterozygous GT is an error)")
+    g.add_argument("--write_haplotype", action="store_true",
+                   help="with --variants: also write <output>_haplotype.fasta, the records as the reads see them, downloaded from the GPU")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

@@ -419,24 +419,11 @@ int iss_genome_upload(iss_ctx *ctx, const uint8_t *ascii, int64_t length, int32_
                            G.packed, G.mask, status);
         G.has_exceptions = exceptions;
     } else {  // (a return below frees what G owns so far)
-        DEV_ALLOC(ctx, G.packed_own, n_pk + PK_PAD);
-        DEV_ALLOC(ctx, G.mask_own, n_mk + 4);
-        DEV_ALLOC(ctx, G.ascii_own, (size_t)length);
-        G.packed = G.packed_own + 1;
-        G.mask = G.mask_own + 1;
-        G.ascii = G.ascii_own;
-        const unsigned long long init[3] = {0ull, (unsigned long long)length, 0ull};
-        hipError_t he = hipMemcpyAsync(G.ascii, ascii, (size_t)length, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess) he = hipMemsetAsync(G.packed_own, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
-        if (he == hipSuccess) he = hipMemsetAsync(G.mask_own, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, ctx->stream);
+        ISS_TRY(genome_alloc_owned(ctx, G, length));
+        const hipError_t he = hipMemcpyAsync(G.ascii, ascii, (size_t)length, hipMemcpyHostToDevice, ctx->stream);
         if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
-        hipLaunchKernelGGL(iss::k_pack_genome, dim3((unsigned)((n_mk + 255) / 256)), dim3(256), 0, ctx->stream, G.ascii, length,
-                           G.packed, G.mask, status);
-        unsigned long long res[3] = {0, 0, 0};
-        he = hipMemcpyAsync(res, status, sizeof res, hipMemcpyDeviceToHost, ctx->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-        if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome pack: ") + hipGetErrorString(he));
+        unsigned long long res[3];
+        ISS_TRY(genome_pack_owned(ctx, G, res));
         if (res[0]) {
             char buf[200];
             snprintf(buf, sizeof buf, "genome letter 0x%02x at offset %llu is outside the rev_comp alphabet (%llu such letters; "
@@ -585,6 +572,7 @@ int iss_genome_clear(iss_ctx *ctx) {
     ctx->genomes.clear();
     ctx->groups.clear();
     ctx->group_stage = {};
+    ctx->vl = {};
     ctx->arena = {};
     ctx->comm = {};
     ctx->it = {};

@@ -48,6 +48,11 @@ struct Genome {
     bool has_exceptions = false;
     int32_t group = -1;     // iss_genome_upload_group: index into iss_ctx::groups; the buffers point into the group's arena
     int64_t coord = 0;      //   at this coordinate
+    // iss_genome_upload_variants: the haplotype's lift tables, kept for iss_variants_lift (var_n == 0: none, the identity)
+    DevMem<uint8_t> var_own;  // one block: out_pos [var_n + 1] | pos0 [var_n] | ref_len [var_n] | alt_len [var_n]
+    int64_t var_n = 0;
+    const int64_t *var_out_pos = nullptr, *var_pos0 = nullptr;    // views into var_own
+    const int32_t *var_ref_len = nullptr, *var_alt_len = nullptr;  // likewise
 };
 
 // iss_genome_upload_group: records packed side by side in iss_generate_batch's arena layout (coordinate 64 first, 32-base
@@ -438,6 +443,10 @@ struct iss_ctx {
         PinMem<uint8_t> h;
         size_t cap = 0;
     } group_stage;
+    struct VarLift {  // iss_variants_lift: the genomes' lift tables by genome id, rebuilt when genomes have come or gone
+        DevMem<iss::VarLiftTab> d_tabs;
+        size_t n = 0;  // genomes it covers
+    } vl;
     // outputs: what iss_output_reserve allocates for `capacity` pairs, replaced as one (`= {}`, free_outputs)
     struct OutputSet {
         int64_t capacity = 0;

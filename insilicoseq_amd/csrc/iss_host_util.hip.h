@@ -93,6 +93,39 @@ int upload(iss_ctx *ctx, const T *host, size_t n, T **dev, std::vector<DevMem<vo
     return 0;
 }
 
+// A record that owns its three buffers (iss_genome_upload's large records, iss_genome_upload_variants): allocated here, views set.
+int genome_alloc_owned(iss_ctx *ctx, Genome &G, int64_t length) {
+    const size_t n_mk = (size_t)(length + 31) / 32, n_pk = 2 * n_mk;
+    G.L = length;
+    DEV_ALLOC(ctx, G.packed_own, n_pk + PK_PAD);
+    DEV_ALLOC(ctx, G.mask_own, n_mk + 4);
+    DEV_ALLOC(ctx, G.ascii_own, (size_t)length);
+    G.packed = G.packed_own + 1;
+    G.mask = G.mask_own + 1;
+    G.ascii = G.ascii_own;
+    return 0;
+}
+
+// ... and packed from its ASCII copy, which what is queued on the context's stream so far has put into G.ascii: k_pack_genome,
+// then its status read back (waits for the stream) -- res[0] letters outside the alphabet, res[1] the offset of the first,
+// res[2] exception letters.
+int genome_pack_owned(iss_ctx *ctx, Genome &G, unsigned long long res[3]) {
+    const size_t n_mk = (size_t)(G.L + 31) / 32, n_pk = 2 * n_mk;
+    unsigned long long *status = reinterpret_cast<unsigned long long *>(ctx->fix_count.get()) + 24;  // 3 words at +192 B
+    const unsigned long long init[3] = {0ull, (unsigned long long)G.L, 0ull};
+    hipError_t he = hipMemsetAsync(G.packed_own, 0, (n_pk + PK_PAD) * sizeof(uint32_t), ctx->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(G.mask_own, 0, (n_mk + 4) * sizeof(uint32_t), ctx->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(status, init, sizeof init, hipMemcpyHostToDevice, ctx->stream);
+    if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome upload: ") + hipGetErrorString(he));
+    hipLaunchKernelGGL(iss::k_pack_genome, dim3((unsigned)((n_mk + 255) / 256)), dim3(256), 0, ctx->stream, G.ascii, G.L,
+                       G.packed, G.mask, status);
+    res[0] = res[1] = res[2] = 0;
+    he = hipMemcpyAsync(res, status, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
+    if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome pack: ") + hipGetErrorString(he));
+    return 0;
+}
+
 // The switches of the library -- each selects a code path the tests force: which indel path a model
 // takes, the tile / guide-bit sweeps, the rounding guard of MT mode.  Read at iss_ctx_create, at every model upload and once
 // per generate call (never per launch).

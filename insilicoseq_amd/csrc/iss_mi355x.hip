@@ -10,7 +10,8 @@
 // iss_ubam.hip.h (the rows as unaligned BAM: records and BGZF members), iss_origins.hip.h (every pair's source intervals as BEDPE text),
 // iss_bgzf_text.hip.h (the VCF and origins text as BGZF members), iss_errtally.hip.h (integer tallies of the mutation rows: what
 // a run did to the reads), iss_fqtally.hip.h (`report`: the tallies of iss_tally.hip.h over FASTQ text), iss_inflate.hip.h (BGZF
-// members inflated: the decoder of iss_inflate_core.h on 64 lanes), iss_bamreads.hip.h (`report --bam`: the same tallies over BAM records).
+// members inflated: the decoder of iss_inflate_core.h on 64 lanes), iss_bamreads.hip.h (`report --bam`: the same tallies over BAM records),
+// iss_variants.hip.h (`generate --variants`: a VCF's alleles spliced into a record, coordinates lifted back; the mapping: iss_variants_core.h).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -55,6 +56,7 @@
 #include "iss_inflate.hip.h"    // k_bgzf_inflate: BGZF members inflated on the device (last, likewise)
 #include "iss_bamreads.hip.h"   // k_br_*: `report --bam`, the tallies of k_fq_* over BAM records (last, likewise)
 #include "iss_bamerrors.hip.h"  // k_be_*: `report --bam --errors`, the errors CIGAR and MD tell of (last, likewise)
+#include "iss_variants.hip.h"   // k_variant_*: `generate --variants`, a record's haplotype spliced in front of k_pack_genome (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
@@ -84,3 +86,4 @@
 #include "iss_api_fqtally.hip.h"
 #include "iss_api_inflate.hip.h"
 #include "iss_api_bamreads.hip.h"
+#include "iss_api_variants.hip.h"

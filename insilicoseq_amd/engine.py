@@ -134,6 +134,76 @@ class ReadEngine(object):
         self._genome_lengths.append(int(length))
         return gid.value
 
+    def add_genome_variants(self, seq, table, record_id=None):
+        """Upload one record with the variants of ``table`` (variants.VariantTable) spliced in on the device: the genome is the
+        haplotype, built in HBM from the record's letters and packed like any record (iss_genome_upload_variants).  Every variant's
+        REF letters must be the record's (case ignored): a mismatch raises EngineError, one line with ``record_id``, the POS and both
+        spellings.  Returns the genome id; genome_length() is the haplotype's length."""
+        self._need_variant_entries()
+        if isinstance(seq, str):
+            seq = seq.encode("ascii")
+        a = np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, dtype=np.uint8)
+        if a.size != table.record_length:
+            raise EngineError(_native.E_INVALID, "add_genome_variants: the table is of a record of %d letters, not %d" % (
+                table.record_length, a.size))
+        gid = C.c_int32(-1)
+        t = table
+        try:
+            self._check(self._lib.iss_genome_upload_variants(
+                self._ctx, a.ctypes.data, a.size, len(t), t.pos0.ctypes.data, t.ref_len.ctypes.data, t.alt_len.ctypes.data,
+                t.alt_off.ctypes.data, t.alt.ctypes.data, t.alt.size, t.ref_off.ctypes.data, t.ref.ctypes.data, t.ref.size,
+                t.out_pos.ctypes.data, C.byref(gid)))
+        except EngineError as e:
+            if record_id is None:
+                raise
+            raise EngineError(e.code, "record %s: %s" % (record_id, e.message)) from None
+        self._genome_lengths.append(int(t.out_pos[-1]))
+        return gid.value
+
+    def genome_letters(self, gid):
+        """The resident ASCII copy of genome ``gid`` as a uint8 array (iss_genome_download; waits for the stream)."""
+        self._need_variant_entries()
+        n = C.c_int64(0)
+        self._check(self._lib.iss_genome_download(self._ctx, int(gid), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        self._check(self._lib.iss_genome_download(self._ctx, int(gid), out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def lift_ptr(self, in_ptr, n, out_ptr, gid=0, gids_ptr=None):
+        """Haplotype coordinates -> record coordinates on the device: ``n`` int64 at the raw device address ``in_ptr`` to
+        ``out_ptr`` (it may be ``in_ptr``), of genome ``gid``, or of the genome ids (int32 [n]) at ``gids_ptr``.  A genome
+        uploaded without variants is the identity.  Asynchronous on the engine's current stream (iss_variants_lift)."""
+        self._need_variant_entries()
+        self._check(self._lib.iss_variants_lift(self._ctx, C.c_void_p(int(gids_ptr)) if gids_ptr else None, int(gid),
+                                                C.c_void_p(int(in_ptr)) if in_ptr else None, int(n),
+                                                C.c_void_p(int(out_ptr)) if out_ptr else None))
+
+    def lift(self, coords, gid=0, gids=None):
+        """``coords`` (any shape) lifted on the device: a torch tensor on this GPU comes back as one (nothing waits on the host
+        beyond torch's own stream hand-over); anything else goes through the device and comes back as a numpy int64 array.
+        ``gids``: a genome id per element instead of ``gid``."""
+        from .tensors import _torch
+
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        on_device = isinstance(coords, torch.Tensor) and coords.is_cuda
+        with torch.cuda.device(self.device):
+            x = (coords if on_device else torch.from_numpy(np.ascontiguousarray(coords, dtype=np.int64)).to(dev)).to(torch.int64).contiguous()
+            g = None
+            if gids is not None:
+                g = (gids if isinstance(gids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gids, dtype=np.int32))).to(dev).to(torch.int32).contiguous()
+                if g.numel() != x.numel():
+                    raise ValueError("lift: one genome id per coordinate")
+            out = torch.empty_like(x)
+            torch.cuda.current_stream().synchronize()  # (made on torch's stream; the engine reads them on its own)
+            self.lift_ptr(x.data_ptr(), x.numel(), out.data_ptr(), gid=gid, gids_ptr=g.data_ptr() if g is not None else None)
+            self.synchronize()
+        return out if on_device else out.cpu().numpy()
+
+    def _need_variant_entries(self):
+        if not hasattr(self._lib, "iss_genome_upload_variants"):  # (no fall-back, like _need_vcf_entries)
+            raise _native.NativeLibraryError("%s does not export iss_genome_upload_variants / iss_variants_lift: rebuild it" % _native.LIB_PATH)
+
     def clear_genomes(self):
         self._check(self._lib.iss_genome_clear(self._ctx))
         self._genome_lengths = []

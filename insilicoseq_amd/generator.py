@@ -187,15 +187,18 @@ def _warn_short_record(eng, record):
 class GenomeStore(object):
     """Which records are resident in one engine's HBM: id(record) -> (record, genome id), the letters they take, and the three
     operations of the work loops: gid() (look up, else upload), the grouped uploads (plan() / upload_groups()), drop().
+    A record with variants -- its ``seq`` a variants.HaplotypeSeq, or its id in ``variants`` -- is uploaded alone, never in a group,
+    and spliced on the device (ReadEngine.add_genome_variants); ``resident`` counts its haplotype's letters.
 
     ``limits`` has GENOME_BUDGET and GROUP_BASES (Worker, or a Worker: read at every call), the store keeps
     GENOME_BUDGET // ``budget_divisor`` letters.  ``drop_on_upload``: gid() drops the resident genomes itself before an upload that
     would pass the budget; otherwise it only notes it (``over``) and the caller drops at a point where nothing names them
     (drop_if_over()).  ``skip_short``: records not longer than the reads are left out of groups."""
 
-    def __init__(self, engine, limits, budget_divisor, drop_on_upload, skip_short):
+    def __init__(self, engine, limits, budget_divisor, drop_on_upload, skip_short, variants=None):
         self.engine, self.limits, self.budget_divisor = engine, limits, budget_divisor
         self.drop_on_upload, self.skip_short = drop_on_upload, skip_short
+        self.variants = variants  # --variants: {record id: variants.VariantTable} for records whose seq is the record's own letters
         self._gids = {}  # id(record) -> (record, genome id on the device; -1: the group did not take it)
         self.resident, self.over = 0, False
         self._plan, self._plan_at = [], {}  # the work list's records (plan()) and the first place of each
@@ -207,6 +210,14 @@ class GenomeStore(object):
     def _hit(self, record):
         hit = self._gids.get(id(record))
         return hit if hit is not None and hit[0] is record else None
+
+    def _spliced(self, record):
+        """(the record's own letters, its table) for a record with variants, else None."""
+        table = getattr(record.seq, "table", None)
+        if table is not None:
+            return record.seq.ref, table
+        table = self.variants.get(record.id) if self.variants else None
+        return (_seq_of(record), table) if table is not None else None
 
     def plan(self, records):
         """Lazy grouping.  The records the work list will ask for, in order: a record's first gid() uploads it in one group
@@ -227,6 +238,12 @@ class GenomeStore(object):
                     self.drop()
                 else:
                     self.over = True
+            spliced = self._spliced(record)
+            if spliced is not None:
+                gid = self.engine.add_genome_variants(spliced[0], spliced[1], record_id=record.id)
+                hit = self._gids[id(record)] = (record, gid)
+                self.resident += self.engine.genome_length(gid)
+                return gid
             at = self._plan_at.get(id(record))
             if at is not None and self._plan[at] is record and len(record.seq) <= SMALL_RECORD:
                 self.upload_groups(self._plan[at:], one_group=True)
@@ -259,6 +276,8 @@ class GenomeStore(object):
                 continue
             if self.skip_short and not (self.engine.read_length < len(record.seq)):
                 continue  # (skipped by the work loop: never uploaded)
+            if self._spliced(record) is not None:
+                continue  # (spliced on the device, alone: through gid())
             seq = _seq_of(record)
             if len(seq) > SMALL_RECORD:
                 continue

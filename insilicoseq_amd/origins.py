@@ -44,9 +44,12 @@ def lines_host(items, record_lengths, cpu_number, coords, read_length):
     return "".join(out).encode()
 
 
-def parse(path):
+def parse(path, lift=None):
     """``<output>_origins.bedpe`` (or its ``.gz``) -> dict of arrays, one entry per line: ``id`` and ``name`` (object arrays of
-    str), ``s1`` ``e1`` ``s2`` ``e2`` ``isz`` (int64).  A line that is not a line of this file raises ValueError."""
+    str), ``s1`` ``e1`` ``s2`` ``e2`` ``isz`` (int64).  A line that is not a line of this file raises ValueError.
+    ``lift`` (a run with --variants: the file is in haplotype coordinates): ``{record id: f}``, f mapping an int64 array of
+    haplotype coordinates to the record's -- VariantTable.lift_host, or ``lambda h: variants.lift_chain(chain, h)`` for a chain
+    of ``<output>_haplotype.chain``; the four interval ends of the records it names are lifted, ``isz`` stays."""
     import gzip
 
     opener = gzip.open if str(path).endswith(".gz") else open
@@ -62,6 +65,10 @@ def parse(path):
     nums = np.asarray(nums, dtype=np.int64).reshape(-1, 5)
     out = {"id": np.asarray(ids, dtype=object), "name": np.asarray(names, dtype=object)}
     out.update({k: nums[:, j].copy() for j, k in enumerate(("s1", "e1", "s2", "e2", "isz"))})
+    for rid, f in (lift or {}).items():
+        rows = out["id"] == rid
+        for k in ("s1", "e1", "s2", "e2"):
+            out[k][rows] = f(out[k][rows])
     return out
 
 

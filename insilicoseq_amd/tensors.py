@@ -21,13 +21,17 @@ from ._native import EXPORT_ENCODINGS, EngineError, E_INVALID, E_NOMEM
 
 ReadBatch = collections.namedtuple("ReadBatch", ["bases", "qual", "coords", "record", "truth", "events", "n_events"],
                                    defaults=(None, None, None))
+ReadBatch.ref_coords = None  # (not a field: a stream with ``variants`` hands out LiftedReadBatch, which has it as its eighth)
+LiftedReadBatch = collections.namedtuple("LiftedReadBatch", ReadBatch._fields + ("ref_coords",), defaults=(None, None, None, None))
 ReadBatch.__doc__ = """bases, qual: torch.uint8 [N, 2, L] (mate 1, mate 2; read length L, no padding); coords: torch.int64 [N, 4]
 (forward_start, reverse_start, reverse_end, insert_size in the record's own coordinates); record: torch.int32 [N] (the index of
 the pair's record in the list the stream was given; the work item for export_tensors).  Only when asked for (else None) --
 truth: torch.uint8 [N, 2, L], ``bases`` with the ``ref`` letter of every recorded substitution put back, same encoding; events:
 torch.int32 [capacity, 6], rows (pair within the batch, mate, type 0 substitution / 1 insertion / 2 deletion, position, ref,
 alt -- ASCII) in the order of ReadEngine.mutations(); n_events: 0-dim torch.int64, the batch's rows (rows from ``capacity`` on
-are not in ``events``; -1: the engine's row slots overflowed).  All on the engine's device, owned by the caller: the engine keeps
+are not in ``events``; -1: the engine's row slots overflowed).  A stream with ``variants`` hands out LiftedReadBatch, the same
+fields and an eighth -- ref_coords: torch.int64 [N, 4], ``coords`` with its three positions lifted from the haplotype to the
+record on the device (ReadEngine.lift_ptr), the insert size copied; on a ReadBatch the attribute is None.  All on the engine's device, owned by the caller: the engine keeps
 no reference and never writes to them again."""
 
 
@@ -356,11 +360,16 @@ class ReadTensorStream(object):
     with ``truth=True`` it shares that reservation, without it the stream reserves ``mutation_slots`` slots of its own (default:
     default_mutation_slots()) and the batches stay without ``truth``.  The overflow rule above covers it: a batch that
     overflowed adds 1 to the tally's ``dropped`` and nothing else, and the stream raises when the next batch is asked for.
-    ``error_tally=False`` (the default): the attribute is None, no launch is added."""
+    ``error_tally=False`` (the default): the attribute is None, no launch is added.
+
+    ``variants``: {record index: variants.VariantTable} -- those records are uploaded with their variants spliced in on the
+    device (ReadEngine.add_genome_variants), every length and coordinate of the stream is the haplotype's, and every batch
+    carries ``ref_coords``, its coordinates lifted back to the record on the device, behind the export, on the same stream.
+    ``variants=None`` (the default): no launch is added, ``ref_coords`` is None."""
 
     def __init__(self, records, error_model, work, batch_pairs, seed=0, device=0, encoding="codes", sequence_type="metagenomics",
                  gc_bias=False, fragment_length=None, fragment_sd=None, truth=False, events_capacity=0, mutation_slots=None, tally=False, depth=False,
-                 error_tally=False):
+                 error_tally=False, variants=None):
         from .engine import ReadEngine
 
         if encoding not in EXPORT_ENCODINGS:
@@ -377,15 +386,24 @@ class ReadTensorStream(object):
         if fragment_length is not None or fragment_sd is not None:
             self.engine.set_fragment(fragment_length, fragment_sd)
         records = list(records)
+        self._variants = dict(variants) if variants else None
+        if self._variants:  # (a record with a table counts with its haplotype's length everywhere below)
+            from .variants import HaplotypeSeq
+
+            records = [HaplotypeSeq(r, self._variants[k]) if k in self._variants else r for k, r in enumerate(records)]
         log = logging.getLogger(__name__)
         usable = [k for k, r in enumerate(records) if len(r) > self.engine.read_length]
         for k in sorted(set(range(len(records))) - set(usable)):
             log.warning("record %d shorter than read length for this ErrorModel" % k)
             log.warning("Skipping record %d. You will have less reads than specified" % k)
-        ids = self.engine.add_genomes([records[k] for k in usable])
+        plain = [k for k in usable if not (self._variants and k in self._variants)]
+        ids = self.engine.add_genomes([records[k] for k in plain])
         gid = {}
-        for k, g in zip(usable, ids):
+        for k, g in zip(plain, ids):
             gid[k] = g if g >= 0 else self.engine.add_genome(records[k])  # (raises what the group could not say)
+        for k in usable:
+            if k not in gid:  # spliced on the device, alone
+                gid[k] = self.engine.add_genome_variants(records[k].ref, records[k].table, record_id=k)
         self.work = [(int(k), int(n)) for k, n in work if int(k) in gid]
         for k, n in work:
             if not 0 <= int(k) < len(records):
@@ -399,6 +417,7 @@ class ReadTensorStream(object):
             dev = torch.device("cuda", self.engine.device)
             # the record of every work item, on the device once: a batch's labels are a gather from its slice
             self._work_record = torch.tensor([k for k, _ in self.work], dtype=torch.int32, device=dev)
+            self._work_gid = torch.from_numpy(self._gids).to(dev) if self._variants else None  # (the lift's genome of every item)
             self.tally = torch.zeros(self.engine.tally_words(), dtype=torch.int64, device=dev) if tally else None
             self.depth_diff = self.depth_table = self._work_table = None
             self._marked = 0
@@ -507,6 +526,18 @@ class ReadTensorStream(object):
                         # no events wanted: the overflow word alone, from an empty window (one small kernel, no row is ordered)
                         count = torch.empty((), dtype=torch.int64, device=out.bases.device)
                         eng.export_mutations(0, 0, events_ptr=self._no_events.data_ptr(), capacity=0, n_events_ptr=count.data_ptr())
+                if self._variants:
+                    # the three positions of every pair, lifted by the pair's genome; the insert size as it is.  The block above has
+                    # ended: the current stream has the export behind it, so torch prepares the lift's inputs there, and the
+                    # engine -- on its side stream when the current one is the null stream -- reads them behind join_inputs()
+                    pair_gid = torch.index_select(self._work_gid[first_item:first_item + len(counts)], 0, out.record.long())
+                    pos = out.coords[:, :3].contiguous()
+                    gids3 = pair_gid.unsqueeze(1).expand(-1, 3).contiguous()
+                    lifted = torch.empty_like(pos)
+                    with _EngineOnCurrentStream(eng, restore=False) as on:
+                        on.join_inputs()
+                        eng.lift_ptr(pos.data_ptr(), pos.numel(), lifted.data_ptr(), gids_ptr=gids3.data_ptr())
+                    out = LiftedReadBatch(*out, ref_coords=torch.cat((lifted, out.coords[:, 3:]), dim=1))
                 if self._rows:
                     word = self._words[index & 1]
                     word.copy_(count, non_blocking=True)
@@ -520,5 +551,5 @@ class ReadTensorStream(object):
             self._check_overflow(pending)
 
 
-__all__ = ["ReadBatch", "ReadTensorStream", "export_tensors", "multinomial_work", "cut_batches", "export_rows_host", "recode",
+__all__ = ["ReadBatch", "LiftedReadBatch", "ReadTensorStream", "export_tensors", "multinomial_work", "cut_batches", "export_rows_host", "recode",
            "row_byte_index", "coords_from_descriptors", "truth_host", "events_host", "default_mutation_slots"]
