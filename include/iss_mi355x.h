@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: (additive) iss_genome_upload_variants / iss_genome_download / iss_variants_lift / iss_variants_apply_tile / iss_variants_host_apply /
+/* 8: (additive) iss_fa_create / iss_fa_destroy / iss_fa_last_error / iss_fa_index / iss_fasta_host_index / iss_fasta_tile /
+ *    iss_fasta_scan_span / iss_genome_upload_fasta: a genome FASTA indexed and stripped on the device.
+ *    (additive) iss_genome_upload_variants / iss_genome_download / iss_variants_lift / iss_variants_apply_tile / iss_variants_host_apply /
  *    iss_variants_host_lift: a VCF's alleles spliced into a record on the device, coordinates lifted back.
  *    (additive) iss_origins_compress / iss_vcf_compress / iss_bgzf_text_code_build: the origins and VCF text as BGZF members built on the device, copies
  *    from the line above.
@@ -929,6 +931,43 @@ int iss_variants_host_apply(const uint8_t *ascii, int64_t length, int64_t n, con
                             uint8_t *out, int64_t capacity);
 int iss_variants_host_lift(int64_t n, const int64_t *pos0, const int32_t *ref_len, const int32_t *alt_len, const int64_t *out_pos,
                            const int64_t *in, int64_t n_coords, int64_t *out);
+
+/*
+ * `generate --device_fasta`: a genome FASTA indexed and its line ends removed ON THE DEVICE, in front of the pack kernels (additive in
+ * ABI 8).  The host sends the bytes as they stand in the file.  The grammar over a text of n bytes:
+ *   a HEADER starts at a '>' that is byte 0 or directly follows '\n'; bytes in front of the first header are ignored;
+ *   header_off: that '>'; header_len: the bytes between it and the next '\n' (or the end of the text); the caller decodes and strips;
+ *   the BODY runs from behind that '\n' (body_off, body_len bytes) to the next header or the end of the text;
+ *   letters: the body's bytes other than '\r' and '\n';
+ *   flags: ISS_FA_ODD when the body holds a byte outside 0x21 .. 0x7E other than '\r' and '\n' -- the caller takes such a record
+ *   through its line-by-line parser.
+ * Every offset is 64-bit and relative to the text.
+ * iss_fa_create / iss_fa_destroy / iss_fa_last_error: a device session without a model, like iss_inflate.
+ * iss_fa_index: `text` is host memory.  *n_records: the headers of the text.  With capacity < *n_records (0: always, unless the text
+ * has no header) nothing else is written; otherwise the six arrays get one row per record.  The text must fit one device allocation.
+ * iss_fasta_host_index (host only, no GPU): the same table from the same grammar source.
+ * iss_fasta_tile: bytes per workgroup of the kernels; iss_fasta_scan_span: tiles per pass of the prefix scan (tests size by both).
+ * iss_genome_upload_fasta: `text` is a host span of the file, n rows with offsets relative to it.  The table is checked on the host
+ * first -- bodies inside the span, ascending, not overlapping, letters <= body_len -- and one that fails is ISS_E_INVALID with nothing
+ * launched.  Records of at most 2^20 letters become ONE group with the arena layout, the ids and the -1 rule (no letters, too many, a
+ * letter outside the rev_comp alphabet) of iss_genome_upload_group; a larger record comes alone (n = 1) and becomes a genome like a
+ * large record of iss_genome_upload, its errors included.  A letter is stored only inside its record's place; a table that does not
+ * fit the text (letters counted wrongly) is ISS_E_INVALID after the kernels ran, and no genome is made.  The call returns when the
+ * genomes are resident; it holds the span on the device while it runs.  The resident ASCII copy is the stripped letters.
+ */
+#define ISS_FA_ODD 1
+typedef struct iss_fa iss_fa;
+int iss_fa_create(int device_ordinal, iss_fa **fa);
+void iss_fa_destroy(iss_fa *fa);
+const char *iss_fa_last_error(const iss_fa *fa);
+int iss_fa_index(iss_fa *fa, const uint8_t *text, int64_t n_bytes, int64_t capacity, int64_t *header_off, int64_t *header_len,
+                 int64_t *body_off, int64_t *body_len, int64_t *letters, int32_t *flags, int64_t *n_records);
+int iss_fasta_host_index(const uint8_t *text, int64_t n_bytes, int64_t capacity, int64_t *header_off, int64_t *header_len, int64_t *body_off,
+                         int64_t *body_len, int64_t *letters, int32_t *flags, int64_t *n_records);
+int iss_fasta_tile(void);
+int iss_fasta_scan_span(void);
+int iss_genome_upload_fasta(iss_ctx *ctx, const uint8_t *text, int64_t n_bytes, int32_t n, const int64_t *body_off, const int64_t *body_len,
+                            const int64_t *letters, int32_t *genome_ids);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,10 @@ EXPORTS = (
     "iss_genome_upload_variants", "iss_genome_download", "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply",
     "iss_variants_host_lift",
 )
+# `generate --device_fasta` (a build from before them still loads; fasta.FastaIndexer and ReadEngine.add_genomes_fasta then raise)
+FASTA_ENTRIES = ("iss_fa_create", "iss_fa_destroy", "iss_fa_last_error", "iss_fa_index", "iss_fasta_host_index", "iss_fasta_tile",
+                 "iss_fasta_scan_span", "iss_genome_upload_fasta")
+EXPORTS += FASTA_ENTRIES
 
 # The stand-alone device contexts (class Session below): entry prefix -> the arguments of its create call between the device ordinal
 # and the handle.  Each has create, destroy, last_error and reset; kernel_ms and tally_words where EXPORTS names them.
@@ -245,6 +249,19 @@ def lib():
         L.iss_variants_apply_tile.argtypes = []
         L.iss_variants_host_apply.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]
         L.iss_variants_host_lift.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp]
+    # (and `generate --device_fasta`: the genome FASTA indexed and stripped on the device -- a session without reset, so not one of
+    #  SESSIONS; without them fasta.FastaIndexer and ReadEngine.add_genomes_fasta raise)
+    if hasattr(L, "iss_fa_index"):
+        L.iss_fa_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.iss_fa_destroy.argtypes = [vp]
+        L.iss_fa_destroy.restype = None
+        L.iss_fa_last_error.argtypes = [vp]
+        L.iss_fa_last_error.restype = C.c_char_p
+        L.iss_fa_index.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+        L.iss_fasta_host_index.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+        L.iss_fasta_tile.argtypes = []
+        L.iss_fasta_scan_span.argtypes = []
+        L.iss_genome_upload_fasta.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
     L.iss_fastq_flush.argtypes = [vp]
     L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
@@ -269,9 +286,9 @@ def lib():
                 "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
                 "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
                 "iss_mutations_tally", "iss_bgzf_scan", "iss_mt_resolver_pick", "iss_genome_upload_variants", "iss_genome_download",
-                "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply", "iss_variants_host_lift")) and not hasattr(L, name):
+                "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply", "iss_variants_host_lift") + FASTA_ENTRIES) and not hasattr(L, name):
             continue
-        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id"):
+        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_fa_destroy", "iss_fa_last_error"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "iss_tally_words"):
         L.iss_tally_words.restype = i64

@@ -186,7 +186,7 @@ def compress_file(path, block_bytes=32 << 20, threads=None):
 
 def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_type, gc_bias, rng, store_mutations,
             fragment, compress=False, mode=None, report=False, depth=False, records=None, ubam=False, origins=False, bgzip=False,
-            error_report=False, variants=None):
+            error_report=False, variants=None, device_fasta=False):
     """One pool process == one GPU.  Records are re-read from the concatenated FASTA (the reference
     pickles them; same content) unless the caller runs in this process and hands its own over.  ``report``: the worker tallies
     its reads on the device into ``<prefix>.tally.npy``; ``depth``: it marks their template intervals into ``<prefix>.depth.npz``
@@ -202,6 +202,10 @@ def _worker(rank, device, genome_file, work_spec, npz, seed, prefix, sequence_ty
         _torch()  # (the tally words / the depth accumulator are torch tensors: torch's HIP runtime has to be the process's first)
     # (records are identified by their ordinal in the concatenated FASTA, not by id: draft assemblies repeat ids)
     reread = records is None
+    if reread and device_fasta:  # (--device_fasta: indexed on this worker's device, the bodies stay in the file)
+        from . import fasta
+
+        records = fasta.read(genome_file, device=device)
     records = list(records if records is not None else parse_fasta(genome_file))
     if variants is not None and reread:
         from . import variants as V
@@ -343,9 +347,10 @@ def _load_variants(args, records):
             with ReadEngine(0) as eng, open(args.output + "_haplotype.fasta", "wb") as fh:
                 for old, new in zip(records, spliced):
                     if new is old:
-                        letters = old.seq.encode("ascii") if isinstance(old.seq, str) else bytes(old.seq)
+                        seq = str(old.seq) if hasattr(old.seq, "body_off") else old.seq  # (--device_fasta: the letters on demand)
+                        letters = seq.encode("ascii") if isinstance(seq, str) else bytes(seq)
                     else:
-                        letters = eng.genome_letters(eng.add_genome_variants(old.seq, new.seq.table, record_id=old.id)).tobytes()
+                        letters = eng.genome_letters(eng.add_genome_variants(new.seq.ref, new.seq.table, record_id=old.id)).tobytes()
                         eng.clear_genomes()
                     fh.write(b">" + (getattr(old, "description", "") or old.id).encode() + b"\n")
                     fh.write(b"\n".join(letters[at:at + 80] for at in range(0, len(letters), 80)) + b"\n")
@@ -464,7 +469,14 @@ def _generate_reads(args, ubam):
     error_model = load_error_model(args.mode, args.seed, args.model, args.fragment_length, args.fragment_length_sd,
                                    args.store_mutations, args.rng)
     # load_genomes (generator.py:424-494): --genomes then --draft into <out>.iss.tmp.genomes.fasta; --n_genomes (no --draft)
-    genome_file, records = drafts.load_genomes(args.genomes, args.draft, args.output, args.n_genomes)
+    # --device_fasta: the records are places in the file (fasta.FastaSeq), indexed on device 0 in a session of its own
+    device_fasta = bool(getattr(args, "device_fasta", False)) or os.environ.get("ISS_DEVICE_FASTA", "") == "1"
+    if device_fasta and any(getattr(args, flag, None) for flag in ("report", "depth", "depth_bin", "error_report")):
+        from .tensors import _torch
+
+        _torch()  # (those flags work on torch tensors later in this process: torch's HIP runtime has to be its first)
+    genome_file, records = drafts.load_genomes(args.genomes, args.draft, args.output, args.n_genomes,
+                                               **({"device_fasta": True} if device_fasta else {}))
     if not records:
         logger.error("Genome(s) file seems empty: %s" % genome_file)
         sys.exit(1)
@@ -513,7 +525,9 @@ def _generate_reads(args, ubam):
             logger.info("%d workers side by side on one device (%s)" % (workers, "final files" if in_place else "temporary files"))
     if workers > 1 and in_place is None:  # one process per worker (and what the set could not take)
         with mp.get_context("spawn").Pool(workers) as pool:
-            if variants_spec is not None:  # (the workers read the records again: the VCF too)
+            if device_fasta:  # (the workers index the file again, each on its device)
+                pool.starmap(_worker, [j + (None, ubam, origins, bgzip, error_report, variants_spec, True) for j in jobs])
+            elif variants_spec is not None:  # (the workers read the records again: the VCF too)
                 pool.starmap(_worker, [j + (None, ubam, origins, bgzip, error_report, variants_spec) for j in jobs])
             elif error_report:
                 pool.starmap(_worker, [j + (None, ubam, origins, bgzip, True) for j in jobs])
@@ -872,6 +886,11 @@ def build_parser():
                         "skipped; an unphased heterozygous GT is an error)")
     g.add_argument("--write_haplotype", action="store_true",
                    help="with --variants: also write <output>_haplotype.fasta, the records as the reads see them, downloaded from the GPU")
+    g.add_argument("--device_fasta", action="store_true",
+                   help="index the genome FASTA on the GPU and upload the records as they stand in the file, their line ends removed "
+                        "there, instead of parsing it on the host (also: ISS_DEVICE_FASTA=1); the output is the same.  Gzip-compressed "
+                        "--genomes / --draft files are taken either way; with this flag or ISS_DEVICE_INFLATE=1 a BGZF file is inflated "
+                        "on the GPU (ISS_HOST_INFLATE=1 keeps gzip on the host)")
     g.add_argument("--output", "-o", required=True)
     g.add_argument("--quiet", "-q", action="store_true")
     m = sub.add_parser("model", help="build a KDE error model from a BAM file (iss model)")

@@ -480,90 +480,29 @@ int iss_genome_upload_packed(iss_ctx *ctx, const uint32_t *codes, int64_t length
 int iss_genome_upload_group(iss_ctx *ctx, int32_t n, const uint8_t *const *ascii, const int64_t *lengths, int32_t *genome_ids) {
     if (!ctx || n < 0 || (n && (!ascii || !lengths || !genome_ids))) return fail(ctx, ISS_E_INVALID, "iss_genome_upload_group: bad argument");
     for (int32_t k = 0; k < n; ++k) genome_ids[k] = -1;
-    // arena coordinates (iss_generate_batch's layout); a record of no letters or too many gets id -1 (its single upload then
-    // reports it) and no place
-    std::vector<int64_t> starts;
-    std::vector<int32_t> which;  // starts[i] is record which[i]
-    starts.reserve((size_t)n + 1);
-    which.reserve((size_t)n);
-    int64_t coord = 64;
-    for (int32_t k = 0; k < n; ++k) {
-        if (lengths[k] < 1 || lengths[k] > iss::MAX_RECORD || !ascii[k]) continue;
-        starts.push_back(coord);
-        which.push_back(k);
-        coord += ((lengths[k] + 31) / 32) * 32 + 64;
-        if (coord >= iss::MAX_RECORD) return fail(ctx, ISS_E_INVALID, "iss_genome_upload_group: the records of one group must stay below 2^34 - 4096 bases");
-    }
-    const int32_t m = (int32_t)which.size();
+    GroupPlan P;
+    ISS_TRY(group_plan(ctx, "iss_genome_upload_group", n, lengths, ascii, P));
+    const int32_t m = (int32_t)P.which.size();
     if (!m) return 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t C = (size_t)coord;  // arena bases (a multiple of 32, 64 of padding behind the last record)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // one block: ascii | starts | status | packed | mask (the first two come in one copy, the rest is cleared in one memset)
-    const size_t asc_b = up(C + 64), st_b = up((size_t)m * 8), stat_b = up((size_t)m * 16);
-    const size_t pk_b = up((C / 16 + 2 + 16) * 4), mk_b = up((C / 32 + 2 + 8) * 4);
-    const size_t total = asc_b + st_b + stat_b + pk_b + mk_b;
-    if (asc_b + st_b + stat_b > ctx->group_stage.cap) {
-        ctx->group_stage = {};
-        const size_t cap = asc_b + st_b + stat_b;
-        PIN_ALLOC(ctx, ctx->group_stage.h, cap);
-        ctx->group_stage.cap = cap;
-    }
+    // the pinned stage: ascii | starts | status (the first two go in one copy)
+    ISS_TRY(group_stage_reserve(ctx, P.asc_b + P.st_b + P.stat_b));
     uint8_t *h = ctx->group_stage.h;
     memset(h, 'A', 64);
     for (int32_t i = 0; i < m; ++i) {
-        const int64_t L = lengths[which[(size_t)i]], s = starts[(size_t)i];
-        const int64_t e = i + 1 < m ? starts[(size_t)i + 1] : (int64_t)asc_b;
-        memcpy(h + s, ascii[which[(size_t)i]], (size_t)L);
+        const int64_t L = lengths[P.which[(size_t)i]], s = P.starts[(size_t)i];
+        const int64_t e = i + 1 < m ? P.starts[(size_t)i + 1] : (int64_t)P.asc_b;
+        memcpy(h + s, ascii[P.which[(size_t)i]], (size_t)L);
         memset(h + s + L, 'A', (size_t)(e - s - L));  // padding up to the next record (the last one: to the end of the region)
     }
-    memcpy(h + asc_b, starts.data(), (size_t)m * 8);
+    memcpy(h + P.asc_b, P.starts.data(), (size_t)m * 8);
     GenomeGroup grp;  // (a return below frees the block if the group owns it)
-    hipError_t he = hipSuccess;
-    if (total <= ARENA_SLAB / 4) {
-        grp.block = ctx->arena.take(total, &he);
-    } else {
-        (void)own_alloc_quiet(grp.own, total, &he);
-        grp.block = grp.own;
-    }
-    if (!grp.block) return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he));
-    grp.ascii = grp.block;
-    const int64_t *d_starts = reinterpret_cast<const int64_t *>(grp.block + asc_b);
-    unsigned long long *d_status = reinterpret_cast<unsigned long long *>(grp.block + asc_b + st_b);
-    grp.packed = reinterpret_cast<uint32_t *>(grp.block + asc_b + st_b + stat_b) + 2;
-    grp.mask = reinterpret_cast<uint32_t *>(grp.block + asc_b + st_b + stat_b + pk_b) + 2;
-    he = hipMemcpyAsync(grp.block, h, asc_b + st_b, hipMemcpyHostToDevice, ctx->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(grp.block + asc_b + st_b, 0, stat_b + pk_b + mk_b, ctx->stream);
+    ISS_TRY(group_block(ctx, P, grp));
+    const hipError_t he = hipMemcpyAsync(grp.block, h, P.asc_b + P.st_b, hipMemcpyHostToDevice, ctx->stream);
     if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he)); }
-    const int64_t n_words = (int64_t)(C / 32);
-    hipLaunchKernelGGL(iss::k_pack_group, dim3((unsigned)((n_words + iss::PACK_GROUP_THREADS - 1) / iss::PACK_GROUP_THREADS)),
-                       dim3(iss::PACK_GROUP_THREADS), 0, ctx->stream, grp.ascii, n_words, d_starts, m, grp.packed, grp.mask, d_status);
-    he = hipGetLastError();
-    unsigned long long *res = reinterpret_cast<unsigned long long *>(h + asc_b + st_b);
-    if (he == hipSuccess) he = hipMemcpyAsync(res, d_status, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);  // (also: the staging buffer is free again)
-    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group pack: ") + hipGetErrorString(he)); }
-    const int32_t gi = (int32_t)ctx->groups.size();
-    uint32_t *const grp_packed = grp.packed, *const grp_mask = grp.mask;
-    uint8_t *const grp_ascii = grp.ascii;
-    ctx->groups.push_back(std::move(grp));
-    for (int32_t i = 0; i < m; ++i) {
-        if (res[2 * (size_t)i]) continue;  // letters outside the alphabet: id -1
-        const int64_t s = starts[(size_t)i];
-        Genome G;
-        G.L = lengths[which[(size_t)i]];
-        G.packed = grp_packed + s / 16;  // (views into the group's block: freed with the group)
-        G.mask = grp_mask + s / 32;
-        G.ascii = grp_ascii + s;
-        G.has_exceptions = res[2 * (size_t)i + 1] != 0;
-        G.group = gi;
-        G.coord = s;
-        ctx->genomes.push_back(std::move(G));
-        genome_ids[which[(size_t)i]] = (int32_t)ctx->genomes.size() - 1;
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));
-    ctx->inputs_pending = true;
-    return 0;
+    unsigned long long *res = reinterpret_cast<unsigned long long *>(h + P.asc_b + P.st_b);
+    ISS_TRY(group_pack(ctx, P, grp, res));
+    return group_adopt(ctx, P, std::move(grp), lengths, res, genome_ids);
 }
 
 int iss_genome_clear(iss_ctx *ctx) {

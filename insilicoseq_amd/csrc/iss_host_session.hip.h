@@ -1,5 +1,5 @@
 // iss_host_session.hip.h -- what the stand-alone device contexts share on the host (iss_api_bam.hip.h, iss_api_fqtally.hip.h,
-// iss_api_inflate.hip.h, iss_api_bamreads.hip.h; struct iss_session and its fail(): iss_host_util.hip.h): the front of a create and
+// iss_api_inflate.hip.h, iss_api_bamreads.hip.h, iss_api_fasta.hip.h; struct iss_session and its fail(): iss_host_util.hip.h): the front of a create and
 // of a destroy, the slot of a two-slot pipeline with its timed kernels, grow-only buffers with their capacity, the first-bad word.
 #pragma once
 

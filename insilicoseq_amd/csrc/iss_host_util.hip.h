@@ -3,7 +3,7 @@
 // reservation empties, the choice of the hot kernel's instantiation (k_main / k_main_g), its LDS size, timing, synchronisation.
 #pragma once
 
-// What the stand-alone device contexts (iss_bam, iss_fq, iss_inflate, iss_br) have in common: each derives from it and stays a C type
+// What the stand-alone device contexts (iss_bam, iss_fq, iss_inflate, iss_br, iss_fa) have in common: each derives from it and stays a C type
 // of its own (include/iss_mi355x.h declares them opaque).  What works on it: iss_host_session.hip.h.
 struct iss_session {
     int device = 0;
@@ -123,6 +123,106 @@ int genome_pack_owned(iss_ctx *ctx, Genome &G, unsigned long long res[3]) {
     he = hipMemcpyAsync(res, status, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
     if (he != hipSuccess) return fail(ctx, ISS_E_HIP, std::string("genome pack: ") + hipGetErrorString(he));
+    return 0;
+}
+
+// iss_genome_upload_group and iss_genome_upload_fasta: where the records of a group stand (iss_generate_batch's arena layout) and how
+// the group's one block is cut -- ascii | starts | status | packed | mask.
+struct GroupPlan {
+    std::vector<int64_t> starts;  // arena coordinates of the records that get a place, ascending
+    std::vector<int32_t> which;   // starts[i] is record which[i] of the call
+    size_t C = 0;                 // arena bases (a multiple of 32, 64 of padding behind the last record)
+    size_t asc_b = 0, st_b = 0, stat_b = 0, pk_b = 0, mk_b = 0, total = 0;
+};
+
+// `ascii` (NULL: every record is there): a record without letters, of too many, or that is not there gets no place -- its id stays
+// -1 and its single upload reports it
+int group_plan(iss_ctx *ctx, const char *who, int32_t n, const int64_t *lengths, const uint8_t *const *ascii, GroupPlan &P) {
+    P.starts.reserve((size_t)n + 1);
+    P.which.reserve((size_t)n);
+    int64_t coord = 64;
+    for (int32_t k = 0; k < n; ++k) {
+        if (lengths[k] < 1 || lengths[k] > iss::MAX_RECORD || (ascii && !ascii[k])) continue;
+        P.starts.push_back(coord);
+        P.which.push_back(k);
+        coord += ((lengths[k] + 31) / 32) * 32 + 64;
+        if (coord >= iss::MAX_RECORD) return fail(ctx, ISS_E_INVALID, std::string(who) + ": the records of one group must stay below 2^34 - 4096 bases");
+    }
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t m = P.which.size();
+    P.C = (size_t)coord;
+    P.asc_b = up(P.C + 64), P.st_b = up(m * 8), P.stat_b = up(m * 16);
+    P.pk_b = up((P.C / 16 + 2 + 16) * 4), P.mk_b = up((P.C / 32 + 2 + 8) * 4);
+    P.total = P.asc_b + P.st_b + P.stat_b + P.pk_b + P.mk_b;
+    return 0;
+}
+
+int group_stage_reserve(iss_ctx *ctx, size_t bytes) {
+    if (bytes > ctx->group_stage.cap) {
+        ctx->group_stage = {};
+        PIN_ALLOC(ctx, ctx->group_stage.h, bytes);
+        ctx->group_stage.cap = bytes;
+    }
+    return 0;
+}
+
+// the group's block, from the arena or its own, and the views into it
+int group_block(iss_ctx *ctx, const GroupPlan &P, GenomeGroup &grp) {
+    hipError_t he = hipSuccess;
+    if (P.total <= ARENA_SLAB / 4) {
+        grp.block = ctx->arena.take(P.total, &he);
+    } else {
+        (void)own_alloc_quiet(grp.own, P.total, &he);
+        grp.block = grp.own;
+    }
+    if (!grp.block) return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he));
+    grp.ascii = grp.block;
+    grp.packed = reinterpret_cast<uint32_t *>(grp.block + P.asc_b + P.st_b + P.stat_b) + 2;
+    grp.mask = reinterpret_cast<uint32_t *>(grp.block + P.asc_b + P.st_b + P.stat_b + P.pk_b) + 2;
+    return 0;
+}
+
+// Behind what brings the arena's letters and the start coordinates into the block on the context's stream: status, packed and mask
+// cleared, k_pack_group, the records' status rows read back into `res` (pinned, two words per placed record); waits for the stream.
+int group_pack(iss_ctx *ctx, const GroupPlan &P, GenomeGroup &grp, unsigned long long *res) {
+    const int32_t m = (int32_t)P.which.size();
+    const int64_t *d_starts = reinterpret_cast<const int64_t *>(grp.block + P.asc_b);
+    unsigned long long *d_status = reinterpret_cast<unsigned long long *>(grp.block + P.asc_b + P.st_b);
+    hipError_t he = hipMemsetAsync(grp.block + P.asc_b + P.st_b, 0, P.stat_b + P.pk_b + P.mk_b, ctx->stream);
+    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group upload: ") + hipGetErrorString(he)); }
+    const int64_t n_words = (int64_t)(P.C / 32);
+    hipLaunchKernelGGL(iss::k_pack_group, dim3((unsigned)((n_words + iss::PACK_GROUP_THREADS - 1) / iss::PACK_GROUP_THREADS)),
+                       dim3(iss::PACK_GROUP_THREADS), 0, ctx->stream, grp.ascii, n_words, d_starts, m, grp.packed, grp.mask, d_status);
+    he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(res, d_status, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);  // (also: the staging buffer is free again)
+    if (he != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, ISS_E_HIP, std::string("genome group pack: ") + hipGetErrorString(he)); }
+    return 0;
+}
+
+// the group joins the context, and its records that hold no letter outside the alphabet become genomes (the others: id -1)
+int group_adopt(iss_ctx *ctx, const GroupPlan &P, GenomeGroup grp, const int64_t *lengths, const unsigned long long *res, int32_t *genome_ids) {
+    const int32_t m = (int32_t)P.which.size();
+    const int32_t gi = (int32_t)ctx->groups.size();
+    uint32_t *const grp_packed = grp.packed, *const grp_mask = grp.mask;
+    uint8_t *const grp_ascii = grp.ascii;
+    ctx->groups.push_back(std::move(grp));
+    for (int32_t i = 0; i < m; ++i) {
+        if (res[2 * (size_t)i]) continue;  // letters outside the alphabet: id -1
+        const int64_t s = P.starts[(size_t)i];
+        Genome G;
+        G.L = lengths[P.which[(size_t)i]];
+        G.packed = grp_packed + s / 16;  // (views into the group's block: freed with the group)
+        G.mask = grp_mask + s / 32;
+        G.ascii = grp_ascii + s;
+        G.has_exceptions = res[2 * (size_t)i + 1] != 0;
+        G.group = gi;
+        G.coord = s;
+        ctx->genomes.push_back(std::move(G));
+        genome_ids[P.which[(size_t)i]] = (int32_t)ctx->genomes.size() - 1;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_inputs, ctx->stream));
+    ctx->inputs_pending = true;
     return 0;
 }
 

@@ -11,7 +11,8 @@
 // iss_bgzf_text.hip.h (the VCF and origins text as BGZF members), iss_errtally.hip.h (integer tallies of the mutation rows: what
 // a run did to the reads), iss_fqtally.hip.h (`report`: the tallies of iss_tally.hip.h over FASTQ text), iss_inflate.hip.h (BGZF
 // members inflated: the decoder of iss_inflate_core.h on 64 lanes), iss_bamreads.hip.h (`report --bam`: the same tallies over BAM records),
-// iss_variants.hip.h (`generate --variants`: a VCF's alleles spliced into a record, coordinates lifted back; the mapping: iss_variants_core.h).
+// iss_variants.hip.h (`generate --variants`: a VCF's alleles spliced into a record, coordinates lifted back; the mapping: iss_variants_core.h),
+// iss_fasta.hip.h (`generate --device_fasta`: the genome FASTA indexed and its line ends removed; the grammar: iss_fasta_core.h).
 #include "iss_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@
 #include "iss_bamreads.hip.h"   // k_br_*: `report --bam`, the tallies of k_fq_* over BAM records (last, likewise)
 #include "iss_bamerrors.hip.h"  // k_be_*: `report --bam --errors`, the errors CIGAR and MD tell of (last, likewise)
 #include "iss_variants.hip.h"   // k_variant_*: `generate --variants`, a record's haplotype spliced in front of k_pack_genome (last, likewise)
+#include "iss_fasta.hip.h"      // k_fa_*: `generate --device_fasta`, a FASTA text indexed and stripped in front of the pack kernels (last, likewise)
 
 // The host side by concern (one translation unit, one shared library; the order is the order of definition):
 #include "iss_own.h"                  // the owning handle (plain C++: device and pinned memory, events, streams)
@@ -87,3 +89,4 @@
 #include "iss_api_inflate.hip.h"
 #include "iss_api_bamreads.hip.h"
 #include "iss_api_variants.hip.h"
+#include "iss_api_fasta.hip.h"

@@ -17,15 +17,21 @@ import random
 import shutil
 import sys
 
-from .generator import parse_fasta
+from .generator import parse_fasta, read_genome_bytes
 
 
-def concatenate(file_list, output):
-    """util.concatenate (iss/util.py:213-234): the files' bytes one after the other."""
+def concatenate(file_list, output, device_inflate=None):
+    """util.concatenate (iss/util.py:213-234): the files' bytes one after the other.  A file that starts with the gzip magic
+    (.fa.gz, bgzip-ped or not) is inflated on the way (generator.read_genome_bytes: BGZF on the device when ``device_inflate`` or
+    ISS_DEVICE_INFLATE=1, gzip on the host otherwise)."""
     with open(output, "wb") as out:
         for name in file_list:
             if name is not None:
                 with open(name, "rb") as fh:
+                    if fh.read(2) == b"\x1f\x8b":
+                        out.write(read_genome_bytes(name, device_inflate))
+                        continue
+                    fh.seek(0)
                     shutil.copyfileobj(fh, out)
 
 
@@ -47,22 +53,31 @@ def write_fasta(records, path):
                 fh.write(seq[i:i + 60] + "\n")
 
 
-def load_genomes(genomes, draft, output, n_genomes, rng=None):
+def load_genomes(genomes, draft, output, n_genomes, rng=None, device_fasta=False):
     """load_genomes (iss/generator.py:424-494) without --ncbi: concatenates --genomes, then --draft into
     ``<output>.iss.tmp.genomes.fasta``; with --n_genomes (and no --draft) keeps a random subset and rewrites the file.
-    Returns (path, records)."""
+    Returns (path, records).  ``device_fasta``: the file is indexed on device 0 and the records' letters stay in it (fasta.read)."""
     logger = logging.getLogger(__name__)
     if not (genomes or draft):
         logger.error("One of --genomes/-g, --draft, --ncbi/-k is required")
         sys.exit(1)
     genome_file = output + ".iss.tmp.genomes.fasta"
-    concatenate(list(genomes or []) + list(draft or []), genome_file)
-    records = list(parse_fasta(genome_file))
+    concatenate(list(genomes or []) + list(draft or []), genome_file, True if device_fasta else None)
+
+    def read():
+        if device_fasta:
+            from . import fasta
+
+            return fasta.read(genome_file, device=0)
+        return list(parse_fasta(genome_file))
+
+    records = read()
     if n_genomes and not draft:
         keep = reservoir_indices(len(records), n_genomes, rng if rng is not None else random.Random())
-        records = [records[i] for i in keep]
+        # (the letters as str before the file they stand in is written anew)
+        records = [type(r)(str(r.seq), id=r.id, description=r.description) if device_fasta else r for r in (records[i] for i in keep)]
         write_fasta(records, genome_file)
-        records = list(parse_fasta(genome_file))
+        records = read()
     return genome_file, records
 
 

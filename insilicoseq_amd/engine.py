@@ -121,6 +121,53 @@ class ReadEngine(object):
                 self._genome_lengths.append(int(a.size))
         return ids.tolist()
 
+    def add_genomes_fasta(self, seqs):
+        """Upload records as they stand in their FASTA file (``seqs``: fasta.FastaSeq): the bytes go to the device with their line
+        ends, which are removed there (iss_genome_upload_fasta).  A call of the library takes a run of records of one file in file
+        order (fasta.upload_runs) and sends the span from the first body to the last; its records of at most 2^20 letters become
+        one group like add_genomes', a larger record is a call of its own.  Returns the genome ids, -1 like add_genomes."""
+        from .fasta import upload_runs
+
+        if not hasattr(self._lib, "iss_genome_upload_fasta"):
+            raise _native.NativeLibraryError("%s has no iss_genome_upload_fasta: rebuild it" % _native.LIB_PATH)
+        ids = []
+        for first, last in [cut for run in upload_runs(seqs) for cut in self._cut_at_large(seqs, *run)]:
+            run = seqs[first:last]
+            base, end = run[0].body_off, run[-1].body_off + run[-1].body_len
+            ids.extend(self.add_genomes_fasta_table(run[0].source.array[base:end], [s.body_off - base for s in run],
+                                                    [s.body_len for s in run], [s.letters for s in run]))
+        return ids
+
+    @staticmethod
+    def _cut_at_large(seqs, first, last):
+        """[first, last) cut so that a record of more than 2^20 letters stands alone."""
+        cuts, at = [], first
+        for k in range(first, last):
+            if seqs[k].letters > (1 << 20):
+                if k > at:
+                    cuts.append((at, k))
+                cuts.append((k, k + 1))
+                at = k + 1
+        if last > at:
+            cuts.append((at, last))
+        return cuts
+
+    def add_genomes_fasta_table(self, span, body_off, body_len, letters):
+        """iss_genome_upload_fasta as it is: ``span`` (bytes or a uint8 array) and the table of its records, offsets relative to it."""
+        a = span if isinstance(span, np.ndarray) else np.frombuffer(span, dtype=np.uint8)
+        body_off, body_len, letters = (np.ascontiguousarray(x, dtype=np.int64) for x in (body_off, body_len, letters))
+        n = body_off.size
+        if not (body_len.size == letters.size == n):
+            raise ValueError("the table's arrays differ in length")
+        ids = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.iss_genome_upload_fasta(self._ctx, a.ctypes.data if a.size else None, a.size, n, body_off.ctypes.data,
+                                                      body_len.ctypes.data, letters.ctypes.data, ids.ctypes.data))
+        for gid, length in zip(ids.tolist(), letters.tolist()):
+            if gid >= 0:
+                assert gid == len(self._genome_lengths)
+                self._genome_lengths.append(int(length))
+        return ids.tolist()
+
     def add_genome_packed(self, codes, length, device_ptr=None):
         """Upload a record of plain A/C/G/T given as 2-bit codes (see distributed.pack_2bit): ``codes`` a uint32 array
         on the host, or ``device_ptr`` the address of the words in this GPU's memory (a slice of the broadcast buffer)."""

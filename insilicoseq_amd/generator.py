@@ -59,6 +59,34 @@ def _parse_fasta_lines(fh):
         yield Record("".join(chunks), id=(header.split(None, 1) or [""])[0], description=header)
 
 
+def body_letters(body):
+    """The sequence of a record's body (bytes): its line ends removed in one pass; a body with white space inside a line goes
+    through the line-by-line form."""
+    if b" " in body or b"\t" in body or b"\x0b" in body or b"\x0c" in body:
+        return "".join(line.strip() for line in body.decode().splitlines())
+    return body.translate(None, b"\r\n").decode()
+
+
+def read_genome_bytes(path, device_inflate=None):
+    """The bytes of a genome file; one that starts with the gzip magic is inflated.  A BGZF file goes through the device inflater
+    (inflate.inflate_file) when ``device_inflate`` (None: ISS_DEVICE_INFLATE=1 in the environment); any other gzip file, and every
+    file when ISS_HOST_INFLATE=1 is set, is inflated with ``gzip``."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:2] != b"\x1f\x8b":
+        return data
+    if device_inflate is None:
+        device_inflate = os.environ.get("ISS_DEVICE_INFLATE", "") == "1"
+    if device_inflate and os.environ.get("ISS_HOST_INFLATE", "") != "1":
+        from . import inflate
+
+        if inflate.is_bgzf(path):
+            return b"".join(piece.tobytes() for piece in inflate.inflate_file(path))
+    import gzip
+
+    return gzip.decompress(data)
+
+
 def parse_fasta(path_or_handle):
     """FASTA -> Records; id = first whitespace-separated token of the header, sequence case-preserved
     (what Bio.SeqIO.parse(..., 'fasta') yields; pinned by iss/test/test_util.py:41-45).  A file given by path is cut
@@ -67,8 +95,7 @@ def parse_fasta(path_or_handle):
     if not isinstance(path_or_handle, (str, bytes, os.PathLike)):
         yield from _parse_fasta_lines(path_or_handle)
         return
-    with open(path_or_handle, "rb") as fh:
-        data = fh.read()
+    data = read_genome_bytes(path_or_handle)
     starts = []  # offsets of the '>' of every header line
     at = 0 if data.startswith(b">") else data.find(b"\n>") + 1
     while at > 0 or (at == 0 and data.startswith(b">") and not starts):
@@ -83,12 +110,7 @@ def parse_fasta(path_or_handle):
         if eol < 0:
             eol = end
         header = data[start + 1:eol].decode().rstrip("\r\n")
-        body = data[eol + 1:end]
-        if b" " in body or b"\t" in body or b"\x0b" in body or b"\x0c" in body:
-            seq = "".join(line.strip() for line in body.decode().splitlines())
-        else:
-            seq = body.translate(None, b"\r\n").decode()
-        yield Record(seq, id=(header.split(None, 1) or [""])[0], description=header)
+        yield Record(body_letters(data[eol + 1:end]), id=(header.split(None, 1) or [""])[0], description=header)
 
 
 def to_coverage(total_n_reads, species_abundance, read_length, genome_size):
@@ -173,6 +195,11 @@ def _seq_of(record):
     return seq if isinstance(seq, (str, bytes, bytearray, np.ndarray)) else str(seq)
 
 
+def _in_file(record):
+    """Is the record's ``seq`` a fasta.FastaSeq (--device_fasta): letters that stand in a file, uploaded as they stand there?"""
+    return hasattr(record.seq, "body_off")
+
+
 def _warn_short_record(eng, record):
     """True for a record not longer than the model's reads, with the reference's two warnings: its simulate_read fails an
     assertion and the record is skipped (iss/generator.py:77-80).  (An MT caller still consumes the reference's draw.)"""
@@ -248,6 +275,12 @@ class GenomeStore(object):
             if at is not None and self._plan[at] is record and len(record.seq) <= SMALL_RECORD:
                 self.upload_groups(self._plan[at:], one_group=True)
                 hit = self._hit(record)
+        if hit is None and _in_file(record) and hasattr(self.engine, "add_genomes_fasta"):
+            # --device_fasta: a large record, or one outside the groups, alone and as it stands in the file
+            hit = (record, self.engine.add_genomes_fasta([record.seq])[0])
+            if hit[1] >= 0:
+                self._gids[id(record)] = hit
+                self.resident += len(record.seq)
         if hit is None or hit[1] < 0:
             # a large record, one outside the groups, or one its group did not take (the upload raises its error here)
             seq = _seq_of(record)
@@ -265,10 +298,19 @@ class GenomeStore(object):
         size = group = 0  # letters picked by this call; letters of the group being filled
 
         def flush():
-            for record, seq, gid in zip(picked, seqs, self.engine.add_genomes(seqs)):
-                self._gids[id(record)] = (record, gid)
-                if gid >= 0:
-                    self.resident += len(seq)
+            # (--device_fasta: runs of records that stand in a file go as they stand there, each run a group of its own)
+            at = 0
+            while at < len(picked):
+                end = at + 1
+                while end < len(picked) and _in_file(picked[end]) == _in_file(picked[at]):
+                    end += 1
+                run = seqs[at:end]
+                gids = self.engine.add_genomes_fasta(run) if _in_file(picked[at]) else self.engine.add_genomes(run)
+                for record, seq, gid in zip(picked[at:end], run, gids):
+                    self._gids[id(record)] = (record, gid)
+                    if gid >= 0:
+                        self.resident += len(seq)
+                at = end
             del picked[:], seqs[:]
 
         for record in records:
@@ -278,7 +320,7 @@ class GenomeStore(object):
                 continue  # (skipped by the work loop: never uploaded)
             if self._spliced(record) is not None:
                 continue  # (spliced on the device, alone: through gid())
-            seq = _seq_of(record)
+            seq = record.seq if _in_file(record) else _seq_of(record)
             if len(seq) > SMALL_RECORD:
                 continue
             # (`resident` holds the groups flushed so far and `size` counts them again: a call that makes several groups stops

@@ -310,7 +310,10 @@ def with_haplotypes(records, tables):
     """The records with the ``seq`` of those that have a table replaced by a HaplotypeSeq (new Record objects; the rest as they are)."""
     from .generator import Record
 
-    return [Record(HaplotypeSeq(r.seq, tables[r.id]), id=r.id, description=getattr(r, "description", "")) if r.id in tables else r
+    def letters(seq):  # (--device_fasta: a record with variants materialises its letters on the host, fasta.FastaSeq.__str__)
+        return str(seq) if hasattr(seq, "body_off") else seq
+
+    return [Record(HaplotypeSeq(letters(r.seq), tables[r.id]), id=r.id, description=getattr(r, "description", "")) if r.id in tables else r
             for r in records]
 
 
