@@ -895,6 +895,41 @@ int64_t iss_br_error_words(const iss_br *br);
 int iss_br_errors_download(iss_br *br, uint64_t *words, int64_t *counts /* [4] */, int64_t *bad_record, int32_t *bad_code);
 
 /*
+ * `report --bam --depth`: where an aligned BAM's reads fall on the references, as their CIGARs tell it, marked ON THE DEVICE by a
+ * fourth stage of the context above (additive in ABI 8) into the CALLER's accumulator in iss_depth_*'s layout:
+ * d_table is device memory, int64 [n_table][2] of (offset, length), row = refID; d_diff the int32 difference array the rows point
+ * into, zeroed by the caller, 4-byte aligned.  iss_depth_finish makes depths, statistics and window sums of it.  The context keeps
+ * nothing but the two pointers: both arrays have to live until the last download, and the entry CANNOT check that every row's
+ * length + 1 words lie inside the array -- that is the caller's to see to.
+ * A record the read tally took (good, mate 0 or 1, neither secondary nor supplementary) counts once, the first that applies:
+ *   counts[1]  not aligned: 0x4 set, n_cigar_op == 0 or refID < 0
+ *   counts[2]  filtered: 0x200 or 0x400 set
+ *   counts[3]  mapq < min_mapq
+ * -- `samtools depth`'s default filter without the supplementary records, which the context skips anyway -- and is otherwise
+ * validated completely before any word is touched, the first ISS_BR_DEPTH_* code that applies deciding; a record whose row has
+ * offset < 0 (checked behind _CIGAR and _REF; its length is not looked at) adds 1 to counts[4] and marks nothing.  A bad record adds
+ * nothing, to no count either, and the smallest (record index over all records fed) << 8 | code is kept.  A valid record adds 1 to
+ * counts[0] (marked) and is walked with a reference cursor that starts at pos: M, = and X cover [cursor, cursor + len) and advance;
+ * D advances, and covers only with ISS_BR_DEPTH_COUNT_DEL; N advances and never covers; I, S, H and P do nothing.  Every covered run
+ * adds +1 at offset + start and -1 at offset + end, and its length to counts[5] (covered bases).  A record's runs are disjoint, so it
+ * adds at most 1 to a base: while the stage is on iss_br_feed refuses (ISS_E_INVALID, nothing launched) the records that would take
+ * the records fed past 2^31 - 1.  All results are exact integers, independent of the launch geometry (ISS_BR_WGS) and of how the
+ * records were cut into feeds.
+ * iss_br_depth_enable is allowed only while nothing has been fed since the context was created or reset (ISS_E_INVALID afterwards,
+ * nothing changed); also ISS_E_INVALID: NULL or misaligned pointers, n_table < 1, flag bits other than ISS_BR_DEPTH_COUNT_DEL,
+ * min_mapq outside 0 .. 255.  Enabling again (before a feed) replaces the pointers and zeroes the counts.  From then on every feed
+ * runs the stage, and the feeds' kernel time includes it.  iss_br_reset zeroes the counts and the first-bad word; it leaves the
+ * caller's array alone and the stage on.  iss_br_depth_download (ISS_E_INVALID for NULL arguments or while the stage is off) waits
+ * for everything fed: when it returns the array is complete, and work on any other stream -- iss_depth_finish -- may read it.
+ */
+#define ISS_BR_DEPTH_COUNT_DEL 1u /* flags: the bases of a D count as covered */
+#define ISS_BR_DEPTH_CIGAR 1 /* an op code above 8 */
+#define ISS_BR_DEPTH_REF 2   /* refID >= n_table */
+#define ISS_BR_DEPTH_SPAN 3  /* pos < 0, or pos + the lengths of M, D, N, =, X (summed in 64 bits) > the row's length */
+int iss_br_depth_enable(iss_br *br, const int64_t *d_table, int32_t n_table, int32_t *d_diff, uint32_t flags, int32_t min_mapq);
+int iss_br_depth_download(iss_br *br, int64_t *counts /* [6] */, int64_t *bad_record, int32_t *bad_code);
+
+/*
  * `generate --variants`: a record with a VCF's alleles spliced in ON THE DEVICE, in front of the pack kernel (additive in ABI 8;
  * DESIGN.md section 30).  The tables of a record of `length` letters with n variants, sorted and disjoint (pos0[i + 1] >= pos0[i] +
  * ref_len[i]; no two pure insertions at one pos0; none empty; none past the record's end):

@@ -41,6 +41,7 @@ EXPORTS = (
     "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
     "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
     "iss_br_kernel_ms", "iss_br_errors_enable", "iss_br_error_words", "iss_br_errors_download",
+    "iss_br_depth_enable", "iss_br_depth_download",
     "iss_mt_resolver_pick",
     "iss_genome_upload_variants", "iss_genome_download", "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply",
     "iss_variants_host_lift",
@@ -83,6 +84,11 @@ BR_ALN_ERRORS = {
     1: "CIGAR with an unknown operation, or one that does not add up to the read's length",
     2: "malformed optional fields", 3: "MD tag does not fit the CIGAR",
 }
+BR_DEPTH_ERRORS = {  # `report --bam --depth` (ISS_BR_DEPTH_*)
+    1: "CIGAR with an unknown operation", 2: "reference index past the header's references",
+    3: "alignment that starts before or ends past its reference",
+}
+BR_DEPTH_COUNT_DEL = 1
 
 
 # the device inflate (include/iss_mi355x.h: ISS_BGZF_*)
@@ -233,6 +239,10 @@ def lib():
         L.iss_br_errors_enable.argtypes = [vp]
         L.iss_br_error_words.argtypes = [vp]
         L.iss_br_errors_download.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
+    # (and the alignments' reference intervals behind `report --bam`; without them BamReadTally(depth=True) raises)
+    if hasattr(L, "iss_br_depth_enable"):
+        L.iss_br_depth_enable.argtypes = [vp, vp, i32, vp, C.c_uint32, i32]
+        L.iss_br_depth_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
     if hasattr(L, "iss_inflate_feed"):
         L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
         L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]

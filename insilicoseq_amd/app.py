@@ -675,6 +675,8 @@ def report_from_fastq(args):
         return fail("report --errors reads the alignments of a BAM file: it goes with --bam")
     if getattr(args, "against_errors", None) and not getattr(args, "errors", False):
         return fail("report --against_errors compares the --errors tally: add --errors")
+    if _report_depth_wanted(args) and not bam:
+        return fail("report --depth reads the alignments of a BAM file: it goes with --bam")
     if bam:
         if args.read2:
             return fail("report --bam takes no -2: the mates of a BAM file are told apart by their flags")
@@ -764,12 +766,40 @@ def _report_write_errors(args, res, against):
             fh.write("\n")
 
 
+def _report_depth_wanted(args):
+    """--depth of `report`, or one of the flags that imply it (--depth_bin) or only make sense with it."""
+    return bool(getattr(args, "depth", False)) or getattr(args, "depth_bin", None) is not None \
+        or bool(getattr(args, "depth_deletions", False)) or getattr(args, "min_mapq", None) is not None \
+        or bool(getattr(args, "against_depth", None))
+
+
+def _report_write_depth(args, dres, bin, other):
+    """The files of --depth from BamReadTally.depth_result(): <prefix>_depth.txt and, with a bin, <prefix>_depth.bedgraph -- byte
+    compatible with `generate --depth`'s --, <prefix>_coverage.txt for `generate --coverage_file` and, with ``other`` (a
+    bam_depth.read_depth_table dict), <prefix>_depth_compare.json."""
+    import json
+
+    from . import bam_depth
+    from . import depth as D
+
+    rows = D.depth_rows(dres["stats"], dres["table"], dres["ids"])
+    D.write_depth_table(args.output + "_depth.txt", rows)
+    if bin > 0:
+        D.write_bedgraph(args.output + "_depth.bedgraph", dres["bins"], dres["table"], dres["ids"], bin)
+    bam_depth.write_coverage_file(args.output + "_coverage.txt", bam_depth.coverage_rows(dres["stats"], dres["table"], dres["ids"]))
+    if other is not None:
+        mine = {row[0]: tuple(row[1:]) for row in rows}
+        with open(args.output + "_depth_compare.json", "w") as fh:
+            json.dump(bam_depth.compare_depth_tables(mine, other), fh, indent=1)
+            fh.write("\n")
+
+
 def _report_from_bam(args, logger):
     """`report --bam`: the reads of a BAM file, insert sizes included (bam_report.py).  The BGZF blocks are inflated in the host
     pool unless --device_inflate or ISS_DEVICE_INFLATE=1 asks for the device; ISS_HOST_INFLATE=1 wins over both.  With --errors
-    also the alignments' errors (bam_errors.py)."""
-    from . import bam_report
-    from ._native import BR_ALN_ERRORS, BR_REC_ERRORS, EngineError, NativeLibraryError
+    also the alignments' errors (bam_errors.py), with --depth the coverage depth of the references (bam_depth.py)."""
+    from . import bam_depth, bam_report
+    from ._native import BR_ALN_ERRORS, BR_DEPTH_ERRORS, BR_REC_ERRORS, EngineError, NativeLibraryError
     from .bam import BamError
     from .inflate import InflateError
     from .modeller import device_inflater
@@ -785,20 +815,45 @@ def _report_from_bam(args, logger):
             *against, message = _report_against_errors(args, other, other_length)
             if message:
                 return fail(message)
+        more = {"errors": True} if errors else {}  # (without the flags: the call as it was)
+        depth, depth_bin, other_depth = _report_depth_wanted(args), int(getattr(args, "depth_bin", None) or 0), None
+        if depth:
+            min_mapq = int(getattr(args, "min_mapq", None) or 0)
+            if getattr(args, "depth_bin", None) is not None and depth_bin < 1:
+                return fail("--depth_bin must be positive")
+            if not 0 <= min_mapq <= 255:
+                return fail("--min_mapq outside 0 .. 255")
+            if getattr(args, "against_depth", None):
+                try:
+                    other_depth = bam_depth.read_depth_table(args.against_depth)  # (before the GPU is opened)
+                except (OSError, ValueError) as e:
+                    return fail("%s: %s" % (args.against_depth, str(e).splitlines()[0] if str(e) else type(e).__name__))
+            more.update(depth=True, depth_flags=bam_depth.COUNT_DEL if getattr(args, "depth_deletions", False) else 0, min_mapq=min_mapq)
         t0 = time.perf_counter()
-        with bam_report.BamReadTally(args.device, args.max_length, **({"errors": True} if errors else {})) as dev, \
+        with bam_report.BamReadTally(args.device, args.max_length, **more) as dev, \
                 device_inflater(args.device, True if args.device_inflate else None) as inflater:
             logger.info("Tallying %s" % args.bam)
             dev.feed_file(args.bam, inflater)
             res = dev.result()
+            dres = dev.depth_result(depth_bin) if depth else None
         logger.info("%d + %d records in %.2f s" % (res["records"][0], res["records"][1], time.perf_counter() - t0))
         if res["bad_record"] >= 0:
             code = res["bad_code"]
             return fail("%s: record %d: %s" % (args.bam, res["bad_record"], BR_REC_ERRORS.get(code, "error %d" % code)))
         if res["records"][1] and res["records"][0] != res["records"][1]:  # (a filtered BAM: normal)
             logger.warning("%s holds %d first and %d second reads" % (args.bam, res["records"][0], res["records"][1]))
-        _report_write(args, res, other, other_length,
-                      {"records_skipped": {"secondary_or_supplementary": int(res["skipped"][0]), "mate_flags": int(res["skipped"][1])}})
+        keys = {"records_skipped": {"secondary_or_supplementary": int(res["skipped"][0]), "mate_flags": int(res["skipped"][1])}}
+        if depth:
+            keys["depth"] = bam_depth.counts_dict(dres["depth_counts"])
+            keys["depth"]["bad_record"] = {"record": int(dres["bad_depth_record"]), "code": int(dres["bad_depth_code"])}
+        _report_write(args, res, other, other_length, keys)
+        if depth:
+            if dres["bad_depth_record"] >= 0:  # (one odd record must not cost the user the report)
+                code = dres["bad_depth_code"]
+                logger.warning("%s: record %d: %s (%d records are in neither the depth nor its counts)"
+                               % (args.bam, dres["bad_depth_record"], BR_DEPTH_ERRORS.get(code, "error %d" % code),
+                                  res["records"][0] + res["records"][1] - sum(dres["depth_counts"][:5])))
+            _report_write_depth(args, dres, depth_bin, other_depth)
         if errors:
             if res["bad_alignment"] >= 0:  # (one odd record must not cost the user the report: the counts are in the json)
                 code = res["bad_alignment_code"]
@@ -932,6 +987,22 @@ def build_parser():
                    help="with --errors: also write <prefix>_errors_compare.json, these errors against another error tally (of generate "
                         "--error_report, or of report --bam --errors); the other side's denominators come from --against "
                         "OTHER_tally.npy when given, else from OTHER_errbases.npy beside the file, else its pairs")
+    r.add_argument("--depth", action="store_true",
+                   help="with --bam: also mark where the alignments fall on the references, on the GPU, as their CIGARs tell it -- "
+                        "<prefix>_depth.txt (per reference of the header: id, length, mean_depth, depth_variance, covered_fraction, "
+                        "max_depth; the file generate --depth writes), <prefix>_coverage.txt (id and mean depth: what generate "
+                        "--coverage_file reads) and the counts under `depth` in <prefix>_report.json.  Counted: the records the "
+                        "tally takes that are aligned, with 0x200 and 0x400 clear (samtools depth's default filter; supplementary "
+                        "records are skipped anyway); M, = and X cover, N never does")
+    r.add_argument("--depth_bin", type=int, default=None, metavar="N",
+                   help="with --depth (implied): also <prefix>_depth.bedgraph, the mean depth of every N-base window of every reference")
+    r.add_argument("--depth_deletions", action="store_true", help="with --depth (implied): the bases of a D count as covered too")
+    r.add_argument("--min_mapq", type=int, default=None, metavar="Q",
+                   help="with --depth (implied): leave out the records whose mapping quality is below Q (0 .. 255, default 0)")
+    r.add_argument("--against_depth", default=None, metavar="OTHER_depth.txt",
+                   help="with --depth (implied): also write <prefix>_depth_compare.json, this depth table against another (of generate "
+                        "--depth, or of report --bam --depth): per id the differences of mean depth and covered fraction, their "
+                        "maxima, the total-variation distance of the normalised mean depths, the ids only one side has")
     r.add_argument("--max_length", type=int, default=1024, metavar="N", help="longest read taken (1 .. 1024, default 1024)")
     r.add_argument("--device", type=int, default=0, help="GPU ordinal")
     r.add_argument("--quiet", "-q", action="store_true")

@@ -173,12 +173,26 @@ class BamReadTally(_native.Session):
 
     PREFIX = "iss_br"
 
-    def __init__(self, device=0, max_len=MAX_LEN, errors=False):
+    def __init__(self, device=0, max_len=MAX_LEN, errors=False, depth=False, depth_flags=0, min_mapq=0):
         """``errors``: also tally the alignments' errors (bam_errors.py; iss_br_errors_enable) -- download() and result() then
-        hold ``errors``, ``error_counts``, ``bad_alignment`` and ``bad_alignment_code`` as well."""
+        hold ``errors``, ``error_counts``, ``bad_alignment`` and ``bad_alignment_code`` as well.  ``depth``: also mark the
+        alignments' reference intervals into a difference array on the device (bam_depth.py; iss_br_depth_enable) with
+        ``depth_flags`` (bam_depth.COUNT_DEL) and ``min_mapq`` -- feed_file() takes the references from the file's header, feed()
+        needs set_depth_table() first, and depth_result() finishes.  download() and result() do not change with it."""
         self.max_len = int(max_len)
         self.errors = bool(errors)
+        self.depth = bool(depth)
+        self.depth_flags, self.min_mapq = int(depth_flags), int(min_mapq)
+        self.references = None  # the (name, length) list the accumulator was laid out for
+        self._depth_table = self._d_table = self._d_diff = None
+        if self.depth:
+            from .tensors import _torch
+
+            self._torch = _torch()  # (the accumulator is torch tensors: torch's HIP runtime has to be the process's first)
         _native.Session.__init__(self, device, self.max_len)
+        if self.depth and not hasattr(self._lib, "iss_br_depth_enable"):
+            self.close()
+            raise _native.NativeLibraryError("%s has no iss_br_depth_* entries: rebuild it" % _native.LIB_PATH)
         if self.errors:
             if not hasattr(self._lib, "iss_br_errors_enable"):
                 self.close()
@@ -197,9 +211,88 @@ class BamReadTally(_native.Session):
                                           offs.ctypes.data if offs.size else None, offs.size))
 
     def feed_file(self, path, inflater=None, chunk_bytes=64 << 20, threads=None):
-        """Every record of a BAM file; ``inflater``: an inflate.BgzfInflater for its BGZF blocks (None: the host pool)."""
-        for chunk in BamReader(path, chunk_bytes, threads, inflater).chunks():
+        """Every record of a BAM file; ``inflater``: an inflate.BgzfInflater for its BGZF blocks (None: the host pool).  With
+        ``depth`` the file's references lay out the accumulator (a file without records too); a further file has to carry the
+        same references."""
+        reader = BamReader(path, chunk_bytes, threads, inflater)
+        first = self.depth
+        for chunk in reader.chunks():
+            if first:
+                self.set_depth_table(reader.references)
+                first = False
             self.feed(chunk)
+        if first:
+            self.set_depth_table(reader.references)
+
+    def set_depth_table(self, references):
+        """The (name, length) list of the references the records' refID index: lays out depth.depth_table of the lengths, allocates
+        and zeroes the accumulator on the device and enables the stage.  Before the first feed; the same list again changes
+        nothing, another one is an EngineError."""
+        if not self.depth:
+            raise _native.EngineError(_native.E_INVALID, "set_depth_table: the context was made without depth=True")
+        references = [(str(name), int(length)) for name, length in references]
+        if self.references is not None:
+            if references != self.references:
+                raise _native.EngineError(_native.E_INVALID, "the BAM files fed into one depth accumulator differ in their references")
+            return
+        if not references:
+            raise _native.EngineError(_native.E_INVALID, "no references in the BAM header: nothing to lay the depth out on")
+        from .depth import depth_table
+
+        torch = self._torch
+        table, n_words = depth_table([length for _name, length in references])
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            self._d_table = torch.from_numpy(table).to(dev)
+            self._d_diff = torch.zeros(n_words, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()  # (made on torch's stream; the context works on its own)
+        self._check(self._lib.iss_br_depth_enable(self._h, C.c_void_p(self._d_table.data_ptr()), table.shape[0],
+                                                  C.c_void_p(self._d_diff.data_ptr()), self.depth_flags, self.min_mapq))
+        self.references, self._depth_table = references, table
+
+    def reset(self):
+        """iss_br_reset; with ``depth`` the accumulator (this object's) is zeroed too, the table and the stage stay."""
+        _native.Session.reset(self)
+        if self._d_diff is not None:
+            with self._torch.cuda.device(self.device):
+                self._d_diff.zero_()
+                self._torch.cuda.synchronize()
+
+    def depth_download(self):
+        """Waits for everything fed -> ``depth_counts`` (bam_depth.COUNT_NAMES), ``bad_depth_record`` (-1: none), ``bad_depth_code``."""
+        if self.references is None:
+            raise _native.EngineError(_native.E_INVALID, "depth: no table yet (feed_file or set_depth_table first)")
+        counts, bad, code = (C.c_int64 * 6)(), C.c_int64(), C.c_int32()
+        self._check(self._lib.iss_br_depth_download(self._h, C.addressof(counts), C.byref(bad), C.byref(code)))
+        return {"depth_counts": list(counts), "bad_depth_record": bad.value, "bad_depth_code": code.value}
+
+    def depth_diff(self):
+        """The difference array as it stands, downloaded (int32; waits for everything fed)."""
+        self.depth_download()
+        return self._d_diff.cpu().numpy()
+
+    def depth_result(self, bin=0):
+        """The stage downloaded, then its accumulator finished on the device through a bare ReadEngine (depth_finish): ``stats``
+        uint64 [n, 4] (depth.STATS_FIELDS), ``bins`` (uint64 window sums, None without ``bin``), ``table``, ``ids``,
+        ``depth_counts``, ``bad_depth_record``, ``bad_depth_code``.  The accumulator stays as it is: more may be fed."""
+        from .depth import n_windows
+        from .engine import ReadEngine
+
+        out = self.depth_download()  # (the wait that orders the engine's stream behind the feeds)
+        torch, table, n = self._torch, self._depth_table, len(self.references)
+        n_bins = int(n_windows(table, bin).sum())
+        with ReadEngine(self.device) as eng, torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_stats = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            d_bins = torch.empty(max(n_bins, 1), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            eng.depth_finish(self._d_diff.data_ptr(), self._d_diff.numel(), None, self._d_table.data_ptr(), n, int(bin), d_stats.data_ptr(),
+                             d_bins.data_ptr() if n_bins else None)
+            eng.synchronize()
+            stats = d_stats.cpu().numpy().view(np.uint64)
+            bins = d_bins.cpu().numpy().view(np.uint64)[:n_bins] if int(bin) > 0 else None
+        out.update(stats=stats, bins=bins, table=table.copy(), ids=[name for name, _length in self.references])
+        return out
 
     def download(self):
         """The twin's dict from the device: ``tally`` at max_len, ``records``, ``skipped``, ``bad_record``, ``bad_code``."""

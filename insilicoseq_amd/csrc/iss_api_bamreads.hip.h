@@ -3,6 +3,7 @@
 // stream, and the kernels of iss_bamreads.hip.h follow on the kernel stream: the copy of chunk i + 1 overlaps the kernels of chunk i.
 // No model, no iss_ctx: a session (iss_host_session.hip.h: open and close, the two timed slots, grown buffers, the first-bad word).
 // With iss_br_errors_enable a third stage follows in every feed: the alignments' errors (iss_bamerrors.hip.h), words of their own.
+// With iss_br_depth_enable a fourth: the alignments' reference intervals marked into the caller's difference array (iss_bamdepth.hip.h).
 #pragma once
 
 struct iss_br : iss_session {
@@ -22,6 +23,12 @@ struct iss_br : iss_session {
     bool errors = false;                 // iss_br_errors_enable: every feed also runs k_be_records and k_be_bases
     DevMem<unsigned long long> d_err;    // be_words(max_len), then BeState
     Grown<DevMem<unsigned long long>> marks;  // [records][ceil(max_len / 64)] of the feed in flight: k_be_records' aligned columns
+    bool depth = false;                  // iss_br_depth_enable: every feed also runs k_bd_records
+    DevMem<iss::bd::BdState> d_depth;    // its counts and first-bad word
+    const int64_t *depth_table = nullptr;  // the caller's device memory, both: nothing but the pointers is kept
+    int32_t *depth_diff = nullptr;
+    int32_t depth_n_table = 0;
+    uint32_t depth_flags = 0, depth_min_mapq = 0;
 };
 
 static_assert(iss::br::BR_MAX_LEN == ISS_BR_MAX_LEN && ISS_BR_MAX_LEN == ISS_FQ_MAX_LEN, "include/iss_mi355x.h: ISS_BR_MAX_LEN");
@@ -32,6 +39,9 @@ static_assert(iss::br::BR_MAX_LEN <= (int)iss::br::BR_D_LEN, "a descriptor holds
 static_assert(iss::be::BE_ALN_CIGAR == ISS_BR_ALN_CIGAR && iss::be::BE_ALN_TAGS == ISS_BR_ALN_TAGS && iss::be::BE_ALN_MD == ISS_BR_ALN_MD,
               "include/iss_mi355x.h: ISS_BR_ALN_*");
 static_assert(sizeof(iss::be::BeState) % sizeof(unsigned long long) == 0, "BeState stands behind the error words");
+static_assert(iss::bd::BD_CIGAR == ISS_BR_DEPTH_CIGAR && iss::bd::BD_REF == ISS_BR_DEPTH_REF && iss::bd::BD_SPAN == ISS_BR_DEPTH_SPAN &&
+                  iss::bd::BD_COUNT_DEL == ISS_BR_DEPTH_COUNT_DEL,
+              "include/iss_mi355x.h: ISS_BR_DEPTH_*");
 
 // room for a chunk of n_bytes and n_records in slot s and in the array of the feed in flight; waits for the device only when it has to free
 static int br_reserve(iss_br *f, iss_br::Slot &s, size_t n_bytes, size_t n_records) {
@@ -52,6 +62,14 @@ static int br_errors_clear(iss_br *f) {
     HIP_TRY(f, hipMemsetAsync(f->d_err, 0, sizeof(unsigned long long) * words + sizeof(iss::be::BeState), f->stream));
     HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_err + words) + offsetof(iss::be::BeState, bad), 0xFF,
                              sizeof(unsigned long long), f->stream));
+    return 0;
+}
+
+// the depth stage's counts zeroed, its first-bad word all ones (on the kernel stream; the caller waits)
+static int br_depth_clear(iss_br *f) {
+    HIP_TRY(f, hipMemsetAsync(f->d_depth, 0, sizeof(iss::bd::BdState), f->stream));
+    HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_depth.get()) + offsetof(iss::bd::BdState, bad), 0xFF, sizeof(unsigned long long),
+                             f->stream));
     return 0;
 }
 
@@ -92,6 +110,7 @@ int iss_br_reset(iss_br *f) {
     HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_tally + words) + offsetof(iss::br::BrState, bad), 0xFF,
                              sizeof(unsigned long long), f->stream));
     if (f->errors) ISS_TRY(br_errors_clear(f));
+    if (f->depth) ISS_TRY(br_depth_clear(f));  // (the caller's array stays as it is, and the stage on)
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (iss_br::Slot &s : f->slot) s.busy = false;
     f->fed = 0;
@@ -104,6 +123,8 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
         return fail(f, ISS_E_INVALID, "iss_br_feed: bad arguments");
     if (n_bytes >= ((int64_t)1 << 31)) return fail(f, ISS_E_INVALID, "iss_br_feed: chunks are limited to 2^31 - 1 bytes");
     if (!n_records) return 0;
+    if (f->depth && n_records > (int64_t)0x7fffffff - f->fed)  // (a record adds at most 1 to a base: the depths stay below 2^31)
+        return fail(f, ISS_E_INVALID, "iss_br_feed: more than 2^31 - 1 records fed while the depth stage is on");
     // every record must lie inside the chunk: the kernels trust these offsets (iss_bam_scan makes them, ascending)
     int64_t before = -1;
     for (int64_t r = 0; r < n_records; ++r) {
@@ -161,6 +182,18 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
         hipLaunchKernelGGL(iss::be::k_be_bases, dim3(plan.pos_tiles, plan.pos_chunks), dim3(iss::be::BE_THREADS), 0, f->stream, E);
         HIP_TRY(f, hipGetLastError());
     }
+    if (f->depth) {
+        iss::bd::BdArgs D{};
+        D.R = A;
+        D.table = f->depth_table;
+        D.diff = f->depth_diff;
+        D.state = f->d_depth;
+        D.n_table = f->depth_n_table;
+        D.flags = f->depth_flags;
+        D.min_mapq = f->depth_min_mapq;
+        hipLaunchKernelGGL(iss::bd::k_bd_records, dim3(iss::bd::bd_record_wgs(n_records, wgs)), dim3(iss::bd::BD_THREADS), 0, f->stream, D);
+        HIP_TRY(f, hipGetLastError());
+    }
     HIP_TRY(f, hipEventRecord(s.done, f->stream));
     s.busy = true;
     ++f->feeds;
@@ -208,6 +241,39 @@ int iss_br_errors_download(iss_br *f, uint64_t *words, int64_t *counts, int64_t 
     HIP_TRY(f, hipMemcpyAsync(&st, f->d_err + n, sizeof(st), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (int k = 0; k < 4; ++k) counts[k] = (int64_t)st.counts[k];
+    bad_word_split(st.bad, bad_record, bad_code);
+    return 0;
+}
+
+int iss_br_depth_enable(iss_br *f, const int64_t *d_table, int32_t n_table, int32_t *d_diff, uint32_t flags, int32_t min_mapq) {
+    if (!f) return fail(nullptr, ISS_E_INVALID, "iss_br_depth_enable: NULL");
+    if (f->fed) return fail(f, ISS_E_INVALID, "iss_br_depth_enable: records have been fed since the last reset");
+    if (!d_table || !d_diff || n_table < 1) return fail(f, ISS_E_INVALID, "iss_br_depth_enable: no table or no difference array");
+    if (flags & ~(uint32_t)ISS_BR_DEPTH_COUNT_DEL) return fail(f, ISS_E_INVALID, "iss_br_depth_enable: unknown flag bits");
+    if (min_mapq < 0 || min_mapq > 255) return fail(f, ISS_E_INVALID, "iss_br_depth_enable: min_mapq outside 0 .. 255");
+    if (reinterpret_cast<uintptr_t>(d_diff) % sizeof(int32_t) || reinterpret_cast<uintptr_t>(d_table) % sizeof(int64_t))
+        return fail(f, ISS_E_INVALID, "iss_br_depth_enable: misaligned table or difference array");
+    HIP_TRY(f, hipSetDevice(f->device));
+    if (!f->d_depth) DEV_ALLOC(f, f->d_depth, 1);
+    ISS_TRY(br_depth_clear(f));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    f->depth_table = d_table;
+    f->depth_diff = d_diff;
+    f->depth_n_table = n_table;
+    f->depth_flags = flags;
+    f->depth_min_mapq = (uint32_t)min_mapq;
+    f->depth = true;
+    return 0;
+}
+
+int iss_br_depth_download(iss_br *f, int64_t *counts, int64_t *bad_record, int32_t *bad_code) {
+    if (!f || !counts || !bad_record || !bad_code) return fail(f, ISS_E_INVALID, "iss_br_depth_download: bad arguments");
+    if (!f->depth) return fail(f, ISS_E_INVALID, "iss_br_depth_download: the depth stage is not enabled");
+    HIP_TRY(f, hipSetDevice(f->device));
+    iss::bd::BdState st;
+    HIP_TRY(f, hipMemcpyAsync(&st, f->d_depth, sizeof(st), hipMemcpyDeviceToHost, f->stream));  // (behind every kernel fed)
+    HIP_TRY(f, hipStreamSynchronize(f->stream));  // (the caller's array is complete: iss_depth_finish on any stream may follow)
+    for (int k = 0; k < 6; ++k) counts[k] = (int64_t)st.counts[k];
     bad_word_split(st.bad, bad_record, bad_code);
     return 0;
 }

@@ -57,6 +57,7 @@
 #include "iss_inflate.hip.h"    // k_bgzf_inflate: BGZF members inflated on the device (last, likewise)
 #include "iss_bamreads.hip.h"   // k_br_*: `report --bam`, the tallies of k_fq_* over BAM records (last, likewise)
 #include "iss_bamerrors.hip.h"  // k_be_*: `report --bam --errors`, the errors CIGAR and MD tell of (last, likewise)
+#include "iss_bamdepth.hip.h"   // k_bd_records: `report --bam --depth`, the reference intervals the CIGARs cover (last, likewise)
 #include "iss_variants.hip.h"   // k_variant_*: `generate --variants`, a record's haplotype spliced in front of k_pack_genome (last, likewise)
 #include "iss_fasta.hip.h"      // k_fa_*: `generate --device_fasta`, a FASTA text indexed and stripped in front of the pack kernels (last, likewise)
 
