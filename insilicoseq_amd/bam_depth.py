@@ -21,7 +21,7 @@ advances and never covers; I, S, H and P do nothing.  A covered run adds +1 at o
 to counts[5]."""
 import numpy as np
 
-from .bam_report import MAX_LEN, _as_chunks, _classify, _field
+from .bam_report import MAX_LEN, _COLUMN_OPS, _REF_OPS, _as_chunks, _cigar, _classify
 
 COUNT_DEL = 1
 DEPTH_CIGAR, DEPTH_REF, DEPTH_SPAN = 1, 2, 3
@@ -45,8 +45,7 @@ def mark_chunk_host(diff, chunk, table, flags=0, min_mapq=0, max_len=MAX_LEN):
     o = np.asarray(chunk.offsets, dtype=np.int64)
     c = _classify(chunk, int(max_len))
     taken = (c["code"] == 0) & (c["mate"] >= 0)
-    ref_id, pos = _field(a, o + 4, 4, True), _field(a, o + 8, 4, True)
-    l_name, mapq, n_cigar, flag = _field(a, o + 12, 1), _field(a, o + 13, 1), _field(a, o + 16, 2), _field(a, o + 18, 2)
+    ref_id, pos, mapq, n_cigar, flag = c["ref_id"], c["pos"], c["mapq"], c["n_cigar"], c["flag"]
     for r in np.flatnonzero(taken).tolist():
         if flag[r] & 4 or not n_cigar[r] or ref_id[r] < 0:
             counts[1] += 1
@@ -57,11 +56,9 @@ def mark_chunk_host(diff, chunk, table, flags=0, min_mapq=0, max_len=MAX_LEN):
         if mapq[r] < int(min_mapq):
             counts[3] += 1
             continue
-        at = int(o[r] + 36 + l_name[r])
-        words = a[at:at + 4 * int(n_cigar[r])].view("<u4").astype(np.int64)
-        ops, lens = (words & 15).tolist(), (words >> 4).tolist()
+        cigar = _cigar(a, o[r], c["l_name"][r], n_cigar[r])
         code = 0
-        if any(op > 8 for op in ops):
+        if any(op > 8 for op, _ in cigar):
             code = DEPTH_CIGAR
         elif ref_id[r] >= table.shape[0]:
             code = DEPTH_REF
@@ -70,7 +67,7 @@ def mark_chunk_host(diff, chunk, table, flags=0, min_mapq=0, max_len=MAX_LEN):
             if off < 0:
                 counts[4] += 1
                 continue
-            if pos[r] < 0 or int(pos[r]) + sum(ln for op, ln in zip(ops, lens) if op in (0, 2, 3, 7, 8)) > length:
+            if pos[r] < 0 or int(pos[r]) + sum(ln for op, ln in cigar if op in _REF_OPS) > length:
                 code = DEPTH_SPAN
         if code:
             if bad_record < 0:
@@ -78,12 +75,12 @@ def mark_chunk_host(diff, chunk, table, flags=0, min_mapq=0, max_len=MAX_LEN):
             continue
         counts[0] += 1
         cursor = int(pos[r])
-        for op, ln in zip(ops, lens):
-            if op in (0, 7, 8) or (op == 2 and int(flags) & COUNT_DEL):
+        for op, ln in cigar:
+            if op in _COLUMN_OPS or (op == 2 and int(flags) & COUNT_DEL):
                 diff[off + cursor] += 1
                 diff[off + cursor + ln] -= 1
                 counts[5] += ln
-            if op in (0, 2, 3, 7, 8):
+            if op in _REF_OPS:
                 cursor += ln
     return counts, bad_record, bad_code
 

@@ -15,13 +15,11 @@ import collections
 import numpy as np
 
 from . import errtally
-from .bam_report import MAX_LEN, _as_chunks, _classify
+from .bam_report import MAX_LEN, _COLUMN_OPS, _QUERY_OPS, _as_chunks, _cigar, _classify
 from .errtally import FIELDS as _ERR_FIELDS, LETTERS, PHREDS, READ_BINS, TYPES, _CODE_TABLE, _trim
 
 ALN_CIGAR, ALN_TAGS, ALN_MD = 1, 2, 3
 FIELDS = _ERR_FIELDS + ("bases",)
-_QUERY_OPS = (0, 1, 4, 7, 8)  # M, I, S, =, X: the operations that consume the read
-_COLUMN_OPS = (0, 7, 8)       # M, =, X: aligned columns, which MD describes
 _SCALAR_SIZE = {ord(c): n for c, n in (("A", 1), ("c", 1), ("C", 1), ("s", 2), ("S", 2), ("i", 4), ("I", 4), ("f", 4))}
 _ELEMENT_SIZE = {ord(c): n for c, n in (("c", 1), ("C", 1), ("s", 2), ("S", 2), ("i", 4), ("I", 4), ("f", 4))}
 _NIBBLE_CODE = [4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4]  # "=ACMGRSVTWYHKDBN"
@@ -161,18 +159,16 @@ def _complement(code):
     return 3 - code if code < 4 else 4
 
 
-def _tally_record(a, o, length, seq, qual, reverse, mate, L, t):
-    """One taken record: adds what it adds to the views t; "tallied", "unaligned", "no_md" or the ALN_* code."""
-    block_size = int.from_bytes(a[o:o + 4], "little", signed=True)
-    l_name, n_cigar = a[o + 12], int.from_bytes(a[o + 16:o + 18], "little")
-    flag = int.from_bytes(a[o + 18:o + 20], "little")
-    if flag & 4 or not n_cigar or not length:
+def _tally_record(a, o, c, r, L, t):
+    """One taken record -- r of the chunk's bytes a at offset o, c the chunk's _classify: adds what it adds to the views t;
+    "tallied", "unaligned", "no_md" or the ALN_* code."""
+    length, seq, qual, reverse, mate = int(c["len"][r]), int(c["seq"][r]), int(c["qual"][r]), bool(c["reverse"][r]), int(c["mate"][r])
+    if c["flag"][r] & 4 or not c["n_cigar"][r] or not length:
         return "unaligned"
-    at = o + 36 + l_name
-    cigar = [(c & 15, c >> 4) for c in (int.from_bytes(a[at + 4 * i:at + 4 * i + 4], "little") for i in range(n_cigar))]
+    cigar = _cigar(a, o, c["l_name"][r], c["n_cigar"][r])
     if any(op > 8 for op, _ in cigar) or sum(n for op, n in cigar if op in _QUERY_OPS) != length:
         return ALN_CIGAR
-    tags = _tag_walk(a, qual + length, o + 4 + block_size)
+    tags = _tag_walk(a, qual + length, o + 4 + int(c["block_size"][r]))
     if tags[0] != "md":
         return "no_md" if tags[0] == "none" else ALN_TAGS
     walk = _md_walk(cigar, a[tags[1]:tags[2]])
@@ -222,8 +218,7 @@ def bam_errors_host(chunks, max_len=MAX_LEN):
         c = _classify(chunk, L)
         for r in np.flatnonzero((c["code"] == 0) & (c["mate"] >= 0)):
             mate = int(c["mate"][r])
-            what = _tally_record(a, int(chunk.offsets[r]), int(c["len"][r]), int(c["seq"][r]), int(c["qual"][r]), bool(c["reverse"][r]),
-                                 mate, L, t)
+            what = _tally_record(a, int(chunk.offsets[r]), c, r, L, t)
             if what == "tallied":
                 counts[mate] += 1
             elif what == "unaligned":

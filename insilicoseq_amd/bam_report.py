@@ -29,6 +29,8 @@ MAX_LEN = _native.BR_MAX_LEN
 REC_SHORT, REC_TOO_LONG, REC_NO_QUAL, REC_QUAL_RANGE = 1, 2, 3, 4
 SEQ_LETTERS = np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)
 _COMPLEMENT = np.array([int("{:04b}".format(c)[::-1], 2) for c in range(16)], dtype=np.uint8)  # the four bits in reverse order
+# CIGAR ops "MIDNSHP=X" (0 .. 8) by class: aligned columns (M = X: what MD describes); with I, S: consume the read; with D, N: the reference
+_COLUMN_OPS, _QUERY_OPS, _REF_OPS = (0, 7, 8), (0, 7, 8, 1, 4), (0, 7, 8, 2, 3)
 
 
 def _field(a, at, n_bytes, signed=False):
@@ -44,11 +46,12 @@ def _field(a, at, n_bytes, signed=False):
 def _classify(chunk, max_len):
     """Per record of a chunk: a dict of int64 / bool arrays -- ``code`` (0: good), ``mate`` (0, 1; -1: skipped as secondary or
     supplementary, -2: skipped for its mate flags; meaningful where code == 0), ``len``, ``seq`` and ``qual`` (byte offsets),
-    ``reverse``, ``insert`` (the bin, or -1)."""
+    ``reverse``, ``insert`` (the bin, or -1); and the header fields as read: ``block_size``, ``ref_id``, ``pos``, ``l_name``,
+    ``mapq``, ``n_cigar``, ``flag``."""
     a = np.frombuffer(chunk.data, dtype=np.uint8)
     o = np.asarray(chunk.offsets, dtype=np.int64)
-    block_size, ref_id = _field(a, o, 4, True), _field(a, o + 4, 4, True)
-    l_name, n_cigar, flag = _field(a, o + 12, 1), _field(a, o + 16, 2), _field(a, o + 18, 2)
+    block_size, ref_id, ref_pos = _field(a, o, 4, True), _field(a, o + 4, 4, True), _field(a, o + 8, 4, True)
+    l_name, mapq, n_cigar, flag = _field(a, o + 12, 1), _field(a, o + 13, 1), _field(a, o + 16, 2), _field(a, o + 18, 2)
     l_seq, next_ref, tlen = _field(a, o + 20, 4, True), _field(a, o + 24, 4, True), _field(a, o + 32, 4, True)
     seq = o + 36 + l_name + 4 * n_cigar
     code = np.zeros(o.size, dtype=np.int64)
@@ -73,7 +76,15 @@ def _classify(chunk, max_len):
     gap = np.clip(np.abs(tlen) - 2 * length, 0, INSERT_BINS - 1)  # (int64: |INT32_MIN| does not wrap)
     has_insert = paired & ((flag & 0xC) == 0) & (ref_id == next_ref) & (ref_id >= 0) & (tlen != 0) & (mate == 0) & (code == 0)
     return {"code": code, "mate": mate, "len": length, "seq": seq, "qual": qual, "reverse": (flag & 0x10) != 0,
-            "insert": np.where(has_insert, gap, -1)}
+            "insert": np.where(has_insert, gap, -1), "block_size": block_size, "ref_id": ref_id, "pos": ref_pos, "l_name": l_name,
+            "mapq": mapq, "n_cigar": n_cigar, "flag": flag}
+
+
+def _cigar(a, offset, l_name, n_cigar):
+    """The CIGAR of the record at byte ``offset`` of the chunk's bytes a -> [(op, length)]."""
+    at = int(offset) + 36 + int(l_name)
+    words = np.frombuffer(bytes(a[at:at + 4 * int(n_cigar)]), dtype="<u4").astype(np.int64)
+    return list(zip((words & 15).tolist(), (words >> 4).tolist()))
 
 
 def _tally_chunk(chunk, max_len, t):

@@ -103,16 +103,8 @@ int iss_bam_feed(iss_bam *b, const uint8_t *data, int64_t n_bytes, const int64_t
     if (n_bytes > (int64_t)UINT32_MAX) return fail(b, ISS_E_INVALID, "iss_bam_feed: chunks are limited to 4 GiB");
     if (!n_records) return 0;
     HIP_TRY(b, hipSetDevice(b->device));
-    // every record must lie inside the chunk: the kernels trust these offsets (iss_bam_scan makes them)
-    b->h_offs.resize((size_t)n_records);
-    for (int64_t r = 0; r < n_records; ++r) {
-        const int64_t o = offsets[r];
-        if (o < 0 || o + 4 + 32 > n_bytes) return fail(b, ISS_E_INVALID, "iss_bam_feed: record offset outside the chunk");
-        int32_t bs;
-        memcpy(&bs, data + o, 4);
-        if (bs < 32 || o + 4 + (int64_t)bs > n_bytes) return fail(b, ISS_E_INVALID, "iss_bam_feed: record outside the chunk");
-        b->h_offs[(size_t)r] = (uint32_t)o;
-    }
+    ISS_TRY(records_inside(b, "iss_bam_feed", data, n_bytes, offsets, n_records, false));
+    b->h_offs.assign(offsets, offsets + n_records);  // (below 2^32: inside the chunk)
     // (the stream is idle between feeds, the wait in front of a replacement costs nothing)
     if ((size_t)n_records > b->rec.cap || (size_t)n_bytes > b->data.cap) HIP_TRY(b, hipStreamSynchronize(b->stream));
     ISS_TRY(reserve(b, b->rec, (size_t)n_records, (size_t)1 << 16));

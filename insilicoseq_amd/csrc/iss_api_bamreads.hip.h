@@ -58,19 +58,13 @@ static int br_reserve(iss_br *f, iss_br::Slot &s, size_t n_bytes, size_t n_recor
 
 // the error words and their state zeroed, the first-bad word all ones (on the kernel stream; the caller waits)
 static int br_errors_clear(iss_br *f) {
-    const size_t words = (size_t)iss::be::be_words(f->max_len);
-    HIP_TRY(f, hipMemsetAsync(f->d_err, 0, sizeof(unsigned long long) * words + sizeof(iss::be::BeState), f->stream));
-    HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_err + words) + offsetof(iss::be::BeState, bad), 0xFF,
-                             sizeof(unsigned long long), f->stream));
-    return 0;
+    const size_t words = sizeof(unsigned long long) * (size_t)iss::be::be_words(f->max_len);
+    return bad_state_clear(f, f->stream, f->d_err, words + sizeof(iss::be::BeState), words + offsetof(iss::be::BeState, bad));
 }
 
 // the depth stage's counts zeroed, its first-bad word all ones (on the kernel stream; the caller waits)
 static int br_depth_clear(iss_br *f) {
-    HIP_TRY(f, hipMemsetAsync(f->d_depth, 0, sizeof(iss::bd::BdState), f->stream));
-    HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_depth.get()) + offsetof(iss::bd::BdState, bad), 0xFF, sizeof(unsigned long long),
-                             f->stream));
-    return 0;
+    return bad_state_clear(f, f->stream, f->d_depth, sizeof(iss::bd::BdState), offsetof(iss::bd::BdState, bad));
 }
 
 extern "C" {
@@ -105,10 +99,8 @@ int iss_br_reset(iss_br *f) {
     if (!f) return fail(nullptr, ISS_E_INVALID, "iss_br_reset: NULL");
     HIP_TRY(f, hipSetDevice(f->device));
     HIP_TRY(f, hipStreamSynchronize(f->copy_stream));
-    const size_t words = (size_t)iss::fq::fq_layout(f->max_len).words;
-    HIP_TRY(f, hipMemsetAsync(f->d_tally, 0, sizeof(unsigned long long) * words + sizeof(iss::br::BrState), f->stream));
-    HIP_TRY(f, hipMemsetAsync(reinterpret_cast<uint8_t *>(f->d_tally + words) + offsetof(iss::br::BrState, bad), 0xFF,
-                             sizeof(unsigned long long), f->stream));
+    const size_t words = sizeof(unsigned long long) * (size_t)iss::fq::fq_layout(f->max_len).words;
+    ISS_TRY(bad_state_clear(f, f->stream, f->d_tally, words + sizeof(iss::br::BrState), words + offsetof(iss::br::BrState, bad)));
     if (f->errors) ISS_TRY(br_errors_clear(f));
     if (f->depth) ISS_TRY(br_depth_clear(f));  // (the caller's array stays as it is, and the stage on)
     HIP_TRY(f, hipStreamSynchronize(f->stream));
@@ -125,17 +117,7 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
     if (!n_records) return 0;
     if (f->depth && n_records > (int64_t)0x7fffffff - f->fed)  // (a record adds at most 1 to a base: the depths stay below 2^31)
         return fail(f, ISS_E_INVALID, "iss_br_feed: more than 2^31 - 1 records fed while the depth stage is on");
-    // every record must lie inside the chunk: the kernels trust these offsets (iss_bam_scan makes them, ascending)
-    int64_t before = -1;
-    for (int64_t r = 0; r < n_records; ++r) {
-        const int64_t o = offsets[r];
-        if (o < 0 || o + 4 + 32 > n_bytes) return fail(f, ISS_E_INVALID, "iss_br_feed: record offset outside the chunk");
-        if (o <= before) return fail(f, ISS_E_INVALID, "iss_br_feed: record offsets do not ascend");
-        int32_t bs;
-        memcpy(&bs, data + o, 4);
-        if (bs < 32 || o + 4 + (int64_t)bs > n_bytes) return fail(f, ISS_E_INVALID, "iss_br_feed: record outside the chunk");
-        before = o;
-    }
+    ISS_TRY(records_inside(f, "iss_br_feed", data, n_bytes, offsets, n_records, true));
     HIP_TRY(f, hipSetDevice(f->device));
     int wgs = 0;
     if (const char *e = getenv("ISS_BR_WGS")) wgs = std::max(1, atoi(e));  // workgroups aimed at (tests: other launch geometries)
@@ -175,11 +157,11 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
         E.state = reinterpret_cast<iss::be::BeState *>(f->d_err + iss::be::be_words(f->max_len));
         E.mask = f->marks.p;
         E.tiles = plan.pos_tiles;
-        const uint32_t record_wgs = iss::be::be_record_wgs(n_records, wgs);
+        const uint32_t record_wgs = iss::br::wave_record_wgs(n_records, wgs);
         E.rounds = iss::be::be_record_rounds(n_records, record_wgs);
-        hipLaunchKernelGGL(iss::be::k_be_records, dim3(record_wgs), dim3(iss::be::BE_THREADS), 0, f->stream, E);
+        hipLaunchKernelGGL(iss::be::k_be_records, dim3(record_wgs), threads, 0, f->stream, E);
         HIP_TRY(f, hipGetLastError());
-        hipLaunchKernelGGL(iss::be::k_be_bases, dim3(plan.pos_tiles, plan.pos_chunks), dim3(iss::be::BE_THREADS), 0, f->stream, E);
+        hipLaunchKernelGGL(iss::be::k_be_bases, dim3(plan.pos_tiles, plan.pos_chunks), threads, 0, f->stream, E);
         HIP_TRY(f, hipGetLastError());
     }
     if (f->depth) {
@@ -191,7 +173,7 @@ int iss_br_feed(iss_br *f, const uint8_t *data, int64_t n_bytes, const int64_t *
         D.n_table = f->depth_n_table;
         D.flags = f->depth_flags;
         D.min_mapq = f->depth_min_mapq;
-        hipLaunchKernelGGL(iss::bd::k_bd_records, dim3(iss::bd::bd_record_wgs(n_records, wgs)), dim3(iss::bd::BD_THREADS), 0, f->stream, D);
+        hipLaunchKernelGGL(iss::bd::k_bd_records, dim3(iss::br::wave_record_wgs(n_records, wgs)), threads, 0, f->stream, D);
         HIP_TRY(f, hipGetLastError());
     }
     HIP_TRY(f, hipEventRecord(s.done, f->stream));

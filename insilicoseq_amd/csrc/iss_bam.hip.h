@@ -7,6 +7,7 @@
 // once per workgroup; a wave processes one record with its lanes over read positions, so the LDS increments of one wave instruction
 // never collide.  DESIGN.md section 11 has the parity contract and the measured numbers.
 #pragma once
+#include "iss_bam_record.h"
 
 namespace iss {
 namespace bam {
@@ -45,10 +46,8 @@ struct TallyLds {
 constexpr size_t TALLY_LDS = sizeof(TallyLds);
 constexpr size_t QHIST_LDS = sizeof(uint32_t) * MAX_LEN * NQ;
 
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+using brec::OP_D, brec::OP_H, brec::OP_I, brec::OP_M, brec::OP_S;
+constexpr uint32_t OPS_MODEL_QUERY = 1u << OP_M | 1u << OP_I | 1u << OP_S, OPS_MODEL = OPS_MODEL_QUERY | 1u << OP_D | 1u << OP_H;  // of a tallied record
 // 4-bit base code ("=ACMGRSVTWYHKDBN") -> index in A, T, C, G order; -1 for every other letter
 __device__ __forceinline__ int nib_base(uint32_t nib) { return nib == 1 ? 0 : nib == 8 ? 1 : nib == 2 ? 2 : nib == 4 ? 3 : -1; }
 __device__ __forceinline__ int md_base(uint32_t ch) {  // an MD letter, either case
@@ -93,14 +92,13 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
         uint2 my_meta = make_uint2(0, 0xFFu);
         if (live) {
             const uint8_t *rec = data + offs[r];
-            const int64_t bs = (int32_t)ld32(rec);
+            const brec::RecHead h = brec::rec_head(rec);
+            const uint32_t flag = h.flag;
+            const int32_t tlen = h.tlen;
             p = rec + 4;
-            const uint32_t l_name = p[8], flag = ld16(p + 14);
-            n_cig = (int)ld16(p + 12);
-            l_seq = (int32_t)ld32(p + 16);
-            const int32_t tlen = (int32_t)ld32(p + 28);
-            const int64_t need = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq;
-            if (l_seq < 0 || need > bs) {
+            n_cig = (int)h.n_cigar;
+            l_seq = h.l_seq;
+            if (!h.fits()) {
                 if (lane == 0) report(err, rec_base + r, E_REC_MALFORMED);
                 live = false;
             } else if (l_seq > MAX_LEN) {
@@ -114,9 +112,9 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
                     if (t > 0 && t < NTLEN && lane == 0) atomicAdd(&L.tlen[t], 1u);
                 }
                 mate = (flag & 64) ? 0 : (flag & 128) ? 1 : -1;
-                cig = p + 32 + l_name;
-                seq = cig + 4 * n_cig;
-                const uint8_t *qual = seq + (l_seq + 1) / 2;
+                cig = rec + h.cigar_at();
+                seq = rec + h.seq_at();
+                const uint8_t *qual = rec + h.qual_at();
                 if (mate >= 0) {  // query_qualities, np.mean -> int (iss/bam.py:132-152, modeller.py:56-59)
                     if (l_seq == 0 || qual[0] == 0xFF) {
                         if (lane == 0) report(err, rec_base + r, E_REC_NO_QUAL);
@@ -151,10 +149,10 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
                 bool bad_op = false;
                 int qsum = 0, msum = 0;
                 for (int i = lane; i < n_cig; i += 64) {
-                    const uint32_t c = ld32(cig + 4 * i), op = c & 15, ln = c >> 4;
-                    bad_op |= !(op == 0 || op == 1 || op == 2 || op == 4 || op == 5);
-                    if (op == 0 || op == 1 || op == 4) qsum += (int)min(ln, 1u << 20);
-                    if (op == 0) msum += (int)min(ln, 1u << 20);
+                    const uint32_t c = brec::u32(cig + 4 * i), op = c & 15, ln = c >> 4;
+                    bad_op |= !brec::in(op, OPS_MODEL);
+                    if (brec::in(op, OPS_MODEL_QUERY)) qsum += (int)min(ln, 1u << 20);
+                    if (op == OP_M) msum += (int)min(ln, 1u << 20);
                 }
                 for (int o = 32; o > 0; o >>= 1) { qsum += __shfl_xor(qsum, o); msum += __shfl_xor(msum, o); }
                 if (__any(bad_op)) {
@@ -169,33 +167,14 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
             if (live) {  // the MD:Z tag (lane 0 walks the optional fields)
                 int found = 0, off = 0, len = 0;
                 if (lane == 0) {
-                    const uint8_t *a = seq + (l_seq + 1) / 2 + l_seq, *end = p + bs;
-                    bool bad = false;
-                    while (a + 3 <= end) {
-                        const uint8_t t0 = a[0], t1 = a[1], ty = a[2];
-                        a += 3;
-                        int64_t sz = -1;
-                        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
-                        else if (ty == 's' || ty == 'S') sz = 2;
-                        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
-                        else if (ty == 'Z' || ty == 'H') {
-                            const uint8_t *z = a;
-                            while (z < end && *z) ++z;
-                            if (z >= end) { bad = true; break; }
-                            if (t0 == 'M' && t1 == 'D' && ty == 'Z') { found = 1; off = (int)(a - p); len = (int)(z - a); break; }
-                            sz = (z - a) + 1;
-                        } else if (ty == 'B') {
-                            if (a + 5 > end) { bad = true; break; }
-                            const uint8_t sub = a[0];
-                            const int64_t cnt = (int32_t)ld32(a + 1);
-                            const int es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-                            if (!es || cnt < 0) { bad = true; break; }
-                            sz = 5 + cnt * es;
-                        }
-                        if (sz < 0 || a + sz > end) { bad = true; break; }
-                        a += sz;
-                    }
-                    if (!found) report(err, rec_base + r, bad ? E_REC_MALFORMED : E_REC_NO_MD);
+                    const uint8_t *const aux = rec + h.aux_at();
+                    int64_t md_at = 0;
+                    uint32_t n = 0;
+                    const int st = brec::be_tag_walk(aux, (rec + h.end()) - aux, &md_at, &n);
+                    found = st == brec::BE_TAGS_MD;
+                    off = (int)((aux - p) + md_at);
+                    len = (int)n;
+                    if (!found) report(err, rec_base + r, st == brec::BE_TAGS_BAD ? E_REC_MALFORMED : E_REC_NO_MD);
                 }
                 found = __shfl(found, 0);
                 md_off = __shfl(off, 0);
@@ -210,10 +189,10 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
         if (live) {
             int q = 0;
             for (int k = 0; k < n_cig; ++k) {
-                const uint32_t c = ld32(cig + 4 * k), op = c & 15, ln = c >> 4;
-                if (op == 0)
+                const uint32_t c = brec::u32(cig + 4 * k), op = c & 15, ln = c >> 4;
+                if (op == OP_M)
                     for (int i = lane; i < (int)ln; i += 64) refc[q + i] = 1;
-                if (op == 0 || op == 1 || op == 4) q += (int)ln;
+                if (brec::in(op, OPS_MODEL_QUERY)) q += (int)ln;
             }
         }
         __syncthreads();
@@ -235,12 +214,12 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
                 } else {
                     int qpos = -1;
                     while (ci < n_cig) {
-                        const uint32_t c = ld32(cig + 4 * ci), op = c & 15, ln = c >> 4;
-                        if (op == 0) {
+                        const uint32_t c = brec::u32(cig + 4 * ci), op = c & 15, ln = c >> 4;
+                        if (op == OP_M) {
                             if (col < cb + (int)ln) { qpos = q0 + (col - cb); break; }
                             cb += (int)ln;
                             q0 += (int)ln;
-                        } else if (op == 1 || op == 4) {
+                        } else if (op == OP_I || op == OP_S) {
                             q0 += (int)ln;
                         }
                         ++ci;
@@ -265,7 +244,7 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
             for (int q = lane; q < l_seq; q += 64) {
                 const uint32_t c = refc[q];
                 if (!c) continue;
-                const int qb = nib_base((seq[q >> 1] >> ((q & 1) ? 0 : 4)) & 15);
+                const int qb = nib_base(brec::seq_nibble(seq, 0u, (uint32_t)q));
                 const int rb = c == 1 ? qb : (int)(c & 7);
                 const bool ok = qb >= 0 && (c == 1 || (rb < 4 && rb != qb));
                 if (!ok) { odd = true; continue; }
@@ -277,32 +256,32 @@ __global__ void __launch_bounds__(TALLY_THREADS) k_bam_tally(const uint8_t *__re
         if (live && has_indels && mate >= 0 && lane == 0) {
             int lo = 0, hi = 0;  // query_alignment_start / end: soft clips behind any hard clip at either end
             for (int k = 0; k < n_cig; ++k) {
-                const uint32_t c = ld32(cig + 4 * k), op = c & 15;
-                if (op == 4) lo += (int)(c >> 4);
-                else if (op != 5) break;
+                const uint32_t c = brec::u32(cig + 4 * k), op = c & 15;
+                if (op == OP_S) lo += (int)(c >> 4);
+                else if (op != OP_H) break;
             }
             for (int k = n_cig - 1; k >= 0; --k) {
-                const uint32_t c = ld32(cig + 4 * k), op = c & 15;
-                if (op == 4) hi += (int)(c >> 4);
-                else if (op != 5) break;
+                const uint32_t c = brec::u32(cig + 4 * k), op = c & 15;
+                if (op == OP_S) hi += (int)(c >> 4);
+                else if (op != OP_H) break;
             }
             if (lo + hi > l_seq) hi = l_seq - lo;  // an all-clipped read: an empty alignment sequence
             const int la = l_seq - lo - hi;
             int64_t pos = 0;
             for (int k = 0; k < n_cig; ++k) {
-                const uint32_t c = ld32(cig + 4 * k), op = c & 15, ln = c >> 4;
-                if (op == 0) {
+                const uint32_t c = brec::u32(cig + 4 * k), op = c & 15, ln = c >> 4;
+                if (op == OP_M) {
                     pos += ln;
-                } else if (op == 1 || op == 2) {
-                    const int lim = op == 1 ? l_seq : la;  // query_sequence[position] / query_alignment_sequence[position]
+                } else if (op == OP_I || op == OP_D) {
+                    const int lim = op == OP_I ? l_seq : la;  // query_sequence[position] / query_alignment_sequence[position]
                     if (pos < -lim || pos >= lim) { report(err, rec_base + r, E_REC_INDEL_INDEX); break; }
-                    const int qi = (op == 1 ? 0 : lo) + (int)(pos < 0 ? pos + lim : pos);
-                    const int b = nib_base((seq[qi >> 1] >> ((qi & 1) ? 0 : 4)) & 15);
+                    const int qi = (op == OP_I ? 0 : lo) + (int)(pos < 0 ? pos + lim : pos);
+                    const int b = nib_base(brec::seq_nibble(seq, 0u, (uint32_t)qi));
                     if (b >= 0) {
                         const int row = (int)(pos < 0 ? pos + MAX_LEN : pos);  // Python's negative index into the 301 rows
-                        atomicAdd(&L.indel[(mate * MAX_LEN + row) * 9 + (op == 1 ? 1 : 5) + b], 1u);
+                        atomicAdd(&L.indel[(mate * MAX_LEN + row) * 9 + (op == OP_I ? 1 : 5) + b], 1u);
                     }
-                    pos = op == 1 ? pos + ln : pos - ln;
+                    pos = op == OP_I ? pos + ln : pos - ln;
                 }
             }
         }

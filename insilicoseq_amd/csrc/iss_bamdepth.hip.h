@@ -21,8 +21,6 @@
 namespace iss {
 namespace bd {
 
-constexpr int BD_THREADS = 256;
-constexpr int BD_WAVES = BD_THREADS / 64;
 constexpr int BD_CIGAR = 1, BD_REF = 2, BD_SPAN = 3;  // (= ISS_BR_DEPTH_*)
 constexpr uint32_t BD_COUNT_DEL = 1u;                 // (= ISS_BR_DEPTH_COUNT_DEL)
 
@@ -43,35 +41,35 @@ struct BdArgs {
 // Wave w of workgroup b takes records b * 4 + w, then every gridDim.x * 4 further: the record is the same for all lanes of a wave,
 // so the shuffles and ballots below run with every lane in step.  The CIGAR of a record the read tally took lies inside the record
 // (k_br_records checked 32 + l_read_name + 4 n_cigar_op + ... <= block_size), so inside the chunk.
-__global__ __launch_bounds__(BD_THREADS) void k_bd_records(const BdArgs E) {
+__global__ __launch_bounds__(br::BR_THREADS) void k_bd_records(const BdArgs E) {
     __shared__ unsigned long long s_counts[6];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     if (tid < 6u) s_counts[tid] = 0ull;
     __syncthreads();
     const bool count_del = (E.flags & BD_COUNT_DEL) != 0u;
-    for (uint64_t r64 = (uint64_t)blockIdx.x * BD_WAVES + w; r64 < E.R.n_rec; r64 += (uint64_t)gridDim.x * BD_WAVES) {
+    for (uint64_t r64 = (uint64_t)blockIdx.x * br::BR_WAVES + w; r64 < E.R.n_rec; r64 += (uint64_t)gridDim.x * br::BR_WAVES) {
         const uint32_t r = (uint32_t)r64;
         if (E.R.desc[r].z & br::BR_D_OUT) continue;
         const uint8_t *const rec = E.R.data + E.R.offs[r];
-        const int32_t ref_id = (int32_t)be::be_u32(rec + 4), pos = (int32_t)be::be_u32(rec + 8);
-        const uint32_t w12 = be::be_u32(rec + 12), w16 = be::be_u32(rec + 16);
-        const uint32_t n_cigar = w16 & 0xFFFFu, flag = w16 >> 16, mapq = (w12 >> 8) & 0xFFu;
+        const brec::RecHead h = brec::rec_head(rec);
+        const int32_t ref_id = h.ref_id, pos = h.pos;
+        const uint32_t n_cigar = h.n_cigar;
         int slot = -1;  // the count of a record that marks nothing
-        if ((flag & 4u) || !n_cigar || ref_id < 0) slot = 1;
-        else if (flag & 0x600u) slot = 2;
-        else if (mapq < E.min_mapq) slot = 3;
+        if ((h.flag & 4u) || !n_cigar || ref_id < 0) slot = 1;
+        else if (h.flag & 0x600u) slot = 2;
+        else if (h.mapq < E.min_mapq) slot = 3;
         if (slot >= 0) {
             if (lane == 0u) atomicAdd(&s_counts[slot], 1ull);
             continue;
         }
-        const uint8_t *const cig = rec + br::BR_FIXED + (w12 & 0xFFu);
+        const uint8_t *const cig = rec + h.cigar_at();
         // ---- pass 1: the ops and the reference span
         bool bad_op = false;
         unsigned long long span = 0ull;
         for (uint32_t i = lane; i < n_cigar; i += 64u) {
-            const uint32_t c = be::be_u32(cig + 4u * i), op = c & 15u;
-            bad_op |= op > 8u;
-            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) span += c >> 4;
+            const uint32_t c = brec::u32(cig + 4u * i), op = c & 15u;
+            bad_op |= op > brec::OP_LAST;
+            if (brec::in(op, brec::OPS_REF)) span += c >> 4;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) span += __shfl_xor(span, o);  // (at most 65 535 ops below 2^28 each: below 2^44)
@@ -99,16 +97,16 @@ __global__ __launch_bounds__(BD_THREADS) void k_bd_records(const BdArgs E) {
         unsigned long long carry = (unsigned long long)pos, covered = 0ull;
         for (uint32_t i0 = 0; i0 < n_cigar; i0 += 64u) {
             const uint32_t i = i0 + lane;
-            const uint32_t c = i < n_cigar ? be::be_u32(cig + 4u * i) : 0u, op = c & 15u, ln = i < n_cigar ? c >> 4 : 0u;
-            const bool column = op == 0u || op == 7u || op == 8u;
-            const unsigned long long step = (column || op == 2u || op == 3u) ? ln : 0u;
+            const uint32_t c = i < n_cigar ? brec::u32(cig + 4u * i) : 0u, op = c & 15u, ln = i < n_cigar ? c >> 4 : 0u;
+            const bool column = op == brec::OP_M || op == brec::OP_EQ || op == brec::OP_X;  // (OPS_COLUMN, OPS_REF: in() costs registers here)
+            const unsigned long long step = (column || op == brec::OP_D || op == brec::OP_N) ? ln : 0u;
             unsigned long long incl = step;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const unsigned long long y = __shfl_up(incl, d);
                 if (lane >= (uint32_t)d) incl += y;
             }
-            if (ln && (column || (count_del && op == 2u))) {
+            if (ln && (column || (count_del && op == brec::OP_D))) {
                 const unsigned long long start = carry + incl - step;
                 (void)__hip_atomic_fetch_add(words + start, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 (void)__hip_atomic_fetch_add(words + start + ln, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -125,12 +123,6 @@ __global__ __launch_bounds__(BD_THREADS) void k_bd_records(const BdArgs E) {
     }
     __syncthreads();
     if (tid < 6u && s_counts[tid]) atomicAdd(&E.state->counts[tid], s_counts[tid]);
-}
-
-// The launch geometry (host): workgroups aimed at wgs (0: BR_TARGET_WGS), no more than their waves have records for.
-inline uint32_t bd_record_wgs(int64_t n_rec, int wgs) {
-    const int64_t target = wgs > 0 ? wgs : br::BR_TARGET_WGS;
-    return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(target, (n_rec + BD_WAVES - 1) / BD_WAVES));
 }
 
 }  // namespace bd

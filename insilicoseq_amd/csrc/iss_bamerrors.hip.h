@@ -16,13 +16,13 @@
 // Every count is an exact integer sum: the words depend neither on the launch geometry nor on how the records were cut into feeds.
 // Plain vector code.  DESIGN.md section 29.  Included by iss_mi355x.hip behind iss_bamreads.hip.h and iss_errtally.hip.h.
 #pragma once
-#include "iss_bamerrors_walk.h"
+#include "iss_bam_record.h"
 
 namespace iss {
 namespace be {
+using brec::RecHead, brec::rec_head, brec::be_tag_walk, brec::BE_TAGS_MD, brec::BE_TAGS_NO_MD, brec::nib_code, brec::seq_nibble;
+using brec::OP_M, brec::OP_I, brec::OP_S, brec::OP_EQ, brec::OP_X;
 
-constexpr int BE_THREADS = 256;
-constexpr int BE_WAVES = BE_THREADS / 64;
 constexpr int BE_MAP = br::BR_MAX_LEN;  // bytes of a wave's map: one per SEQ index
 constexpr int BE_NK = ERRTALLY_NK;      // rows-per-read bins
 // a wave's map, per SEQ index: 0 soft-clipped, BE_COL an M / = / X column that matches, BE_INS an inserted base,
@@ -45,28 +45,24 @@ struct BeArgs {
 
 __host__ __device__ inline int64_t be_words(int L) { return errtally_layout(L).words + 2 * (int64_t)L * ERRTALLY_NQ; }
 
-__device__ __forceinline__ uint32_t be_nib_code(uint32_t nib) {  // "=ACMGRSVTWYHKDBN": A, C, G, T 0 .. 3, every other letter 4
-    return nib == 1u ? 0u : nib == 2u ? 1u : nib == 4u ? 2u : nib == 8u ? 3u : 4u;
-}
-
 // Stage c.  Wave w of workgroup b takes record (i * gridDim.x + b) * 4 + w in round i; every wave of a workgroup runs the same
 // number of rounds (BeArgs::rounds), so that workgroup barriers separate the phases (lane 0 writes the map that all lanes read).
 // The CIGAR's sum is checked before the map is written and the MD walk stays inside the CIGAR's columns: no map index reaches
 // len <= 1 024.
-__global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
-    __shared__ uint8_t s_map[BE_WAVES][BE_MAP];
+__global__ __launch_bounds__(br::BR_THREADS) void k_be_records(const BeArgs E) {
+    __shared__ uint8_t s_map[br::BR_WAVES][BE_MAP];
     __shared__ uint32_t s_pr[2 * 3 * BE_NK];
     __shared__ uint32_t s_misc[8];  // tallied per mate [2], unaligned, no_md, dropped
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, L = (uint32_t)E.R.L;
-    for (uint32_t i = tid; i < 2u * 3u * BE_NK; i += BE_THREADS) s_pr[i] = 0u;
+    for (uint32_t i = tid; i < 2u * 3u * BE_NK; i += br::BR_THREADS) s_pr[i] = 0u;
     if (tid < 8u) s_misc[tid] = 0u;
     uint8_t *const map = s_map[w];
     __syncthreads();
     const uint8_t *const data = E.R.data;
     const ErrTallyLayout lay = errtally_layout((int)L);
-    const uint64_t per_round = (uint64_t)gridDim.x * BE_WAVES;
+    const uint64_t per_round = (uint64_t)gridDim.x * br::BR_WAVES;
     for (uint64_t it = 0; it < E.rounds; ++it) {
-        const uint64_t r64 = it * per_round + (uint64_t)blockIdx.x * BE_WAVES + w;
+        const uint64_t r64 = it * per_round + (uint64_t)blockIdx.x * br::BR_WAVES + w;
         // ---- phase A: taken or not, aligned or not, the CIGAR's ops and sum, the optional fields up to MD:Z
         enum { NONE, UNALIGNED, NO_MD, BAD, LIVE } kind = NONE;
         uint32_t code = 0u, len = 0u, n_cigar = 0u, md_len = 0u, mate = 0u, seq_at = 0u, qual_at = 0u;
@@ -76,25 +72,24 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
             const uint4 d = E.R.desc[(uint32_t)r64];
             if (!(d.z & br::BR_D_OUT)) {
                 const uint8_t *const rec = data + E.R.offs[(uint32_t)r64];
-                const int64_t block_size = (int32_t)be_u32(rec);  // (the record is good: its fields fit block_size)
-                const uint32_t w12 = be_u32(rec + 12), w16 = be_u32(rec + 16), flag = w16 >> 16;
-                n_cigar = w16 & 0xFFFFu;
+                const RecHead h = rec_head(rec);  // (the record is good: its fields fit block_size)
+                n_cigar = h.n_cigar;
                 len = d.z & br::BR_D_LEN;
                 mate = (d.z & br::BR_D_MATE) ? 1u : 0u;
                 reverse = (d.z & br::BR_D_REVERSE) != 0u;
                 seq_at = d.x;
                 qual_at = d.y;
-                cig = rec + br::BR_FIXED + (w12 & 0xFFu);
-                if ((flag & 4u) || !n_cigar || !len) {
+                cig = rec + h.cigar_at();
+                if ((h.flag & 4u) || !n_cigar || !len) {
                     kind = UNALIGNED;
                 } else {
                     bool bad_op = false, del = false;
                     unsigned long long qsum = 0ull;
                     for (uint32_t i = lane; i < n_cigar; i += 64u) {
-                        const uint32_t c = be_u32(cig + 4u * i), op = c & 15u;
-                        bad_op |= op > 8u;
-                        del |= op == 2u;
-                        if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qsum += c >> 4;
+                        const uint32_t c = u32(cig + 4u * i), op = c & 15u;
+                        bad_op |= op > OP_LAST;
+                        del |= op == OP_D;  // (OPS_QUERY spelled out, and the sum shuffled in halves: in() or a 64-bit shuffle
+                        if (op == OP_M || op == OP_I || op == OP_S || op == OP_EQ || op == OP_X) qsum += c >> 4;  // costs registers)
                     }
                     uint32_t lo = (uint32_t)qsum, hi = (uint32_t)(qsum >> 32);  // (at most 65 535 ops below 2^28 each)
 #pragma unroll
@@ -114,7 +109,7 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
                         if (lane == 0u) {
                             const uint8_t *const aux = data + qual_at + len;
                             int64_t md_at = 0;
-                            st = be_tag_walk(aux, (rec + 4 + block_size) - aux, &md_at, &n);
+                            st = be_tag_walk(aux, (rec + h.end()) - aux, &md_at, &n);
                             at = (uint32_t)md_at;  // (inside the record, so below 2^31)
                         }
                         st = __shfl(st, 0);
@@ -134,10 +129,10 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
         if (kind == LIVE) {
             uint32_t q = 0u;
             for (uint32_t k = 0; k < n_cigar; ++k) {
-                const uint32_t c = be_u32(cig + 4u * k), op = c & 15u, ln = c >> 4;
-                if (op == 0u || op == 7u || op == 8u || op == 1u)
-                    for (uint32_t i = lane; i < ln; i += 64u) map[q + i] = (uint8_t)(op == 1u ? BE_INS : BE_COL);
-                if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q += ln;
+                const uint32_t c = u32(cig + 4u * k), op = c & 15u, ln = c >> 4;
+                if (in(op, OPS_COLUMN | 1u << OP_I))
+                    for (uint32_t i = lane; i < ln; i += 64u) map[q + i] = (uint8_t)(op == OP_I ? BE_INS : BE_COL);
+                if (in(op, OPS_QUERY)) q += ln;
             }
         }
         __syncthreads();
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
                 const bool sub = (c & BE_MISMATCH) != 0u, ins = c == BE_INS;
                 if (sub || ins) {
                     const uint64_t mp = mp0 + (reverse ? len - 1u - q : q);
-                    uint32_t alt = be_nib_code(((uint32_t)data[seq_at + (q >> 1)] >> ((q & 1u) ? 0u : 4u)) & 15u);
+                    uint32_t alt = nib_code(seq_nibble(data, seq_at, q));
                     if (reverse) alt = be_complement(alt);
                     if (sub) {
                         const uint32_t ref = reverse ? be_complement(c & 7u) : (c & 7u), ph = data[qual_at + q];  // (k_br_records saw ph <= 93)
@@ -205,7 +200,7 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
         }
         __syncthreads();  // (the map is zeroed again in the next round)
     }
-    for (uint32_t i = tid; i < 2u * 3u * BE_NK; i += BE_THREADS)
+    for (uint32_t i = tid; i < 2u * 3u * BE_NK; i += br::BR_THREADS)
         if (s_pr[i]) atomicAdd(&E.err[lay.per_read + i], (unsigned long long)s_pr[i]);
     if (tid < 4u && s_misc[tid]) atomicAdd(&E.state->counts[tid], (unsigned long long)s_misc[tid]);
     if (tid == 4u && s_misc[4]) atomicAdd(&E.err[lay.dropped], (unsigned long long)s_misc[4]);
@@ -214,14 +209,14 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_records(const BeArgs E) {
 
 // Stage d.  k_br_positions' geometry and phred tables: workgroup (t, c) holds positions [64 t, 64 t + 64) of both mates, a wave takes
 // a record, a lane a position, and counts its phred where the record's word t of marks has the lane's bit.
-__global__ __launch_bounds__(BE_THREADS) void k_be_bases(const BeArgs E) {
+__global__ __launch_bounds__(br::BR_THREADS) void k_be_bases(const BeArgs E) {
     __shared__ uint32_t s_qual[2 * br::BR_POS_TILE * TALLY_QPITCH];
     const uint32_t tid = threadIdx.x, pos0 = blockIdx.x * (uint32_t)br::BR_POS_TILE;
     if (pos0 >= E.R.head->longest) return;  // (the same word for every lane of the workgroup: nobody waits at a barrier below)
-    for (uint32_t i = tid; i < 2u * br::BR_POS_TILE * TALLY_QPITCH; i += BE_THREADS) s_qual[i] = 0u;
+    tile_qual_zero<2>(s_qual, tid);
     __syncthreads();
     const uint32_t lane = tid & 63u, L = (uint32_t)E.R.L, pos = pos0 + lane;
-    for (uint64_t r64 = (uint64_t)blockIdx.y * BE_WAVES + (tid >> 6); r64 < E.R.n_rec; r64 += (uint64_t)gridDim.y * BE_WAVES) {
+    for (uint64_t r64 = (uint64_t)blockIdx.y * br::BR_WAVES + (tid >> 6); r64 < E.R.n_rec; r64 += (uint64_t)gridDim.y * br::BR_WAVES) {
         const uint4 d = E.R.desc[(uint32_t)r64];
         const uint32_t len = d.z & br::BR_D_LEN;
         if ((d.z & br::BR_D_OUT) || pos >= len) continue;  // (len <= L: the word read below was written, blockIdx.x < tiles)
@@ -230,22 +225,12 @@ __global__ __launch_bounds__(BE_THREADS) void k_be_bases(const BeArgs E) {
         atomicAdd(&s_qual[(((d.z & br::BR_D_MATE) ? (uint32_t)br::BR_POS_TILE : 0u) + lane) * TALLY_QPITCH + q], 1u);
     }
     __syncthreads();
-    const int64_t bases = errtally_layout((int)L).words;
-    for (uint32_t i = tid; i < 2u * br::BR_POS_TILE * TALLY_NQ; i += BE_THREADS) {
-        const uint32_t slot = i / TALLY_NQ, ph = i - slot * TALLY_NQ;
-        const uint32_t n = s_qual[slot * TALLY_QPITCH + ph], p = pos0 + (slot & 63u);
-        const int64_t m = slot >> 6;
-        if (n && p < L) atomicAdd(&E.err[bases + (m * L + p) * TALLY_NQ + ph], (unsigned long long)n);
-    }
+    tile_qual_flush<2>(s_qual, tid, pos0, L, E.err + errtally_layout((int)L).words);
 }
 
-// The launch geometry (host): k_be_records' workgroups aimed at wgs (0: BR_TARGET_WGS), no more than its waves have records for;
-// k_be_bases takes k_br_positions' grid.
-inline uint32_t be_record_wgs(int64_t n_rec, int wgs) {
-    const int64_t target = wgs > 0 ? wgs : br::BR_TARGET_WGS;
-    return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(target, (n_rec + BE_WAVES - 1) / BE_WAVES));
-}
-inline uint32_t be_record_rounds(int64_t n_rec, uint32_t wgs) { return (uint32_t)((n_rec + (int64_t)wgs * BE_WAVES - 1) / ((int64_t)wgs * BE_WAVES)); }
+// The launch geometry (host): k_be_records runs br::wave_record_wgs workgroups and this many rounds; k_be_bases takes
+// k_br_positions' grid.
+inline uint32_t be_record_rounds(int64_t n_rec, uint32_t wgs) { return (uint32_t)((n_rec + (int64_t)wgs * br::BR_WAVES - 1) / ((int64_t)wgs * br::BR_WAVES)); }
 
 }  // namespace be
 }  // namespace iss

@@ -15,18 +15,20 @@
 // gathered in LDS (u32) and added to the u64 words once per workgroup, one global atomic per non-zero counter (iss_tally.hip.h).
 // Plain vector code.  DESIGN.md section 28.  Included by iss_mi355x.hip.
 #pragma once
+#include "iss_bam_record.h"
 
 namespace iss {
 namespace br {
 
 constexpr int BR_THREADS = 256;
+constexpr int BR_WAVES = BR_THREADS / 64;  // records of a workgroup and turn in the wave-per-record kernels (k_br_positions, k_be_*, k_bd_records)
 constexpr int BR_MAX_LEN = 1024;         // (= ISS_BR_MAX_LEN = ISS_FQ_MAX_LEN)
 constexpr int BR_GROUP = 16;             // lanes of a record in k_br_records: 8 bases a lane, 128 bases a step
 constexpr int BR_LANE_BASES = 8;         // 4 bytes of SEQ and 8 of QUAL
 constexpr int BR_POS_TILE = 64;          // positions of a workgroup's tables in k_br_positions: a wave's lanes
+static_assert(BR_THREADS == TALLY_THREADS && BR_POS_TILE == TALLY_TILE, "k_br_positions and k_be_bases use iss_tally.hip.h's phred tile");
 constexpr int BR_TARGET_WGS = 2048;      // workgroups of a launch, about: 8 per compute unit
 constexpr int BR_PAD = 16;               // bytes readable behind the chunk: k_br_records reads up to 7 past a record's qualities
-constexpr int BR_FIXED = 36;             // block_size and the 32 fixed bytes of a record
 
 constexpr int BR_REC_SHORT = 1, BR_REC_TOO_LONG = 2, BR_REC_NO_QUAL = 3, BR_REC_QUAL_RANGE = 4;
 
@@ -56,12 +58,6 @@ struct BrArgs {
     int32_t L;               // the context's max_len
 };
 
-__device__ __forceinline__ uint32_t br_u32(const uint8_t *p) {  // (a record starts at any alignment)
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
 // words of k_br_records' LDS: length and gc [2][L + 1] each, meanq [2][94], insert [2048], then good records [2], skipped [2], longest
 inline size_t br_records_lds(int L) { return sizeof(uint32_t) * (size_t)(4 * (L + 1) + 2 * TALLY_NQ + TALLY_NINS + 5); }
 
@@ -86,19 +82,16 @@ __global__ __launch_bounds__(BR_THREADS) void k_br_records(const BrArgs A) {
         int32_t ref_id = 0, next_ref = 0, tlen = 0;
         if (lane == 0u) {
             const uint8_t *const rec = data + A.offs[r];
-            const int32_t block_size = (int32_t)br_u32(rec), l_seq = (int32_t)br_u32(rec + 20);
-            const uint32_t w12 = br_u32(rec + 12), w16 = br_u32(rec + 16);
-            const uint32_t l_name = w12 & 0xFFu, n_cigar = w16 & 0xFFFFu;
-            flag = w16 >> 16;
-            ref_id = (int32_t)br_u32(rec + 4);
-            next_ref = (int32_t)br_u32(rec + 24);
-            tlen = (int32_t)br_u32(rec + 32);
-            const uint32_t var = l_name + 4u * n_cigar;  // (at most 255 + 4 * 65535)
-            if (l_name == 0u || l_seq < 0 || 32ll + var + ((int64_t)l_seq + 1) / 2 + l_seq > (int64_t)block_size) code = BR_REC_SHORT;
-            else if ((uint32_t)l_seq > L) code = BR_REC_TOO_LONG;
+            const brec::RecHead h = brec::rec_head(rec);
+            flag = h.flag;
+            ref_id = h.ref_id;
+            next_ref = h.next_ref;
+            tlen = h.tlen;
+            if (h.l_name == 0u || !h.fits()) code = BR_REC_SHORT;
+            else if ((uint32_t)h.l_seq > L) code = BR_REC_TOO_LONG;
             else {
-                len = (uint32_t)l_seq;
-                seq_at = A.offs[r] + (uint32_t)BR_FIXED + var;  // (inside the record, so inside the chunk)
+                len = (uint32_t)h.l_seq;
+                seq_at = A.offs[r] + (uint32_t)h.seq_at();  // (inside the record, so inside the chunk)
                 if (len && data[seq_at + (len + 1u) / 2u] == 0xFFu) code = BR_REC_NO_QUAL;
             }
         }
@@ -109,8 +102,8 @@ __global__ __launch_bounds__(BR_THREADS) void k_br_records(const BrArgs A) {
         uint32_t gc = 0u, qs = 0u, out_of_range = 0u;
         if (!code) {
             for (uint32_t at = lane * BR_LANE_BASES; at < len; at += BR_GROUP * BR_LANE_BASES) {
-                const uint32_t bw = br_u32(data + seq_at + at / 2u);  // bases at .. at + 7: byte k holds at + 2k (high nibble), at + 2k + 1
-                const uint32_t q0 = br_u32(data + qual_at + at), q1 = br_u32(data + qual_at + at + 4u);
+                const uint32_t bw = brec::u32(data + seq_at + at / 2u);  // bases at .. at + 7: byte k holds at + 2k (high nibble), at + 2k + 1
+                const uint32_t q0 = brec::u32(data + qual_at + at), q1 = brec::u32(data + qual_at + at + 4u);
                 const uint32_t nv = min((uint32_t)BR_LANE_BASES, len - at);
 #pragma unroll
                 for (uint32_t j = 0; j < (uint32_t)BR_LANE_BASES; ++j) {
@@ -183,37 +176,28 @@ __global__ __launch_bounds__(BR_THREADS) void k_br_positions(const BrArgs A) {
     __shared__ uint32_t s_base[2 * BR_POS_TILE * 5];
     const uint32_t tid = threadIdx.x, pos0 = blockIdx.x * (uint32_t)BR_POS_TILE;
     if (pos0 >= A.head->longest) return;  // (the same word for every lane of the workgroup: nobody waits at a barrier below)
-    for (uint32_t i = tid; i < 2u * BR_POS_TILE * TALLY_QPITCH; i += BR_THREADS) s_qual[i] = 0u;
+    tile_qual_zero<2>(s_qual, tid);
     for (uint32_t i = tid; i < 2u * BR_POS_TILE * 5u; i += BR_THREADS) s_base[i] = 0u;
     __syncthreads();
-    const uint32_t lane = tid & 63u, waves = BR_THREADS / 64, L = (uint32_t)A.L;
+    const uint32_t lane = tid & 63u, L = (uint32_t)A.L;
     const uint32_t pos = pos0 + lane;
-    for (uint64_t r64 = (uint64_t)blockIdx.y * waves + (tid >> 6); r64 < A.n_rec; r64 += (uint64_t)gridDim.y * waves) {
+    for (uint64_t r64 = (uint64_t)blockIdx.y * BR_WAVES + (tid >> 6); r64 < A.n_rec; r64 += (uint64_t)gridDim.y * BR_WAVES) {
         const uint4 d = A.desc[(uint32_t)r64];
         const uint32_t len = d.z & BR_D_LEN;
         if ((d.z & BR_D_OUT) || pos >= len) continue;  // (len <= L)
         const uint32_t src = (d.z & BR_D_REVERSE) ? len - 1u - pos : pos;
-        uint32_t nib = ((uint32_t)A.data[d.x + (src >> 1)] >> ((src & 1u) ? 0u : 4u)) & 15u;
+        uint32_t nib = brec::seq_nibble(A.data, d.x, src);
         if (d.z & BR_D_REVERSE) nib = __brev(nib) >> 28;  // the complement: the four bits in reverse order
         const uint32_t q = A.data[d.y + src];             // (k_br_records saw q <= 93)
-        const uint32_t c = nib == 1u ? 0u : nib == 2u ? 1u : nib == 4u ? 2u : nib == 8u ? 3u : 4u;  // A, C, G, T, any other letter
+        const uint32_t c = brec::nib_code(nib);           // (in front of the adds: both loads are in flight together)
         const uint32_t slot = ((d.z & BR_D_MATE) ? (uint32_t)BR_POS_TILE : 0u) + lane;
         atomicAdd(&s_qual[slot * TALLY_QPITCH + q], 1u);
         atomicAdd(&s_base[slot * 5u + c], 1u);
     }
     __syncthreads();
     const fq::FqLayout lay = fq::fq_layout((int)L);
-    for (uint32_t i = tid; i < 2u * BR_POS_TILE * TALLY_NQ; i += BR_THREADS) {
-        const uint32_t slot = i / TALLY_NQ, ph = i - slot * TALLY_NQ;
-        const uint32_t n = s_qual[slot * TALLY_QPITCH + ph], p = pos0 + (slot & 63u);
-        const int64_t m = slot >> 6;
-        if (n && p < L) atomicAdd(&A.tally[lay.t.qual + (m * L + p) * TALLY_NQ + ph], (unsigned long long)n);
-    }
-    for (uint32_t i = tid; i < 2u * BR_POS_TILE * 5u; i += BR_THREADS) {
-        const uint32_t slot = i / 5u, p = pos0 + (slot & 63u);
-        const int64_t m = slot >> 6;
-        if (s_base[i] && p < L) atomicAdd(&A.tally[lay.t.base + (m * L + p) * 5 + (i - slot * 5u)], (unsigned long long)s_base[i]);
-    }
+    tile_qual_flush<2>(s_qual, tid, pos0, L, A.tally + lay.t.qual);
+    tile_base_flush<2>(s_base, tid, pos0, L, A.tally + lay.t.base);
 }
 
 // The launch geometry (host): wgs workgroups aimed at (0: BR_TARGET_WGS) by k_br_records and by every tile column of
@@ -221,13 +205,18 @@ __global__ __launch_bounds__(BR_THREADS) void k_br_positions(const BrArgs A) {
 struct BrPlan {
     uint32_t rec_wgs, pos_tiles, pos_chunks;
 };
+// workgroups of a wave-per-record kernel (k_be_records, k_bd_records, a tile column of k_br_positions): no more than have records
+inline uint32_t wave_record_wgs(int64_t n_rec, int wgs) {
+    const int64_t target = wgs > 0 ? wgs : BR_TARGET_WGS;
+    return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(target, (n_rec + BR_WAVES - 1) / BR_WAVES));
+}
 inline BrPlan br_plan(int64_t n_rec, int L, int wgs) {
     const int64_t target = wgs > 0 ? wgs : BR_TARGET_WGS;
     BrPlan p;
     p.rec_wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(target, (n_rec + BR_THREADS / BR_GROUP - 1) / (BR_THREADS / BR_GROUP)));
     p.pos_tiles = (uint32_t)((L + BR_POS_TILE - 1) / BR_POS_TILE);
     // (per tile column: the host does not know the longest read, and the columns beyond it leave at their first instruction)
-    p.pos_chunks = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(target, (n_rec + BR_THREADS / 64 - 1) / (BR_THREADS / 64)), 65535));
+    p.pos_chunks = std::min<uint32_t>(wave_record_wgs(n_rec, wgs), 65535u);
     return p;
 }
 

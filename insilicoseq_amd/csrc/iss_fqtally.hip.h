@@ -26,6 +26,7 @@ constexpr int FQ_HEAD_PER = 8;            // tile counts per lane and pass of k_
 constexpr int FQ_MAX_LEN = 1024;          // (= ISS_FQ_MAX_LEN)
 constexpr int FQ_GROUP = 16;              // lanes of a record in k_fq_records: 4 bytes a lane, 64 bytes a step
 constexpr int FQ_POS_TILE = 64;           // positions of a workgroup's tables in k_fq_positions: a wave's lanes
+static_assert(FQ_THREADS == TALLY_THREADS && FQ_POS_TILE == TALLY_TILE, "k_fq_positions uses iss_tally.hip.h's phred tile");
 constexpr int FQ_TARGET_WGS = 2048;       // workgroups of a launch, about: 8 per compute unit
 constexpr uint32_t FQ_BAD = 0xFFFFFFFFu;  // rec_len of a record that is not tallied
 
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(FQ_THREADS) void k_fq_positions(const FqArgs A) {
     __shared__ uint32_t s_base[FQ_POS_TILE * 5];
     const uint32_t tid = threadIdx.x, pos0 = blockIdx.x * (uint32_t)FQ_POS_TILE;
     if (pos0 >= A.head->longest) return;  // (the same word for every lane of the workgroup: nobody waits at a barrier below)
-    for (uint32_t i = tid; i < (uint32_t)FQ_POS_TILE * TALLY_QPITCH; i += FQ_THREADS) s_qual[i] = 0u;
+    tile_qual_zero<1>(s_qual, tid);
     for (uint32_t i = tid; i < (uint32_t)FQ_POS_TILE * 5u; i += FQ_THREADS) s_base[i] = 0u;
     __syncthreads();
     const uint32_t lane = tid & 63u, waves = FQ_THREADS / 64, L = (uint32_t)A.L;
@@ -269,15 +270,8 @@ __global__ __launch_bounds__(FQ_THREADS) void k_fq_positions(const FqArgs A) {
     __syncthreads();
     const FqLayout lay = fq_layout((int)L);
     const int64_t m = A.mate;
-    for (uint32_t i = tid; i < (uint32_t)FQ_POS_TILE * TALLY_NQ; i += FQ_THREADS) {
-        const uint32_t slot = i / TALLY_NQ, ph = i - slot * TALLY_NQ;
-        const uint32_t n = s_qual[slot * TALLY_QPITCH + ph], p = pos0 + slot;
-        if (n && p < L) atomicAdd(&A.tally[lay.t.qual + (m * L + p) * TALLY_NQ + ph], (unsigned long long)n);
-    }
-    for (uint32_t i = tid; i < (uint32_t)FQ_POS_TILE * 5u; i += FQ_THREADS) {
-        const uint32_t slot = i / 5u, p = pos0 + slot;
-        if (s_base[i] && p < L) atomicAdd(&A.tally[lay.t.base + (m * L + p) * 5 + (i - slot * 5u)], (unsigned long long)s_base[i]);
-    }
+    tile_qual_flush<1>(s_qual, tid, pos0, L, A.tally + lay.t.qual + m * L * TALLY_NQ);
+    tile_base_flush<1>(s_base, tid, pos0, L, A.tally + lay.t.base + m * L * 5);
 }
 
 // The launch geometry of stages b and c (host): wgs workgroups aimed at (0: FQ_TARGET_WGS) by k_fq_records and by every tile

@@ -1,6 +1,7 @@
 // iss_host_session.hip.h -- what the stand-alone device contexts share on the host (iss_api_bam.hip.h, iss_api_fqtally.hip.h,
 // iss_api_inflate.hip.h, iss_api_bamreads.hip.h, iss_api_fasta.hip.h; struct iss_session and its fail(): iss_host_util.hip.h): the front of a create and
-// of a destroy, the slot of a two-slot pipeline with its timed kernels, grow-only buffers with their capacity, the first-bad word.
+// of a destroy, the slot of a two-slot pipeline with its timed kernels, grow-only buffers with their capacity, the first-bad word, the
+// check of a BAM chunk's record offsets.
 #pragma once
 
 namespace {
@@ -88,7 +89,29 @@ struct Grown {  // one buffer: Grown<DevMem<T>>, Grown<PinMem<T>>
     int alloc(iss_session *owner, size_t n, const char *what) { return own_alloc(owner, p, n, what); }
 };
 
+// Every record of a BAM chunk must lie inside the chunk, its fixed fields and its block_size both: the kernels trust these offsets
+// (iss_bam_scan makes them, ascending).  who: the entry point, for the message.
+int records_inside(iss_session *s, const char *who, const uint8_t *data, int64_t n_bytes, const int64_t *offsets, int64_t n_records, bool ascending) {
+    int64_t before = -1;
+    for (int64_t r = 0; r < n_records; ++r) {
+        const int64_t o = offsets[r];
+        if (o < 0 || o + 4 + 32 > n_bytes) return fail(s, ISS_E_INVALID, std::string(who) + ": record offset outside the chunk");
+        if (ascending && o <= before) return fail(s, ISS_E_INVALID, std::string(who) + ": record offsets do not ascend");
+        int32_t bs;
+        memcpy(&bs, data + o, 4);
+        if (bs < 32 || o + 4 + (int64_t)bs > n_bytes) return fail(s, ISS_E_INVALID, std::string(who) + ": record outside the chunk");
+        before = o;
+    }
+    return 0;
+}
+
 // A first-bad word as the kernels keep it, (index << 8) | code with the smallest winning; all ones: none, index -1 and code 0.
+// bad_state_clear: n_bytes at p zeroed (counters, a state struct) and the first-bad word bad_at bytes in set to none; the caller waits.
+int bad_state_clear(iss_session *s, hipStream_t stream, void *p, size_t n_bytes, size_t bad_at) {
+    HIP_TRY(s, hipMemsetAsync(p, 0, n_bytes, stream));
+    HIP_TRY(s, hipMemsetAsync(static_cast<uint8_t *>(p) + bad_at, 0xFF, sizeof(unsigned long long), stream));
+    return 0;
+}
 void bad_word_split(unsigned long long word, int64_t *index, int32_t *code) {
     *index = word == ~0ull ? -1 : (int64_t)(word >> 8);
     *code = word == ~0ull ? 0 : (int32_t)(word & 0xFF);

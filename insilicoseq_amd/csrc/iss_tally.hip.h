@@ -16,6 +16,8 @@ constexpr int TALLY_QPITCH = 95;        // LDS words per (mate, position) of the
 constexpr int TALLY_TARGET_WGS = 2048;  // workgroups of a launch, about: 8 per compute unit
 constexpr int64_t TALLY_MAX_WG_PAIRS = (int64_t)1 << 30;  // pairs of one workgroup at most: a u32 LDS counter cannot wrap
 
+constexpr int TALLY_TILE = 64;          // positions of a phred tile: a wave's lanes
+
 struct TallyLayout {  // word offsets of the fields for read length L
     int64_t qual, base, gc, meanq, insert, words;
 };
@@ -69,6 +71,31 @@ struct TallyArgs {
 
 constexpr size_t TALLY_LINES_LDS = sizeof(uint32_t) * (64 * TALLY_QPITCH + 64 * 5);
 inline size_t tally_reads_lds(int RL) { return sizeof(uint32_t) * (size_t)(TALLY_NINS + 2 * TALLY_NQ + 2 * (RL + 1)); }
+
+// The phred tile of k_fq_positions, k_br_positions and k_be_bases: u32 [MATES x 64][TALLY_QPITCH] in LDS, slot = mate * 64 + position
+// in the tile; beside it [MATES x 64][5] base codes.  A flush adds the non-zero counters of positions pos0 .. pos0 + 63 below L to a
+// field [..][L][94] (or [..][L][5]) of u64 words, `field` its word 0 for the tile's mate 0.  All TALLY_THREADS threads call.
+template <int MATES>
+__device__ __forceinline__ void tile_qual_zero(uint32_t *s_qual, uint32_t tid) {
+    for (uint32_t i = tid; i < (uint32_t)(MATES * TALLY_TILE * TALLY_QPITCH); i += TALLY_THREADS) s_qual[i] = 0u;
+}
+template <int MATES>
+__device__ __forceinline__ void tile_qual_flush(const uint32_t *s_qual, uint32_t tid, uint32_t pos0, uint32_t L, unsigned long long *field) {
+    for (uint32_t i = tid; i < (uint32_t)(MATES * TALLY_TILE * TALLY_NQ); i += TALLY_THREADS) {
+        const uint32_t slot = i / TALLY_NQ, ph = i - slot * TALLY_NQ;
+        const uint32_t n = s_qual[slot * TALLY_QPITCH + ph], p = pos0 + (slot & 63u);
+        const int64_t m = slot >> 6;
+        if (n && p < L) atomicAdd(&field[(m * L + p) * TALLY_NQ + ph], (unsigned long long)n);
+    }
+}
+template <int MATES>
+__device__ __forceinline__ void tile_base_flush(const uint32_t *s_base, uint32_t tid, uint32_t pos0, uint32_t L, unsigned long long *field) {
+    for (uint32_t i = tid; i < (uint32_t)(MATES * TALLY_TILE * 5); i += TALLY_THREADS) {
+        const uint32_t slot = i / 5u, p = pos0 + (slot & 63u);
+        const int64_t m = slot >> 6;
+        if (s_base[i] && p < L) atomicAdd(&field[(m * L + p) * 5 + (i - slot * 5u)], (unsigned long long)s_base[i]);
+    }
+}
 
 // The per-position tables.  Workgroup (l, c) reads line l -- 128 bytes: the 32 positions 32 l .. 32 l + 31 of both mates -- of
 // every pair of its chunk, at stride `row`; its tables are those of one line: 64 (mate, position) x (94 phreds + 5 base codes).

@@ -1,4 +1,4 @@
-"""The tag walk and the MD walk of k_be_records (insilicoseq_amd/csrc/iss_bamerrors_walk.h) compiled for the host and driven by
+"""The tag walk and the MD walk of k_be_records (insilicoseq_amd/csrc/iss_bam_record.h) compiled for the host and driven by
 tools/bam_errors_walk.cpp over every valid and damaged case: the verdicts and the row counts of the constructions, under
 AddressSanitizer and UBSan where the compiler has them (a stand-alone program; nothing is loaded into Python)."""
 import os

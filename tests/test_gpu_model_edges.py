@@ -128,6 +128,59 @@ def test_split_feeds(dev, twin_all):
         assert not mismatch(unpack_tallies(words), twin_all), size
 
 
+# ---- 2b. the optional fields: `model` and `report --bam --errors` read them with one walk (iss_bam_record.h: be_tag_walk)
+
+def _tag_cases():
+    import bam_error_cases as EC
+
+    cases = [r for r in EC.damaged_cases() if "raw_aux" in r] + [r for r in EC.op_cases() if r["name"] == "two_bytes_left"]
+    assert sorted(str(r["_case"]["expect"]) for r in cases) == ["2"] * 10 + ["no_md"] * 3 + ["tallied"]
+    return EC, cases
+
+
+def _tag_verdict(r, index):
+    """(bad record, code) of `model` from the case's own expectation: ALN_TAGS -> E_REC_MALFORMED, "no_md" -> E_REC_NO_MD."""
+    what = r["_case"]["expect"]
+    return (-1, 0) if what == "tallied" else (index, 5 if what == "no_md" else 1)
+
+
+def _tag_tallies(dev, recs, good, case_recs):
+    """Feeds recs; -> (bad record, code), and the fields that differ from the twin.  A record dropped for its optional fields has
+    added its header phase by then (taken, the quality slice: k_bam_tally's phase A, as before), so those fields are the twin's
+    of the record with a plain MD:Z in place of its bytes; subst, indel and tlen are those of the good records alone."""
+    dev.reset()
+    feed(dev, recs)
+    words, bad, code = dev.tallies()
+    from insilicoseq_amd.modeller import unpack_tallies
+
+    got = unpack_tallies(words)
+    plain = [dict(r, tags=r["tags"] or [("MD", "Z", "20")], raw_aux=b"") for r in case_recs]
+    rows, head = twin(good + [p for p in plain if p["_case"]["expect"] == "tallied"]), twin(good + plain)
+    exp = dict(head, subst=rows["subst"], indel=rows["indel"], tlen=rows["tlen"])
+    return (bad, code), mismatch(got, exp)
+
+
+def test_optional_fields_get_the_error_stage_verdict(dev):
+    """The records of bam_error_cases whose optional fields are raw bytes (ten damaged: code 1; three without MD:Z: code 5; one that
+    ends two bytes behind its MD:Z: tallied), each alone, each between two good records, and all of them in one feed (which can
+    show the first bad record only).  Of the tallies, subst, indel and tlen equal the twin of the good neighbours alone.  taken,
+    nread, minlen and qhist do not and never did: k_bam_tally counts a record's header phase before it looks at the optional
+    fields, so these are held to the twin of the neighbours plus each dropped record with a plain MD:Z:20 (_tag_tallies)."""
+    EC, cases = _tag_cases()
+    failed = []
+    for r in cases:
+        for recs, index in (([r], 0), (EC.between_good(r, 1), 1)):
+            good = [g for g in recs if g is not r]
+            verdict, miss = _tag_tallies(dev, recs, good, [r])
+            if verdict != _tag_verdict(r, index) or miss:
+                failed.append((r["name"], len(recs), verdict, miss))
+    assert not failed, failed
+    recs = [x for r in cases for x in EC.between_good(r, 1)]
+    good = [x for x in recs if not any(x is r for r in cases)]
+    verdict, miss = _tag_tallies(dev, recs, good, cases)
+    assert (verdict, miss) == (_tag_verdict(cases[0], 1), [])
+
+
 def _good(n):
     return (TABLE * (-(-n // len(TABLE))))[:n]
 

@@ -1,5 +1,6 @@
-// bam_errors_walk.cpp -- the two serial walks of `report --bam --errors` (insilicoseq_amd/csrc/iss_bamerrors_walk.h, the code lane 0
-// of k_be_records runs) driven on the host, one record at a time, so that a sanitizer can watch them on damaged records:
+// bam_errors_walk.cpp -- the record view and the tag walk every BAM kernel reads through and the MD walk of `report --bam --errors`
+// (insilicoseq_amd/csrc/iss_bam_record.h) -- the code lane 0 of k_be_records runs, the tag walk lane 0 of k_bam_tally too -- driven
+// on the host, one record at a time, so that a sanitizer can watch them on damaged records:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -I insilicoseq_amd/csrc -o bam_errors_walk tools/bam_errors_walk.cpp
 //   ./bam_errors_walk records.bin
 // records.bin: the raw alignment records (block_size first) back to back, as tests/test_bam_errors_walk_host.py writes them from the
@@ -9,35 +10,36 @@
 #include <cstdlib>
 #include <vector>
 
-#include "iss_bamerrors_walk.h"
+#include "iss_bam_record.h"
 
 using namespace iss::be;
+using namespace iss::brec;
 
 static void one(const uint8_t *rec, int64_t size) {
-    const int64_t block_size = (int32_t)be_u32(rec);
-    const uint32_t l_name = rec[12], n_cigar = be_u32(rec + 16) & 0xFFFFu, flag = be_u32(rec + 16) >> 16;
-    const int64_t l_seq = (int32_t)be_u32(rec + 20);
-    if (size != 4 + block_size || l_seq < 0 || 32 + l_name + 4ll * n_cigar + (l_seq + 1) / 2 + l_seq > block_size) {
+    const RecHead h = rec_head(rec);
+    const uint32_t n_cigar = h.n_cigar;
+    const int64_t l_seq = h.l_seq;
+    if (size != h.end() || !h.fits()) {
         puts("S");  // not a record the read tally takes: the walks never see it
         return;
     }
-    if ((flag & 4u) || !n_cigar || !l_seq) {
+    if ((h.flag & 4u) || !n_cigar || !l_seq) {
         puts("U");
         return;
     }
-    const uint8_t *const cig = rec + 36 + l_name;
+    const uint8_t *const cig = rec + h.cigar_at();
     unsigned long long qsum = 0;
     bool bad_op = false;
     for (uint32_t i = 0; i < n_cigar; ++i) {
-        const uint32_t c = be_u32(cig + 4 * i), op = c & 15u;
-        bad_op |= op > 8u;
-        if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qsum += c >> 4;
+        const uint32_t c = u32(cig + 4 * i), op = c & 15u;
+        bad_op |= op > OP_LAST;
+        if (in(op, OPS_QUERY)) qsum += c >> 4;
     }
     if (bad_op || qsum != (unsigned long long)l_seq) {
         printf("%d\n", BE_ALN_CIGAR);
         return;
     }
-    const uint8_t *const aux = cig + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+    const uint8_t *const aux = rec + h.aux_at();
     int64_t md_at = 0;
     uint32_t md_len = 0;
     const int st = be_tag_walk(aux, (rec + size) - aux, &md_at, &md_len);
@@ -67,7 +69,7 @@ int main(int argc, char **argv) {
     for (;;) {
         uint8_t head[4];
         if (fread(head, 1, 4, fh) != 4) break;
-        const int64_t block_size = (int32_t)be_u32(head);
+        const int64_t block_size = (int32_t)u32(head);
         if (block_size < 32 || block_size > (1 << 28)) {
             fprintf(stderr, "block_size %lld: not a record\n", (long long)block_size);
             return 2;

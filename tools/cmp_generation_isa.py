@@ -3,7 +3,10 @@
 A change that adds kernels of its own must leave them alone; --all compares every kernel of the first file instead (a change of
 the host side alone must leave all of them as they are).  Compared per kernel: every instruction, directive and label, with
 comments dropped and the function number taken out of the basic-block labels (.LBB<function>_<block>: hipcc numbers the
-functions of a translation unit in order, so a kernel added in front of another renumbers labels and nothing else).
+functions of a translation unit in order, so a kernel added in front of another renumbers labels and nothing else) and the
+suffix out of a renumbered private symbol (.crctable.92: the compiler numbers function-local statics that share a name across
+the translation unit, so a header whose statics move renumbers them and nothing else; two numbered statics of one name that a kernel swaps would
+pass unseen).
 For each kernel that differs, both files' instruction count and register use (amdhsa.kernels metadata) are printed.
 
 Usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -I include -S --cuda-device-only -cuid=iss -o new.s insilicoseq_amd/csrc/iss_mi355x.hip
@@ -13,6 +16,7 @@ import re
 import sys
 
 GENERATION = re.compile(r"k_main|k_setup|k_indel_|k_perfect|k_mt_")
+PRIVATE_NUMBER = re.compile(r"(?<![\w.])(\.[A-Za-z_]\w*)\.\d+(?=@|\b)")  # .crctable.92@rel32@lo -> .crctable.N@rel32@lo
 
 
 def kernels(path):
@@ -28,7 +32,7 @@ def kernels(path):
                 continue
             line = line.split(";", 1)[0].rstrip()
             if line:
-                out[name].append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+                out[name].append(PRIVATE_NUMBER.sub(r"\1.N", re.sub(r"\.LBB\d+_", ".LBB_", line)))
     return out
 
 
