@@ -13,48 +13,6 @@ E_INVALID, E_HIP, E_NOMEM, E_SHORT_RECORD, E_IO = -1, -2, -3, -4, -5
 SEQ_TYPES = {"metagenomics": 0, "amplicon": 1}
 EXPORT_ENCODINGS = {"ascii": 0, "codes": 1}  # ISS_EXPORT_ASCII / ISS_EXPORT_CODES
 
-# every symbol include/iss_mi355x.h declares (tests check the library exports all of them)
-EXPORTS = (
-    "iss_abi_version", "iss_ctx_create", "iss_ctx_destroy", "iss_last_error", "iss_ctx_set_stream",
-    "iss_model_upload", "iss_genome_upload", "iss_genome_upload_packed", "iss_genome_upload_group", "iss_genome_clear", "iss_output_reserve", "iss_output_pitch",
-    "iss_output_device_ptrs", "iss_output_row", "iss_generate", "iss_synchronize", "iss_output_download",
-    "iss_output_download_coords", "iss_timing_enable", "iss_timing_read", "iss_stats_read", "iss_build_id", "iss_fastq_write",
-    "iss_mt_seed", "iss_generate_mt", "iss_mt_peek", "iss_mt_mutations_reserve", "iss_mt_mutations_download",
-    "iss_mt_set_fragment", "iss_set_fragment", "iss_mutations_reserve", "iss_mutations_download",
-    "iss_mt_path_counts", "iss_fastq_emit", "iss_fastq_flush", "iss_fastq_compress", "iss_deflate_code_build",
-    "iss_generate_batch", "iss_fastq_emit_batch", "iss_gen_phred_scores", "iss_mut_sequence", "iss_random_insert_size",
-    "iss_introduce_indels", "iss_ev_step", "iss_mt_workers_seed", "iss_generate_mt_workers", "iss_mt_workers_peek",
-    "iss_main_kernel", "iss_fastq_emit_scatter", "iss_vcf_emit", "iss_vcf_flush",
-    "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download", "iss_vcf_emit_workers",
-    "iss_bam_scan", "iss_bam_create", "iss_bam_destroy", "iss_bam_last_error", "iss_bam_reset", "iss_bam_feed",
-    "iss_bam_tally_download", "iss_bam_kde",
-    "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export",
-    "iss_tally_words", "iss_output_tally",
-    "iss_depth_mark", "iss_depth_finish",
-    "iss_ubam_emit_batch", "iss_ubam_flush", "iss_ubam_host_records",
-    "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
-    "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build",
-    "iss_error_tally_words", "iss_mutations_tally",
-    "iss_fq_create", "iss_fq_destroy", "iss_fq_last_error", "iss_fq_reset", "iss_fq_tally_words", "iss_fq_feed", "iss_fq_download",
-    "iss_fq_kernel_ms",
-    "iss_bgzf_scan", "iss_inflate_create", "iss_inflate_destroy", "iss_inflate_last_error", "iss_inflate_reset", "iss_inflate_feed",
-    "iss_inflate_collect", "iss_inflate_first_bad", "iss_inflate_kernel_ms",
-    "iss_br_create", "iss_br_destroy", "iss_br_last_error", "iss_br_reset", "iss_br_tally_words", "iss_br_feed", "iss_br_download",
-    "iss_br_kernel_ms", "iss_br_errors_enable", "iss_br_error_words", "iss_br_errors_download",
-    "iss_br_depth_enable", "iss_br_depth_download",
-    "iss_mt_resolver_pick",
-    "iss_genome_upload_variants", "iss_genome_download", "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply",
-    "iss_variants_host_lift",
-)
-# `generate --device_fasta` (a build from before them still loads; fasta.FastaIndexer and ReadEngine.add_genomes_fasta then raise)
-FASTA_ENTRIES = ("iss_fa_create", "iss_fa_destroy", "iss_fa_last_error", "iss_fa_index", "iss_fasta_host_index", "iss_fasta_tile",
-                 "iss_fasta_scan_span", "iss_genome_upload_fasta")
-EXPORTS += FASTA_ENTRIES
-
-# The stand-alone device contexts (class Session below): entry prefix -> the arguments of its create call between the device ordinal
-# and the handle.  Each has create, destroy, last_error and reset; kernel_ms and tally_words where EXPORTS names them.
-SESSIONS = {"iss_bam": (), "iss_fq": (C.c_int32,), "iss_inflate": (), "iss_br": (C.c_int32,)}
-
 # `model` tallies (include/iss_mi355x.h: ISS_BAM_*)
 BAM_MAX_LEN, BAM_NQ, BAM_NTLEN = 301, 94, 2000
 BAM_OFF_INDEL, BAM_OFF_QHIST, BAM_OFF_TLEN, BAM_OFF_NREAD, BAM_OFF_MINLEN, BAM_OFF_TAKEN, BAM_TALLY_WORDS = (
@@ -124,6 +82,146 @@ class ModelTables(C.Structure):
     ]
 
 
+# The binding, one row per declaration of include/iss_mi355x.h in the header's order: (name, restype, argtypes, group).  group None: every
+# supported build has the entry.  A label: the entries that arrived together, additive to ABI 8 -- a build from before them still loads
+# (ISS_MI355X_LIB, A/B runs against an older library) and need() raises where they are asked for.  To add an entry: its declaration in
+# the header and its row here; tests/test_native_table_host.py holds the two to each other, type for type.
+P, vp, str_, int_, i32, i64, u32, u64, f64 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
+TABLE = (
+    ("iss_abi_version", int_, (), None),
+    ("iss_build_id", str_, (), None),
+    ("iss_ctx_create", int_, (int_, P(vp)), None),
+    ("iss_ctx_destroy", None, (vp,), None),
+    ("iss_last_error", str_, (vp,), None),
+    ("iss_ctx_set_stream", int_, (vp, vp), None),
+    ("iss_model_upload", int_, (vp, P(ModelTables)), None),
+    ("iss_genome_upload", int_, (vp, vp, i64, P(i32)), None),
+    ("iss_genome_upload_packed", int_, (vp, vp, i64, i32, P(i32)), None),
+    ("iss_genome_upload_group", int_, (vp, i32, vp, vp, vp), None),
+    ("iss_genome_clear", int_, (vp,), None),
+    ("iss_output_reserve", int_, (vp, i64), None),
+    ("iss_output_pitch", int_, (vp,), None),
+    ("iss_output_device_ptrs", int_, (vp, P(vp), P(vp), P(vp), P(vp)), None),
+    ("iss_output_row", int_, (vp,), None),
+    ("iss_generate", int_, (vp, i32, i64, u64, u64, i32, i32, i64), None),
+    ("iss_generate_batch", int_, (vp, i32, vp, vp, u64, u64, i32, i32, i64), None),
+    ("iss_set_fragment", int_, (vp, i32, f64, f64), None),
+    ("iss_synchronize", int_, (vp,), None),
+    ("iss_gen_phred_scores", int_, (vp, i32, i64, u64, u64, vp), None),
+    ("iss_mut_sequence", int_, (vp, i32, i64, u64, u64, vp, vp, vp), None),
+    ("iss_random_insert_size", int_, (vp, i64, u64, u64, vp), None),
+    ("iss_introduce_indels", int_, (vp, i32, i64, u64, u64, vp, vp, vp, i64, vp, vp, vp), None),
+    ("iss_ev_step", int_, (vp, i32, i64, vp, vp, vp, vp, vp, vp), None),
+    ("iss_mutations_reserve", int_, (vp, i64), None),
+    ("iss_mutations_download", int_, (vp, vp, i64, P(i64)), None),
+    ("iss_output_download", int_, (vp, i64, i64, vp, vp, vp, vp), None),
+    ("iss_output_download_coords", int_, (vp, i64, i64, vp), None),
+    ("iss_output_export", int_, (vp, i64, i64, i32, vp, vp, vp, vp), "export"),
+    ("iss_mutations_export", int_, (vp, i64, i64, i32, vp, vp, i64, vp), "mutations_export"),
+    ("iss_tally_words", i64, (vp,), "tally"),
+    ("iss_output_tally", int_, (vp, i64, i64, vp), "tally"),
+    ("iss_depth_mark", int_, (vp, i64, i64, vp, i32, vp), "depth"),
+    ("iss_depth_finish", int_, (vp, vp, i64, vp, vp, i32, i32, vp, vp), "depth"),
+    ("iss_error_tally_words", i64, (vp,), "errtally"),
+    ("iss_mutations_tally", int_, (vp, i32, i64, i64, vp), "errtally"),
+    ("iss_ctx_set_stream_ordered", int_, (vp, vp), "export"),
+    ("iss_timing_enable", int_, (vp, int_), None),
+    ("iss_timing_read", int_, (vp, P(f64 * 4), P(i64)), None),
+    ("iss_stats_read", int_, (vp, P(i64), P(i64)), None),
+    ("iss_main_kernel", int_, (vp, vp, int_), None),
+    ("iss_mt_seed", int_, (vp, u64), None),
+    ("iss_generate_mt", int_, (vp, i32, i64, i32, i32, i64, P(i64)), None),
+    ("iss_mt_peek", int_, (vp, vp, vp, i32), None),
+    ("iss_mt_path_counts", int_, (vp, P(i64), P(i64)), None),
+    ("iss_mt_resolver_pick", int_, (vp, P(i32 * 3)), "mt_resolver"),
+    ("iss_mt_workers_seed", int_, (vp, i32, vp), None),
+    ("iss_generate_mt_workers", int_, (vp, i32, vp, vp, vp, i32, i32, vp, vp), None),
+    ("iss_mt_workers_peek", int_, (vp, i32, vp, vp, i32), None),
+    ("iss_mt_set_fragment", int_, (vp, i32, f64, f64), None),
+    ("iss_mt_mutations_reserve", int_, (vp, i64), None),
+    ("iss_mt_mutations_download", int_, (vp, vp, i64, P(i64)), None),
+    ("iss_mt_workers_mutations_reserve", int_, (vp, i64), "set_rows"),
+    ("iss_mt_workers_mutations_download", int_, (vp, i32, vp, i64, P(i64)), "set_rows"),
+    ("iss_fastq_emit", int_, (vp, int_, int_, str_, i64, i32, i64, i64, i32), None),
+    ("iss_fastq_emit_batch", int_, (vp, int_, int_, i32, vp, vp, vp, vp, i32), None),
+    ("iss_fastq_emit_scatter", int_, (vp, int_, int_, i32, vp, vp, vp, vp, vp, vp, i32), None),
+    ("iss_fastq_flush", int_, (vp,), None),
+    ("iss_vcf_emit", int_, (vp, int_, i32, i32, vp, vp, vp, vp, i32, P(i64)), "vcf"),
+    ("iss_vcf_emit_workers", int_, (vp, i32, vp, vp, vp, vp, vp, vp), "set_rows"),
+    ("iss_vcf_flush", int_, (vp,), "vcf"),
+    ("iss_fastq_compress", int_, (vp, i32), None),
+    ("iss_deflate_code_build", int_, (vp, u32, vp, vp, vp, vp), None),
+    ("iss_fastq_write", int_, (int_, int_, str_, i64, i32, i64, i32, i32, vp, vp, vp, vp, i32), None),
+    ("iss_ubam_emit_batch", int_, (vp, int_, i32, vp, vp, vp, vp, i32), "ubam"),
+    ("iss_ubam_flush", int_, (vp,), "ubam"),
+    ("iss_ubam_host_records", int_, (int_, str_, i64, i32, i64, i32, i32, vp, vp, vp, vp), "ubam"),
+    ("iss_origins_emit_batch", int_, (vp, int_, i32, vp, vp, vp, vp, vp, i32), "origins"),
+    ("iss_origins_flush", int_, (vp,), "origins"),
+    ("iss_origins_host_text", int_, (int_, str_, i64, i32, i64, i32, i64, vp), "origins"),
+    ("iss_origins_compress", int_, (vp, i32), "bgzip"),
+    ("iss_vcf_compress", int_, (vp, i32), "bgzip"),
+    ("iss_bgzf_text_code_build", int_, (vp, vp, vp, vp, vp), "bgzip"),
+    ("iss_bam_scan", int_, (vp, i64, vp, i64, P(i64), P(i64)), None),
+    ("iss_bam_create", int_, (int_, P(vp)), None),
+    ("iss_bam_destroy", None, (vp,), None),
+    ("iss_bam_last_error", str_, (vp,), None),
+    ("iss_bam_reset", int_, (vp,), None),
+    ("iss_bam_feed", int_, (vp, vp, i64, vp, vp, i64), None),
+    ("iss_bam_tally_download", int_, (vp, vp, P(i64), P(i32)), None),
+    ("iss_bam_kde", int_, (vp, i32, i32, vp, vp), None),
+    ("iss_fq_create", int_, (int_, i32, P(vp)), "fq"),
+    ("iss_fq_destroy", None, (vp,), "fq"),
+    ("iss_fq_last_error", str_, (vp,), "fq"),
+    ("iss_fq_reset", int_, (vp,), "fq"),
+    ("iss_fq_tally_words", i64, (vp,), "fq"),
+    ("iss_fq_feed", int_, (vp, i32, vp, i64), "fq"),
+    ("iss_fq_download", int_, (vp, vp, vp, vp, vp), "fq"),
+    ("iss_fq_kernel_ms", int_, (vp, P(f64)), "fq"),
+    ("iss_bgzf_scan", int_, (vp, i64, vp, vp, vp, vp, vp, i64, P(i64), P(i64)), "inflate"),
+    ("iss_inflate_create", int_, (int_, P(vp)), "inflate"),
+    ("iss_inflate_destroy", None, (vp,), "inflate"),
+    ("iss_inflate_last_error", str_, (vp,), "inflate"),
+    ("iss_inflate_reset", int_, (vp,), "inflate"),
+    ("iss_inflate_feed", int_, (vp, vp, i64, vp, vp, vp, vp, i64), "inflate"),
+    ("iss_inflate_collect", int_, (vp, P(vp), P(i64), P(vp), P(i64)), "inflate"),
+    ("iss_inflate_first_bad", int_, (vp, P(i64), P(i32)), "inflate"),
+    ("iss_inflate_kernel_ms", int_, (vp, P(f64)), "inflate"),
+    ("iss_br_create", int_, (int_, i32, P(vp)), "br"),
+    ("iss_br_destroy", None, (vp,), "br"),
+    ("iss_br_last_error", str_, (vp,), "br"),
+    ("iss_br_reset", int_, (vp,), "br"),
+    ("iss_br_tally_words", i64, (vp,), "br"),
+    ("iss_br_feed", int_, (vp, vp, i64, vp, i64), "br"),
+    ("iss_br_download", int_, (vp, vp, vp, vp, P(i64), P(i32)), "br"),
+    ("iss_br_kernel_ms", int_, (vp, P(f64)), "br"),
+    ("iss_br_errors_enable", int_, (vp,), "br_errors"),
+    ("iss_br_error_words", i64, (vp,), "br_errors"),
+    ("iss_br_errors_download", int_, (vp, vp, vp, P(i64), P(i32)), "br_errors"),
+    ("iss_br_depth_enable", int_, (vp, vp, i32, vp, u32, i32), "br_depth"),
+    ("iss_br_depth_download", int_, (vp, vp, P(i64), P(i32)), "br_depth"),
+    ("iss_genome_upload_variants", int_, (vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, P(i32)), "variants"),
+    ("iss_genome_download", int_, (vp, i32, vp, i64, P(i64)), "variants"),
+    ("iss_variants_lift", int_, (vp, vp, i32, vp, i64, vp), "variants"),
+    ("iss_variants_apply_tile", int_, (), "variants"),
+    ("iss_variants_host_apply", int_, (vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64), "variants"),
+    ("iss_variants_host_lift", int_, (i64, vp, vp, vp, vp, vp, i64, vp), "variants"),
+    ("iss_fa_create", int_, (int_, P(vp)), "fasta"),
+    ("iss_fa_destroy", None, (vp,), "fasta"),
+    ("iss_fa_last_error", str_, (vp,), "fasta"),
+    ("iss_fa_index", int_, (vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, P(i64)), "fasta"),
+    ("iss_fasta_host_index", int_, (vp, i64, i64, vp, vp, vp, vp, vp, vp, P(i64)), "fasta"),
+    ("iss_fasta_tile", int_, (), "fasta"),
+    ("iss_fasta_scan_span", int_, (), "fasta"),
+    ("iss_genome_upload_fasta", int_, (vp, vp, i64, i32, vp, vp, vp, vp), "fasta"),
+)
+EXPORTS = tuple(row[0] for row in TABLE)  # every symbol include/iss_mi355x.h declares (tests check the library exports all of them)
+GROUPS = {g: tuple(row[0] for row in TABLE if row[3] == g) for g in dict.fromkeys(row[3] for row in TABLE if row[3])}  # label -> entries
+GROUP_HINTS = {"vcf": ", or set ISS_HOST_VCF=1 for the rows-to-host route"}  # what need() adds to its message
+
+# The stand-alone device contexts with a reset (class Session below), by entry prefix: each has create, destroy, last_error and reset
+# in TABLE, kernel_ms and tally_words where TABLE has them.
+SESSIONS = ("iss_bam", "iss_fq", "iss_inflate", "iss_br")
+
 _lib = None
 
 
@@ -140,190 +238,22 @@ def lib():
         L = C.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
-    L.iss_abi_version.restype = C.c_int
-    L.iss_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.iss_ctx_destroy.argtypes = [vp]
-    L.iss_ctx_destroy.restype = None
-    L.iss_last_error.argtypes = [vp]
-    L.iss_last_error.restype = C.c_char_p
-    L.iss_ctx_set_stream.argtypes = [vp, vp]
-    L.iss_model_upload.argtypes = [vp, C.POINTER(ModelTables)]
-    L.iss_genome_upload.argtypes = [vp, vp, i64, C.POINTER(i32)]
-    L.iss_genome_upload_packed.argtypes = [vp, vp, i64, i32, C.POINTER(i32)]
-    L.iss_genome_upload_group.argtypes = [vp, i32, vp, vp, vp]
-    L.iss_genome_clear.argtypes = [vp]
-    L.iss_output_reserve.argtypes = [vp, i64]
-    L.iss_output_pitch.argtypes = [vp]
-    L.iss_output_row.argtypes = [vp]
-    L.iss_output_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.iss_generate.argtypes = [vp, i32, i64, u64, u64, i32, i32, i64]
-    L.iss_synchronize.argtypes = [vp]
-    L.iss_output_download.argtypes = [vp, i64, i64, vp, vp, vp, vp]
-    L.iss_output_download_coords.argtypes = [vp, i64, i64, vp]
-    L.iss_timing_enable.argtypes = [vp, C.c_int]
-    L.iss_timing_read.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(i64)]
-    L.iss_stats_read.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
-    L.iss_build_id.restype = C.c_char_p
-    L.iss_build_id.argtypes = []
-    L.iss_mt_seed.argtypes = [vp, u64]
-    L.iss_generate_mt.argtypes = [vp, i32, i64, i32, i32, i64, C.POINTER(i64)]
-    L.iss_mt_peek.argtypes = [vp, vp, vp, i32]
-    L.iss_mt_path_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
-    L.iss_mt_workers_seed.argtypes = [vp, i32, vp]
-    L.iss_generate_mt_workers.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp]
-    L.iss_mt_workers_peek.argtypes = [vp, i32, vp, vp, i32]
-    L.iss_mt_mutations_reserve.argtypes = [vp, i64]
-    L.iss_mt_set_fragment.argtypes = [vp, i32, C.c_double, C.c_double]
-    L.iss_set_fragment.argtypes = [vp, i32, C.c_double, C.c_double]
-    L.iss_mutations_reserve.argtypes = [vp, i64]
-    L.iss_mutations_download.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.iss_mt_mutations_download.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.iss_fastq_emit.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, i64, i32, i64, i64, i32]
-    L.iss_fastq_emit_batch.argtypes = [vp, C.c_int, C.c_int, i32, vp, vp, vp, vp, i32]
-    L.iss_fastq_emit_scatter.argtypes = [vp, C.c_int, C.c_int, i32, vp, vp, vp, vp, vp, vp, i32]
-    # (the two entries a build from before them lacks: such a build still loads -- ISS_MI355X_LIB, A/B runs against an older
-    #  library -- and ReadEngine.vcf_emit raises; build() and the tests check that the in-tree library exports every name)
-    if hasattr(L, "iss_vcf_emit") and hasattr(L, "iss_vcf_flush"):
-        L.iss_vcf_emit.argtypes = [vp, C.c_int, i32, i32, vp, vp, vp, vp, i32, C.POINTER(i64)]
-        L.iss_vcf_flush.argtypes = [vp]
-    # (additive to ABI 8 as well: --store_mutations for the workers of a set)
-    if hasattr(L, "iss_vcf_emit_workers"):
-        L.iss_mt_workers_mutations_reserve.argtypes = [vp, i64]
-        L.iss_mt_workers_mutations_download.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
-        L.iss_vcf_emit_workers.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-    # (additive to ABI 8: the rows as dense device arrays; a build from before them still loads and ReadEngine.export raises)
-    if hasattr(L, "iss_output_export"):
-        L.iss_output_export.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
-        L.iss_ctx_set_stream_ordered.argtypes = [vp, vp]
-    # (additive to ABI 8 again: the mutation rows as dense device arrays; without it ReadEngine.export_mutations raises)
-    if hasattr(L, "iss_mutations_export"):
-        L.iss_mutations_export.argtypes = [vp, i64, i64, i32, vp, vp, i64, vp]
-    # (additive to ABI 8 once more: tallies of the rows built on the device; without them ReadEngine.tally raises)
-    if hasattr(L, "iss_output_tally"):
-        L.iss_tally_words.argtypes = [vp]
-        L.iss_output_tally.argtypes = [vp, i64, i64, vp]
-    # (and again: per-base coverage depth built on the device; without them ReadEngine.depth_mark / depth_finish raise)
-    if hasattr(L, "iss_depth_mark"):
-        L.iss_depth_mark.argtypes = [vp, i64, i64, vp, i32, vp]
-        L.iss_depth_finish.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp]
-    # (and once more: unaligned BAM built on the device; without them ReadEngine.ubam_emit_batch / ubam_flush raise)
-    if hasattr(L, "iss_ubam_emit_batch"):
-        L.iss_ubam_emit_batch.argtypes = [vp, C.c_int, i32, vp, vp, vp, vp, i32]
-        L.iss_ubam_flush.argtypes = [vp]
-        L.iss_ubam_host_records.argtypes = [C.c_int, C.c_char_p, i64, i32, i64, i32, i32, vp, vp, vp, vp]
-    # (and the pairs' source intervals as BEDPE text built on the device; without them ReadEngine.origins_emit_batch / origins_flush raise)
-    if hasattr(L, "iss_origins_emit_batch"):
-        L.iss_origins_emit_batch.argtypes = [vp, C.c_int, i32, vp, vp, vp, vp, vp, i32]
-        L.iss_origins_flush.argtypes = [vp]
-        L.iss_origins_host_text.argtypes = [C.c_int, C.c_char_p, i64, i32, i64, i32, i64, vp]
-    # (and the BGZF stage of the two text pipes; without them ReadEngine.origins_compress / vcf_compress raise)
-    if hasattr(L, "iss_origins_compress"):
-        L.iss_origins_compress.argtypes = [vp, i32]
-        L.iss_vcf_compress.argtypes = [vp, i32]
-        L.iss_bgzf_text_code_build.argtypes = [vp, vp, vp, vp, vp]
-    # (and tallies of the mutation rows built on the device; without them ReadEngine.error_tally raises)
-    if hasattr(L, "iss_mutations_tally"):
-        L.iss_error_tally_words.argtypes = [vp]
-        L.iss_mutations_tally.argtypes = [vp, i32, i64, i64, vp]
-    # (and `report`, `report --bam` and the device inflate: their own entries here, what every session has in the loop over
-    #  SESSIONS below; without them FastqTally, BamReadTally and BgzfInflater raise)
-    if hasattr(L, "iss_fq_feed"):
-        L.iss_fq_feed.argtypes = [vp, i32, vp, i64]
-        L.iss_fq_download.argtypes = [vp, vp, vp, vp, vp]
-    if hasattr(L, "iss_br_feed"):
-        L.iss_br_feed.argtypes = [vp, vp, i64, vp, i64]
-        L.iss_br_download.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
-    # (and the alignments' errors behind `report --bam`; without them BamReadTally(errors=True) raises)
-    if hasattr(L, "iss_br_errors_enable"):
-        L.iss_br_errors_enable.argtypes = [vp]
-        L.iss_br_error_words.argtypes = [vp]
-        L.iss_br_errors_download.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
-    # (and the alignments' reference intervals behind `report --bam`; without them BamReadTally(depth=True) raises)
-    if hasattr(L, "iss_br_depth_enable"):
-        L.iss_br_depth_enable.argtypes = [vp, vp, i32, vp, C.c_uint32, i32]
-        L.iss_br_depth_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
-    if hasattr(L, "iss_inflate_feed"):
-        L.iss_bgzf_scan.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-        L.iss_inflate_feed.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64]
-        L.iss_inflate_collect.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64)]
-        L.iss_inflate_first_bad.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
-    # (and which resolver instantiation MT mode takes; without it ReadEngine.mt_resolver raises)
-    if hasattr(L, "iss_mt_resolver_pick"):
-        L.iss_mt_resolver_pick.argtypes = [vp, C.POINTER(i32 * 3)]
-    # (and `generate --variants`: a record's haplotype spliced on the device; without them ReadEngine.add_genome_variants raises)
-    if hasattr(L, "iss_genome_upload_variants"):
-        L.iss_genome_upload_variants.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, C.POINTER(i32)]
-        L.iss_genome_download.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
-        L.iss_variants_lift.argtypes = [vp, vp, i32, vp, i64, vp]
-        L.iss_variants_apply_tile.argtypes = []
-        L.iss_variants_host_apply.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]
-        L.iss_variants_host_lift.argtypes = [i64, vp, vp, vp, vp, vp, i64, vp]
-    # (and `generate --device_fasta`: the genome FASTA indexed and stripped on the device -- a session without reset, so not one of
-    #  SESSIONS; without them fasta.FastaIndexer and ReadEngine.add_genomes_fasta raise)
-    if hasattr(L, "iss_fa_index"):
-        L.iss_fa_create.argtypes = [C.c_int, C.POINTER(vp)]
-        L.iss_fa_destroy.argtypes = [vp]
-        L.iss_fa_destroy.restype = None
-        L.iss_fa_last_error.argtypes = [vp]
-        L.iss_fa_last_error.restype = C.c_char_p
-        L.iss_fa_index.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
-        L.iss_fasta_host_index.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
-        L.iss_fasta_tile.argtypes = []
-        L.iss_fasta_scan_span.argtypes = []
-        L.iss_genome_upload_fasta.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-    L.iss_main_kernel.argtypes = [vp, vp, C.c_int]
-    L.iss_fastq_flush.argtypes = [vp]
-    L.iss_generate_batch.argtypes = [vp, i32, vp, vp, C.c_uint64, C.c_uint64, i32, i32, i64]
-    L.iss_fastq_compress.argtypes = [vp, i32]
-    L.iss_deflate_code_build.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
-    L.iss_gen_phred_scores.argtypes = [vp, i32, i64, u64, u64, vp]
-    L.iss_mut_sequence.argtypes = [vp, i32, i64, u64, u64, vp, vp, vp]
-    L.iss_random_insert_size.argtypes = [vp, i64, u64, u64, vp]
-    L.iss_introduce_indels.argtypes = [vp, i32, i64, u64, u64, vp, vp, vp, i64, vp, vp, vp]
-    L.iss_ev_step.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp]
-    L.iss_fastq_write.argtypes = [C.c_int, C.c_int, C.c_char_p, i64, i32, i64, i32, i32, vp, vp, vp, vp, i32]
-    L.iss_bam_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.iss_bam_feed.argtypes = [vp, vp, i64, vp, vp, i64]
-    L.iss_bam_tally_download.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i32)]
-    L.iss_bam_kde.argtypes = [vp, i32, i32, vp, vp]
-    session_entries = tuple(prefix + "_" for prefix in SESSIONS)
-    for name in EXPORTS:
-        if (name.startswith(session_entries) or name in (
-                "iss_vcf_emit", "iss_vcf_flush", "iss_mt_workers_mutations_reserve", "iss_mt_workers_mutations_download",
-                "iss_vcf_emit_workers", "iss_output_export", "iss_ctx_set_stream_ordered", "iss_mutations_export", "iss_tally_words",
-                "iss_output_tally", "iss_depth_mark", "iss_depth_finish", "iss_ubam_emit_batch", "iss_ubam_flush",
-                "iss_ubam_host_records", "iss_origins_emit_batch", "iss_origins_flush", "iss_origins_host_text",
-                "iss_origins_compress", "iss_vcf_compress", "iss_bgzf_text_code_build", "iss_error_tally_words",
-                "iss_mutations_tally", "iss_bgzf_scan", "iss_mt_resolver_pick", "iss_genome_upload_variants", "iss_genome_download",
-                "iss_variants_lift", "iss_variants_apply_tile", "iss_variants_host_apply", "iss_variants_host_lift") + FASTA_ENTRIES) and not hasattr(L, name):
-            continue
-        if name not in ("iss_ctx_destroy", "iss_last_error", "iss_build_id", "iss_fa_destroy", "iss_fa_last_error"):
-            getattr(L, name).restype = C.c_int
-    if hasattr(L, "iss_tally_words"):
-        L.iss_tally_words.restype = i64
-    if hasattr(L, "iss_error_tally_words"):
-        L.iss_error_tally_words.restype = i64
-    if hasattr(L, "iss_br_error_words"):
-        L.iss_br_error_words.restype = i64
-    # what every session has (a library from before a prefix still loads, and that prefix's Session raises); the entries whose
-    # restype is not int are set here, behind the loop above
-    for prefix, create_args in SESSIONS.items():
-        if not hasattr(L, prefix + "_create"):
-            continue
-        getattr(L, prefix + "_create").argtypes = [C.c_int] + list(create_args) + [C.POINTER(vp)]
-        getattr(L, prefix + "_destroy").argtypes = [vp]
-        getattr(L, prefix + "_destroy").restype = None
-        getattr(L, prefix + "_last_error").argtypes = [vp]
-        getattr(L, prefix + "_last_error").restype = C.c_char_p
-        getattr(L, prefix + "_reset").argtypes = [vp]
-        if prefix + "_kernel_ms" in EXPORTS:
-            getattr(L, prefix + "_kernel_ms").argtypes = [vp, C.POINTER(C.c_double)]
-        if prefix + "_tally_words" in EXPORTS:
-            getattr(L, prefix + "_tally_words").argtypes = [vp]
-            getattr(L, prefix + "_tally_words").restype = i64
+    for name, restype, argtypes, group in TABLE:
+        if not hasattr(L, name):
+            if group is None:
+                raise NativeLibraryError("%s does not export %s: rebuild it" % (LIB_PATH, name))
+            continue  # (a build from before the group: it still loads, and need() names what it lacks when that is asked for)
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, list(argtypes)
     _lib = L
     return L
+
+
+def need(L, group):
+    """Raise NativeLibraryError when the library ``L`` lacks an entry of ``group`` (there is no fall-back for a missing entry)."""
+    missing = [name for name in GROUPS[group] if not hasattr(L, name)]
+    if missing:
+        raise NativeLibraryError("%s does not export %s: rebuild it%s" % (LIB_PATH, " / ".join(missing), GROUP_HINTS.get(group, "")))
 
 
 def check(ctx, rc):

@@ -201,18 +201,15 @@ class BamReadTally(_native.Session):
 
             self._torch = _torch()  # (the accumulator is torch tensors: torch's HIP runtime has to be the process's first)
         _native.Session.__init__(self, device, self.max_len)
-        if self.depth and not hasattr(self._lib, "iss_br_depth_enable"):
-            self.close()
-            raise _native.NativeLibraryError("%s has no iss_br_depth_* entries: rebuild it" % _native.LIB_PATH)
-        if self.errors:
-            if not hasattr(self._lib, "iss_br_errors_enable"):
-                self.close()
-                raise _native.NativeLibraryError("%s has no iss_br_errors_* entries: rebuild it" % _native.LIB_PATH)
-            try:
+        try:
+            if self.depth:
+                _native.need(self._lib, "br_depth")
+            if self.errors:
+                _native.need(self._lib, "br_errors")
                 self._check(self._lib.iss_br_errors_enable(self._h))
-            except _native.EngineError:
-                self.close()
-                raise
+        except (_native.NativeLibraryError, _native.EngineError):
+            self.close()
+            raise
 
     def feed(self, chunk):
         """One bam.Chunk of whole records; its arrays are free again when the call returns."""

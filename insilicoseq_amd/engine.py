@@ -21,6 +21,13 @@ def _u64(a):
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
+def _item_arrays(items, cols, id_col=0, bytes_ids=False):
+    """What the emit entries take of a work list: [ids as (c_char_p * n) from column ``id_col``, an int64 array per column of ``cols``].
+    The caller holds the list across the call.  ``bytes_ids``: an id may be bytes as well as str."""
+    ids = [it[id_col] if bytes_ids and isinstance(it[id_col], bytes) else str(it[id_col]).encode() for it in items]
+    return [(C.c_char_p * len(items))(*ids)] + [np.array([it[k] for it in items], dtype=np.int64) for k in cols]
+
+
 class ReadEngine(object):
     def __init__(self, device=0):
         self._lib = _native.lib()
@@ -53,6 +60,10 @@ class ReadEngine(object):
 
     def _check(self, rc):
         return check(self._ctx, rc)
+
+    def _need(self, group):
+        """No fall-back: a library from before the entries of ``group`` (_native.TABLE) cannot take this route."""
+        _native.need(self._lib, group)
 
     # ------------------------------------------------------------------ uploads
     def load_model(self, dense):
@@ -128,8 +139,7 @@ class ReadEngine(object):
         one group like add_genomes', a larger record is a call of its own.  Returns the genome ids, -1 like add_genomes."""
         from .fasta import upload_runs
 
-        if not hasattr(self._lib, "iss_genome_upload_fasta"):
-            raise _native.NativeLibraryError("%s has no iss_genome_upload_fasta: rebuild it" % _native.LIB_PATH)
+        self._need("fasta")
         ids = []
         for first, last in [cut for run in upload_runs(seqs) for cut in self._cut_at_large(seqs, *run)]:
             run = seqs[first:last]
@@ -186,7 +196,7 @@ class ReadEngine(object):
         haplotype, built in HBM from the record's letters and packed like any record (iss_genome_upload_variants).  Every variant's
         REF letters must be the record's (case ignored): a mismatch raises EngineError, one line with ``record_id``, the POS and both
         spellings.  Returns the genome id; genome_length() is the haplotype's length."""
-        self._need_variant_entries()
+        self._need("variants")
         if isinstance(seq, str):
             seq = seq.encode("ascii")
         a = np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, dtype=np.uint8)
@@ -209,7 +219,7 @@ class ReadEngine(object):
 
     def genome_letters(self, gid):
         """The resident ASCII copy of genome ``gid`` as a uint8 array (iss_genome_download; waits for the stream)."""
-        self._need_variant_entries()
+        self._need("variants")
         n = C.c_int64(0)
         self._check(self._lib.iss_genome_download(self._ctx, int(gid), None, 0, C.byref(n)))
         out = np.empty(n.value, dtype=np.uint8)
@@ -220,7 +230,7 @@ class ReadEngine(object):
         """Haplotype coordinates -> record coordinates on the device: ``n`` int64 at the raw device address ``in_ptr`` to
         ``out_ptr`` (it may be ``in_ptr``), of genome ``gid``, or of the genome ids (int32 [n]) at ``gids_ptr``.  A genome
         uploaded without variants is the identity.  Asynchronous on the engine's current stream (iss_variants_lift)."""
-        self._need_variant_entries()
+        self._need("variants")
         self._check(self._lib.iss_variants_lift(self._ctx, C.c_void_p(int(gids_ptr)) if gids_ptr else None, int(gid),
                                                 C.c_void_p(int(in_ptr)) if in_ptr else None, int(n),
                                                 C.c_void_p(int(out_ptr)) if out_ptr else None))
@@ -246,10 +256,6 @@ class ReadEngine(object):
             self.lift_ptr(x.data_ptr(), x.numel(), out.data_ptr(), gid=gid, gids_ptr=g.data_ptr() if g is not None else None)
             self.synchronize()
         return out if on_device else out.cpu().numpy()
-
-    def _need_variant_entries(self):
-        if not hasattr(self._lib, "iss_genome_upload_variants"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_genome_upload_variants / iss_variants_lift: rebuild it" % _native.LIB_PATH)
 
     def clear_genomes(self):
         self._check(self._lib.iss_genome_clear(self._ctx))
@@ -447,13 +453,13 @@ class ReadEngine(object):
         """Enable (rows_per_worker > 0) / disable --store_mutations row capture of generate_mt_workers: every worker of the set
         owns a region of that many rows.  A worker that makes more rows fails the call with E_NOMEM (the set must be seeded
         again)."""
-        self._need_set_rows_entries()
+        self._need("set_rows")
         self._check(self._lib.iss_mt_workers_mutations_reserve(self._ctx, int(rows_per_worker)))
         self._set_mut_cap = int(rows_per_worker)
 
     def mt_workers_mutations(self, worker):
         """Rows of worker ``worker`` in the last generate_mt_workers call as a structured array (see mt_mutations)."""
-        self._need_set_rows_entries()
+        self._need("set_rows")
         cap = getattr(self, "_set_mut_cap", 0)
         out = np.zeros(cap, dtype=MUT_DTYPE)
         n = C.c_int64(0)
@@ -467,19 +473,11 @@ class ReadEngine(object):
         workers.  items: one entry per worker of the set, (fd, record id, first pair id, first output row, pairs, cpu number) --
         pairs 0: the worker sat the call out.  Worker k's text is appended to its fd (asynchronous; ``vcf_flush`` before the
         files are used)."""
-        self._need_set_rows_entries()
-        n = len(items)
-        fds = np.array([it[0] for it in items], dtype=np.int32)
-        ids = (C.c_char_p * n)(*[str(it[1]).encode() for it in items])
-        cols = [np.array([it[k] for it in items], dtype=np.int64) for k in (2, 3, 4)]
-        cpus = np.array([it[5] for it in items], dtype=np.int32)
-        self._check(self._lib.iss_vcf_emit_workers(self._ctx, n, fds.ctypes.data, ids, cols[0].ctypes.data, cols[1].ctypes.data,
-                                                   cols[2].ctypes.data, cpus.ctypes.data))
-
-    def _need_set_rows_entries(self):
-        if not hasattr(self._lib, "iss_vcf_emit_workers"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_mt_workers_mutations_reserve / iss_vcf_emit_workers: "
-                                             "rebuild it" % _native.LIB_PATH)
+        self._need("set_rows")
+        fds, cpus = (np.array([it[k] for it in items], dtype=np.int32) for k in (0, 5))
+        ids, first_i, first_pair, n_pairs = _item_arrays(items, (2, 3, 4), id_col=1)
+        self._check(self._lib.iss_vcf_emit_workers(self._ctx, len(items), fds.ctypes.data, ids, first_i.ctypes.data, first_pair.ctypes.data,
+                                                   n_pairs.ctypes.data, cpus.ctypes.data))
 
     def mt_peek(self, n=8):
         """The next n 32-bit words of (CPython random, numpy) -- not consumed."""
@@ -496,25 +494,20 @@ class ReadEngine(object):
 
     def fastq_emit_batch(self, fd_r1, fd_r2, items, cpu_number):
         """items: (record id, first pair id, first output row, pairs) per work item -- one text job for all of them."""
-        n = len(items)
-        ids = (C.c_char_p * n)(*[str(it[0]).encode() for it in items])
-        first_i = np.array([it[1] for it in items], dtype=np.int64)
-        first_pair = np.array([it[2] for it in items], dtype=np.int64)
-        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
-        self._check(self._lib.iss_fastq_emit_batch(self._ctx, int(fd_r1), int(fd_r2), n, ids, first_i.ctypes.data,
+        ids, first_i, first_pair, n_pairs = _item_arrays(items, (1, 2, 3))
+        self._check(self._lib.iss_fastq_emit_batch(self._ctx, int(fd_r1), int(fd_r2), len(items), ids, first_i.ctypes.data,
                                                    first_pair.ctypes.data, n_pairs.ctypes.data, int(cpu_number)))
 
     def fastq_emit_scatter(self, fd_r1, fd_r2, items, n_threads=1):
         """items: (record id, first pair id, first output row, pairs, cpu number, byte offset in both files) -- one text job, every
         item's text written at its own place (the workers of a set straight into the final files; text mode only)."""
-        n = len(items)
-        if not n:
+        if not items:
             return
-        ids = (C.c_char_p * n)(*[str(it[0]).encode() for it in items])
-        cols = [np.array([it[k] for it in items], dtype=np.int64) for k in (1, 2, 3, 5)]
+        ids, first_i, first_pair, n_pairs, file_off = _item_arrays(items, (1, 2, 3, 5))
         cpus = np.array([it[4] for it in items], dtype=np.int32)
-        self._check(self._lib.iss_fastq_emit_scatter(self._ctx, int(fd_r1), int(fd_r2), n, ids, cols[0].ctypes.data, cols[1].ctypes.data,
-                                                     cols[2].ctypes.data, cpus.ctypes.data, cols[3].ctypes.data, int(n_threads)))
+        self._check(self._lib.iss_fastq_emit_scatter(self._ctx, int(fd_r1), int(fd_r2), len(items), ids, first_i.ctypes.data,
+                                                     first_pair.ctypes.data, n_pairs.ctypes.data, cpus.ctypes.data, file_off.ctypes.data,
+                                                     int(n_threads)))
 
     def vcf_emit(self, fd, items, cpu_number, source="philox"):
         """The --store_mutations rows of the last generate() / generate_batch() call (``source="philox"``) or generate_mt() call
@@ -523,26 +516,17 @@ class ReadEngine(object):
         Philox call that overflowed its row buffer raises E_NOMEM and leaves ``mutation_slots_needed`` like mutations()."""
         if source not in ("philox", "mt"):
             raise ValueError("source must be 'philox' or 'mt'")
-        self._need_vcf_entries()
-        n = len(items)
-        ids = (C.c_char_p * n)(*[str(it[0]).encode() for it in items])
-        first_i = np.array([it[1] for it in items], dtype=np.int64)
-        first_pair = np.array([it[2] for it in items], dtype=np.int64)
-        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
+        self._need("vcf")
+        ids, first_i, first_pair, n_pairs = _item_arrays(items, (1, 2, 3))
         need = C.c_int64(0)
-        rc = self._lib.iss_vcf_emit(self._ctx, int(fd), 0 if source == "philox" else 1, n, ids, first_i.ctypes.data,
+        rc = self._lib.iss_vcf_emit(self._ctx, int(fd), 0 if source == "philox" else 1, len(items), ids, first_i.ctypes.data,
                                     first_pair.ctypes.data, n_pairs.ctypes.data, int(cpu_number), C.byref(need))
         self.mutation_slots_needed = need.value if rc == _native.E_NOMEM else 0  # (what a retry has to reserve)
         self._check(rc)
 
     def vcf_flush(self):
-        self._need_vcf_entries()
+        self._need("vcf")
         self._check(self._lib.iss_vcf_flush(self._ctx))
-
-    def _need_vcf_entries(self):
-        if not hasattr(self._lib, "iss_vcf_emit"):  # (no fall-back: a library from before these entries cannot take this route)
-            raise _native.NativeLibraryError("%s does not export iss_vcf_emit / iss_vcf_flush: rebuild it, or set ISS_HOST_VCF=1 "
-                                             "for the rows-to-host route" % _native.LIB_PATH)
 
     def fastq_compress(self, on=True):
         """`--compress` on the device: every fastq_emit appends one gzip member per file instead of text."""
@@ -556,62 +540,43 @@ class ReadEngine(object):
         records (R1 then R2 of every pair: flags 77 / 141, names "{id}_{i}_{cpu}", lower-case bases as their capitals) in BGZF
         blocks built on the device, appended to ``fd`` (asynchronous; ``ubam_flush`` before the file is used).  Record blocks
         only: the BAM header and the EOF block are the caller's (ubam.py).  Ids may be str or bytes."""
-        self._need_ubam_entries()
-        n = len(items)
-        ids = (C.c_char_p * n)(*[it[0] if isinstance(it[0], bytes) else str(it[0]).encode() for it in items])
-        first_i = np.array([it[1] for it in items], dtype=np.int64)
-        first_pair = np.array([it[2] for it in items], dtype=np.int64)
-        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
-        self._check(self._lib.iss_ubam_emit_batch(self._ctx, int(fd), n, ids, first_i.ctypes.data, first_pair.ctypes.data,
+        self._need("ubam")
+        ids, first_i, first_pair, n_pairs = _item_arrays(items, (1, 2, 3), bytes_ids=True)
+        self._check(self._lib.iss_ubam_emit_batch(self._ctx, int(fd), len(items), ids, first_i.ctypes.data, first_pair.ctypes.data,
                                                   n_pairs.ctypes.data, int(cpu_number)))
 
     def ubam_flush(self):
-        self._need_ubam_entries()
+        self._need("ubam")
         self._check(self._lib.iss_ubam_flush(self._ctx))
-
-    def _need_ubam_entries(self):
-        if not hasattr(self._lib, "iss_ubam_emit_batch"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_ubam_emit_batch / iss_ubam_flush: rebuild it" % _native.LIB_PATH)
 
     def origins_emit_batch(self, fd, items, record_lengths, cpu_number):
         """Where the pairs of the items of fastq_emit_batch -- (record id, first pair id, first output row, pairs), in ascending
         row order -- came from, as BEDPE text built on the device and appended to ``fd`` (asynchronous; ``origins_flush`` before
         the file is used): one line "{id} s1 e1 {id} s2 e2 {id}_{i}_{cpu} . + - isz" per pair, the two template intervals clamped
         against ``record_lengths[k]``, the length of item k's record (origins.py).  Ids may be str or bytes."""
-        self._need_origins_entries()
+        self._need("origins")
         n = len(items)
         if len(record_lengths) != n:
             raise ValueError("one record length per item")
-        ids = (C.c_char_p * n)(*[it[0] if isinstance(it[0], bytes) else str(it[0]).encode() for it in items])
-        first_i = np.array([it[1] for it in items], dtype=np.int64)
-        first_pair = np.array([it[2] for it in items], dtype=np.int64)
-        n_pairs = np.array([it[3] for it in items], dtype=np.int64)
+        ids, first_i, first_pair, n_pairs = _item_arrays(items, (1, 2, 3), bytes_ids=True)
         lengths = np.array([int(x) for x in record_lengths], dtype=np.int64)
         self._check(self._lib.iss_origins_emit_batch(self._ctx, int(fd), n, ids, first_i.ctypes.data, first_pair.ctypes.data,
                                                      n_pairs.ctypes.data, lengths.ctypes.data, int(cpu_number)))
 
     def origins_flush(self):
-        self._need_origins_entries()
+        self._need("origins")
         self._check(self._lib.iss_origins_flush(self._ctx))
 
     def origins_compress(self, on=True):
         """Mode of ``origins_emit_batch``: False (default) appends the text, True the text's BGZF members built on the device
         (bgzf.py frames the file).  Switched only while nothing is queued (after ``origins_flush``)."""
-        self._need_bgzip_entries()
+        self._need("bgzip")
         self._check(self._lib.iss_origins_compress(self._ctx, 1 if on else 0))
 
     def vcf_compress(self, on=True):
         """The same for ``vcf_emit``; ``vcf_emit_workers`` raises in this mode."""
-        self._need_bgzip_entries()
+        self._need("bgzip")
         self._check(self._lib.iss_vcf_compress(self._ctx, 1 if on else 0))
-
-    def _need_bgzip_entries(self):
-        if not hasattr(self._lib, "iss_origins_compress"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_origins_compress / iss_vcf_compress: rebuild it" % _native.LIB_PATH)
-
-    def _need_origins_entries(self):
-        if not hasattr(self._lib, "iss_origins_emit_batch"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_origins_emit_batch / iss_origins_flush: rebuild it" % _native.LIB_PATH)
 
     def mt_path_counts(self):
         """(pairs resolved in parallel, pairs walked sequentially) by generate_mt so far."""
@@ -622,8 +587,7 @@ class ReadEngine(object):
     def mt_resolver(self):
         """The resolver instantiation generate_mt / generate_mt_workers take for the loaded model and the current ISS_MT_PATH:
         (python ring half in K words, numpy ring half in K words, digit rows in LDS), or None when every pair is walked."""
-        if not hasattr(self._lib, "iss_mt_resolver_pick"):  # (no fall-back)
-            raise _native.NativeLibraryError("%s does not export iss_mt_resolver_pick: rebuild it" % _native.LIB_PATH)
+        self._need("mt_resolver")
         out = (C.c_int32 * 3)()
         self._check(self._lib.iss_mt_resolver_pick(self._ctx, C.byref(out)))
         return (out[0], out[1], bool(out[2])) if out[0] else None
@@ -656,7 +620,7 @@ class ReadEngine(object):
         if wait:
             self._check(self._lib.iss_ctx_set_stream(self._ctx, C.c_void_p(hip_stream_ptr or None)))
         else:
-            self._need_export_entries()
+            self._need("export")
             self._check(self._lib.iss_ctx_set_stream_ordered(self._ctx, C.c_void_p(hip_stream_ptr or None)))
         self.stream_ptr = int(hip_stream_ptr or 0)
 
@@ -668,7 +632,7 @@ class ReadEngine(object):
         generation; nothing waits on the host (include/iss_mi355x.h: iss_output_export)."""
         if encoding not in _native.EXPORT_ENCODINGS:
             raise EngineError(_native.E_INVALID, "export: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
-        self._need_export_entries()
+        self._need("export")
         ptrs = [C.c_void_p(int(p)) if p else None for p in (bases_ptr, qual_ptr, coords_ptr, item_ptr)]
         self._check(self._lib.iss_output_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding], *ptrs))
 
@@ -682,15 +646,14 @@ class ReadEngine(object):
         waits on the host (include/iss_mi355x.h: iss_mutations_export)."""
         if encoding not in _native.EXPORT_ENCODINGS:
             raise EngineError(_native.E_INVALID, "export_mutations: encoding must be 'ascii' or 'codes', not %r" % (encoding,))
-        if not hasattr(self._lib, "iss_mutations_export"):  # (no fall-back, like _need_export_entries)
-            raise _native.NativeLibraryError("%s does not export iss_mutations_export: rebuild it" % _native.LIB_PATH)
+        self._need("mutations_export")
         ptrs = [C.c_void_p(int(p)) if p else None for p in (truth_ptr, events_ptr, n_events_ptr)]
         self._check(self._lib.iss_mutations_export(self._ctx, int(first_pair), int(n_pairs), _native.EXPORT_ENCODINGS[encoding],
                                                    ptrs[0], ptrs[1], int(capacity), ptrs[2]))
 
     def tally_words(self):
         """uint64 words of a tally of this engine's model (include/iss_mi355x.h: iss_tally_words; tally.tally_layout)."""
-        self._need_tally_entries()
+        self._need("tally")
         n = self._lib.iss_tally_words(self._ctx)
         if n < 0:
             raise EngineError(_native.E_INVALID, "tally_words: upload a model first")
@@ -701,16 +664,12 @@ class ReadEngine(object):
         reads, insert sizes, pairs -- to the tally_words() uint64 words at ``tally_ptr`` (a raw device address; the caller's
         memory, zeroed by the caller).  Asynchronous on the engine's current stream, behind the generation; nothing waits on the
         host (include/iss_mi355x.h: iss_output_tally; tally.split_tally names the fields)."""
-        self._need_tally_entries()
+        self._need("tally")
         self._check(self._lib.iss_output_tally(self._ctx, int(first_pair), int(n_pairs), C.c_void_p(int(tally_ptr)) if tally_ptr else None))
-
-    def _need_tally_entries(self):
-        if not hasattr(self._lib, "iss_output_tally"):  # (no fall-back, like _need_export_entries)
-            raise _native.NativeLibraryError("%s does not export iss_tally_words / iss_output_tally: rebuild it" % _native.LIB_PATH)
 
     def error_tally_words(self):
         """uint64 words of an error tally of this engine's model (include/iss_mi355x.h: iss_error_tally_words; errtally.layout)."""
-        self._need_errtally_entries()
+        self._need("errtally")
         n = self._lib.iss_error_tally_words(self._ctx)
         if n < 0:
             raise EngineError(_native.E_INVALID, "error_tally_words: upload a model first")
@@ -726,13 +685,9 @@ class ReadEngine(object):
         iss_mutations_tally; errtally.split names the fields)."""
         if source not in ("philox", "mt"):
             raise ValueError("source must be 'philox' or 'mt'")
-        self._need_errtally_entries()
+        self._need("errtally")
         self._check(self._lib.iss_mutations_tally(self._ctx, 0 if source == "philox" else 1, int(first_pair), int(n_pairs),
                                                   C.c_void_p(int(tally_ptr)) if tally_ptr else None))
-
-    def _need_errtally_entries(self):
-        if not hasattr(self._lib, "iss_mutations_tally"):  # (no fall-back, like _need_tally_entries)
-            raise _native.NativeLibraryError("%s does not export iss_error_tally_words / iss_mutations_tally: rebuild it" % _native.LIB_PATH)
 
     def depth_mark(self, first_pair, n_pairs, table_ptr, n_table, diff_ptr):
         """Add the template intervals of rows [first_pair, +n_pairs) to the int32 difference array at ``diff_ptr``: +1 at the
@@ -741,7 +696,7 @@ class ReadEngine(object):
         last generate_batch() (row 0 for other rows); offset < 0: the pair is skipped.  Raw device addresses, the caller's memory.
         Asynchronous on the engine's current stream, behind the generation; nothing waits on the host.  The caller marks no more
         than 2^30 pairs into one accumulator (depth.count_marked) (include/iss_mi355x.h: iss_depth_mark)."""
-        self._need_depth_entries()
+        self._need("depth")
         self._check(self._lib.iss_depth_mark(self._ctx, int(first_pair), int(n_pairs), C.c_void_p(int(table_ptr)) if table_ptr else None,
                                              int(n_table), C.c_void_p(int(diff_ptr)) if diff_ptr else None))
 
@@ -751,18 +706,9 @@ class ReadEngine(object):
         ``stats_ptr``: sum, sum of squares, covered bases, maximum) and, with ``bin`` > 0, the sums over ``bin``-base windows
         (uint64 [depth.n_windows(table, bin).sum()] at ``bins_ptr``); None: not wanted.  Works on an engine with no model.
         Asynchronous on the engine's current stream (include/iss_mi355x.h: iss_depth_finish; depth.finish_host is its twin)."""
-        self._need_depth_entries()
+        self._need("depth")
         ptrs = [C.c_void_p(int(p)) if p else None for p in (diff_ptr, depth_ptr, table_ptr, stats_ptr, bins_ptr)]
         self._check(self._lib.iss_depth_finish(self._ctx, ptrs[0], int(n_words), ptrs[1], ptrs[2], int(n_table), int(bin), ptrs[3], ptrs[4]))
-
-    def _need_depth_entries(self):
-        if not hasattr(self._lib, "iss_depth_mark"):  # (no fall-back, like _need_tally_entries)
-            raise _native.NativeLibraryError("%s does not export iss_depth_mark / iss_depth_finish: rebuild it" % _native.LIB_PATH)
-
-    def _need_export_entries(self):
-        if not hasattr(self._lib, "iss_output_export"):  # (no fall-back, like _need_vcf_entries)
-            raise _native.NativeLibraryError("%s does not export iss_output_export / iss_ctx_set_stream_ordered: rebuild it"
-                                             % _native.LIB_PATH)
 
     # ------------------------------------------------------------------ measurement
     def timing_enable(self, on=True):

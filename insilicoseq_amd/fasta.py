@@ -78,8 +78,7 @@ def _index_call(call, data):
 def index_native_host(data):
     """The table from the library's host entry (iss_fasta_host_index: the kernels' grammar source compiled for the host, no GPU)."""
     lib = _native.lib()
-    if not hasattr(lib, "iss_fasta_host_index"):
-        raise _native.NativeLibraryError("%s has no iss_fasta_* entries: rebuild it" % _native.LIB_PATH)
+    _native.need(lib, "fasta")
     return _index_call(lambda *args: _native.check(None, lib.iss_fasta_host_index(*args)), data)
 
 
